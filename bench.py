@@ -10,8 +10,12 @@ metric     = rendered Mpix/s (fwd+bwd): T*H*W output pixels per step / step time
 N > 1      = the SAME frame is split into N row bands (strong scaling, north star "tiles shard across the 8 GPUs");
              each rank owns the stack rows its band touches, ONE RCCL all-gather of the composited band per step
              (overlapped with the backward on a side stream), no collective on the gradient path.
-Also reported on the same JSON line: roofline (HIP-event kernel times vs algorithmic bytes), cpu_baseline (the CPU oracle
-timed on this box's host cores on a bounded sample), and the stage-2 looping-loss iters/s.
+A plain run sets up, warms up, times the --steps steps and prints the JSON line: headline, ms_per_step and roofline (HIP-event
+kernel times of those steps vs algorithmic bytes).  --full adds everything else, as before: the checksums of the frame and the
+gradient, the gather check and band loss at N > 1, the cpu_baseline (the CPU oracle timed on the host's cores on a bounded
+sample), the stage-2 looping-loss iters/s and the other legs, their side file and the flat summary of them.
+--dump-outputs DIR writes what the last timed step computed (rgb, alpha, the stack gradient; fixed seeded samples of the large
+ones, see dump_outputs) as DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -56,7 +60,14 @@ def parse():
                          "training-complete, every replica of a stack row ends the step with the single-GPU gradient)")
     ap.add_argument("--no-loss-band", dest="loss_band", action="store_false",
                     help="N > 1: leave out the extra (untimed) leg, the looping loss on this rank's rows of the gathered frame")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (checksums, loss, stage-1/2 legs, CPU baseline, ...) and write their side file; "
+                         "off: the headline steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rgb, alpha, stack gradient) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.config:
         a.D, a.T, a.H, a.W, a.stack_dtype = {"cfg3": (32, 50, 720, 1280, "f32"), "cfg4": (64, 80, 1080, 1920, "f32"),
                                               "cfg5": (96, 120, 2160, 3840, "f16")}[a.config]
@@ -194,6 +205,36 @@ def loss_bench(dev, H, W, T, Ty, steps):
     return out
 
 
+DUMP_SAMPLE = 1 << 22       # elements kept of a larger output: 16 MB of float32 each (rgb, grad_stack; alpha keeps half): 40 MB in all
+
+
+def sample_output(t, n, seed):
+    """t as a float32 host array: whole (in its shape) if it has at most n elements, else the n elements at fixed flat indices drawn
+    from a seeded generator and sorted -- the same indices for every tensor of that size, whatever build or run computed it."""
+    t = t.detach()
+    if t.numel() > n:
+        idx = torch.randint(0, t.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, rgb, alpha, grad, grad_sums):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- rgb [T,H,W,3], alpha [T,H,W], the stack
+    gradient (D,T,Hs,Ws,4) -- as path/<name>.npy, samples of DUMP_SAMPLE elements when larger; grad_sums (fp64 sum and absolute sum
+    of the whole gradient) beside them.  alpha and the gradient are band-local at N > 1 and are written at N = 1 only."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    outs = {"rgb": sample_output(rgb, DUMP_SAMPLE, 1)}
+    if alpha is not None:
+        outs["alpha"] = sample_output(alpha, DUMP_SAMPLE // 2, 2)
+    if grad is not None:
+        outs["grad_stack"] = sample_output(grad, DUMP_SAMPLE, 3)
+    if grad_sums is not None:
+        outs["grad_sums"] = np.asarray(grad_sums, dtype=np.float64)
+    for name, arr in outs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     a = parse()
     # ONE JSON line on stdout: whatever the legs' own code prints (pyramid / dataset messages of the drivers) goes to stderr
@@ -295,7 +336,7 @@ def main():
         if timed:
             fwd_ms.append((e0, e1))
             bwd_ms.append((e1, e2))
-        last["rgb"], last["frame"], last["gs"] = rgb.detach(), frame, gs
+        last["rgb"], last["frame"], last["gs"], last["alpha"] = rgb.detach(), frame, gs, alpha.detach()
         return gs
 
     def fence():
@@ -330,9 +371,9 @@ def main():
             tot += int(part.contiguous().view(torch.int32).to(torch.int64).sum().item())
         return tot
     frame = last["frame"]
-    frame_checksum = bits_sum(frame)
+    frame_checksum = bits_sum(frame) if a.full else None
     gather_check = None
-    if world > 1:
+    if world > 1 and a.full:
         mine = bits_sum(last["rgb"])
         sums = [None] * world
         dist.all_gather_object(sums, mine)
@@ -354,7 +395,9 @@ def main():
             tota += float(pd.abs().sum().item())
         return tot, tota
     gs_last = last.pop("gs")
-    if world == 1:
+    if not (a.full or a.dump_outputs):
+        grad_sums = None
+    elif world == 1:
         grad_sums = f64_sums(gs_last)
     elif a.exchange_halo_grads:
         hi = bands[rank + 1].src0 if rank + 1 < world else band.src1
@@ -363,6 +406,8 @@ def main():
         grad_sums = (float(tg[0].item()), float(tg[1].item()))
     else:
         grad_sums = None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, frame, last["alpha"] if world == 1 else None, gs_last if world == 1 else None, grad_sums)
     del gs_last
     ms_per_step = dt / a.steps * 1e3
     pix_per_step = T * H * W
@@ -425,7 +470,7 @@ def main():
             "halo_grad_exchange": {"in_step": bool(a.exchange_halo_grads), "peers": len(ov),
                                    "bytes_sent": sum((hi - lo) for _, lo, hi in ov) * D * T * Ws * 16},
         }
-    if world > 1 and a.loss_band:
+    if world > 1 and a.loss_band and a.full:
         # the looping loss on this rank's rows of the gathered frame (dist.looping_loss_band): halo patch rows recomputed, one scalar
         # all-reduce; x = the gathered frame (T + 2 loop-padded frames), y = a synthetic captured clip
         from videoloop3d_amd.dist import looping_loss_band
@@ -447,8 +492,8 @@ def main():
             fence()
         res["loss_band"] = {"iters_per_s": 3 / (time.perf_counter() - tl), "loss": float(tot[0] / tot[1]), "cfg": "other (ps 3, stride 2), Ty = 75"}
     if rank == 0:
-        # the extra legs (loss, stage-1 shape, storage / culling variants, end-to-end iteration, CPU baseline) run at N = 1 only
-        if world > 1:
+        # the extra legs (loss, stage-1 shape, storage / culling variants, end-to-end iteration, CPU baseline) run with --full at N = 1 only
+        if world > 1 or not a.full:
             a.no_loss = a.no_stage2 = a.no_cpu_baseline = True
         if not a.no_loss:
             try:
@@ -649,13 +694,16 @@ def main():
         # Every leg in full goes to a side file (per-level arrays, histograms, footprints, workloads); the stdout line carries the headline,
         # `roofline`, `cpu_baseline`, `build` and -- LAST, where a consumer that keeps only the tail of the line still finds it -- a flat
         # `summary` of every leg.  The line stays under 6 KB.
-        detail_path = os.environ.get("VL3D_BENCH_DETAIL") or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-            with open(detail_path, "w") as fh:
-                json.dump(res, fh)
-        except OSError as e:
-            detail_path = f"(not written: {e})"
+        # (a plain run has no legs and writes no side file)
+        detail_path = None
+        if a.full:
+            detail_path = os.environ.get("VL3D_BENCH_DETAIL") or os.path.join(ROOT, "bench_out", "bench_detail.json")
+            try:
+                os.makedirs(os.path.dirname(detail_path), exist_ok=True)
+                with open(detail_path, "w") as fh:
+                    json.dump(res, fh)
+            except OSError as e:
+                detail_path = f"(not written: {e})"
         summ = {}
         for cfg_ in ("ref", "other"):
             summ[f"loss720_{cfg_}_it_s"] = pick(res, "loss", cfg_, "iters_per_s")
@@ -692,7 +740,8 @@ def main():
         head = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                 "stack_storage", "config", "frame_checksum", "grad_sums", "collective", "loss_band", "roofline", "cpu_baseline", "build"]
         line = {k: res[k] for k in head if k in res}
-        line["detail_file"] = os.path.relpath(detail_path, ROOT) if os.path.isabs(detail_path) else detail_path
+        if detail_path is not None:
+            line["detail_file"] = os.path.relpath(detail_path, ROOT) if os.path.isabs(detail_path) else detail_path
         line["summary"] = {k: r4(v) for k, v in summ.items()}
         text = json.dumps(line)
         for k_ in ("build", "collective"):      # never silently exceed what the record keeps: the longest free-text fields go first

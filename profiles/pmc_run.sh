@@ -1,7 +1,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/pmc
-B="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-loss --T 10"
+B="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-loss --T 10"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc/trace -o t -- $B > gpurun_out/pmc/trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc/fetch -o p -- $B > gpurun_out/pmc/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc/write -o p -- $B > gpurun_out/pmc/write.log 2>&1

@@ -2,7 +2,7 @@
 # round 6: run the bench's stage-2 legs until a stalled level shows, print its interval diagnostics (device vs host clock)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for i in $(seq 1 ${1:-10}); do
-  VL3D_BENCH_DETAIL=/tmp/detail.json timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-loss > /dev/null 2>&1
+  VL3D_BENCH_DETAIL=/tmp/detail.json timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-loss > /dev/null 2>&1
   python - <<PY
 import json
 d = json.load(open("/tmp/detail.json"))["stage2_schedule"]

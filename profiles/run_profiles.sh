@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 R=${1:-r01}
 O=gpurun_out/$R
 mkdir -p $O
-python bench.py --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-stage2 > $O/trace.log 2>&1
+python bench.py --full --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-stage2 > $O/trace.log 2>&1
 B="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-loss --no-stage2"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o p -- $B > $O/fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o p -- $B > $O/write.log 2>&1

@@ -8,8 +8,8 @@ R=${1:-r03}
 O=gpurun_out/$R
 mkdir -p $O
 if [ "$2" != "pmc-only" ]; then
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1
 fi
 B="python profiles/pmc_target.py 50"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ttrace -o t -- $B > $O/ttrace.log 2>&1

@@ -10,8 +10,8 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 R=${1:-r06}
 O=gpurun_out/$R
 mkdir -p $O
-VL3D_BENCH_DETAIL=$GRAFT_REPO_ROOT/$O/bench_detail.json python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1
+VL3D_BENCH_DETAIL=$PWD/$O/bench_detail.json python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1
 B="python profiles/pmc_target.py 50 fp16"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ttrace -o t -- $B > $O/ttrace.log 2>&1
 timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o p -- $B > $O/fetch.log 2>&1
@@ -47,8 +47,8 @@ done
 
 # N = 4 dry run of the multi-GPU path on ONE MI355X (device kernels per rank, host collectives over gloo: a check of the N > 1 code, not a timing):
 # four row bands whose parallax halos span two ranks, direct gather with one message per peer, halo-gradient exchange, band loss
-VL3D_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 4 --steps 3 --warmup 1 --gather-algo direct > $O/n4_gloo.json 2> $O/n4_gloo.err
-VL3D_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 2 --steps 3 --warmup 1 > $O/n2_gloo.json 2> $O/n2_gloo.err
+VL3D_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 4 --steps 3 --warmup 1 --gather-algo direct > $O/n4_gloo.json 2> $O/n4_gloo.err
+VL3D_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus 2 --steps 3 --warmup 1 > $O/n2_gloo.json 2> $O/n2_gloo.err
 # ... and at the node size north_star names: eight processes, eight bands of 90 rows
-VL3D_BENCH_BACKEND=gloo timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 8 --steps 2 --warmup 1 > $O/n8_gloo.json 2> $O/n8_gloo.err
+VL3D_BENCH_BACKEND=gloo timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus 8 --steps 2 --warmup 1 > $O/n8_gloo.json 2> $O/n8_gloo.err
 tail -c 600 $O/n4_gloo.json
