@@ -552,6 +552,33 @@ int vl3d_robust_fwd(int64_t n, const float *x, const float *y2x, int32_t kind, f
 int vl3d_robust_bwd(int64_t n, const float *x, const float *y2x, int32_t kind, float rou, float scale,
                     const float *grad_out, float inv_n, float *grad_x, vl3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation (scripts/script_evaluate_ours.py:149-181, evaluations/metrics.py:15-89 with skimage's structural_similarity /
+ * peak_signal_noise_ratio as that file calls them).  One test view: gt uint8 [F,H0,W0,3] and pred uint8 [T,H0,W0,3] (F != T allowed),
+ * each addressed through byte strides per frame (*_sf) and row (*_sr) with pixel stride 3 and channel stride 1; the crop window
+ * (row0, col0, h, w) is read in place.  mask: uint8 [h,w] holding 0/1 (the static region, metrics.py:43-56), or NULL = all ones;
+ * mask_ones = its number of ones, counted by the caller (1 .. h*w; an all-zero mask is refused with VL3D_EINVAL, where the reference
+ * yields nan / -inf).  A sample is a = w / 255 with the integer w = (2u - 255) m.
+ * Outputs, for every frame f < Fm = min(F, T):
+ *   sse[f]      = sum over h*w*3 of (w_gt - w_pred)^2                       (int64, exact; mse = sse / (255^2 h w 3))
+ *   ssim_sum[f] = sum over pixels and channels of S * m                      (fp64; frame SSIM = ssim_sum / sum(m) / 3, metrics.py:80)
+ *                 S: skimage's SSIM map, win 7, uniform weights, data_range 2, cov_norm 49/48, window sums of scipy's uniform_filter
+ *                 with mode 'reflect' (half-sample symmetric: d c b a | a b c d); the window sums are exact integers
+ *   gt_min[f]   = min over h*w*3 of w_gt                                     (int32; skimage's data_range is 2 if < 0, else 1)
+ * and dyn_sum[0] = sum over h*w*3 of (std_F(gt) - std_T(pred))^2 on 0..255 values, population std, each clip over its own frames
+ * (script_evaluate_ours.py:176-178; dyn = dyn_sum / (h w 3)).  F, T <= 32768; h, w >= 7 (skimage's win_size; VL3D_EINVAL otherwise).
+ * Two launches (statistics, then a fixed-order reduction over workgroups): no float atomics, identical bits on every call.
+ * scratch: vl3d_eval_scratch_bytes(desc) bytes of device memory (-1 for an invalid descriptor). */
+typedef struct vl3d_eval_desc {
+    int32_t F, T;                  /* frames of gt / pred */
+    int32_t row0, col0, h, w;      /* crop window */
+    int64_t gt_sf, gt_sr;          /* byte strides of gt: frame, row */
+    int64_t pred_sf, pred_sr;      /* byte strides of pred: frame, row */
+} vl3d_eval_desc;
+int64_t vl3d_eval_scratch_bytes(const vl3d_eval_desc *desc);
+int vl3d_eval_view(const vl3d_eval_desc *desc, const uint8_t *gt, const uint8_t *pred, const uint8_t *mask, int64_t mask_ones,
+                   int64_t *sse, double *ssim_sum, int32_t *gt_min, double *dyn_sum, void *scratch, vl3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,11 @@ _P = C.c_void_p
 _I32, _I64, _F = C.c_int32, C.c_int64, C.c_float
 
 
+class EvalDesc(C.Structure):
+    _fields_ = [("F", C.c_int32), ("T", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("gt_sf", C.c_int64), ("gt_sr", C.c_int64), ("pred_sf", C.c_int64), ("pred_sr", C.c_int64)]
+
+
 class AdamWindow(C.Structure):
     _fields_ = [("Hs", C.c_int32), ("Ws", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32),
                 ("param", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("last_step", _P), ("hist", _P),
@@ -125,6 +130,8 @@ SIGNATURES = {
     "vl3d_linear_head_bwd": ([_I32, _P, _P, _P, _P], C.c_int),
     "vl3d_robust_fwd": ([_I64, _P, _P, _I32, _F, _F, _P, _P], C.c_int),
     "vl3d_robust_bwd": ([_I64, _P, _P, _I32, _F, _F, _P, _F, _P, _P], C.c_int),
+    "vl3d_eval_scratch_bytes": ([C.POINTER(EvalDesc)], C.c_int64),
+    "vl3d_eval_view": ([C.POINTER(EvalDesc), _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], C.c_int),
 }
 
 _lib = None

@@ -69,3 +69,19 @@ def make_cameras(H, W, device="cpu", dtype=torch.float32):
 def make_video(T, H, W, seed, device="cpu"):
     """[1,3,T,H,W] hash-uniform video in [0,1)."""
     return hash_uniform((1, 3, T, H, W), seed, device=device)
+
+
+def eval_clip(F, H, W, seed, noise_seed=None, lo=0, hi=255, block=6, speed=2, noise=24):
+    """uint8 [F,H,W,3] structured clip for the evaluation metrics (integer arithmetic, CPU): a texture of block x block tiles with levels in
+    [lo, hi], static on the left half and moving `speed` pixels per frame on the right half, plus per-frame noise of up to +-`noise` levels
+    (its own seed), clamped to [lo, hi]."""
+    noise_seed = seed + 1 if noise_seed is None else noise_seed
+    f = torch.arange(F, dtype=torch.int64).view(F, 1, 1, 1)
+    y = torch.arange(H, dtype=torch.int64).view(1, H, 1, 1)
+    x = torch.arange(W, dtype=torch.int64).view(1, 1, W, 1)
+    c = torch.arange(3, dtype=torch.int64).view(1, 1, 1, 3)
+    xs = torch.where(x < W // 2, x, x + speed * f)
+    tex = hash32((((y // block) << 20) + xs // block) * 3 + c, seed) % (hi - lo + 1)      # (a clip's first frames do not depend on F)
+    idx = ((f * H + y) * W + x) * 3 + c
+    nz = hash32(idx, noise_seed) % (2 * noise + 1) - noise
+    return (lo + tex + nz).clamp(lo, hi).to(torch.uint8)
