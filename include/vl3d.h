@@ -158,6 +158,25 @@ int vl3d_render_bwd_culled(const vl3d_render_desc *desc, const void *stack, cons
                            const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
                            float *grad_stack, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
 
+/* Row bands with PER-PLANE source windows (videoloop3d_amd/dist.py plan_plane_bands; csrc/vl3d_render_plane_rows.hip).  The stack is a
+ * rank's local (D, T, R, Ws, 4) rows: local row r of plane d is plane row plane_row0[d] + r (plane_row0: device int32[D]).  desc is the
+ * descriptor of the same band rendered from the full stack: desc->Hs is the TRUE plane height, (row0, col0) the band's window, and the
+ * texel coordinate is computed exactly as the full-frame kernels compute it -- the plane's integer origin is subtracted from the base tap's
+ * row index only, so the bilinear weights are the full-frame bits and the hard cut is at the true plane border.  Rows a band pixel's taps
+ * cannot reach (past a plane's own window) are padding: the backward leaves them 0.  The caller's windows must hold every row the band's
+ * taps reach (the planner's corner argument + margin); the kernels clamp the local tap row into [0, R - 2] so that a wrong table cannot
+ * address outside the allocation.  Built for the planar MPV convention (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, VL3D_ACT_POST,
+ * sigmoid / sigmoid), fp32 and fp16 stacks; no regularisers, tile culling or uv noise.  2 <= R <= Hs.
+ * The backward is the dense render's owner-computes frame-pair path (no atomics, deterministic bits): its plan, tile windows and owner
+ * table live in `scratch`, vl3d_render_plane_rows_scratch_bytes(desc, R) bytes, written and read by the call.  Geometry outside that
+ * path's preconditions (or scratch == NULL) takes the atomics sweep on a cleared gradient, as vl3d_render_bwd does. */
+int vl3d_render_fwd_plane_rows(const vl3d_render_desc *desc, const void *stack, const int32_t *plane_row0, int32_t R, const float *homos,
+                               float *rgb, float *alpha, vl3d_stream_t stream);
+int64_t vl3d_render_plane_rows_scratch_bytes(const vl3d_render_desc *desc, int32_t R);
+int vl3d_render_bwd_plane_rows(const vl3d_render_desc *desc, const void *stack, const int32_t *plane_row0, int32_t R, const float *homos,
+                               const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha, void *grad_stack,
+                               void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
+
 /* Static tiles of a tile-culled VIDEO stack (MPV.py:235-288: one static atlas shared by all frames).  In place on the stack
  * gradient (D,T,Hs,Ws,4): texels that only static quads can read get the sum over the T frames in every frame (the T copies
  * then stay one texture under any optimiser), texels no kept quad can read get 0, texels a dynamic quad can read are left

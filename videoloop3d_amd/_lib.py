@@ -93,6 +93,9 @@ SIGNATURES = {
     "vl3d_render_cull_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_fwd_culled": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P], C.c_int),
     "vl3d_render_bwd_culled": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
+    "vl3d_render_fwd_plane_rows": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_plane_rows_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
+    "vl3d_render_bwd_plane_rows": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_reg_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_reg": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_mask": ([C.POINTER(RenderDesc)] + [_P] * 10, C.c_int),

@@ -195,7 +195,8 @@ def exchange_halo_grads(g_local: torch.Tensor, bands: List[Band], rank: int = No
     w.r.t. those rows.  Rows inside a parallax halo are replicated on the neighbouring rank(s), each holding only a partial
     gradient for them; an optimiser step on the partial gradients would let the replicas drift apart.  This adds, IN PLACE, the
     peers' partial gradients of every shared row range: one grouped send/recv of the overlapping strips per step (point to point
-    over xGMI; cfg3 at N = 8: a ~70-row strip x D x T = ~0.45 GB per neighbour), no all-reduce of the 23.6 GB gradient.
+    over xGMI; cfg3 at N = 8: a 17-19-row strip x D x T = 0.56-0.62 GB per neighbour and direction -- exchange_plane_halo_grads moves
+    0.16-0.25 GB on the per-plane windows of plan_plane_bands), no all-reduce of the 23.6 GB gradient.
     Afterwards every replica of a row holds the same complete gradient -- the single-GPU gradient of that row -- bit for bit on
     all its holders (the partial sums are added in rank order on every holder).  g_local: (D,T,src1-src0,Ws,4)."""
     import torch.distributed as dist
@@ -239,6 +240,166 @@ def exchange_halo_grads(g_local: torch.Tensor, bands: List[Band], rank: int = No
                 acc = part.clone() if acc is None else acc + part
             g_local[:, :, r - me.src0:e - me.src0] = acc
         r = e
+    return g_local
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Row bands with PER-PLANE source windows (opt-in; plan_bands / render_band / exchange_halo_grads are unchanged).  source_row_range takes one
+# window over all D planes, but parallax moves every plane's footprint by a different amount: the union is much taller than any one plane's
+# footprint, every rank stores the union for every plane, and neighbours share a thick strip of every plane.  Here rank r holds, for each plane
+# d, only the rows [src0_d, src1_d) its band's pixels can touch ON THAT PLANE, as a local (D, T, R, Ws, C) stack, R = max_d(src1_d - src0_d):
+# local row k of plane d is plane row src0_d + k, rows past src1_d - src0_d are padding (zero).
+
+@dataclass(frozen=True)
+class PlaneBand:
+    rank: int
+    row0: int          # first output row of the band
+    rows: int          # number of output rows
+    src0: tuple        # per plane: first plane-stack row held by this rank
+    src1: tuple        # per plane: one past the last row held
+    R: int             # local rows per plane: max_d(src1_d - src0_d)
+
+
+def plane_source_row_ranges(homos: torch.Tensor, row0: int, rows: int, W: int, Hs: int, spec: RenderSpec, margin: int = 2):
+    """[(lo_d, hi_d)] per plane: source_row_range's corner argument (the band's four corners, the bilinear +1 tap, the margin) applied to one
+    plane at a time.  A plane with w <= 0 at a corner keeps the whole range [0, Hs).  A window holds at least two rows, inside [0, Hs): the
+    kernels clamp the base tap into [0, Hs - 2], so a footprint wholly above or below the plane still addresses two of its rows."""
+    if spec.coord_mode != "affine":
+        raise RuntimeError("per-plane row windows need coord_mode='affine' (use RenderSpec.mpv() or an affine spec)")
+    if Hs < 2:
+        raise RuntimeError("per-plane row windows need planes of at least two rows")
+    hm = homos.detach().double().cpu()
+    c = float(spec.pixel_center)
+    xs = torch.tensor([0.0 + c, W - 1.0 + c], dtype=torch.float64)
+    ys = torch.tensor([row0 + c, row0 + rows - 1.0 + c], dtype=torch.float64)
+    pts = torch.stack([xs[[0, 1, 0, 1]], ys[[0, 0, 1, 1]], torch.ones(4, dtype=torch.float64)], 0)   # 3,4
+    p = hm @ pts                                                                                  # D,3,4
+    out = []
+    for d in range(hm.shape[0]):
+        if (p[d, 2] <= 0).any():
+            out.append((0, Hs))     # degenerate view of this plane: keep all of it
+            continue
+        ty = p[d, 1] / p[d, 2] * spec.scale[1] + spec.offset[1]
+        lo = max(0, int(torch.floor(ty.min()).item()) - margin)
+        hi = min(Hs, int(torch.ceil(ty.max()).item()) + 1 + margin)
+        lo = min(lo, Hs - 2)
+        out.append((lo, max(hi, lo + 2)))
+    return out
+
+
+def plan_plane_bands(homos: torch.Tensor, H: int, W: int, Hs: int, world: int, spec: RenderSpec, margin: int = 2) -> List[PlaneBand]:
+    """One PlaneBand per rank: the bands of plan_bands (split_rows), each with its per-plane source windows.  coord_mode='affine' only."""
+    out = []
+    for rank, (r0, n) in enumerate(split_rows(H, world)):
+        win = plane_source_row_ranges(homos, r0, n, W, Hs, spec, margin)
+        out.append(PlaneBand(rank, r0, n, tuple(a for a, _ in win), tuple(b for _, b in win), max(b - a for a, b in win)))
+    return out
+
+
+def plane_band_local(stack: torch.Tensor, pband: PlaneBand) -> torch.Tensor:
+    """This rank's local stack (D, T, R, Ws, C) cut out of a full stack (D, T, Hs, Ws, C): plane d's rows [src0_d, src1_d), then zero padding."""
+    D, T, _, Ws, C = stack.shape
+    local = stack.new_zeros((D, T, pband.R, Ws, C))
+    for d in range(D):
+        local[d, :, :pband.src1[d] - pband.src0[d]] = stack[d, :, pband.src0[d]:pband.src1[d]]
+    return local
+
+
+def plane_row0_table(pband: PlaneBand, device) -> torch.Tensor:
+    """the kernels' per-plane origin table: int32 [D] = src0 on `device`"""
+    return torch.tensor(pband.src0, dtype=torch.int32).to(device)
+
+
+def render_plane_band(local, homos, pband: PlaneBand, W: int, Hs: int, spec: RenderSpec, plane_row0=None):
+    """Render this rank's band from its per-plane local rows (D, T, R, Ws, 4) -> (rgb [T,rows,W,3], alpha [T,rows,W]); the backward returns the
+    gradient in the same local layout (padding rows 0).  The bits of render_planes on the full stack: the kernels take the texel coordinate
+    of the full plane and subtract the plane's row origin from the base tap's row only (render.render_plane_rows).  `plane_row0`: the
+    origin table (plane_row0_table) when the caller keeps one on the device."""
+    from .render import render_plane_rows
+    if spec.coord_mode != "affine":
+        raise RuntimeError("per-plane row windows need coord_mode='affine' (use RenderSpec.mpv() or an affine spec)")
+    assert local.shape[0] == len(pband.src0) and local.shape[2] == pband.R
+    if plane_row0 is None:
+        plane_row0 = plane_row0_table(pband, local.device)
+    return render_plane_rows(local, homos, plane_row0, pband.rows, W, Hs, spec, window=(pband.row0, 0))
+
+
+def plane_halo_overlaps(pbands: List[PlaneBand], rank: int, T: int = 1, Ws: int = 1, C: int = 4, itemsize: int = 4):
+    """[(peer, [(lo_d, hi_d)] per plane, bytes)]: the plane-stack rows this rank holds in common with each other rank, plane by plane (empty
+    ranges have lo_d == hi_d), and what they weigh in a (D, T, R, Ws, C) stack of `itemsize`-byte elements (T = Ws = 1: a row count)."""
+    me = pbands[rank]
+    out = []
+    for b in pbands:
+        if b.rank == rank:
+            continue
+        ranges = []
+        for d in range(len(me.src0)):
+            lo, hi = max(me.src0[d], b.src0[d]), min(me.src1[d], b.src1[d])
+            ranges.append((lo, max(lo, hi)))
+        nrows = sum(hi - lo for lo, hi in ranges)
+        if nrows:
+            out.append((b.rank, ranges, nrows * T * Ws * C * itemsize))
+    return out
+
+
+def exchange_plane_halo_grads(g_local: torch.Tensor, pbands: List[PlaneBand], rank: int = None, group=None) -> torch.Tensor:
+    """exchange_halo_grads for the per-plane layout: IN PLACE on g_local (D, T, R, Ws, C), every row shared with a peer on some plane becomes
+    the sum of all its holders' partial gradients.  Per peer every plane's shared strip is packed into ONE contiguous buffer: one send and one
+    receive per peer in one grouped launch.  The holders' parts are added in rank order on every holder, so all replicas of a row end with
+    identical bits; padding rows are not touched."""
+    import torch.distributed as dist
+    if rank is None:
+        rank = dist.get_rank(group)
+    me = pbands[rank]
+    D = len(me.src0)
+    assert g_local.shape[0] == D and g_local.shape[2] == me.R
+    ov = plane_halo_overlaps(pbands, rank)
+    if not ov:
+        return g_local
+    send, recv, views = {}, {}, {}
+    for p, ranges, _ in ov:
+        send[p] = torch.cat([g_local[d, :, lo - me.src0[d]:hi - me.src0[d]].reshape(-1) for d, (lo, hi) in enumerate(ranges) if hi > lo])
+        recv[p] = torch.empty_like(send[p])
+    ops = []
+    for p, _, _ in ov:
+        peer = p if group is None else dist.get_global_rank(group, p)
+        ops.append(dist.P2POp(dist.isend, send[p], peer, group))
+        ops.append(dist.P2POp(dist.irecv, recv[p], peer, group))
+    for w in dist.batch_isend_irecv(ops):
+        w.wait()
+    T, Ws, C = g_local.shape[1], g_local.shape[3], g_local.shape[4]
+    for p, ranges, _ in ov:      # the peer's strips as (T, rows, Ws, C) views, plane by plane, keyed by their first row
+        k, views[p] = 0, {}
+        for d, (lo, hi) in enumerate(ranges):
+            if hi > lo:
+                n = T * (hi - lo) * Ws * C
+                views[p][d] = (lo, recv[p][k:k + n].view(T, hi - lo, Ws, C))
+                k += n
+    for d in range(D):
+        lo_me, hi_me = me.src0[d], me.src1[d]
+        holders = {}
+        for p, ranges, _ in ov:
+            lo, hi = ranges[d]
+            for r in range(lo, hi):
+                holders.setdefault(r, []).append(p)
+        # runs of rows with the same holder set: all holders' parts summed in rank order, identically everywhere
+        r = lo_me
+        while r < hi_me:
+            hs = tuple(sorted(holders.get(r, [])))
+            e = r + 1
+            while e < hi_me and tuple(sorted(holders.get(e, []))) == hs:
+                e += 1
+            if hs:
+                acc = None
+                for q in sorted(hs + (rank,)):
+                    if q == rank:
+                        part = g_local[d, :, r - lo_me:e - lo_me]
+                    else:
+                        lo_q, v = views[q][d]
+                        part = v[:, r - lo_q:e - lo_q]
+                    acc = part.clone() if acc is None else acc + part
+                g_local[d, :, r - lo_me:e - lo_me] = acc
+            r = e
     return g_local
 
 

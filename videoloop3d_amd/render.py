@@ -379,6 +379,63 @@ def render_planes_with_regularisers(stack, homos, H, W, spec: RenderSpec = Rende
                                bool(grad_culled_unwritten), fused_adam)
 
 
+class _RenderPlaneRows(torch.autograd.Function):
+    """render_planes of a row band from PER-PLANE local rows (vl3d_render_fwd_plane_rows / _bwd_plane_rows): local row r of plane d is
+    plane row plane_row0[d] + r; the gradient comes back in the same local layout, padding rows 0."""
+
+    @staticmethod
+    def forward(ctx, local, homos, plane_row0, H, W, Hs, spec, row0, col0):
+        L.check_cuda(local, homos, plane_row0)
+        if local.dtype not in (torch.float32, torch.float16) or local.dim() != 5 or local.shape[4] != 4:
+            raise RuntimeError("per-plane local stack must be float32 / float16 (D,T,R,Ws,4)")
+        D, T, R = local.shape[:3]
+        if homos.shape != (D, 3, 3):
+            raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
+        if plane_row0.dtype != torch.int32 or tuple(plane_row0.shape) != (D,) or plane_row0.device != local.device:
+            raise RuntimeError(f"plane_row0 must be an int32 [D] = [{D}] tensor on the stack's device")
+        local = local.contiguous()
+        homos = homos.detach().to(torch.float32).contiguous()
+        plane_row0 = plane_row0.contiguous()
+        desc = _desc(local, H, W, spec, row0, col0)
+        desc.Hs = int(Hs)             # the TRUE plane height: coverage / hard cut (the stack holds R rows per plane)
+        rgb = torch.empty((T, H, W, 3), dtype=torch.float32, device=local.device)
+        alpha = torch.empty((T, H, W), dtype=torch.float32, device=local.device)
+        with torch.cuda.device(local.device):
+            L.check(L.lib().vl3d_render_fwd_plane_rows(desc, L.ptr(local), L.ptr(plane_row0), int(R), L.ptr(homos), L.ptr(rgb), L.ptr(alpha),
+                                                       L.stream_ptr(local.device)), "vl3d_render_fwd_plane_rows")
+        ctx.save_for_backward(local, homos, plane_row0, rgb, alpha)
+        ctx.desc, ctx.R = desc, int(R)
+        return rgb, alpha
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_alpha):
+        local, homos, plane_row0, rgb, alpha = ctx.saved_tensors
+        dev = local.device
+        g_rgb = g_rgb.contiguous() if g_rgb is not None else torch.zeros_like(rgb)
+        g_alpha = g_alpha.contiguous() if g_alpha is not None else None
+        g_local = torch.empty(local.shape, dtype=local.dtype, device=dev)
+        with torch.cuda.device(dev):
+            nscratch = int(L.lib().vl3d_render_plane_rows_scratch_bytes(ctx.desc, ctx.R))
+            # plan, tile windows and owner table of the owner-computes backward: every word read is written by the same call
+            scratch = torch.empty((nscratch + 3) // 4, dtype=torch.float32, device=dev)
+            L.check(L.lib().vl3d_render_bwd_plane_rows(ctx.desc, L.ptr(local), L.ptr(plane_row0), ctx.R, L.ptr(homos), L.ptr(rgb), L.ptr(alpha),
+                                                       L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_local), L.ptr(scratch), nscratch, L.stream_ptr(dev)),
+                    "vl3d_render_bwd_plane_rows")
+        global LAST_BWD_SCRATCH
+        LAST_BWD_SCRATCH = scratch
+        return g_local, None, None, None, None, None, None, None, None
+
+
+def render_plane_rows(local, homos, plane_row0, H, W, Hs, spec: RenderSpec, window=(0, 0)):
+    """The H x W window at frame pixel `window` = (row0, col0) rendered from per-plane local rows: local (D,T,R,Ws,4), plane d's local row r
+    being its plane row plane_row0[d] + r (plane_row0: int32 [D] on the device), Hs the true plane height.  The same bits as
+    render_planes(full_stack, ..., window=window) wherever the windows hold every row the band's taps reach (dist.plan_plane_bands).
+    The planar MPV convention (RenderSpec.mpv(), sigmoid / sigmoid), fp32 or fp16 stacks.  -> (rgb [T,H,W,3], alpha [T,H,W])."""
+    if spec.coord_mode != "affine" or spec.border != "hardcut" or spec.act_order != "post":
+        raise RuntimeError("per-plane row windows render in the planar MPV convention (RenderSpec.mpv())")
+    return _RenderPlaneRows.apply(local, homos, plane_row0, int(H), int(W), int(Hs), spec, int(window[0]), int(window[1]))
+
+
 @torch.no_grad()
 def render_planes_packed(layout, pool, frames, homos, H, W, spec: RenderSpec, quad_keep, culled_alpha, out=None, frames_dev=None):
     """The forward of a PACKED tile-culled model straight from its pool (videoloop3d_amd/packed.py; the reference renders a sparsified model
