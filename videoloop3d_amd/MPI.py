@@ -10,7 +10,8 @@ are the analytic per-plane homography instead of pytorch3d's rasteriser.
     (tiles.classify_quads_atlas, golden G15) into culled / static / dynamic maps instead of re-packing atlases; afterwards render() passes the
     quad map to the culled kernels (a sample in a culled quad is not covered: MPI.py:483-487, 544-548; train_3d.py:282-285 keeps training it).
   * init_from_mpi reads this package's checkpoints and the reference's (a sparsified one texel for texel onto its tile lattice);
-    reference_state_dict / save_* write the reference's layout (videoloop3d_amd/export.py).
+    reference_state_dict / save_* write the reference's layout (videoloop3d_amd/export.py); both, like the camera set-up, plane_homographies
+    and get_lrate / update_step, are shared with MPMeshVid (videoloop3d_amd/plane_model.py).
   * l_smooth / d_smooth / normalize_blendweight_fordepth / variables['mpi' | 'blend_weight' | 'disp_norm' | 'loopmask3d'] (off in every shipped
     configuration) come from the materialised-layer slow path (videoloop3d_amd/layers.py); direct2sh is out of scope.
 Module-level parity: tests/test_gpu_reference_modules.py (the reference's own forward, golden G17), tests/test_gpu_mpv.py (oracle).
@@ -22,9 +23,9 @@ import torch
 import torch.nn as nn
 
 from . import tiles
-from .MPV import ACTIVATES, _PixelTerms, get_new_intrin, sparsity_ratio
-from .render import RenderSpec, mask_channel_supported, render_planes, render_planes_with_mask, render_planes_with_regularisers
-from .utils_mpi import compute_homography, make_depths
+from .MPV import _PixelTerms, sparsity_ratio
+from .plane_model import PlaneModel
+from .render import mask_channel_supported, render_planes, render_planes_with_mask, render_planes_with_regularisers
 
 ALPHA_INIT_VAL = -3.     # MPI.py:33
 
@@ -61,54 +62,31 @@ def crop_aware_pays(stack_shape, view_h, view_w):
     return D_ * Hs_ * Ws_ * 16 >= 768 * 2 ** 20 and view_h * view_w * 3 <= Hs_ * Ws_
 
 
-class MPMesh(nn.Module):
+class MPMesh(PlaneModel):
+    BASE_CONFIG = "mpi_base.txt"
+
     def __init__(self, args, H, W, ref_extrin, ref_intrin, near, far, pixel_center=0.5, texel_scale=(1.0, 1.0), atlas_exact=False):
         """atlas_exact=True: sample the stack exactly like the reference samples its atlas of plane cells (MPI.py:75-81, 490-520: cell pitch
         (Aw-1)/(gw*(mpi_w-1)), per-cell sub-texel origin, neighbour-cell bleed) -- videoloop3d_amd/atlas.py, as MPMeshVid(atlas_exact=True).  A
         parity mode for dense weights that come from / go to the reference (MPV.atlas_to_stack / stack_to_atlas): the image and the loop-mask label
         (a second pass), no fused regularisers, no tile culling; needs args.atlas_grid_h."""
-        super().__init__()
-        self.atlas_exact = bool(atlas_exact)
-        self.args = args
-        mpi_h, mpi_w = int(args.mpi_h_scale * H), int(args.mpi_w_scale * W)
-        self.mpi_h, self.mpi_w = mpi_h, mpi_w
-        self.mpi_d, self.near, self.far = args.mpi_d, near, far
-        self.H, self.W = H, W
-        if getattr(args, "rgb_mlp_type", "direct") != "direct":
-            raise RuntimeError(f"rgbmlp_type = {args.rgb_mlp_type} not supported (shipped configs use 'direct', mpi_base.txt:28)")
-        ref_extrin, ref_intrin = np.asarray(ref_extrin), np.asarray(ref_intrin)
-        assert ref_extrin.shape == (4, 4) and ref_intrin.shape == (3, 3)
-        self.register_buffer("ref_extrin", torch.tensor(ref_extrin))
-        self.register_buffer("ref_intrin", torch.tensor(ref_intrin).float())
-        self.register_buffer("planedepth", make_depths(self.mpi_d, near, far).float().flip(0))     # MPI.py:57
-        self.H_start, self.W_start = (mpi_h - H) // 2, (mpi_w - W) // 2
-        self.register_buffer("ref_intrin_mpi", get_new_intrin(self.ref_intrin, -self.H_start, -self.W_start))
-        stack = torch.rand((self.mpi_d, 1, mpi_h, mpi_w, 4))                                       # MPI.py:102-103
+        super().__init__(args, H, W, ref_extrin, ref_intrin, near, far, pixel_center, texel_scale, atlas_exact)
+        stack = torch.rand((self.mpi_d, 1, self.mpi_h, self.mpi_w, 4))                             # MPI.py:102-103
         stack[..., -1] = ALPHA_INIT_VAL
         self.stack = nn.Parameter(stack, requires_grad=True)
         self.learn_loop_mask = bool(getattr(args, "learn_loop_mask", False))
         if self.learn_loop_mask:
-            self.stack_mask = nn.Parameter(torch.ones((self.mpi_d, 1, mpi_h, mpi_w)) * ALPHA_INIT_VAL, requires_grad=True)
-        if args.rgb_activate not in ACTIVATES or args.alpha_activate not in ACTIVATES:
-            raise RuntimeError(f"activation ({args.rgb_activate}, {args.alpha_activate}) not implemented by the HIP kernels")
-        self.texel_scale = tuple(float(v) for v in texel_scale)
-        self.spec = dataclasses.replace(RenderSpec.mpv(rgb_act=args.rgb_activate, alpha_act=args.alpha_activate,
-                                                       scale=self.texel_scale), pixel_center=float(pixel_center))
+            self.stack_mask = nn.Parameter(torch.ones((self.mpi_d, 1, self.mpi_h, self.mpi_w)) * ALPHA_INIT_VAL, requires_grad=True)
         # the loop-mask pass: label = sigmoid(mask), alpha = the (detached) layer alpha with the model's activation
         self.spec_mask = dataclasses.replace(self.spec, rgb_act="sigmoid")
-        self.alpha_activate = ACTIVATES[args.alpha_activate]
         # quads of the vertex grid (utils_mpi.py:80-89); classified by sparsify_faces
         self.quad_h, self.quad_w = max(int(getattr(args, "mpi_h_verts", 12)) - 1, 1), max(int(getattr(args, "mpi_w_verts", 15)) - 1, 1)
-        self.is_sparse = False
-        self.tile_own = None             # (th, tw): tile-exact layout of a sparsified REFERENCE checkpoint (init_from_mpi)
-        self.has_dyn = False
-        self._window_opt = None          # the crop-aware optimiser handed out by get_optimizer (optim.Stage1Adam): training renders go through its window
 
-    def _flush_deferred_updates(self):
-        """bring the whole stack up to date with the optimiser handed out last (optim.WindowAdam defers the zero-gradient updates of texels
-        outside the training crops' windows): before anything reads the stack as a whole."""
-        if self._window_opt is not None:
-            self._window_opt.flush()
+    def _tile_grid(self, hs, ws):
+        th, tw = self.tile_own
+        if (self.quad_h * th, self.quad_w * tw) != (hs, ws):
+            raise RuntimeError(f"tile-exact checkpoint: planes of {(hs, ws)} texels are not {self.quad_h} x {self.quad_w} tiles of {self.tile_own}")
+        return self.quad_h, self.quad_w, th, tw
 
     def _apply(self, fn, *a, **k):
         self._flush_deferred_updates()
@@ -212,17 +190,6 @@ class MPMesh(nn.Module):
             return torch.optim.SGD(params=params, lr=a.lrate, momentum=0.9)
         raise RuntimeError(f"Unrecongnized optimizer type {a.optimizer}")
 
-    def get_lrate(self, step):
-        """MPI.py:143-152."""
-        a = self.args
-        scaling = 0.1 ** (step / (a.lrate_decay * 1000))
-        return [("lr", a.lrate * scaling), ("vertlr", a.lrate * getattr(a, "optimize_verts_gain", 1) * scaling)]
-
-    def update_step(self, step):
-        """MPI.py:154-156; geometry optimisation itself is not on the planar path."""
-        if step >= getattr(self.args, "optimize_geo_start", 10000000):
-            self.optimize_geometry = True
-
     def init_from_mpi(self, state_dict, tile_layout=None):
         """MPI.py:174-205 (resume / warm start, train_3d.py:176-186): a state_dict of this class, or of the REFERENCE's MPMesh (plane
         meshes + packed atlas: resampled onto the dense stack, quad maps recovered from its face lists; the loop-mask texture of a
@@ -232,24 +199,12 @@ class MPMesh(nn.Module):
         copies of a border sample apart (golden G19 j); "lattice" = neighbouring quads share them."""
         self._window_opt = None          # (the parameters are replaced: the driver asks for a new optimiser)
         if "stack" not in state_dict and "atlas" in state_dict:
-            hv, wv = int(self.args.mpi_h_verts), int(self.args.mpi_w_verts)
-            layout = tile_layout if tile_layout is not None else getattr(self.args, "tile_layout", "exact")
-            if layout not in ("exact", "lattice"):
-                raise RuntimeError(f"tile_layout must be 'exact' or 'lattice', got {layout!r}")
-            sparse = bool(state_dict.get("self.is_sparse", False))
-            tile_ref = tiles.reference_tile_size(state_dict, hv, wv) if sparse else None
-            own = layout == "exact" and tile_ref is not None and not self.atlas_exact
-            st, keep, dyn = tiles.stack_from_reference_state(state_dict, self.mpi_h, self.mpi_w, hv, wv, 1, own_borders=own)
-            state_dict = {"ref_extrin": state_dict["ref_extrin"], "ref_intrin": state_dict["ref_intrin"], "planedepth": state_dict["planedepth"],
-                          "stack": st[:, :1], "quad_keep": keep, "quad_dyn": dyn, "self.is_sparse": sparse, "self.has_dyn": sparse,
-                          "self.tile_own": tile_ref if own else None}
+            state_dict = self._from_reference_state(state_dict, tile_layout, 1)
+            state_dict["stack"] = state_dict["stack"][:, :1]
         to = state_dict.get("self.tile_own", None)
         self.tile_own = None if to is None else (int(to[0]), int(to[1]))
         dev = self.stack.device
-        self.ref_extrin.data = state_dict['ref_extrin'].type_as(self.ref_extrin)
-        self.ref_intrin.data = state_dict['ref_intrin'].type_as(self.ref_intrin)
-        self.planedepth.data = state_dict['planedepth'].type_as(self.planedepth)
-        self.ref_intrin_mpi.data = get_new_intrin(self.ref_intrin, -self.H_start, -self.W_start)
+        self._load_camera(state_dict)
         st = state_dict["stack"]
         if st.dim() != 5 or st.shape[0] != self.mpi_d or st.shape[1] != 1 or st.shape[-1] != 4:
             raise RuntimeError(f"checkpoint stack {tuple(st.shape)} does not match this model's {tuple(self.stack.shape)}")
@@ -264,77 +219,15 @@ class MPMesh(nn.Module):
                 self.stack.copy_(st.to(dev))
             if "stack_mask" in state_dict and hasattr(self, "stack_mask"):
                 self.stack_mask.copy_(state_dict["stack_mask"].to(dev))
-        hs, ws = self.stack.shape[2:4]
-        if self.tile_own is not None:      # tile-exact layout: the scale gives the LATTICE coordinate, the spec carries the tile (render.RenderSpec.tile)
-            th, tw = self.tile_own
-            if (self.quad_h * th, self.quad_w * tw) != (hs, ws):
-                raise RuntimeError(f"tile-exact checkpoint: planes of {(hs, ws)} texels are not {self.quad_h} x {self.quad_w} tiles of {self.tile_own}")
-            self.spec = dataclasses.replace(self.spec, tile=(th, tw), scale=(self.texel_scale[0] * self.quad_w * (tw - 1) / max(self.mpi_w - 1, 1),
-                                                                             self.texel_scale[1] * self.quad_h * (th - 1) / max(self.mpi_h - 1, 1)))
-        else:
-            self.spec = dataclasses.replace(self.spec, tile=(0, 0), scale=(self.texel_scale[0] * (ws - 1) / max(self.mpi_w - 1, 1),
-                                                                           self.texel_scale[1] * (hs - 1) / max(self.mpi_h - 1, 1)))
+        self._set_texture_geometry(*self.stack.shape[2:4])
         self.spec_mask = dataclasses.replace(self.spec, rgb_act="sigmoid")
         self.is_sparse = bool(state_dict.get("self.is_sparse", False))
         self.has_dyn = bool(state_dict.get("self.has_dyn", False))
         if self.is_sparse:
-            self.register_buffer("quad_keep", state_dict["quad_keep"].to(dev).bool())
-            self.register_buffer("quad_dyn", state_dict["quad_dyn"].to(dev).bool())
+            self._set_quad_maps(state_dict["quad_keep"], state_dict["quad_dyn"], dev)
             self.args.learn_loop_mask = self.learn_loop_mask = False
             if hasattr(self, "stack_mask"):
                 del self.stack_mask
-
-    def reference_state_dict(self):
-        """the state_dict of the REFERENCE's MPMesh for these weights (MPI.py:207-221): plane mesh + packed atlas tiles."""
-        from .export import reference_state_dict
-        self._flush_deferred_updates()
-        return reference_state_dict(self)
-
-    def save_mesh(self, prefix):
-        """MPI.py:223-240."""
-        from .export import save_mesh
-        return save_mesh(self, prefix, self.reference_state_dict())
-
-    def save_texture(self, prefix):
-        """MPI.py:242-261."""
-        from .export import save_texture
-        return save_texture(self, prefix, self.reference_state_dict())
-
-    def _host_np(self, name):
-        """numpy mirror of a (small, constant) camera buffer, refreshed when the buffer changes."""
-        buf = getattr(self, name)
-        cache = self.__dict__.setdefault("_host_np_mirrors", {})
-        key = (buf.data_ptr(), buf._version, str(buf.device))
-        if cache.get(name, (None,))[0] != key:
-            cache[name] = (key, buf.detach().cpu().numpy().copy())
-        return cache[name][1]
-
-    def _on(self, dev, name):
-        """the (small, constant) camera buffers on the device of the pose tensors: poses that arrive on the HOST (as the DataLoader
-        produces them, train_3d.py:190-191) are turned into homographies there -- the 4 x 4 inverse and the chain of small matrix
-        products were ~40 kernel launches per view on the device."""
-        buf = getattr(self, name)
-        if buf.device == dev:
-            return buf
-        cache = self.__dict__.setdefault("_host_mirrors", {})
-        key = (str(dev), buf.data_ptr(), buf._version)
-        if cache.get(name, (None,))[0] != key:
-            cache[name] = (key, buf.detach().to(dev))
-        return cache[name][1]
-
-    def plane_homographies(self, extrin, intrin):
-        dev = extrin.device
-        if dev.type == "cpu" and extrin.dtype == torch.float64 and not extrin.requires_grad and not getattr(self.args, "torch_homographies", False):
-            # float64 host poses: the closed form in numpy (utils_mpi.plane_homographies_host) -- the same bits as the torch spelling below at a
-            # third of the host time.  (float32 poses, as the reference's drivers hold them, keep the torch operators: their rounding is the
-            # reference's own, which the goldens pin.)
-            from .utils_mpi import plane_homographies_host
-            return plane_homographies_host(self._host_np("ref_intrin_mpi"), self._host_np("planedepth"), extrin[0].numpy(),
-                                           torch.as_tensor(intrin)[0].detach().cpu().numpy())
-        eye = torch.eye(4, dtype=extrin.dtype, device=dev)[None]
-        normal = torch.tensor([0., 0., 1.], dtype=extrin.dtype, device=dev).expand(1, self.mpi_d, 3)
-        return compute_homography(eye, self._on(dev, "ref_intrin_mpi")[None].to(extrin.dtype), extrin, intrin.to(dev), normal,
-                                  self._on(dev, "planedepth")[None].to(extrin.dtype))[0].float()
 
     def _layer_variables(self, homos, H, W, extrin, qk):
         """the materialised tensors of one view (slow path, videoloop3d_amd/layers.py): `mpi` [1,H,W,K,4] and `loopmask3d` [1,H,W,K,1] in hit-slot
@@ -443,13 +336,7 @@ class MPMesh(nn.Module):
             else:
                 rgb, alpha = render_planes(stack, homos, H, W, spec, quad_keep=qk, cull_window=cull_window if qk is not None else None,
                                            grad_culled_unwritten=lean and qk is not None, fused_adam=fused_adam)
-            if len(self.args.bg_color) > 0:                                                       # MPI.py:550-556
-                if self.args.bg_color == "random":
-                    bg = torch.rand(3).type_as(rgb)
-                else:
-                    r, g, b_ = map(float, self.args.bg_color.split('#'))
-                    bg = torch.tensor([r, g, b_]).type_as(rgb)
-                rgb = rgb * alpha[..., None] + bg[None, None, None] * (- alpha[..., None] + 1)
+            rgb = self._composite_bg(rgb, alpha)                                                  # MPI.py:550-556
             rgbs.append(rgb)
             alphas.append(alpha)
             if need_layers:

@@ -14,6 +14,9 @@ geometry -- which is all the shipped configs ever produce (vertices get no gradi
     resampled onto the dense stack, tiles.stack_from_reference_state); static quads stay one shared texture because their
     gradient is summed over the frames.  reference_state_dict / save_mesh / save_texture export back to the reference's layout
     (videoloop3d_amd/export.py).
+What the module shares with the stage-1 MPMesh -- the plane / camera set-up, plane_homographies, the render spec of a texture size, get_lrate /
+update_step, the checkpoint helpers and the export -- is videoloop3d_amd/plane_model.py; the texture's storage, lod, the optimiser, render and
+forward are here.
 """
 import dataclasses
 
@@ -21,21 +24,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .render import RenderSpec, render_planes, render_planes_with_regularisers
-from .utils_mpi import compute_homography, make_depths, overcompose
+from .plane_model import ACTIVATES, PlaneModel, get_new_intrin  # noqa: F401  (ACTIVATES / get_new_intrin: imported from here by drivers and tests)
+from .render import render_planes, render_planes_with_regularisers
+from .utils_mpi import overcompose
 from .utils_vid import Patch3DAvg, Patch3DGPNNDirectLoss, Patch3DGPNNLowMemLoss, Patch3DMSE
-
-# activations the HIP kernels implement (subset of MPI.py:21-31; shipped configs use sigmoid/sigmoid)
-ACTIVATES = {'relu': torch.relu, 'sigmoid': torch.sigmoid, 'none': lambda x: x,
-             'clamp': lambda x: torch.clamp(x, 0, 1), 'abs': torch.abs}
-
-
-def get_new_intrin(old_intrin, new_h_start, new_w_start):
-    """utils.py:196-200."""
-    new_intrin = old_intrin.clone() if isinstance(old_intrin, torch.Tensor) else old_intrin.copy()
-    new_intrin[..., 0, 2] -= new_w_start
-    new_intrin[..., 1, 2] -= new_h_start
-    return new_intrin
 
 
 def sparsity_ratio(alpha_sums, eps):
@@ -227,7 +219,9 @@ def stack_to_atlas(stack, grid_h):
     return cells.reshape(T, C, grid_h * mh, grid_w * mw).contiguous()
 
 
-class MPMeshVid(nn.Module):
+class MPMeshVid(PlaneModel):
+    BASE_CONFIG = "mpv_base.txt"
+
     def __init__(self, args, H, W, ref_extrin, ref_intrin, near, far, pixel_center=0.5, texel_scale=(1.0, 1.0), atlas_exact=False, device=None):
         """device: where the plane stack is CREATED (an addition to the reference's signature: its `torch.randn` on the host followed by `.to(device)`
         is 7 GB and ~7 s for the shipped stage-2 shape -- D = 32, T = 50, 396 x 704 planes -- before init_from_mpi overwrites it; the small camera
@@ -235,53 +229,26 @@ class MPMeshVid(nn.Module):
         atlas_exact=True: sample the stack exactly like the reference samples its atlas of plane cells (MPV.py:75-81, 394-439:
         pitch (Aw-1)/(gw*(mpi_w-1)), per-cell sub-texel origin, neighbour-cell bleed at cell edges) -- videoloop3d_amd/atlas.py.
         A parity mode for weights that come from / go to the reference (atlas_to_stack / stack_to_atlas); needs args.atlas_grid_h."""
-        super().__init__()
-        self.atlas_exact = bool(atlas_exact)
-        self.per_plane_boxes = True      # crop-aware optimiser: each plane's own texel box inside the crop's window (optim.WindowAdam); False = the union window for every plane
-        self.atlas_grid_h = int(getattr(args, "atlas_grid_h", 1))
-        if self.atlas_exact and args.mpi_d % self.atlas_grid_h != 0:
+        atlas_grid_h = int(getattr(args, "atlas_grid_h", 1))
+        if atlas_exact and args.mpi_d % atlas_grid_h != 0:
             raise RuntimeError("mpi_d and atlas_grid_h should match")                                    # MPV.py:38
-        self.args = args
-        self.frm_num = args.mpv_frm_num
-        self.isloop = args.mpv_isloop
-        mpi_h, mpi_w = int(args.mpi_h_scale * H), int(args.mpi_w_scale * W)
-        self.mpi_h, self.mpi_w = mpi_h, mpi_w
-        self.mpi_d, self.near, self.far = args.mpi_d, near, far
-        self.H, self.W = H, W
         if getattr(args, "fp16", False):
             raise RuntimeError("fp16 is marked 'do NOT use' in the reference (config_parser.py:32-33); fp32 only")
-        if getattr(args, "rgb_mlp_type", "direct") != "direct":
-            raise RuntimeError(f"rgbmlp_type = {args.rgb_mlp_type} not supported (shipped configs use 'direct', mpv_base.txt:28)")
-        ref_extrin, ref_intrin = np.asarray(ref_extrin), np.asarray(ref_intrin)
-        assert ref_extrin.shape == (4, 4) and ref_intrin.shape == (3, 3)
-        self.register_buffer("ref_extrin", torch.tensor(ref_extrin))
-        self.register_buffer("ref_intrin", torch.tensor(ref_intrin).float())
-        self.register_buffer("planedepth", make_depths(self.mpi_d, near, far).float().flip(0))   # plane 0 = nearest (MPV.py:51)
-        # intrinsics that map the whole (larger) MPI plane to plane pixels (MPV.py:55-56)
-        self.H_start, self.W_start = (mpi_h - H) // 2, (mpi_w - W) // 2
-        self.register_buffer("ref_intrin_mpi", get_new_intrin(self.ref_intrin, -self.H_start, -self.W_start))
+        super().__init__(args, H, W, ref_extrin, ref_intrin, near, far, pixel_center, texel_scale, atlas_exact)
+        self.per_plane_boxes = True      # crop-aware optimiser: each plane's own texel box inside the crop's window (optim.WindowAdam); False = the union window for every plane
+        self.atlas_grid_h = atlas_grid_h
+        self.frm_num = args.mpv_frm_num
+        self.isloop = args.mpv_isloop
 
-        stack = torch.randn((self.mpi_d, self.frm_num, mpi_h, mpi_w, 4), device=device) * args.init_std          # MPV.py:84-85
+        stack = torch.randn((self.mpi_d, self.frm_num, self.mpi_h, self.mpi_w, 4), device=device) * args.init_std          # MPV.py:84-85
         stack[..., -1] = -2                                                                       # MPV.py:109-110
         self.stack = nn.Parameter(stack, requires_grad=True)
 
-        if args.rgb_activate not in ACTIVATES or args.alpha_activate not in ACTIVATES:
-            raise RuntimeError(f"activation ({args.rgb_activate}, {args.alpha_activate}) not implemented by the HIP kernels")
-        self.rgb_activate, self.alpha_activate = ACTIVATES[args.rgb_activate], ACTIVATES[args.alpha_activate]
-        self.texel_scale = tuple(float(v) for v in texel_scale)
-        self.spec = dataclasses.replace(RenderSpec.mpv(rgb_act=args.rgb_activate, alpha_act=args.alpha_activate,
-                                                       scale=self.texel_scale), pixel_center=float(pixel_center))
-        self.optimize_geometry = False
-        self.is_sparse, self.has_dyn = False, False
-        self.register_buffer("quad_keep", None)      # [D,QH,QW] bool maps of a sparsified stage-1 MPI (init_from_mpi)
-        self.register_buffer("quad_dyn", None)
+        self._set_quad_maps(None, None)  # [D,QH,QW] bool maps of a sparsified stage-1 MPI (init_from_mpi)
         self._tie_hook = None
         self._static_compact = False
-        self._window_opt = None          # the crop-aware Adam handed out by get_optimizer (dense CUDA models)
         self.packed = None               # packed.PackedLayout once pack_() has replaced the dense stack by the pool `stack_pool`
         self.tile_full = None            # (th, tw): texels per quad of a model loaded from a sparsified REFERENCE checkpoint (tile lattice)
-        self.tile_own = None             # (th, tw) at the current pyramid level when every quad owns its border texels (TILE-EXACT layout, the
-                                         # default for sparsified reference checkpoints: init_from_mpi); None: neighbouring quads share them
 
         self.swd_patch_size, self.swd_patcht_size = args.swd_patch_size, args.swd_patcht_size
         self.swd_stride, self.swd_stridet = args.swd_stride, args.swd_stridet
@@ -319,22 +286,25 @@ class MPMeshVid(nn.Module):
             return self.packed.unpack_plane(self.stack_pool.data, d, frames)
         return self.stack.data[d] if frames is None else self.stack.data[d, torch.as_tensor(frames, device=self.stack.device).long()]
 
-    def _set_texture_geometry(self, hs, ws):
-        """the render spec of a texture of hs x ws texels per plane: the planes keep their extent (MPV.py:75-81: normalised UVs), so the
-        plane-pixel -> texel scale follows the texture size; in the tile-exact layout the scale gives the LATTICE coordinate (a quad spans
-        tile - 1 of them) and the spec carries the tile size (render.RenderSpec.tile)."""
-        if self.tile_own is not None:
-            qh, qw = int(self.args.mpi_h_verts) - 1, int(self.args.mpi_w_verts) - 1
-            th, tw = hs // qh, ws // qw
-            if (qh * th, qw * tw) != (hs, ws) or min(th, tw) < 2:
-                raise RuntimeError(f"tile-exact layout: planes of {(hs, ws)} texels are not {qh} x {qw} whole tiles")
-            self.tile_own = (th, tw)
-            self.spec = dataclasses.replace(self.spec, tile=(th, tw),
-                                            scale=(self.texel_scale[0] * (qw * (tw - 1)) / max(self.mpi_w - 1, 1),
-                                                   self.texel_scale[1] * (qh * (th - 1)) / max(self.mpi_h - 1, 1)))
-            return
-        self.spec = dataclasses.replace(self.spec, tile=(0, 0), scale=(self.texel_scale[0] * (ws - 1) / max(self.mpi_w - 1, 1),
-                                                                       self.texel_scale[1] * (hs - 1) / max(self.mpi_h - 1, 1)))
+    def _tile_grid(self, hs, ws):
+        qh, qw = int(self.args.mpi_h_verts) - 1, int(self.args.mpi_w_verts) - 1
+        th, tw = hs // qh, ws // qw
+        if (qh * th, qw * tw) != (hs, ws) or min(th, tw) < 2:
+            raise RuntimeError(f"tile-exact layout: planes of {(hs, ws)} texels are not {qh} x {qw} whole tiles")
+        return qh, qw, th, tw
+
+    def _install_pool(self, pool, lay):
+        """the packed pool `stack_pool` + its block table become the texture (whatever it was stored as before)."""
+        for name in ("stack", "stack_pool"):
+            self._parameters.pop(name, None)
+        self.register_parameter("stack_pool", nn.Parameter(pool, requires_grad=True))
+        self.packed, self.frm_num = lay, lay.T
+
+    def _install_stack(self, new):
+        """the dense (D,T,Hs,Ws,4) tensor `new` becomes the texture (whatever it was stored as before)."""
+        self._parameters.pop("stack_pool", None)
+        self.packed = None
+        self.register_parameter("stack", nn.Parameter(new, requires_grad=True))
 
     @torch.no_grad()
     def pack_(self, stack=None):
@@ -360,13 +330,7 @@ class MPMeshVid(nn.Module):
         if self._tie_hook is not None:
             self._tie_hook.remove()
             self._tie_hook = None
-        if "stack" in self._parameters:
-            del self._parameters["stack"]
-        if "stack_pool" in self._parameters:
-            del self._parameters["stack_pool"]
-        self.register_parameter("stack_pool", nn.Parameter(pool, requires_grad=True))
-        self.packed = lay
-        self.frm_num = lay.T
+        self._install_pool(pool, lay)
         return self
 
     # ---- stage-1 -> stage-2 hand-over (MPV.py:235-304) ------------------------------------------------------------------
@@ -382,34 +346,19 @@ class MPMeshVid(nn.Module):
         texture shared by all frames (their gradient is summed over the frames, as the reference's static atlas sees it),
         dynamic quads are free per frame; without them everything is dynamic ("load static as dynamic", MPV.py:266-288)."""
         if "stack" not in state_dict and ("atlas" in state_dict or "atlas_dyn" in state_dict):
-            # a checkpoint of the REFERENCE (plane meshes + packed texture atlases, MPI.py:207-221 / MPV.py:290-304): resample its
-            # tiles onto the dense stack and recover the culled / static / dynamic quad maps from its face lists
-            from . import tiles
-            hv, wv = int(self.args.mpi_h_verts), int(self.args.mpi_w_verts)
-            layout = tile_layout if tile_layout is not None else getattr(self.args, "tile_layout", "exact")
-            if layout not in ("exact", "lattice"):
-                raise RuntimeError(f"tile_layout must be 'exact' or 'lattice', got {layout!r}")
-            sparse = bool(state_dict.get("self.is_sparse", False))
-            tile_ref = tiles.reference_tile_size(state_dict, hv, wv) if sparse else None      # (th, tw) of a checkpoint `sparsify_faces` wrote
-            own = layout == "exact" and tile_ref is not None and not self.atlas_exact
-            st, keep, dyn = tiles.stack_from_reference_state(state_dict, self.mpi_h, self.mpi_w, hv, wv, self.frm_num, own_borders=own)
-            # a sparsified checkpoint arrives tile for tile (identical weights); the tile size drives lod() like the reference's (MPV.py:146-151)
-            tile_own = tile_ref if own else None
-            if own and "self.atlas_full_h" in state_dict and int(state_dict.get("self.atlas_grid_h", 0)) > 0 and int(state_dict.get("self.atlas_grid_w", 0)) > 0:
+            # a checkpoint of the REFERENCE: a sparsified one arrives tile for tile (identical weights) or on the tile lattice; the tile size
+            # at FULL resolution drives lod() like the reference's (MPV.py:146-151)
+            ref = state_dict
+            state_dict = self._from_reference_state(ref, tile_layout, self.frm_num)
+            hv, wv, st = int(self.args.mpi_h_verts), int(self.args.mpi_w_verts), state_dict["stack"]
+            tile = state_dict["self.tile_own"]
+            if tile is None and tuple(st.shape[2:4]) != (self.mpi_h, self.mpi_w):
+                tile = ((st.shape[2] - 1) // (hv - 1) + 1, (st.shape[3] - 1) // (wv - 1) + 1)
+            elif tile is not None and "self.atlas_full_h" in ref and int(ref.get("self.atlas_grid_h", 0)) > 0 and int(ref.get("self.atlas_grid_w", 0)) > 0:
                 # (a checkpoint saved at a pyramid level: the FULL tile size is what lod() scales, MPV.py:149-151)
-                tile_ref_full = (int(state_dict["self.atlas_full_h"]) // int(state_dict["self.atlas_grid_h"]),
-                                 int(state_dict["self.atlas_full_w"]) // int(state_dict["self.atlas_grid_w"]))
-            else:
-                tile_ref_full = tile_ref
-            tile = tile_ref_full if own else (((st.shape[2] - 1) // (hv - 1) + 1, (st.shape[3] - 1) // (wv - 1) + 1)
-                                         if tuple(st.shape[2:4]) != (self.mpi_h, self.mpi_w) else None)
-            state_dict = {"ref_extrin": state_dict["ref_extrin"], "ref_intrin": state_dict["ref_intrin"],
-                          "planedepth": state_dict["planedepth"], "stack": st, "quad_keep": keep, "quad_dyn": dyn,
-                          "self.is_sparse": sparse, "self.has_dyn": sparse, "self.tile_full": tile, "self.tile_own": tile_own}
-        self.ref_extrin.data = state_dict['ref_extrin'].type_as(self.ref_extrin)
-        self.ref_intrin.data = state_dict['ref_intrin'].type_as(self.ref_intrin)
-        self.planedepth.data = state_dict['planedepth'].type_as(self.planedepth)
-        self.ref_intrin_mpi.data = get_new_intrin(self.ref_intrin, -self.H_start, -self.W_start)
+                tile = (int(ref["self.atlas_full_h"]) // int(ref["self.atlas_grid_h"]), int(ref["self.atlas_full_w"]) // int(ref["self.atlas_grid_w"]))
+            state_dict["self.tile_full"] = tile
+        self._load_camera(state_dict)
         dev = self._param().device
         tf = state_dict.get("self.tile_full", None)
         self.tile_full = None if tf is None else (int(tf[0]), int(tf[1]))
@@ -418,16 +367,13 @@ class MPMeshVid(nn.Module):
         if "stack_pool" in state_dict:       # a checkpoint of a packed model of this package: quad maps + dims rebuild the block table
             from .packed import PackedLayout
             D, T, hs, ws = (int(v) for v in state_dict["self.packed_dims"])
-            self.register_buffer("quad_keep", state_dict["quad_keep"].to(dev).bool())
-            self.register_buffer("quad_dyn", state_dict["quad_dyn"].to(dev).bool())
+            self._set_quad_maps(state_dict["quad_keep"], state_dict["quad_dyn"], dev)
             lay = PackedLayout(self.quad_keep, self.quad_dyn, T, hs, ws, self.tile_own)
             pool = state_dict["stack_pool"].to(dev, torch.float32).reshape(-1, 4).contiguous()
             if pool.shape[0] != lay.n_slots * 64:
                 raise RuntimeError("packed checkpoint: the pool does not match the block table of its quad maps")
-            for name in ("stack", "stack_pool"):
-                self._parameters.pop(name, None)
-            self.register_parameter("stack_pool", nn.Parameter(pool, requires_grad=True))
-            self.packed, self.frm_num, self.is_sparse, self.has_dyn = lay, T, True, True
+            self._install_pool(pool, lay)
+            self.is_sparse, self.has_dyn = True, True
             self._window_opt = None
             self._set_texture_geometry(hs, ws)
             return
@@ -441,29 +387,19 @@ class MPMeshVid(nn.Module):
             if not bool(state_dict.get("self.is_sparse", False)):
                 raise RuntimeError("init_from_mpi(packed=True) needs a sparsified checkpoint (quad maps)")
             self.is_sparse, self.has_dyn = True, bool(state_dict.get("self.has_dyn", False))
-            self.register_buffer("quad_keep", state_dict["quad_keep"].to(dev).bool())
-            self.register_buffer("quad_dyn", state_dict["quad_dyn"].to(dev).bool())
+            self._set_quad_maps(state_dict["quad_keep"], state_dict["quad_dyn"], dev)
             hs, ws = mpi.shape[2:4]
             self._set_texture_geometry(hs, ws)
             self.pack_(stack=mpi.float().expand(-1, self.frm_num, -1, -1, -1))      # (a view: a static MPI is not copied T times)
             return
-        if self.packed is not None:
-            self._parameters.pop("stack_pool", None)
-            self.packed = None
         with torch.no_grad():
-            new = mpi.to(dev, torch.float32).expand(-1, self.frm_num, -1, -1, -1).contiguous()
-        self.register_parameter("stack", nn.Parameter(new, requires_grad=True))
+            self._install_stack(mpi.to(dev, torch.float32).expand(-1, self.frm_num, -1, -1, -1).contiguous())
         # planes saved at a pyramid level (lod) keep their extent: the plane-pixel -> texel scale follows the texture size
-        hs, ws = new.shape[2:4]
-        self._set_texture_geometry(hs, ws)
+        self._set_texture_geometry(*self.stack.shape[2:4])
         self.is_sparse = bool(state_dict.get("self.is_sparse", False))
         self.has_dyn = bool(state_dict.get("self.has_dyn", False))
-        if self.is_sparse:
-            self.register_buffer("quad_keep", state_dict["quad_keep"].to(self.stack.device).bool())
-            self.register_buffer("quad_dyn", state_dict["quad_dyn"].to(self.stack.device).bool())
-        else:
-            self.register_buffer("quad_keep", None)
-            self.register_buffer("quad_dyn", None)
+        maps = (state_dict["quad_keep"], state_dict["quad_dyn"]) if self.is_sparse else (None, None)
+        self._set_quad_maps(*maps, self.stack.device)
         self._install_tie_hook()
 
     def _install_tie_hook(self):
@@ -514,6 +450,7 @@ class MPMeshVid(nn.Module):
         # the later ones up-sample, where the two filters coincide.  Default: the pinned release's; `args.lod_antialias = True` for the newer one.
         aa = bool(getattr(self.args, "lod_antialias", False))
         h, w = max(int(self.mpi_h * factor), 2), max(int(self.mpi_w * factor), 2)
+        tile = None
         if self.tile_full is not None:
             # a model on the reference's tile lattice: every quad holds max(int(tile * factor), 2) texels per axis at this level, as the
             # reference resizes its tiles (MPV.py:146-151); neighbouring quads share their border texels
@@ -525,95 +462,63 @@ class MPMeshVid(nn.Module):
             # tile-exact layout: the reference's own operation (MPV.py:146-163) -- every tile resized ON ITS OWN to max(int(tile_full * factor), 2)
             # texels per axis (nothing bleeds between tiles, static and dynamic tiles alike; culled tiles hold nothing that is ever read)
             qh, qw = int(self.args.mpi_h_verts) - 1, int(self.args.mpi_w_verts) - 1
-            nth, ntw = max(int(self.tile_full[0] * factor), 2), max(int(self.tile_full[1] * factor), 2)
-            h, w = qh * nth, qw * ntw
-            print(f"MPV.lod:: Sparse! Resizing the tiles from {self.tile_own} to {(nth, ntw)}")
-            if (hs, ws) != (h, w):
-                oth, otw = self.tile_own
-
-                def resize_plane(planes):          # (T,hs,ws,4) -> (T,h,w,4), tile by tile
-                    t_ = planes.shape[0]
-                    tl = planes.reshape(t_, qh, oth, qw, otw, 4).permute(0, 1, 3, 5, 2, 4).reshape(t_ * qh * qw, 4, oth, otw)
-                    tl = _resize_tiles(tl, nth, ntw, aa)
-                    return tl.reshape(t_, qh, qw, 4, nth, ntw).permute(0, 1, 4, 2, 5, 3).reshape(t_, h, w, 4)
-                with torch.no_grad():
-                    if self.packed is not None:
-                        from .packed import PackedLayout
-                        dev = self.stack_pool.device
-                        lay = PackedLayout(self.quad_keep.to(dev), self.quad_dyn.to(dev), T, h, w, (nth, ntw))
-                        pool = lay.new_pool(dev)
-                        for d in range(D):
-                            lay.pack_plane_(pool, d, resize_plane(self.packed.unpack_plane(self.stack_pool.data, d)))
-                        del self._parameters["stack_pool"]
-                        self.register_parameter("stack_pool", nn.Parameter(pool, requires_grad=True))
-                        self.packed = lay
-                    else:
-                        from . import tiles
-                        new = torch.empty((D, T, h, w, 4), dtype=self.stack.dtype, device=self.stack.device)
-                        for d in range(D):
-                            new[d] = resize_plane(self.stack.data[d])
-                        tiles.cull_stack_(new, self.quad_keep, (nth, ntw))
-                        self.register_parameter("stack", nn.Parameter(new, requires_grad=True))
-            self._set_texture_geometry(h, w)
-            self._install_tie_hook()
-            print("MPV.los:: Resizing successful !")
-            return
-        print(f"MPV.lod:: Resizing the planes from {(hs, ws)} to {(h, w)}")
-        if (hs, ws) != (h, w) and self.packed is not None:
-            # packed model: plane by plane through the dense form of ONE plane (1/D of the dense stack), the same mask-weighted filter
-            from . import tiles
-            from .packed import PackedLayout
-            with torch.no_grad():
-                dev = self.stack_pool.device
-                lay = PackedLayout(self.quad_keep.to(dev), self.quad_dyn.to(dev), T, h, w)
-                pool = lay.new_pool(dev)
-                for d in range(D):
-                    planes = self.packed.unpack_plane(self.stack_pool.data, d).permute(0, 3, 1, 2)               # T,4,hs,ws
-                    m = tiles.quad_to_texel_mask(self.quad_keep[d:d + 1], hs, ws).to(planes.dtype)[None]         # 1,1,hs,ws
-                    num = torch.nn.functional.interpolate(planes * m, size=(h, w), mode="bilinear", align_corners=False, antialias=aa)
-                    den = torch.nn.functional.interpolate(m, size=(h, w), mode="bilinear", align_corners=False, antialias=aa)
-                    new = (num / den.clamp_min(1e-6)).permute(0, 2, 3, 1).contiguous()
-                    tiles.cull_stack_(new[None], self.quad_keep[d:d + 1])
-                    lay.pack_plane_(pool, d, new)
-            del self._parameters["stack_pool"]
-            self.register_parameter("stack_pool", nn.Parameter(pool, requires_grad=True))
-            self.packed = lay
-        elif (hs, ws) != (h, w):
-            sparse = self.is_sparse and self.quad_keep is not None
-            with torch.no_grad():
-                new = torch.empty((D, T, h, w, 4), dtype=self.stack.dtype, device=self.stack.device)
-                if sparse:
-                    # The reference resizes every tile on its own (MPV.py:157-164), so nothing bleeds between tiles.  On the dense
-                    # stack the culled texels hold the alpha logit CULLED_ALPHA (-1e4): a plain filter would pull the logits of
-                    # kept texels next to a culled region to -1e3..-1e4 (sigmoid = 0, zero gradient: dead for good).  Resample
-                    # with the kept-texel mask as the weight -- interpolate(v * m) / interpolate(m), a convex combination of
-                    # KEPT values only -- and re-apply the culling at the new resolution.
-                    from . import tiles
-                    kept = tiles.quad_to_texel_mask(self.quad_keep, hs, ws).to(self.stack.dtype)            # D,hs,ws
-                for d in range(D):      # plane by plane: bounds the temporaries at stage-2 sizes
-                    planes = self.stack.data[d].permute(0, 3, 1, 2)                                          # T,4,hs,ws
-                    if sparse:
-                        m = kept[d][None, None]                                                              # 1,1,hs,ws
-                        num = torch.nn.functional.interpolate(planes * m, size=(h, w), mode="bilinear", align_corners=False, antialias=aa)
-                        den = torch.nn.functional.interpolate(m, size=(h, w), mode="bilinear", align_corners=False, antialias=aa)
-                        planes = num / den.clamp_min(1e-6)
-                    else:
-                        planes = torch.nn.functional.interpolate(planes, size=(h, w), mode="bilinear", align_corners=False, antialias=aa)
-                    new[d] = planes.permute(0, 2, 3, 1)
-                if sparse:
-                    tiles.cull_stack_(new, self.quad_keep)
-            self.register_parameter("stack", nn.Parameter(new, requires_grad=True))
-        sx = self.texel_scale[0] * (w - 1) / max(self.mpi_w - 1, 1)
-        sy = self.texel_scale[1] * (h - 1) / max(self.mpi_h - 1, 1)
-        self.spec = dataclasses.replace(self.spec, scale=(sx, sy))
+            tile = (max(int(self.tile_full[0] * factor), 2), max(int(self.tile_full[1] * factor), 2))
+            h, w = qh * tile[0], qw * tile[1]
+            print(f"MPV.lod:: Sparse! Resizing the tiles from {self.tile_own} to {tile}")
+        else:
+            print(f"MPV.lod:: Resizing the planes from {(hs, ws)} to {(h, w)}")
+        if (hs, ws) != (h, w):
+            self._resample(h, w, tile, aa)
+        self._set_texture_geometry(h, w)
         self._install_tie_hook()
         print("MPV.los:: Resizing successful !")
 
-    def _flush_deferred_updates(self):
-        """the crop-aware Adam defers the zero-gradient updates of texels outside the current crop's window: replay them before
-        anything reads the whole stack (checkpoints, lod, evaluation renders)."""
-        if self._window_opt is not None:
-            self._window_opt.flush()
+    @torch.no_grad()
+    def _resample(self, h, w, tile, antialias):
+        """lod(): every plane read from the storage the model has, resampled to h x w texels (tile = the new (th, tw) of a tile-exact
+        model) and written into the same kind of storage -- plane by plane, which bounds the temporaries at stage-2 sizes (a packed model
+        goes through the dense form of ONE plane, 1/D of the dense stack)."""
+        from . import tiles
+        D, T, hs, ws = self.stack_dims()
+        dev = self._param().device
+
+        def interp(t):
+            return torch.nn.functional.interpolate(t, size=(h, w), mode="bilinear", align_corners=False, antialias=antialias)
+        if tile is not None:
+            qh, qw, (oth, otw), (nth, ntw) = h // tile[0], w // tile[1], self.tile_own, tile
+
+            def resample(planes, d):          # (T,hs,ws,4) -> (T,h,w,4), tile by tile
+                tl = planes.reshape(T, qh, oth, qw, otw, 4).permute(0, 1, 3, 5, 2, 4).reshape(T * qh * qw, 4, oth, otw)
+                tl = _resize_tiles(tl, nth, ntw, antialias)
+                return tl.reshape(T, qh, qw, 4, nth, ntw).permute(0, 1, 4, 2, 5, 3).reshape(T, h, w, 4)
+        elif self.is_sparse and self.quad_keep is not None:
+            # The reference resizes every tile on its own (MPV.py:157-164), so nothing bleeds between tiles.  On the dense
+            # stack the culled texels hold the alpha logit CULLED_ALPHA (-1e4): a plain filter would pull the logits of
+            # kept texels next to a culled region to -1e3..-1e4 (sigmoid = 0, zero gradient: dead for good).  Resample
+            # with the kept-texel mask as the weight -- interpolate(v * m) / interpolate(m), a convex combination of
+            # KEPT values only -- and re-apply the culling at the new resolution.
+            def resample(planes, d):
+                keep = self.quad_keep[d:d + 1]
+                m = tiles.quad_to_texel_mask(keep, hs, ws).to(planes.dtype)[None]                           # 1,1,hs,ws
+                new = (interp(planes.permute(0, 3, 1, 2) * m) / interp(m).clamp_min(1e-6)).permute(0, 2, 3, 1).contiguous()
+                return tiles.cull_stack_(new[None], keep)[0]
+        else:
+            def resample(planes, d):
+                return interp(planes.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        if self.packed is not None:
+            from .packed import PackedLayout
+            lay = PackedLayout(self.quad_keep.to(dev), self.quad_dyn.to(dev), T, h, w, tile)
+            pool = lay.new_pool(dev)
+            for d in range(D):
+                lay.pack_plane_(pool, d, resample(self.stack_plane(d), d))
+            self._install_pool(pool, lay)
+        else:
+            new = torch.empty((D, T, h, w, 4), dtype=self.stack.dtype, device=dev)
+            for d in range(D):
+                new[d] = resample(self.stack_plane(d), d)
+            if tile is not None:
+                tiles.cull_stack_(new, self.quad_keep, tile)
+            self._install_stack(new)
 
     def crop_window(self, homos, H, W, margin=3, per_plane=False):
         """texel window (y0, x0, wh, ww), aligned to the optimiser's bookkeeping tiles, that contains every tap of every pixel of the
@@ -624,29 +529,6 @@ class MPMeshVid(nn.Module):
         from .optim import crop_window
         Hs, Ws = self.stack_dims()[2:4]
         return crop_window(self.spec, Hs, Ws, homos, H, W, margin=margin, per_plane=per_plane)
-
-    # ---- export to the reference's layout (MPV.py:290-341) ------------------------------------------------------------------
-    def reference_state_dict(self):
-        """the state_dict of the REFERENCE's MPMeshVid for these weights: plane meshes + packed static / dynamic atlases."""
-        self._flush_deferred_updates()
-        from .export import reference_state_dict
-        return reference_state_dict(self)
-
-    def save_mesh(self, prefix):
-        """MPV.py:306-323."""
-        from .export import save_mesh
-        return save_mesh(self, prefix, self.reference_state_dict())
-
-    def save_texture(self, prefix):
-        """MPV.py:325-341 (dynamic frames as PNG files: no imageio / ffmpeg here)."""
-        from .export import save_texture
-        return save_texture(self, prefix, self.reference_state_dict())
-
-    def get_lrate(self, step):
-        """MPV.py:216-225."""
-        args = self.args
-        scaling = 0.1 ** (step / (args.lrate_decay * 1000))
-        return [("lr", args.lrate * scaling), ("vertlr", args.lrate * getattr(args, "optimize_verts_gain", 1) * scaling)]
 
     def get_optimizer(self, step):
         """MPV.py:199-214.  The planar path has no vertex parameters, so there is one parameter group (the reference's
@@ -659,52 +541,40 @@ class MPMeshVid(nn.Module):
         if self.packed is not None and self.args.optimizer != 'adam':
             raise RuntimeError(f"a packed model trains through the crop-aware Adam only (optimizer = {self.args.optimizer})")
         if self.args.optimizer == 'adam':
-            if self.packed is not None:
-                from .optim import WindowAdam
-                from .tiles import CULLED_ALPHA
-                self._window_opt = WindowAdam([{'params': [self.stack_pool]}], lr=base_lr, betas=(0.9, 0.999), eps=6e-8, quad_keep=self.quad_keep,
-                                              quad_dyn=self.quad_dyn, culled_alpha=CULLED_ALPHA, layout=self.packed, tile=self.tile_own,
-                                              fused_backward=bool(getattr(self.args, "fused_adam_backward", True))
-                                              and not getattr(self.args, "finite_window_grad", False))
-                return self._window_opt
-            if self.stack.is_cuda and self.is_sparse and getattr(self.args, "tile_adam", False):
+            from .tiles import CULLED_ALPHA, TileAdam
+            cuda = self._param().is_cuda
+            if self.packed is None and cuda and self.is_sparse and getattr(self.args, "tile_adam", False):
                 # (the round-1 optimiser of sparsified models, kept selectable: one pass over the kept texels of the WHOLE stack, static
                 # gradients summed into frame 0 by the tie hook while it is the optimiser handed out last)
-                from .tiles import TileAdam
                 self._static_compact = True
                 return TileAdam(params, lr=base_lr, betas=(0.9, 0.999), eps=6e-8, quad_keep=self.quad_keep, quad_dyn=self.quad_dyn, tile=self.tile_own)
-            if self.stack.is_cuda and self.is_sparse and not self.atlas_exact:
-                # sparsified model: the crop-aware Adam with the quad maps -- culled texels are no parameters, a static texel is ONE
-                # parameter stored once (frame 0; the window copy shows it in every frame, its gradient is summed over the frames inside
-                # the step), dynamic texels one per frame; only the crop's window is touched per step
-                from .optim import WindowAdam
-                from .tiles import CULLED_ALPHA
-                # (fused: dynamic texels are stepped inside the render's backward, static ones by the step kernel behind it -- see the dense branch)
-                fused = bool(getattr(self.args, "fused_adam_backward", True)) and not getattr(self.args, "finite_window_grad", False)
-                self._window_opt = WindowAdam(params, lr=base_lr, betas=(0.9, 0.999), eps=6e-8, quad_keep=self.quad_keep,
-                                              quad_dyn=self.quad_dyn, culled_alpha=CULLED_ALPHA, fused_backward=fused, tile=self.tile_own)
-                return self._window_opt
-            if self.stack.is_cuda and not self.atlas_exact:
-                # dense model: crop-aware Adam -- the render reads a compact copy of the crop's texel window, the backward writes a
-                # compact gradient, the step touches the window only; the zero-gradient updates of everything else are deferred and
-                # replayed exactly (videoloop3d_amd/optim.py).  While it is attached, training renders go through its window.
+            # The crop-aware Adam (videoloop3d_amd/optim.py): the render reads a compact copy of the crop's texel window, the backward writes
+            # a compact gradient, the step touches the window only; the zero-gradient updates of everything else are deferred and replayed
+            # exactly.  While it is attached, training renders go through its window.
+            window = None
+            if self.packed is not None:      # the window is gathered from / scattered to the pool (any device)
+                window = dict(quad_keep=self.quad_keep, quad_dyn=self.quad_dyn, culled_alpha=CULLED_ALPHA, tile=self.tile_own, layout=self.packed)
+            elif cuda and self.is_sparse and not self.atlas_exact:
+                # sparsified model: with the quad maps -- culled texels are no parameters, a static texel is ONE parameter stored once
+                # (frame 0; the window copy shows it in every frame, its gradient is summed over the frames inside the step), dynamic
+                # texels one per frame
+                window = dict(quad_keep=self.quad_keep, quad_dyn=self.quad_dyn, culled_alpha=CULLED_ALPHA, tile=self.tile_own)
+            elif cuda and not self.atlas_exact:
+                window = {}
+            if window is not None:
                 from .optim import WindowAdam
                 # The step is taken INSIDE the render's backward (vl3d_render_bwd_adam: the owner's store applies it; same bits as the two
-                # kernels, 6 instead of 9 streams of the window) -- `loss.backward(); optimizer.step()` of train_3dvid.py:242-244 then update
-                # the parameters at the backward.  args.fused_adam_backward = False or args.finite_window_grad (someone reads the window
-                # leaf's gradient: clipping, norm logging) keep the gradient tensor and the separate step kernel.
+                # kernels, 6 instead of 9 streams of the window; with quad maps the dynamic texels, static ones by the step kernel behind
+                # it) -- `loss.backward(); optimizer.step()` of train_3dvid.py:242-244 then update the parameters at the backward.
+                # args.fused_adam_backward = False or args.finite_window_grad (someone reads the window leaf's gradient: clipping, norm
+                # logging) keep the gradient tensor and the separate step kernel.
                 fused = bool(getattr(self.args, "fused_adam_backward", True)) and not getattr(self.args, "finite_window_grad", False)
-                self._window_opt = WindowAdam(params, lr=base_lr, betas=(0.9, 0.999), eps=6e-8, fused_backward=fused)
+                self._window_opt = WindowAdam(params, lr=base_lr, betas=(0.9, 0.999), eps=6e-8, fused_backward=fused, **window)
                 return self._window_opt
             return torch.optim.Adam(params=params, lr=base_lr, betas=(0.9, 0.999), eps=6e-8)
         if self.args.optimizer == 'sgd':
             return torch.optim.SGD(params=params, lr=base_lr, momentum=0.9)
         raise RuntimeError(f"Unrecongnized optimizer type {self.args.optimizer}")
-
-    def update_step(self, step):
-        """MPV.py:227-229; geometry optimisation itself is not on the planar path."""
-        if step >= getattr(self.args, "optimize_geo_start", 10000000):
-            self.optimize_geometry = True
 
     # ---- geometry ----------------------------------------------------------------------------------------------------
     def reserve_windows(self, views):
@@ -728,43 +598,6 @@ class MPMeshVid(nn.Module):
         if best:
             opt.reserve(best)
         return best
-
-    def plane_homographies(self, extrin, intrin):
-        """[D,3,3] target pixel -> plane pixel for the view `extrin` (ref -> target, [1,4,4]) / `intrin` [1,3,3]
-        (utils_mpi.py:240-273 with src = the reference camera, plane normal (0,0,1), distance = planedepth)."""
-        dev = extrin.device
-        if dev.type == "cpu" and extrin.dtype == torch.float64 and not extrin.requires_grad and not getattr(self.args, "torch_homographies", False):
-            # float64 host poses: the closed form in numpy (utils_mpi.plane_homographies_host) -- the same bits as the torch spelling below at a
-            # third of the host time.  (float32 poses, as the reference's drivers hold them, keep the torch operators: their rounding is the
-            # reference's own, which the goldens pin.)
-            from .utils_mpi import plane_homographies_host
-            return plane_homographies_host(self._host_np("ref_intrin_mpi"), self._host_np("planedepth"), extrin[0].numpy(),
-                                           torch.as_tensor(intrin)[0].detach().cpu().numpy())
-        eye = torch.eye(4, dtype=extrin.dtype, device=dev)[None]
-        normal = torch.tensor([0., 0., 1.], dtype=extrin.dtype, device=dev).expand(1, self.mpi_d, 3)
-        return compute_homography(eye, self._on(dev, "ref_intrin_mpi")[None].to(extrin.dtype), extrin, intrin.to(dev), normal,
-                                  self._on(dev, "planedepth")[None].to(extrin.dtype))[0].float()
-
-    def _host_np(self, name):
-        """numpy mirror of a (small, constant) camera buffer, refreshed when the buffer changes."""
-        buf = getattr(self, name)
-        cache = self.__dict__.setdefault("_host_np_mirrors", {})
-        key = (buf.data_ptr(), buf._version, str(buf.device))
-        if cache.get(name, (None,))[0] != key:
-            cache[name] = (key, buf.detach().cpu().numpy().copy())
-        return cache[name][1]
-
-    def _on(self, dev, name):
-        """the (small, constant) camera buffers on the device of the pose tensors: poses that arrive on the HOST (as the DataLoader
-        produces them, train_3dvid.py:214-216) are turned into homographies there, with no device round trip."""
-        buf = getattr(self, name)
-        if buf.device == dev:
-            return buf
-        cache = self.__dict__.setdefault("_host_mirrors", {})
-        key = (name, str(dev), buf.data_ptr(), buf._version)
-        if cache.get(name, (None,))[0] != key:
-            cache[name] = (key, buf.detach().to(dev))
-        return cache[name][1]
 
     # ---- render ------------------------------------------------------------------------------------------------------
     def _all_frames(self, ts):
@@ -792,14 +625,7 @@ class MPMeshVid(nn.Module):
                                               self.quad_keep, CULLED_ALPHA)
             variables = {"pix_to_face": None, "blend_weight": None, "mpi": None, "disp_norm": None, "alpha": alpha, "smooth_sums": None,
                          "alpha_sums": None}
-            if len(self.args.bg_color) > 0:                                                     # MPV.py:455-461 (as written)
-                if self.args.bg_color == "random":
-                    bg_color = torch.rand(3).type_as(rgb)
-                else:
-                    r, g, b = map(float, self.args.bg_color.split('#'))
-                    bg_color = torch.tensor([r, g, b]).type_as(rgb)
-                rgb = rgb * alpha[..., None] + bg_color[None, None, None] * (- alpha[..., None] + 1)
-            return rgb[..., :3], variables
+            return self._composite_bg(rgb, alpha)[..., :3], variables
         if self.packed is not None and not self._all_frames(ts):
             self._flush_deferred_updates()
         # an evaluation render of a run of consecutive frames of a dense model reads them where they lie (vl3d_render_fwd_frames): gathering
@@ -896,14 +722,7 @@ class MPMeshVid(nn.Module):
             variables["mpi"] = mpi
             variables["blend_weight"] = overcompose(mpi[..., -1], mpi[..., :-1])[1]
             variables["disp_norm"] = (overcompose(planes[..., -1], planes[..., :-1])[1] * inv_z[None]).sum(-1)
-        if len(self.args.bg_color) > 0:                                                     # MPV.py:455-461 (as written)
-            if self.args.bg_color == "random":
-                bg_color = torch.rand(3).type_as(rgb)
-            else:
-                r, g, b = map(float, self.args.bg_color.split('#'))
-                bg_color = torch.tensor([r, g, b]).type_as(rgb)
-            rgb = rgb * alpha[..., None] + bg_color[None, None, None] * (- alpha[..., None] + 1)
-        return rgb[..., :3], variables
+        return self._composite_bg(rgb, alpha)[..., :3], variables
 
     def _layers(self, stack, homos, H, W, spec=None, cull_window=None, extrin=None):
         """warped + activated per-layer rgba via the unfused warp kernel (differentiable, videoloop3d_amd/layers.py): (slot-ordered
@@ -959,8 +778,7 @@ class MPMeshVid(nn.Module):
         return total, parts[0], {k: parts[1 + i] for i, k in enumerate(names)}
 
     def stack_device_is_cuda(self):
-        p = self.stack_pool if self.packed is not None else self.stack
-        return p.is_cuda
+        return self._param().is_cuda
 
     def forward(self, h, w, tar_extrins, tar_intrins, ts=None, res=None, losscfg=None, _head=False):
         """MPV.py:477-556.  train -> (None, {'swd': [1,1], ...}); eval -> (rgb [T',3,h,w], {})."""

@@ -21,8 +21,6 @@ learning rate is the group's at the time of the backward (train_3dvid.py:263-277
 for bit those of the two-kernel path.  Contract: one backward per window_leaf(), nothing else reads the leaf's gradient (it stays None).
 """
 import ctypes as C
-
-import struct
 import warnings
 
 import torch
