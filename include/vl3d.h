@@ -117,7 +117,9 @@ int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stac
  * kernel otherwise), 1 force atomics, 3 owner-computes kernel, one frame per thread in 64 x 16-pixel regions (2: the 8-row regions of
  * round 1, no longer built, selects 3), 4 = 3 with the 3x3 gather everywhere (reference for the 2x2 gather of no-minification tiles, which
  * must equal it bit for bit), 5 = one frame per thread in 32 x 16-pixel regions (the shipped planar convention with fp32 stacks; = 3
- * elsewhere).  All of them produce the same gradient bits. */
+ * elsewhere), 6 / 7 = two frames per thread in 32 x 16 / 64 x 12-pixel regions wherever 0 takes frame pairs (dense stacks at the frame's
+ * resolution, T >= 2, no layer regularisers; = 3 elsewhere): 0 picks between the two by measurement.  All of them produce the same
+ * gradient bits. */
 int64_t vl3d_render_bwd_scratch_bytes(const vl3d_render_desc *desc);
 int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float *homos,
                     const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha,

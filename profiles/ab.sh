@@ -7,7 +7,7 @@ for r in 1 2 3; do
     python - "$so" <<'PY'
 import json, sys
 d = json.load(open('/tmp/_ab.json'))
-print(f"{sys.argv[1]:24s} {d['value']:8.1f} Mpix/s  fwd {d['roofline_fwd']['avg_ms']:.3f} ms  bwd {d['roofline_bwd']['avg_ms']:.3f} ms")
+print(f"{sys.argv[1]:24s} {d['value']:8.1f} Mpix/s  fwd {d['summary']['fwd_ms']:.3f} ms  bwd {d['summary']['bwd_ms']:.3f} ms")
 PY
   done
 done

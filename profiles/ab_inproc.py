@@ -2,7 +2,10 @@
 """In-process A/B of render kernel variants on ONE resident cfg3 stack (same buffers, same clocks, interleaved rounds): separate
 processes differ by up to 10 % on the same box (allocation, clock state), which is more than most variants are worth.
   python profiles/ab_inproc.py --variants 0,3 [--rounds 6] [--reps 4] [--stack-scale 1.0] [--reg] [--dtype f32|f16] [--T 50]
-Prints per variant the median / min of the forward and backward times (HIP events on the launch stream)."""
+Prints per variant the median / min of the forward and backward times (HIP events on the launch stream).
+A variant may be listed TWICE (--variants 6,7,6: the frame pairs in 32 x 16 regions, in 64 x 12 regions, and the 32 x 16 ones again): every
+entry is timed as a leg of its own, and the difference between the medians of two legs of the same variant is the harness's own repeatability
+in that run -- the yardstick a gain has to clear (printed as `spread`; every other leg's backward is printed against the first leg's)."""
 import argparse
 import os
 import statistics
@@ -42,7 +45,7 @@ stack = synth.make_plane_stack(D, T, Hs, Ws, seed=2, device=dev, dtype=torch.flo
 g = synth.hash_uniform((T, H, W, 3), seed=5, device=dev) - 0.5
 variants = [int(v, 0) for v in a.variants.split(",")]
 ev = lambda: torch.cuda.Event(enable_timing=True)
-res = {v: ([], []) for v in variants}
+res = [([], []) for _ in variants]      # one leg per ENTRY: a variant listed twice is measured twice
 
 
 def once(v):
@@ -72,12 +75,17 @@ for v in variants:
     elif T <= 4:
         print(f"variant {v:#x}: gradient bits equal to variant {variants[0]:#x}: {torch.equal(g_first, once.last)}")
 for r in range(a.rounds):
-    for v in variants:
+    for i, v in enumerate(variants):
         for _ in range(a.reps):
             f, b = once(v)
-            res[v][0].append(f)
-            res[v][1].append(b)
+            res[i][0].append(f)
+            res[i][1].append(b)
 print(f"D={D} T={T} {H}x{W} stack {Hs}x{Ws} {a.dtype} reg={a.reg}: {a.rounds} rounds x {a.reps} reps, interleaved")
-for v in variants:
-    f, b = res[v]
-    print(f"variant {v:#6x}  fwd median {statistics.median(f):7.3f} min {min(f):7.3f}   bwd median {statistics.median(b):7.3f} min {min(b):7.3f} ms")
+bmed = [statistics.median(b) for _, b in res]
+for i, v in enumerate(variants):
+    f, b = res[i]
+    print(f"variant {v:#6x}  fwd median {statistics.median(f):7.3f} min {min(f):7.3f}   bwd median {bmed[i]:7.3f} min {min(b):7.3f} ms"
+          + (f"   bwd vs leg 0: {100.0 * (bmed[i] / bmed[0] - 1.0):+6.2f} %" if i else ""))
+spread = max([abs(bmed[i] - bmed[j]) for i in range(len(variants)) for j in range(i) if variants[i] == variants[j]], default=None)
+if spread is not None:
+    print(f"spread (backward medians of the legs that repeat a variant): {spread:.3f} ms = {100.0 * spread / bmed[0]:.2f} %; a gain counts from 3x that: {3 * spread:.3f} ms")

@@ -349,7 +349,7 @@ __global__ void rw8_k(const f2_t *__restrict__ src, f2_t *__restrict__ dst, size
 }
 
 int main(int argc, char **argv) {
-    const bool aligned_only = argc > 1 && (argv[1][0] == 'a' || argv[1][0] == 'h' || argv[1][0] == 'f' || argv[1][0] == 'v' || argv[1][0] == 'p');      // ./rw_bw aligned | halo: only that comparison at the end
+    const bool aligned_only = argc > 1 && (argv[1][0] == 'a' || argv[1][0] == 'h' || argv[1][0] == 'f' || argv[1][0] == 'v' || argv[1][0] == 'p' || argv[1][0] == 'w');      // ./rw_bw aligned | halo: only that comparison at the end
     const bool halo_only = argc > 1 && argv[1][0] == 'h';
     const size_t unit = 8ull << 30, n = unit / 16;     // 8 GiB per stream
     f4 *src, *dst;
@@ -490,6 +490,38 @@ int main(int argc, char **argv) {
         // (streaming reference at 8 bytes per lane: what the HBM gives a read:write = 1:1 kernel whose accesses are 8-byte wide)
         run("rw 1:1, 8-byte lanes, nt-store (grid-strided)", [&] { hipLaunchKernelGGL((rw8_k), dim3(256 * 16), dim3(512), 0, 0, reinterpret_cast<const f2 *>(src),
                                                                                     reinterpret_cast<f2 *>(dst), unit / 8); }, 2.0 * unit);
+        return 0;
+    }
+    // Frame pairs in 64 x 12 regions (768 threads, two workgroups per CU) against the shipped 32 x 16 x 2 and the two 64-wide shapes that were
+    // built and lost (64 x 8 x 2, 64 x 16 x 1; 64 x 16 x 2 for reference): ./rw_bw w.  Halo 1, ragged 62-texel segments, owner table, non-temporal
+    // stores; the 8-byte rows are the fp16 stack's pattern.  Three rounds in one process: the spread of a row across rounds is its repeatability.
+    if (argc > 1 && argv[1][0] == 'w') {
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        const int D = 32, T = 12, Hs = 720, Ws = 1280;
+        const size_t texels = (size_t)D * T * Hs * Ws;
+        unsigned short *owner;
+        hipMalloc(&owner, (size_t)D * Hs * Ws * 2 + 4096);
+        hipMemset(owner, 0, (size_t)D * Hs * Ws * 2 + 4096);
+#define BLW(RX, RY, FR)                                                                                                        \
+        {                                                                                                                      \
+            const int tx = (Ws + RX - 3) / (RX - 2), ty = (Hs + RY - 3) / (RY - 2);                                            \
+            snprintf(name, sizeof name, "bwd_like  16-byte texels  region %3d x %2d  frames %d  (halo x%.2f, %4d threads)", RX, RY, FR,           \
+                     (double)RX * RY / ((RX - 2) * (RY - 2)), RX * RY);                                                         \
+            run(name, [&] { hipLaunchKernelGGL((bwd_like_k<RX, RY, FR, 4, true, 0, 8, 1>), dim3((unsigned)(tx * ty * (T / FR))), dim3(RX * RY), 0, 0, \
+                                               src, dst, owner, D, T, Hs, Ws, tx, ty); }, 2.0 * texels * 16);                  \
+        }
+#define BLW8(RX, RY, FR)                                                                                                       \
+        {                                                                                                                      \
+            const int tx = (Ws + RX - 3) / (RX - 2), ty = (Hs + RY - 3) / (RY - 2);                                            \
+            snprintf(name, sizeof name, "bwd_like   8-byte texels  region %3d x %2d  frames %d  (halo x%.2f, %4d threads)", RX, RY, FR,           \
+                     (double)RX * RY / ((RX - 2) * (RY - 2)), RX * RY);                                                         \
+            run(name, [&] { hipLaunchKernelGGL((bwd_like_e_k<f2, RX, RY, FR>), dim3((unsigned)(tx * ty * (T / FR))), dim3(RX * RY), 0, 0, \
+                                               reinterpret_cast<const f2 *>(src), reinterpret_cast<f2 *>(dst), owner, D, T, Hs, Ws, tx, ty); }, 2.0 * texels * 8); \
+        }
+        for (int rep = 0; rep < 3; ++rep) {
+            BLW(32, 16, 2) BLW(64, 12, 2) BLW(64, 8, 2) BLW(64, 16, 1) BLW(64, 16, 2)
+            BLW8(32, 16, 2) BLW8(64, 12, 2) BLW8(64, 8, 2) BLW8(64, 16, 1)
+        }
         return 0;
     }
     // A backward WITHOUT the vertical halo (round 5): the shipped pattern against its no-vertical-halo upper bound, same geometry.

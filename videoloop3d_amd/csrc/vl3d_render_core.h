@@ -1776,14 +1776,14 @@ constexpr int PROWS = 16;      // region rows.  The region width PW is a templat
 // accumulators, two stores.  sg0 / sg1: staged gradients of frames t and t+1, st: staged texel coordinates (this plane's buffers).
 // ADAM: the owner applies the optimiser's step where it would have stored the gradient (vl3d_render_bwd_adam): (d, t0) = the plane and the
 // pair's first frame.
-template <int ORDER, int RACT, int AACT, bool F16, bool ADAM = false, int PW = 32>
+template <int ORDER, int RACT, int AACT, bool F16, bool ADAM = false, int PW = 32, int PR = PROWS>
 __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const float4 *sg0, const float4 *sg1, const float2 *st, int X0, int Y0,
                                                   int ww, int wh, bool apart, unsigned my_tile, unsigned e0, const unsigned short *oplane,
                                                   const char *plane0, char *gplane0, size_t f1, size_t frame_b, bool has1, int col, int row,
                                                   int d = 0, int t0 = 0) {
     const unsigned win0 = (unsigned)(Y0 * a.Ws + X0);
     auto gather = [&](unsigned e, int wx, int wy, unsigned tix) {
-        constexpr int SLOT_BITS = PW == 64 ? 10 : 9;      // PW * 16 slots of the region (bwd_owner_table_k)
+        constexpr int SLOT_BITS = PW == 64 ? 10 : 9;      // PW * PR slots of the region (bwd_owner_table_k)
         if ((e >> SLOT_BITS) != my_tile) return;
         const int lc = (int)(e & ((1u << SLOT_BITS) - 1u));
         const f2 tau = f2{(float)(X0 + wx), (float)(Y0 + wy)};
@@ -1837,14 +1837,14 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
         }
     };
     if (row < wh && col < ww) gather(e0, col, row, win0 + (unsigned)(row * a.Ws + col));
-    // rest of a window larger than 32 x 16: columns beyond 32 as a packed strip, rows beyond 16 one half-wave per row
+    // rest of a window larger than the PW x PR region: columns beyond PW as a packed strip, rows beyond PR one region row per window row
     const int nec = ww - PW;
     if (nec > 0) {
         const int necp = min(nec, PW);
-        const int sh = necp > 1 ? 32 - __builtin_clz((unsigned)(necp - 1)) : 0, rpg = PW >> sh, rmain = min(wh, PROWS);
+        const int sh = necp > 1 ? 32 - __builtin_clz((unsigned)(necp - 1)) : 0, rpg = PW >> sh, rmain = min(wh, PR);
         const int c = col & ((1 << sh) - 1), r = col >> sh;          // a 32-thread row group takes rpg window rows of the strip
         for (int wxb = PW; wxb < ww; wxb += (1 << sh))
-            for (int wy0 = row * rpg; wy0 < rmain; wy0 += PROWS * rpg) {
+            for (int wy0 = row * rpg; wy0 < rmain; wy0 += PR * rpg) {
                 const int wy = wy0 + r, wx = wxb + c;
                 if (c < necp && wx < ww && wy < rmain) {
                     const unsigned tix = win0 + (unsigned)(wy * a.Ws + wx);
@@ -1852,7 +1852,7 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
                 }
             }
     }
-    for (int wy = row + PROWS; wy < wh; wy += PROWS)
+    for (int wy = row + PR; wy < wh; wy += PR)
         for (int wx = col; wx < ww; wx += PW) {
             const unsigned tix = win0 + (unsigned)(wy * a.Ws + wx);
             gather(oplane[tix], wx, wy, tix);
@@ -2005,8 +2005,6 @@ __global__ __launch_bounds__(PW * PROWS, VL3D_PAIR_MIN_WAVES) void render_bwd_pa
     }
 }
 
-#undef VL3D_PAIR_GRAD
-
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool REG = false, bool ADAM = false, int PW = 32>
 void launch_pair(const RenderArgs &a, hipStream_t s) {
     constexpr int RH = 1, IW = PW - 2 * RH, IH = PROWS - 2 * RH;
@@ -2019,6 +2017,106 @@ void launch_pair(const RenderArgs &a, hipStream_t s) {
                        const_cast<unsigned short *>(a.owner), PW, PW == 64 ? 10 : 9);
     hipLaunchKernelGGL((render_bwd_pair_k<COORD, BORDER, ORDER, RACT, AACT, F16, REG, ADAM, PW>),
                        dim3((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), dim3(PW * PROWS), 0, s, b);
+}
+
+// Frame pairs in 64 x 12-pixel regions (62 x 10 owned, 768 threads): the plain pair kernel -- no layer regularisers, no fused optimiser
+// step -- in the shape its memory pattern prefers.  The owner's row segments are 992 bytes instead of 480 (fp16 stacks: 496 instead of 240):
+// profiles/microbench/rw_bw.hip w reads 4.06 against 3.82 TB/s for the pattern alone (8-byte texels 3.81 against 2.94).  Unlike the two
+// 64-wide shapes built before it keeps TWO workgroups per CU (2 x 768 threads, 2 x 60 KB of LDS, <= 80 VGPRs for 6 waves per SIMD) -- 64 x 16 x 2
+// ran alone on its CU -- at x1.24 pixels swept per pixel owned -- 64 x 8 x 2 swept x1.38.  Per frame the arithmetic is render_bwd_pair_k's,
+// instruction for instruction (same bits); the pre-pass kernels are shared (region width 64, 10-bit slots, 3 + 3 bits of tile code: tiles
+// that share a code are 8 steps = 80 pixel rows apart, more than the 48 of the flat 64 x 8 one-frame regions that use the same code).
+// A kernel of its own: render_bwd_pair_k's schedule is what tests/test_kernel_schedule_canary.py pins, and its template parameters stay.
+constexpr int P12W = 64, P12ROWS = 12;
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
+__global__ __launch_bounds__(P12W * P12ROWS, 6) void render_bwd_pair12_k(RenderArgs a) {      // 6 waves per SIMD = 2 workgroups per CU: <= 80 VGPRs
+    constexpr int PW = P12W, PR = P12ROWS, PNT = PW * PR;
+    if (!reinterpret_cast<const int *>(a.plan)[0]) return;
+    __shared__ float4 s_g[2][2][PNT];   // [buffer][frame][pixel]
+    __shared__ float2 s_t[2][PNT];
+    const int tid = threadIdx.x, col = tid & (PW - 1), row = tid / PW;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_x = bid % a.tiles_x, rest = bid / a.tiles_x;
+    const int tile_y = rest % a.tiles_y, t0 = (rest / a.tiles_y) * 2;
+    const bool has1 = t0 + 1 < a.T;          // odd T: the last pair sweeps frame t0 twice and stores it once
+    const int rx0 = tile_x * (PW - 2) - 1, ry0 = tile_y * (PR - 2) - 1;
+    const int x = rx0 + col, y = ry0 + row;
+    const bool inimg = (x >= 0) && (x < a.W) && (y >= 0) && (y < a.H);
+    const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
+    constexpr size_t TEXB = F16 ? 8 : 16;
+    const size_t frame_b = (size_t)a.Hs * a.Ws * TEXB;
+    const size_t plane_stride_b = (size_t)a.T * frame_b;
+    const char *plane0 = reinterpret_cast<const char *>(a.stack) + (size_t)t0 * frame_b;
+    char *gplane0 = reinterpret_cast<char *>(a.g_stack) + (size_t)t0 * frame_b;
+    const size_t f1 = has1 ? frame_b : 0;
+    float Gr0 = 0.f, Gg0 = 0.f, Gb0 = 0.f, gA0 = 0.f, S0 = 0.f, Gr1 = 0.f, Gg1 = 0.f, Gb1 = 0.f, gA1 = 0.f, S1 = 0.f;
+    if (inimg) {
+        size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
+        Gr0 = a.g_rgb[pix * 3 + 0]; Gg0 = a.g_rgb[pix * 3 + 1]; Gb0 = a.g_rgb[pix * 3 + 2];
+        gA0 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
+        S0 = dot3p(Gr0, a.rgb[pix * 3 + 0], Gg0, a.rgb[pix * 3 + 1], Gb0, a.rgb[pix * 3 + 2], gA0 * a.alpha[pix]);
+        if (has1) pix += (size_t)a.H * a.W;
+        Gr1 = a.g_rgb[pix * 3 + 0]; Gg1 = a.g_rgb[pix * 3 + 1]; Gb1 = a.g_rgb[pix * 3 + 2];
+        gA1 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
+        S1 = dot3p(Gr1, a.rgb[pix * 3 + 0], Gg1, a.rgb[pix * 3 + 1], Gb1, a.rgb[pix * 3 + 2], gA1 * a.alpha[pix]);
+    }
+    float Tr0 = 1.0f, P0 = 0.0f, Tr1 = 1.0f, P1 = 0.0f;
+    const TapStep st = make_tap_step<F16>(a.Hs, a.Ws);
+    const unsigned my_tile_id = (unsigned)(tile_y * a.tiles_x + tile_x);
+    const unsigned my_tile = (unsigned)((tile_y & 7) << 3 | (tile_x & 7));      // 10-bit slots: 3 + 3 bits of tile code (bwd_owner_table_k)
+    const unsigned toff_thread = (unsigned)(row * a.Ws + col);
+    const cint_p wrec = (cint_p)a.plan + plan_win_off(a.D) + (size_t)my_tile_id * a.D * 4;
+    typedef typename TapVal<F16, ORDER>::type tapv_t;
+    const f4 ex = f4{0.f, 0.f, 0.f, 0.f};      // (no regularisers: VL3D_PAIR_GRAD's extra term, as in render_bwd_pair_k<REG = false>)
+    for (int d = 0; d < a.D; ++d, plane0 += plane_stride_b, gplane0 += plane_stride_b) {
+        float h[VL3D_HN];
+        load_uniform(a.homos + VL3D_HS * d, h);
+        const int X0 = wrec[4 * d], Y0 = wrec[4 * d + 1], wwh = wrec[4 * d + 2];
+        const int ww = wwh & 0xffff, wh = (wwh >> 16) & 0x3fff;
+        const bool apart = (wwh & 0x40000000) != 0;
+        const int buf = d & 1;
+        const unsigned short *oplane = a.owner + (size_t)d * a.Hs * a.Ws;
+        const unsigned e0 = oplane[(unsigned)(Y0 * a.Ws + X0) + toff_thread];     // unconditional (padded table), arrives in the shadow of the sweep
+        // sweep: one set of taps, two frames
+        float2 tc = make_float2(0.f, 0.f);
+        float4 gv0 = make_float4(0.f, 0.f, 0.f, 0.f), gv1 = gv0;
+        if (inimg) {
+            const Taps2 tp = make_taps2<COORD, BORDER>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
+            tapv_t tv0[4], tv1[4];
+            load_taps2<F16>(plane0, tp, st, tv0);
+            load_taps2<F16>(plane0 + f1, tp, st, tv1);
+            f4 pre0, pre1;
+            const f4 o0 = shade2<ORDER, RACT, AACT>(tp, tv0, &pre0);
+            const f4 o1 = shade2<ORDER, RACT, AACT>(tp, tv1, &pre1);
+            VL3D_PAIR_GRAD(o0, pre0, Gr0, Gg0, Gb0, gA0, S0, P0, Tr0, gv0, ex)
+            VL3D_PAIR_GRAD(o1, pre1, Gr1, Gg1, Gb1, gA1, S1, P1, Tr1, gv1, ex)
+            tc = make_float2(tp.tx, tp.ty);
+            if (!(tp.cov > 0.0f)) { gv0 = make_float4(0.f, 0.f, 0.f, 0.f); gv1 = gv0; }
+        }
+        s_t[buf][tid] = tc;
+        s_g[buf][0][tid] = gv0;
+        s_g[buf][1][tid] = gv1;
+        __syncthreads();
+        // gather: one set of weights, two accumulators
+        pair_gather_plane<ORDER, RACT, AACT, F16, false, PW, PR>(a, s_g[buf][0], s_g[buf][1], s_t[buf], X0, Y0, ww, wh, apart, my_tile, e0, oplane, plane0,
+                                                                 gplane0, f1, frame_b, has1, col, row, d, t0);
+    }
+}
+
+#undef VL3D_PAIR_GRAD
+
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
+void launch_pair12(const RenderArgs &a, hipStream_t s) {
+    constexpr int RH = 1, IW = P12W - 2 * RH, IH = P12ROWS - 2 * RH;
+    RenderArgs b = a;
+    b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
+    const int nwin = b.tiles_x * b.tiles_y * a.D;
+    hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
+                       reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
+    hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
+                       const_cast<unsigned short *>(a.owner), P12W, 10);
+    hipLaunchKernelGGL((render_bwd_pair12_k<COORD, BORDER, ORDER, RACT, AACT, F16>),
+                       dim3((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), dim3(P12W * P12ROWS), 0, s, b);
 }
 
 // =====================================================================================================
@@ -2229,8 +2327,13 @@ void launch_t(const RenderArgs &a, hipStream_t s) {
                 // the extra gather passes of the small tiles cost more than the pairs save (1.1x: 13.3 ms tile kernel, 13.9 ms
                 // pairs): crops of a larger stack and the reference's 1.1x stacks keep the 64 x 16 tile kernel.
                 const bool fits = (int64_t)a.Hs * 100 <= (int64_t)a.H * 107 || (int64_t)a.Ws * 100 <= (int64_t)a.W * 107;
-                if (a.tile_rows == 17 && a.T >= 2 && !a.g_reg && !a.g_asum && !a.quad_keep && fits) {
-                    launch_pair<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
+                // The pairs come in two region shapes: 64 x 12 (62 x 10 owned, 768 threads; render_bwd_pair12_k) is the default, 32 x 16 the
+                // kernel it replaced there (tile_rows 19 = variant 6 keeps it: the A/B partner and the reference of the bitwise tests;
+                // 20 = variant 7 forces the 64 x 12 regions).
+                const bool pairs_ok = (a.tile_rows == 17 || a.tile_rows == 19 || a.tile_rows == 20) && a.T >= 2 && !a.g_reg && !a.g_asum && !a.quad_keep && fits;
+                if (pairs_ok) {
+                    if (a.tile_rows == 19) launch_pair<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
+                    else launch_pair12<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
                     done = true;
                 }
                 // with the layer regularisers the pair kernel wins at every stack size (round 3, in process: 15.7 ms against 20.0 ms for
