@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""The playback model end to end: bake a small MPMeshVid (the `--small` shape of examples/pipeline.py: 180 x 320, D = 16, T = 12, 17 x 31 quads,
+synthetic weights and a synthetic quad map), render the same spiral from the float model and from the baked one (frames / s of
+`render_video.render_frames` for both, PSNR between the two frame sets), then write the viewer package (geometry.obj, static.png,
+dynamic/%04d.png, meta.json).  `--full`: 720p, D = 32, T = 50."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+
+def run(full=False, outdir=None, dev="cuda:0"):
+    from videoloop3d_amd import render_video as RV
+    from videoloop3d_amd import synth, tiles
+    from videoloop3d_amd.baked import bake
+    from videoloop3d_amd.export import save_viewer_package
+    from videoloop3d_amd.MPV import MPMeshVid
+    dev = torch.device(dev)
+    H, W, D, T, hv, wv, N = (720, 1280, 32, 50, 36, 64, 150) if full else (180, 320, 16, 12, 18, 32, 60)
+    args = types.SimpleNamespace(mpv_frm_num=T, mpv_isloop=True, mpi_h_scale=1.1, mpi_w_scale=1.1, mpi_d=D, mpi_h_verts=hv, mpi_w_verts=wv, atlas_grid_h=4,
+                                 init_std=0.02, rgb_mlp_type="direct", rgb_activate="sigmoid", alpha_activate="sigmoid", bg_color="", scale_invariant=True,
+                                 fp16=False, swd_patch_size=3, swd_patcht_size=3, swd_stride=2, swd_stridet=1, sparsity_loss_weight=0.0,
+                                 rgb_smooth_loss_weight=0.0, a_smooth_loss_weight=0.0, density_loss_weight=0.0, d_smooth_loss_weight=0.0,
+                                 optimizer="adam", lrate=0.1, lrate_decay=30)
+    K = np.array([[0.9 * W, 0, W / 2], [0, 0.9 * W, H / 2], [0, 0, 1]])
+    model = MPMeshVid(args, H, W, np.eye(4), K, 1.0, 100.0, device=dev).to(dev).eval()
+    keep = synth.hash_uniform((D, hv - 1, wv - 1), seed=31) < 0.4
+    dyn = keep & (synth.hash_uniform((D, hv - 1, wv - 1), seed=32) < 0.3)
+    with torch.no_grad():
+        model.stack.copy_(synth.make_plane_stack(*model.stack.shape[:4], seed=5, device=dev, alpha_bias=0.0))
+        tiles.cull_stack_(model.stack.data, keep.to(dev))
+    model._set_quad_maps(keep, dyn, dev)
+    model.is_sparse = model.has_dyn = True
+    sync = torch.cuda.synchronize
+    out = {}
+    sync(); t0 = time.perf_counter()
+    baked = bake(model)
+    sync(); t1 = time.perf_counter()
+    out["bake"] = {"seconds": t1 - t0, "float_MB": model.stack.numel() * 4 / 1e6, "baked_MB": baked.nbytes / 1e6}
+    ext = np.stack([np.eye(4, dtype=np.float32)] * N)      # a spiral of cameras around the reference view
+    for i in range(N):
+        a = 2 * np.pi * i / N
+        ext[i, :3, 3] = [0.05 * np.cos(a), 0.03 * np.sin(a), 0.01 * np.sin(2 * a)]
+    intr, rt = np.stack([K.astype(np.float32)] * N), np.arange(N) % T
+    frames = {}
+    for name, kw in (("float", {}), ("baked", {"baked": baked})):
+        RV.render_frames(model, H, W, ext[:4], intr[:4], rt[:4], **kw)      # untimed: code objects, allocator
+        sync(); t0 = time.perf_counter()
+        frames[name] = RV.render_frames(model, H, W, ext, intr, rt, **kw)
+        sync(); dt = time.perf_counter() - t0
+        out[name] = {"frames": N, "frames_per_s": N / dt, "ms_per_frame": dt / N * 1e3}
+    mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
+    out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
+    poses = np.linalg.inv(ext[:8])[:, :3, :4]              # eight of the cameras as the capture's views (camera-to-world)
+    with tempfile.TemporaryDirectory() as tmp:
+        where = outdir or tmp
+        sync(); t0 = time.perf_counter()
+        files = save_viewer_package(model, where, poses, intr[:8], np.array([1.0, 100.0]))
+        out["package"] = {"seconds": time.perf_counter() - t0, "files": len(files), "MB": sum(os.path.getsize(f) for f in files) / 1e6,
+                          "dir": outdir or "(temporary)"}
+    out["shape"] = f"{H}x{W}, D={D}, T={T}, planes {tuple(model.stack.shape[2:4])}, {float(keep.float().mean()):.0%} of the quads kept, {N} spiral frames"
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--out", default=None, help="directory for the viewer package (default: a temporary one)")
+    a = ap.parse_args()
+    import __graft_entry__ as g
+    g.build()
+    print(json.dumps(run(a.full, a.out)))

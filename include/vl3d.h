@@ -42,7 +42,9 @@ enum { VL3D_COORD_UTILS_MPI = 0, VL3D_COORD_AFFINE = 1, VL3D_COORD_AFFINE_PLANES
 enum { VL3D_BORDER_ZEROS = 0, VL3D_BORDER_HARDCUT = 1 };
 /* PRE: activate texels, then sample (sigmoid -> warp_homography chain).  POST: sample, then activate (MPV.py:425-435). */
 enum { VL3D_ACT_PRE = 0, VL3D_ACT_POST = 1 };
-enum { VL3D_F32 = 0, VL3D_F16 = 1 };
+enum { VL3D_F32 = 0, VL3D_F16 = 1, VL3D_U8 = 2 };
+/* VL3D_U8: the baked RGBA8 texels of the playback model (vl3d_bake_rgba8 / vl3d_render_fwd_baked below) -- accepted by
+ * vl3d_render_fwd_baked alone; every other entry point returns VL3D_EINVAL for it. */
 
 const char *vl3d_last_error(void);
 int vl3d_version(void);
@@ -63,7 +65,7 @@ typedef struct vl3d_render_desc {
     int32_t H, W;
     int32_t row0, col0;
     int32_t coord_mode, border_mode, act_order, rgb_act, alpha_act;
-    int32_t stack_dtype;   /* VL3D_F32 | VL3D_F16 (grad_stack has the same dtype) */
+    int32_t stack_dtype;   /* VL3D_F32 | VL3D_F16 (grad_stack has the same dtype); VL3D_U8: vl3d_render_fwd_baked only */
     float pixel_center;    /* 0 (utils_mpi) or 0.5 (pytorch3d pixel centres) */
     float sx, sy, ox, oy;  /* VL3D_COORD_AFFINE only */
     int32_t variant;       /* kernel selector for bitwise cross-checks between EXACT kernels; 0 = default.  Bits 0-3: backward (see
@@ -105,6 +107,26 @@ int vl3d_render_fwd_frames(const vl3d_render_desc *desc, const void *stack, int3
 int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
                                   const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
                                   vl3d_stream_t stream);
+
+/* Baked playback (csrc/vl3d_render_baked.hip).  The viewer package the reference exports (scripts/script_export_mesh.py:117-191) holds
+ * ACTIVATED 8-bit atlases, and a player filters those texels bilinearly after the activation -- not the picture the float kernels above
+ * compute (fp32 texels, interpolate, then activate).
+ *   vl3d_bake_rgba8: the one bake rule, per channel u8 = uint8(trunc(clip(act(s) * 255, 0, 255))) -- act = rgb_act (VL3D_ACT_*) for channels
+ *     0-2, alpha_act for channel 3; truncation, not rounding (script_export_mesh.py:130-138); straight RGBA, not premultiplied.  stack:
+ *     n_texels rgba texels, fp32 (VL3D_F32) or fp16 (VL3D_F16), 16-byte aligned; out: n_texels * 4 bytes.
+ *   vl3d_render_fwd_baked: frames frame0 .. frame0 + desc->T - 1 of a baked clip (D, T_alloc, Hs, Ws, 4) uint8, read in place.  Per covered
+ *     (pixel, plane) the value is the bilinear blend of the four decoded taps u8 / 255 with NO activation behind it, composited front to back
+ *     (SURVEY.md 9.3); rgb (T,H,W,3) and alpha (T,H,W) fp32 as vl3d_render_fwd_frames lays them out.  Sample position, hard cut, kept-quad
+ *     test, tile-exact quad offset and tap weights are the float forward's own device functions: the two renders agree on every pixel's
+ *     coverage.  desc: the planar convention only -- VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, pixel_center, sx / sy / ox / oy, stack_dtype =
+ *     VL3D_U8, uv_noise_seed = 0, variant = 0, Hs, Ws >= 2 (act_order / rgb_act / alpha_act are not read: the texels are activated already);
+ *     quad_keep NULL = a dense model, else vl3d_render_fwd_frames_culled's map, quad grid (negative: tile-exact layout), desc->cull_* window
+ *     and cull_scratch (vl3d_render_cull_scratch_bytes).  Anything else: VL3D_EINVAL, nothing launched.  Forward only. */
+int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stack_dtype, int32_t rgb_act, int32_t alpha_act, uint8_t *out,
+                    vl3d_stream_t stream);
+int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                          const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
+                          vl3d_stream_t stream);
 
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).

@@ -16,6 +16,7 @@ ACT = {"none": 0, "sigmoid": 1, "relu": 2, "clamp": 3, "abs": 4}
 COORD = {"utils_mpi": 0, "affine": 1, "affine_planes": 2}
 BORDER = {"zeros": 0, "hardcut": 1}
 ACT_ORDER = {"pre": 0, "post": 1}
+STACK_DTYPE = {"f32": 0, "f16": 1, "u8": 2}
 RHO = {"mse": 0, "abs": 1, "barron": 2}
 
 
@@ -71,6 +72,8 @@ SIGNATURES = {
     "vl3d_render_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_frames": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_frames_culled": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
+    "vl3d_bake_rgba8": ([_I64, _P, _I32, _I32, _I32, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),

@@ -1,0 +1,265 @@
+// The playback model (include/vl3d.h "Baked playback"): what the viewer package ships and what a player shows.
+//
+// The reference's export (scripts/script_export_mesh.py:117-191) activates the atlases, multiplies by 255, clips and truncates to 8 bits; a
+// player then filters those 8-bit texels bilinearly, AFTER the activation.  Two kernels:
+//   * bake_rgba8_k: the bake rule u8 = uint8(trunc(clip(act(s) * 255, 0, 255))), elementwise over the activation table of vl3d_common.h;
+//     one 16-byte load and one 4-byte store per fp32 texel (two texels per 16-byte load of an fp16 stack).
+//   * render_fwd_baked_k: the forward of MPV.py:351-454 on a (D, T_alloc, Hs, Ws, 4) uint8 stack.  Sample position, hard cut, kept-quad test,
+//     tile-exact quad offset and the tent weights are make_taps2 / plane_cull of vl3d_render_core.h -- the float forward's own device functions,
+//     called with the float forward's own arguments, so the two renders cannot disagree about the coverage of a pixel --, the plane list of a
+//     tile-culled model is cull_fwd_plan_k's.  What differs is the instruction stream behind the taps: a texel is 4 bytes, the two taps of a
+//     texel row are ONE 8-byte load (the base tap's x0 <= Ws - 2), a channel is a byte of that word ((w >> 8k) & 0xff: v_cvt_f32_ubyte<k>),
+//     the 1 / 255 of the decode is folded into the four blend weights once per plane, and nothing is activated.  The launch shape is the float
+//     forward's: 64 x 8 pixels per workgroup, XCD remap, two frames per thread for T >= 2 (an odd tail frame composited twice, stored once).
+// Forward only: a baked model is not trained.
+#include "vl3d_render_core.h"
+
+using vl3d_render_detail::RenderArgs;
+
+namespace {
+
+typedef unsigned u2w __attribute__((ext_vector_type(2)));
+typedef u2w u2w_a4 __attribute__((aligned(4)));      // two 4-byte texels of a row: 4-byte aligned (x0 may be odd)
+
+// ---- bake ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float act_rt(int act, float v) {      // (the activation is uniform: a scalar branch)
+    switch (act) {
+    case VL3D_ACT_SIGMOID: return act_fwd<VL3D_ACT_SIGMOID>(v);
+    case VL3D_ACT_RELU: return act_fwd<VL3D_ACT_RELU>(v);
+    case VL3D_ACT_CLAMP: return act_fwd<VL3D_ACT_CLAMP>(v);
+    case VL3D_ACT_ABS: return act_fwd<VL3D_ACT_ABS>(v);
+    default: return v;
+    }
+}
+__device__ __forceinline__ unsigned bake_channel(float a) {      // trunc(clip(a * 255, 0, 255)); a NaN bakes to 0 (fmaxf returns the number)
+    return (unsigned)fminf(fmaxf(a * 255.0f, 0.0f), 255.0f);
+}
+__device__ __forceinline__ unsigned bake_texel(f4 s, int ract, int aact) {
+    return bake_channel(act_rt(ract, s.x)) | bake_channel(act_rt(ract, s.y)) << 8 | bake_channel(act_rt(ract, s.z)) << 16 |
+           bake_channel(act_rt(aact, s.w)) << 24;
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256) void bake_rgba8_k(int64_t n, const char *__restrict__ stack, int ract, int aact, unsigned *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // one 16-byte load: a texel (fp32) or two (fp16)
+    if constexpr (F16) {
+        const int64_t t0 = i * 2;
+        if (t0 >= n) return;
+        if (t0 + 1 < n) {
+            typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+            const h8 v = *reinterpret_cast<const h8 *>(stack + t0 * 8);
+            out[t0] = bake_texel(f4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}, ract, aact);
+            out[t0 + 1] = bake_texel(f4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]}, ract, aact);
+        } else {      // odd texel count: the last texel alone (8 bytes)
+            out[t0] = bake_texel(__builtin_convertvector(*reinterpret_cast<const h4 *>(stack + t0 * 8), f4), ract, aact);
+        }
+    } else {
+        if (i >= n) return;
+        out[i] = bake_texel(*reinterpret_cast<const f4 *>(stack + i * 16), ract, aact);
+    }
+}
+
+// ---- render -------------------------------------------------------------------------------------------------------------------------------
+// the four taps of a sample: texels (x0, x0 + 1) of rows y0 and y0 + 1, one 8-byte load per row against a uniform plane base
+struct BakedTaps { u2w r0, r1; };
+__device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, const Taps2 &t, unsigned row_b) {
+    const size_t o = (size_t)(t.off >> 2);      // make_taps2 gives the byte offset of 16-byte texels
+    return BakedTaps{*reinterpret_cast<const u2w_a4 *>(plane + o), *reinterpret_cast<const u2w_a4 *>(plane + row_b + o)};
+}
+template <int K>
+__device__ __forceinline__ float chan(unsigned w) { return (float)((w >> (8 * K)) & 0xffu); }
+// bilinear blend of the decoded taps; w255 = the tent weights * (1 / 255).  Associated like shade2: tap 3 first, then 2, 1, 0.
+template <int K>
+__device__ __forceinline__ float blend(const BakedTaps &v, f4 w255) {
+    return fmaf(chan<K>(v.r0.x), w255[0], fmaf(chan<K>(v.r0.y), w255[1], fmaf(chan<K>(v.r1.x), w255[2], chan<K>(v.r1.y) * w255[3])));
+}
+
+template <int NF, bool CULL>
+__global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y) {
+    static_assert(NF == 1 || NF == 2, "one frame or a frame pair per thread");
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_x = b % tiles_x, rest = b / tiles_x;
+    const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;
+    const bool has1 = NF == 2 && t0 + 1 < a.T;      // odd T: the last pair composites frame t0 twice and stores it once
+    const int x = tile_x * 64 + (threadIdx.x & 63);
+    const int y = tile_y * 8 + (threadIdx.x >> 6);
+    if (x >= a.W || y >= a.H) return;
+    const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
+    const unsigned row_b = (unsigned)a.Ws * 4u;
+    const size_t frame_b = (size_t)a.Hs * a.Ws * 4;
+    const size_t plane_stride_b = (size_t)a.Tstride * frame_b;
+    const char *base[NF];
+    base[0] = reinterpret_cast<const char *>(a.stack) + (size_t)t0 * frame_b;
+    if constexpr (NF == 2) base[1] = base[0] + (has1 ? frame_b : 0);
+    float Tr[NF], cr[NF], cg[NF], cb[NF], A[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) { Tr[f] = 1.0f; cr[f] = cg[f] = cb[f] = A[f] = 0.0f; }
+    BakedTaps vA[NF], vB[NF];
+    // The fused multiply-adds are spelt out and nothing else may be contracted: left to -ffp-contract=fast, hipcc fuses cb += w * c in the
+    // frame-pair kernel and not in the one-frame kernel (where it packs the add with A += w instead), and a frame would depend, in its last
+    // bit, on the length of the run it is rendered in.
+    auto composite = [&](const Taps2 &t, const BakedTaps *v) {
+#pragma clang fp contract(off)
+        const f4 w255 = t.w * (1.0f / 255.0f);      // the decode's 1 / 255, once per plane for every channel and frame
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const float al = blend<3>(v[f], w255) * t.cov;      // uncovered: a = 0 -> the plane drops out of the composite
+            const float w = al * Tr[f];
+            cr[f] = fmaf(w, blend<0>(v[f], w255), cr[f]); cg[f] = fmaf(w, blend<1>(v[f], w255), cg[f]); cb[f] = fmaf(w, blend<2>(v[f], w255), cb[f]);
+            A[f] += w;
+            Tr[f] *= (1.0f - al);
+        }
+    };
+    auto fetch = [&](int d, Taps2 &t, BakedTaps *v) {
+        float h[VL3D_HN];
+        load_uniform(a.homos + VL3D_HS * d, h);
+        if constexpr (CULL) t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
+        else t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
+#pragma unroll
+        for (int f = 0; f < NF; ++f) v[f] = load_baked(base[f] + (size_t)d * plane_stride_b, t, row_b);
+        asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
+    };
+    Taps2 tA, tB;
+    if constexpr (CULL) {
+        // the workgroup's plane list (cull_fwd_plan_k): two 64-bit words in SGPRs, scalar bit scans; a pixel inside a culled quad is uncovered
+        // (make_taps2), so walking only the listed planes changes no result
+        const unsigned long long *mk = a.cull_masks + (size_t)(tile_y * tiles_x + tile_x) * 2;
+        unsigned long long m0 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[0];
+        unsigned long long m1 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[1];
+        auto next = [&]() {
+            int d = -1;
+            if (m0) { d = __builtin_ctzll(m0); m0 &= m0 - 1; }
+            else if (m1) { d = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
+            return d;
+        };
+        int dA = next();
+        if (dA >= 0) {
+            fetch(dA, tA, vA);
+            for (;;) {
+                const int dB = next();
+                fetch(dB < 0 ? dA : dB, tB, vB);      // unconditional prefetch (re-reads the current plane past the end)
+                composite(tA, vA);
+                if (dB < 0) break;
+                const int dC = next();
+                fetch(dC < 0 ? dB : dC, tA, vA);
+                composite(tB, vB);
+                if (dC < 0) break;
+                dA = dC;
+            }
+        }
+    } else {
+        // two register sets (A / B): the taps of plane d + 1 are in flight while plane d is composited; the prefetch is unconditional
+        // (past the end it re-reads the last plane), as in the float forward
+        fetch(0, tA, vA);
+        for (int d = 0;; d += 2) {
+            fetch(min(d + 1, a.D - 1), tB, vB);
+            composite(tA, vA);
+            if (d + 1 >= a.D) break;
+            fetch(min(d + 2, a.D - 1), tA, vA);
+            composite(tB, vB);
+            if (d + 2 >= a.D) break;
+        }
+    }
+    size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
+    a.rgb[pix * 3 + 0] = cr[0]; a.rgb[pix * 3 + 1] = cg[0]; a.rgb[pix * 3 + 2] = cb[0];
+    a.alpha[pix] = A[0];
+    if constexpr (NF == 2) {
+        if (has1) {
+            pix += (size_t)a.H * a.W;
+            a.rgb[pix * 3 + 0] = cr[1]; a.rgb[pix * 3 + 1] = cg[1]; a.rgb[pix * 3 + 2] = cb[1];
+            a.alpha[pix] = A[1];
+        }
+    }
+}
+
+template <int NF>
+void launch_baked(const RenderArgs &a, hipStream_t s) {
+    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
+    const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
+    if (a.quad_keep) {      // tile culling: the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
+        auto *masks = const_cast<unsigned long long *>(a.cull_masks);
+        (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
+        const int n = tiles_x * tiles_y * a.D;
+        hipLaunchKernelGGL((cull_fwd_plan_k<VL3D_COORD_AFFINE>), dim3((n + 255) / 256), dim3(256), 0, s, a, 8, tiles_x, tiles_y, masks);
+        hipLaunchKernelGGL((render_fwd_baked_k<NF, true>), grid, block, 0, s, a, tiles_x, tiles_y);
+        return;
+    }
+    hipLaunchKernelGGL((render_fwd_baked_k<NF, false>), grid, block, 0, s, a, tiles_x, tiles_y);
+}
+
+bool known_act(int act) { return act >= VL3D_ACT_NONE && act <= VL3D_ACT_ABS; }
+
+}  // namespace
+
+extern "C" int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stack_dtype, int32_t rgb_act, int32_t alpha_act, uint8_t *out,
+                               vl3d_stream_t stream) {
+    VL3D_REQUIRE(n_texels > 0 && n_texels < (1ll << 38), "vl3d_bake_rgba8: texel count out of range");
+    VL3D_REQUIRE(stack && out, "vl3d_bake_rgba8: null pointer");
+    VL3D_REQUIRE(stack_dtype == VL3D_F32 || stack_dtype == VL3D_F16, "vl3d_bake_rgba8: stack_dtype must be VL3D_F32 or VL3D_F16");
+    VL3D_REQUIRE(known_act(rgb_act) && known_act(alpha_act), "vl3d_bake_rgba8: unknown activation");
+    VL3D_REQUIRE(((uintptr_t)stack & 15) == 0 && ((uintptr_t)out & 3) == 0, "vl3d_bake_rgba8: stack must be 16-byte aligned, out 4-byte aligned");
+    const bool f16 = stack_dtype == VL3D_F16;
+    const int64_t threads = f16 ? (n_texels + 1) / 2 : n_texels;
+    const dim3 grid((unsigned)ceil_div64(threads, 256)), block(256);
+    if (f16) hipLaunchKernelGGL((bake_rgba8_k<true>), grid, block, 0, (hipStream_t)stream, n_texels, (const char *)stack, rgb_act, alpha_act, (unsigned *)out);
+    else hipLaunchKernelGGL((bake_rgba8_k<false>), grid, block, 0, (hipStream_t)stream, n_texels, (const char *)stack, rgb_act, alpha_act, (unsigned *)out);
+    VL3D_CHECK_LAUNCH();
+    return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
+                                     vl3d_stream_t stream) {
+    VL3D_REQUIRE(desc != nullptr, "null render desc");
+    VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked: no kernel variants (desc->variant = 0)");
+    VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked: non-positive render dims");
+    // a row's two taps are one 8-byte load, the two rows a constant step apart: planes of at least 2 x 2 texels
+    VL3D_REQUIRE(desc->Hs >= 2 && desc->Ws >= 2, "vl3d_render_fwd_baked: planes of at least 2 x 2 texels");
+    VL3D_REQUIRE(desc->Hs < (1 << 24) && desc->Ws < (1 << 24) && (int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32),
+                 "vl3d_render_fwd_baked: plane too large for 32-bit tap offsets");
+    VL3D_REQUIRE(desc->stack_dtype == VL3D_U8, "vl3d_render_fwd_baked: stack_dtype must be VL3D_U8 (the baked RGBA8 texels of vl3d_bake_rgba8)");
+    VL3D_REQUIRE(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT,
+                 "vl3d_render_fwd_baked: the planar MPV convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
+    VL3D_REQUIRE(desc->uv_noise_seed == 0, "vl3d_render_fwd_baked: add_uv_noise is a training switch (uv_noise_seed = 0)");
+    VL3D_REQUIRE(baked && homos && rgb && alpha, "vl3d_render_fwd_baked: null pointer");
+    VL3D_REQUIRE(((uintptr_t)baked & 3) == 0, "vl3d_render_fwd_baked: the texels must be 4-byte aligned");
+    VL3D_REQUIRE(T_alloc > 0 && frame0 >= 0 && frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
+    RenderArgs a{};
+    a.D = desc->D; a.T = desc->T; a.Hs = desc->Hs; a.Ws = desc->Ws; a.H = desc->H; a.W = desc->W;
+    a.Tstride = T_alloc;
+    a.row0 = desc->row0; a.col0 = desc->col0;
+    a.pc = desc->pixel_center; a.sx = desc->sx; a.sy = desc->sy; a.ox = desc->ox; a.oy = desc->oy;
+    a.stack = reinterpret_cast<const float *>(baked + (size_t)frame0 * desc->Hs * desc->Ws * 4);
+    a.homos = homos; a.rgb = rgb; a.alpha = alpha;
+    if (quad_keep) {
+        VL3D_REQUIRE((QH > 0 && QW > 0) || (QH < 0 && QW < 0), "vl3d_render_fwd_baked: empty quad grid (both positive, or both negative for the tile-exact layout)");
+        VL3D_REQUIRE(desc->D <= 128, "tile culling supports at most 128 planes");
+        VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
+        const bool win = desc->cull_Hs > 0 && desc->cull_Ws > 0;
+        VL3D_REQUIRE((desc->cull_Hs == 0 && desc->cull_Ws == 0) ||
+                         (win && desc->cull_row0 >= 0 && desc->cull_col0 >= 0 && desc->cull_row0 + desc->Hs <= desc->cull_Hs && desc->cull_col0 + desc->Ws <= desc->cull_Ws),
+                     "vl3d_render_fwd_baked: the stack window (cull_row0, cull_col0) + (Hs, Ws) leaves the plane (cull_Hs, cull_Ws)");
+        a.quad_keep = quad_keep;
+        a.cull_masks = (const unsigned long long *)cull_scratch;
+        a.q_Hs = win ? desc->cull_Hs : desc->Hs;
+        a.q_Ws = win ? desc->cull_Ws : desc->Ws;
+        a.q_x0 = win ? (float)desc->cull_col0 : 0.0f;
+        a.q_y0 = win ? (float)desc->cull_row0 : 0.0f;
+        if (QH < 0) {      // tile-exact layout (include/vl3d.h): |QH| x |QW| tiles, every quad owning its border texels
+            VL3D_REQUIRE(a.q_Hs % (-QH) == 0 && a.q_Ws % (-QW) == 0 && a.q_Hs / (-QH) >= 2 && a.q_Ws / (-QW) >= 2,
+                         "tile-exact layout: the plane must be |QH| x |QW| whole tiles of at least 2 x 2 texels");
+            a.QH = -QH; a.QW = -QW;
+            a.q_th = a.q_Hs / a.QH; a.q_tw = a.q_Ws / a.QW;
+            a.q_inv_cw = 1.0f / (float)(a.q_tw - 1);
+            a.q_inv_ch = 1.0f / (float)(a.q_th > 1 ? a.q_th - 1 : 1);
+        } else {
+            a.QH = QH; a.QW = QW;
+            a.q_inv_cw = (float)QW / (float)(a.q_Ws - 1);
+            a.q_inv_ch = (float)QH / (float)(a.q_Hs - 1);
+        }
+    }
+    if (desc->T >= 2) launch_baked<2>(a, (hipStream_t)stream);
+    else launch_baked<1>(a, (hipStream_t)stream);
+    VL3D_CHECK_LAUNCH();
+    return VL3D_OK;
+}

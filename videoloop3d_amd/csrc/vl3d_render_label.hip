@@ -72,6 +72,7 @@ int check(const vl3d_render_desc *d, const char *who) {
     if (vl3d_check_variant(d->variant) != VL3D_OK) return VL3D_EINVAL;
     VL3D_REQUIRE(d->D > 0 && d->T > 0 && d->Hs > 0 && d->Ws > 0 && d->H > 0 && d->W > 0 && d->T <= 65535, "non-positive render dims");
     VL3D_REQUIRE((int64_t)d->Hs * d->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
+    VL3D_REQUIRE(d->stack_dtype == VL3D_F32 || d->stack_dtype == VL3D_F16, "stack_dtype must be VL3D_F32 or VL3D_F16 (baked VL3D_U8 texels: vl3d_render_fwd_baked)");
     if (!(d->coord_mode == VL3D_COORD_AFFINE && d->border_mode == VL3D_BORDER_HARDCUT && d->act_order == VL3D_ACT_POST && d->stack_dtype == VL3D_F32)) {
         vl3d_set_error((std::string(who) + ": the planar MPI convention only -- (affine, hardcut, post), fp32 stack (MPI.py:452-594)").c_str());
         return VL3D_EUNSUPPORTED;

@@ -12,6 +12,10 @@ of the reference produce (MPV.py:290-341), from the dense plane stack + quad map
   save_texture(model, prefix)   -> prefix_static.png (activated rgba) and prefix_dyn_%04d.png (activated rgb * alpha per frame).
                                    The reference writes the dynamic frames as one .mov through imageio/ffmpeg (MPV.py:341), which this
                                    image does not have: the same frames go out as PNG files instead.
+  save_viewer_package(model, outdir, poses, intrins, bds)
+                                -> the package a web player loads (scripts/script_export_mesh.py:76-191): geometry.obj (static + dynamic mesh,
+                                   vertex colours, faces far to near), static.png / dynamic/%04d.png (straight RGBA, baked by baked.bake_texels
+                                   -- the one bake rule, shared with the on-device playback model) and meta.json (camera and clip facts).
 The reader of this layout is videoloop3d_amd.tiles.stack_from_reference_state (used by MPMeshVid.init_from_mpi): export -> read
 round-trips (tests/test_export_cpu.py).  Unpinned like every statement about the reference's packed format: no checkpoint ships
 with the reference and its MPI.py / MPV.py cannot be imported here (oracle/ckpt_oracle.py restates the packing for the tests).
@@ -247,3 +251,80 @@ def save_texture(model, prefix, state=None):
             list(ex.map(write_png, names, frames))
         out.extend(names)
     return out
+
+
+def _viewer_meta(poses, intrins, bds, frame_count, fps):
+    """script_export_mesh.py:88-111: what the player needs to know about the cameras -- vertical field of view of the mean pinhole, depth range,
+    the views' mean up axis (y flipped: the player's y points up), the point the spiral looks at (3 : 1 in inverse depth between 0.9 x near
+    and 5 x far, as render_video.load_llff_poses) and how far the viewer may move per axis (0.8 x the largest camera offset)."""
+    poses, intrins, bds = np.asarray(poses, dtype=np.float64), np.asarray(intrins, dtype=np.float64), np.asarray(bds, dtype=np.float64)
+    up = poses[:, :3, 1].sum(0)
+    up = up / np.linalg.norm(up)
+    look_near, look_far = bds.min() * .9, bds.max() * 5.
+    return {"fps": fps,
+            "fov": float(np.degrees(2 * np.arctan(intrins[:, 1, 2].mean() / intrins[:, 0, 0].mean()))),
+            "frame_count": int(frame_count),
+            "near": float(bds.min()), "far": float(bds.max()),
+            "up": [float(up[0]), float(-up[1]), float(up[2])],
+            "lookat": [0, 0, float(1. / (.25 / look_near + .75 / look_far))],
+            "limit": (np.abs(poses[:, :3, 3]).max(0) * 0.8).tolist()}
+
+
+def _write_viewer_obj(path, sd):
+    """geometry.obj of the package (script_export_mesh.py:155-184): the static mesh (vertex colour 1,0,0) and the dynamic mesh (0,1,0) in one
+    file -- unused vertices dropped per mesh, UVs at texel centres of their own atlas, the dynamic indices shifted behind the static ones --
+    with the faces sorted far to near by the depth of their first vertex (the player blends them in file order)."""
+    verts = sd["_verts"].numpy().reshape(-1, 3)
+    v_all, uv_all, f_all, uvf_all = [], [], [], []
+    nv = nuv = 0
+    for faces_k, uvs_k, uvf_k, atlas_k, colour in (("faces", "uvs", "uvfaces", "atlas", (1.0, 0.0, 0.0)),
+                                                   ("faces_dyn", "uvs_dyn", "uvfaces_dyn", "atlas_dyn", (0.0, 1.0, 0.0))):
+        faces = sd[faces_k].numpy().reshape(-1, 3)
+        if len(faces) == 0:
+            continue
+        v, f = _cull_unused(verts, faces)
+        uv, uvf = _cull_unused(normalize_uv(sd[uvs_k].numpy(), sd[atlas_k].shape[2], sd[atlas_k].shape[3]), sd[uvf_k].numpy().reshape(-1, 3))
+        v_all.append(np.concatenate([v, np.broadcast_to(np.array(colour), v.shape)], axis=1))
+        uv_all.append(uv)
+        f_all.append(f + nv)
+        uvf_all.append(uvf + nuv)
+        nv, nuv = nv + len(v), nuv + len(uv)
+    v_all, uv_all = np.concatenate(v_all), np.concatenate(uv_all)
+    f_all, uvf_all = np.concatenate(f_all), np.concatenate(uvf_all)
+    order = np.argsort(-v_all[f_all[:, 0], 2], kind="stable")
+    with open(path, "w") as f:
+        for p in v_all:
+            f.write(f"v {p[0]} {p[1]} {p[2]} {p[3]} {p[4]} {p[5]}\n")
+        for uv in uv_all:
+            f.write(f"vt {uv[0]} {uv[1]}\n")
+        for face, uvface in zip(f_all[order] + 1, uvf_all[order] + 1):
+            f.write(f"f {face[0]}/{uvface[0]} {face[1]}/{uvface[1]} {face[2]}/{uvface[2]}\n")
+
+
+@torch.no_grad()
+def save_viewer_package(model, outdir, poses, intrins, bds, fps=25):
+    """scripts/script_export_mesh.py:76-191: the viewer package of `model` (MPMeshVid, dense or sparsified) in `outdir` -- geometry.obj,
+    static.png, dynamic/%04d.png, meta.json; poses [V,3,4] camera-to-world, intrins [V,3,3], bds (near, far) as render_video.load_llff_poses
+    returns them.  The PNGs are the atlases of reference_state_dict(model) through baked.bake_texels: activated, times 255, clipped, truncated,
+    straight RGBA -- the texels a player filters and baked.BakedMPV renders from.  Returns the paths written."""
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    from .baked import bake_texels
+    if hasattr(model, "_flush_deferred_updates"):
+        model._flush_deferred_updates()
+    sd = reference_state_dict(model)
+    if "atlas_dyn" not in sd:
+        raise RuntimeError("save_viewer_package: a video model (MPMeshVid) with its dynamic atlas")
+    os.makedirs(os.path.join(outdir, "dynamic"), exist_ok=True)
+    acts = (model.args.rgb_activate, model.args.alpha_activate)
+    static = bake_texels(sd["atlas"][0].permute(1, 2, 0).float().cpu(), *acts).numpy()
+    frames = bake_texels(sd["atlas_dyn"].permute(0, 2, 3, 1).float().cpu(), *acts).numpy()
+    meta = _viewer_meta(poses, intrins, bds, len(frames), fps)
+    out = [os.path.join(outdir, "meta.json"), os.path.join(outdir, "geometry.obj"), os.path.join(outdir, "static.png")]
+    with open(out[0], "w") as f:
+        f.write(json.dumps(meta, indent=4))
+    _write_viewer_obj(out[1], sd)
+    names = [os.path.join(outdir, "dynamic", f"{i:04d}.png") for i in range(len(frames))]
+    with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(frames) + 1))) as ex:      # (zlib releases the interpreter lock)
+        list(ex.map(write_png, [out[2]] + names, [static] + list(frames)))
+    return out + names

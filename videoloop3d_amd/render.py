@@ -343,6 +343,54 @@ def render_frame_run(stack, frame0, nframes, homos, H, W, spec: RenderSpec = Ren
     return rgb, alpha
 
 
+def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, quad_keep=None):
+    """render_frame_run on the BAKED texels of a playback model (videoloop3d_amd/baked.py; vl3d_render_fwd_baked): `baked` [D,T,Hs,Ws,4] uint8 --
+    activated, times 255, truncated (baked.bake_texels) -- filtered bilinearly AFTER the activation, as a player filters the exported 8-bit
+    atlases; nothing is activated behind the blend, so spec.rgb_act / alpha_act / act_order are not read.  Coverage (hard cut, culled quads,
+    tile-exact layout) is decided by the float kernels' own code.  The planar convention only (RenderSpec.mpv()); forward only -- a baked
+    model is not trained: inputs that require a gradient are refused.  -> (rgb [n,H,W,3], alpha [n,H,W]) float32."""
+    L.check_cuda(baked, homos)
+    if baked.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
+        raise RuntimeError("render_frame_run_baked: baked texels have no backward (train the float model, then bake it)")
+    if baked.dtype != torch.uint8 or baked.dim() != 5 or baked.shape[4] != 4 or not baked.is_contiguous():
+        raise RuntimeError("render_frame_run_baked: a contiguous uint8 clip [D,T,Hs,Ws,4] (baked.bake_texels)")
+    if spec.coord_mode != "affine" or spec.border != "hardcut":
+        raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
+    D, T = baked.shape[:2]
+    if not (0 <= frame0 and nframes >= 1 and frame0 + nframes <= T):
+        raise RuntimeError(f"render_frame_run_baked: frames {frame0} .. {frame0 + nframes - 1} leave the clip of {T}")
+    if homos.shape != (D, 3, 3):
+        raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
+    if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
+        raise RuntimeError("RenderSpec.tile (tile-exact layout) belongs to a tile-culled model: pass its quad_keep map")
+    homos = homos.detach().to(torch.float32).contiguous()
+    desc = _desc(baked, H, W, spec, 0, 0)
+    desc.T = int(nframes)
+    desc.stack_dtype = L.STACK_DTYPE["u8"]
+    dev = baked.device
+    if out is None:
+        rgb = torch.empty((nframes, H, W, 3), dtype=torch.float32, device=dev)
+        alpha = torch.empty((nframes, H, W), dtype=torch.float32, device=dev)
+    else:
+        rgb, alpha = out
+        if tuple(rgb.shape) != (nframes, H, W, 3) or tuple(alpha.shape) != (nframes, H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
+            raise RuntimeError("render_frame_run_baked: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
+    qk, grid, cull = None, (0, 0), None
+    if quad_keep is not None:
+        L.check_cuda(quad_keep)
+        if quad_keep.dim() != 3 or quad_keep.shape[0] != D:
+            raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {D}, got {tuple(quad_keep.shape)}")
+        from .tiles import as_u8
+        qk = as_u8(quad_keep)
+        grid = _qgrid(qk, spec)
+    with torch.cuda.device(dev):
+        if qk is not None:
+            cull = torch.empty((int(L.lib().vl3d_render_cull_scratch_bytes(desc)) + 3) // 4, dtype=torch.float32, device=dev)
+        L.check(L.lib().vl3d_render_fwd_baked(desc, L.ptr(baked), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *grid, L.ptr(cull), L.ptr(rgb),
+                                              L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked")
+    return rgb, alpha
+
+
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,
                   fused_adam=None):
     """stack (D,T,Hs,Ws,4) pre-activation fp32 (plane 0 = nearest), homos [D,3,3] (target pixel -> plane pixel).

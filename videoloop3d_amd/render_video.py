@@ -161,13 +161,19 @@ def to8b(x):
     return (255 * x.clamp(0, 1)).to(torch.uint8)
 
 
-def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, chunk):
+def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, chunk, baked=None):
     """render_frames for a dense model on the device: the plane homographies of every DISTINCT camera of the path are formed up front (the
     module's own `plane_homographies`, the same bits as its forward) and uploaded in ONE copy, every frame -- or run of consecutive frames of
     one camera -- is rendered where it lies in the clip (render.render_frame_run: no gather of stack[:, ts]), straight into a chunk buffer
     that is converted to uint8 once (a sparsified model with its quad map; a packed one through its block table).  None when the model is
-    not one this path serves (atlas_exact / CPU)."""
-    from .render import render_frame_run, render_planes_packed
+    not one this path serves (atlas_exact / CPU).  `baked` (baked.BakedMPV): the frames come from ITS uint8 texels, quad map, geometry,
+    camera and background through the same runs (render.render_frame_run_baked); the float model is not read."""
+    from .render import render_frame_run, render_frame_run_baked
+    if baked is not None:
+        if baked.bg_color == "random":
+            return None
+        return _in_place_runs(baked.camera, baked.texels, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
+                              render_t, chunk, render_frame_run_baked)
     packed = getattr(module, "packed", None)
     stack = module.stack_pool.data if packed is not None else getattr(module, "stack", None)
     if (stack is None or not stack.is_cuda or not stack.is_contiguous() or module.atlas_exact or module.training
@@ -175,22 +181,30 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
         return None
     if getattr(module, "_window_opt", None) is not None:
         module._flush_deferred_updates()
+    qk = module.quad_keep.to(torch.uint8).contiguous() if (module.is_sparse and getattr(module, "quad_keep", None) is not None) else None
+    return _in_place_runs(module, stack, packed, qk, module.spec, module.args.bg_color, H, W, view_extrins, view_intrins, render_t, chunk,
+                          render_frame_run)
+
+
+def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run):
+    """the frame loop of _render_frames_in_place: `camera` gives the homographies (`plane_homographies`, `ref_extrin`), `run` renders a run of
+    consecutive frames of the dense clip `stack` in place (render_frame_run / render_frame_run_baked); `packed`: the pool's layout instead."""
+    from .render import render_planes_packed
     n, T, dev = len(render_t), (packed.T if packed is not None else stack.shape[1]), stack.device
     if packed is not None:      # a packed model reads its pool through the block table (vl3d_render_fwd_packed): the frame indices go up once
         from .tiles import CULLED_ALPHA
         t_dev = torch.as_tensor(render_t.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-    qk = module.quad_keep.to(torch.uint8).contiguous() if (module.is_sparse and getattr(module, "quad_keep", None) is not None) else None
-    ref_inv = module._on(view_extrins.device, "ref_extrin")[None, ...].inverse().to(view_extrins.dtype)
+    ref_inv = camera._on(view_extrins.device, "ref_extrin")[None, ...].inverse().to(view_extrins.dtype)
     cams, cam_of = {}, []
     for i in range(n):
         key = (view_extrins[i].numpy().tobytes(), view_intrins[i].numpy().tobytes())
         if key not in cams:
-            cams[key] = (len(cams), module.plane_homographies(view_extrins[i:i + 1] @ ref_inv, view_intrins[i:i + 1]))
+            cams[key] = (len(cams), camera.plane_homographies(view_extrins[i:i + 1] @ ref_inv, view_intrins[i:i + 1]))
         cam_of.append(cams[key][0])
     homos = torch.stack([h for _, h in sorted(cams.values(), key=lambda c: c[0])]).pin_memory().to(dev, non_blocking=True)      # [cameras, D, 3, 3]
     bg = None
-    if len(module.args.bg_color) > 0:                                                        # MPV.py:455-461
-        bg = torch.tensor([float(v) for v in module.args.bg_color.split('#')], dtype=torch.float32, device=dev)
+    if len(bg_color) > 0:                                                                    # MPV.py:455-461
+        bg = torch.tensor([float(v) for v in bg_color.split('#')], dtype=torch.float32, device=dev)
     out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
     chunk = max(1, min(int(chunk), n))
     rgb, alpha = torch.empty((chunk, H, W, 3), dtype=torch.float32, device=dev), torch.empty((chunk, H, W), dtype=torch.float32, device=dev)
@@ -206,10 +220,10 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
             if not (0 <= t0 and t0 + (j - i) <= T):
                 raise IndexError(f"frame index {t0} .. {t0 + j - i - 1} outside the clip of {T} frames")
             if packed is not None:
-                render_planes_packed(packed, stack, render_t[i:j].tolist(), homos[cam_of[i]], H, W, module.spec, qk, CULLED_ALPHA,
+                render_planes_packed(packed, stack, render_t[i:j].tolist(), homos[cam_of[i]], H, W, spec, qk, CULLED_ALPHA,
                                      out=(rgb[i - c0:j - c0], alpha[i - c0:j - c0]), frames_dev=t_dev[i:j])
             else:
-                render_frame_run(stack, t0, j - i, homos[cam_of[i]], H, W, module.spec, out=(rgb[i - c0:j - c0], alpha[i - c0:j - c0]), quad_keep=qk)
+                run(stack, t0, j - i, homos[cam_of[i]], H, W, spec, out=(rgb[i - c0:j - c0], alpha[i - c0:j - c0]), quad_keep=qk)
             i = j
         m = c1 - c0
         x = rgb[:m]
@@ -221,12 +235,14 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
 
 
 @torch.no_grad()
-def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64, in_place=True):
+def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64, in_place=True, baked=None):
     """script_render_video.py:129-139: `nerf(H, W, extrin, intrin, t)` in eval mode for every output frame -> uint8 [N,H,W,3] on the
     model's device.  A dense model on the device renders every frame where it lies in the clip, with the path's homographies uploaded once
     (`_render_frames_in_place`: 720p, D = 32, T = 50 along a spiral 1430 -> several thousand frames / s; `in_place=False` keeps the loop below).
     Otherwise runs of consecutive frames with one camera are rendered by ONE call of the module with `ts` a vector (at most `max_batch` frames:
-    the frames of a call are resident together)."""
+    the frames of a call are resident together).
+    `baked` (baked.BakedMPV, the product of baked.bake(model)): the frames of the PLAYBACK model -- its 8-bit texels filtered after the
+    activation, what the exported viewer package shows -- through the same run logic; the float stack is not read."""
     module = getattr(nerf, "module", nerf)
     was_training = module.training
     nerf.eval()
@@ -236,7 +252,9 @@ def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64
     # script_render_video.py:129 loops over the POSES: a `--t` range longer than the camera path renders len(view_poses) frames
     render_t = render_t[:len(view_extrins)]
     res = None
-    if in_place and hasattr(module, "plane_homographies") and len(render_t) > 0:
+    if baked is not None and len(render_t) > 0 and (in_place or baked.bg_color != "random"):
+        res = _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, max_batch, baked=baked)
+    elif in_place and hasattr(module, "plane_homographies") and len(render_t) > 0:
         res = _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, max_batch)
     if res is None:
         out, i, n = [], 0, len(render_t)
@@ -244,7 +262,10 @@ def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64
             j = i + 1
             while j < n and j - i < max_batch and torch.equal(view_extrins[j], view_extrins[i]) and torch.equal(view_intrins[j], view_intrins[i]):
                 j += 1
-            rgb, _ = nerf(H, W, view_extrins[i:i + 1], view_intrins[i:i + 1], torch.as_tensor(render_t[i:j]))
+            if baked is not None:      # (a random background: one draw per call, the model's own render)
+                rgb, _ = baked.render(H, W, view_extrins[i:i + 1], view_intrins[i:i + 1], torch.as_tensor(render_t[i:j]))
+            else:
+                rgb, _ = nerf(H, W, view_extrins[i:i + 1], view_intrins[i:i + 1], torch.as_tensor(render_t[i:j]))
             out.append(to8b(rgb.permute(0, 2, 3, 1)))
             i = j
         res = torch.cat(out, 0)
