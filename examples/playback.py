@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The playback model end to end: bake a small MPMeshVid (the `--small` shape of examples/pipeline.py: 180 x 320, D = 16, T = 12, 17 x 31 quads,
-synthetic weights and a synthetic quad map), render the same spiral from the float model and from the baked one (frames / s of
-`render_video.render_frames` for both, PSNR between the two frame sets), then write the viewer package (geometry.obj, static.png,
+synthetic weights and a synthetic quad map), render the same spiral from the float model, from the baked one and from the baked POOL
+(`baked.bake_pool`: static blocks once, dynamic blocks per frame, culled blocks not at all -- no dense clip) -- frames / s of
+`render_video.render_frames` for each, bytes of the three textures, PSNR between the float and the baked frames, and whether the pool's
+frames equal the dense baked frames --, then write the viewer package (geometry.obj, static.png,
 dynamic/%04d.png, meta.json).  `--full`: 720p, D = 32, T = 50."""
 import argparse
 import json
@@ -19,7 +21,7 @@ import torch
 def run(full=False, outdir=None, dev="cuda:0"):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth, tiles
-    from videoloop3d_amd.baked import bake
+    from videoloop3d_amd.baked import bake, bake_pool
     from videoloop3d_amd.export import save_viewer_package
     from videoloop3d_amd.MPV import MPMeshVid
     dev = torch.device(dev)
@@ -36,6 +38,9 @@ def run(full=False, outdir=None, dev="cuda:0"):
     with torch.no_grad():
         model.stack.copy_(synth.make_plane_stack(*model.stack.shape[:4], seed=5, device=dev, alpha_bias=0.0))
         tiles.cull_stack_(model.stack.data, keep.to(dev))
+        # a static quad is ONE texture shared by all frames (what training keeps true): frame 0 over every texel no dynamic quad reads
+        dyn_t = tiles.quad_to_texel_mask(dyn.to(dev), *model.stack.shape[2:4])
+        model.stack.copy_(torch.where(dyn_t[:, None, :, :, None], model.stack.data, model.stack.data[:, :1]))
     model._set_quad_maps(keep, dyn, dev)
     model.is_sparse = model.has_dyn = True
     sync = torch.cuda.synchronize
@@ -44,13 +49,18 @@ def run(full=False, outdir=None, dev="cuda:0"):
     baked = bake(model)
     sync(); t1 = time.perf_counter()
     out["bake"] = {"seconds": t1 - t0, "float_MB": model.stack.numel() * 4 / 1e6, "baked_MB": baked.nbytes / 1e6}
+    sync(); t0 = time.perf_counter()
+    pool = bake_pool(model)
+    sync(); t1 = time.perf_counter()
+    out["bake_pool"] = {"seconds": t1 - t0, "pool_MB": pool.nbytes / 1e6, "slots": pool.layout.n_slots, "blocks_static": pool.layout.n_static,
+                        "blocks_dynamic": pool.layout.n_dynamic, "dense_baked_over_pool": baked.nbytes / pool.nbytes}
     ext = np.stack([np.eye(4, dtype=np.float32)] * N)      # a spiral of cameras around the reference view
     for i in range(N):
         a = 2 * np.pi * i / N
         ext[i, :3, 3] = [0.05 * np.cos(a), 0.03 * np.sin(a), 0.01 * np.sin(2 * a)]
     intr, rt = np.stack([K.astype(np.float32)] * N), np.arange(N) % T
     frames = {}
-    for name, kw in (("float", {}), ("baked", {"baked": baked})):
+    for name, kw in (("float", {}), ("baked", {"baked": baked}), ("baked_pool", {"baked": pool})):
         RV.render_frames(model, H, W, ext[:4], intr[:4], rt[:4], **kw)      # untimed: code objects, allocator
         sync(); t0 = time.perf_counter()
         frames[name] = RV.render_frames(model, H, W, ext, intr, rt, **kw)
@@ -58,6 +68,7 @@ def run(full=False, outdir=None, dev="cuda:0"):
         out[name] = {"frames": N, "frames_per_s": N / dt, "ms_per_frame": dt / N * 1e3}
     mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
     out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
+    out["pool_frames_equal_baked_frames"] = bool(torch.equal(frames["baked_pool"], frames["baked"]))
     poses = np.linalg.inv(ext[:8])[:, :3, :4]              # eight of the cameras as the capture's views (camera-to-world)
     with tempfile.TemporaryDirectory() as tmp:
         where = outdir or tmp

@@ -44,7 +44,7 @@ enum { VL3D_BORDER_ZEROS = 0, VL3D_BORDER_HARDCUT = 1 };
 enum { VL3D_ACT_PRE = 0, VL3D_ACT_POST = 1 };
 enum { VL3D_F32 = 0, VL3D_F16 = 1, VL3D_U8 = 2 };
 /* VL3D_U8: the baked RGBA8 texels of the playback model (vl3d_bake_rgba8 / vl3d_render_fwd_baked below) -- accepted by
- * vl3d_render_fwd_baked alone; every other entry point returns VL3D_EINVAL for it. */
+ * vl3d_render_fwd_baked and vl3d_render_fwd_baked_pool alone; every other entry point returns VL3D_EINVAL for it. */
 
 const char *vl3d_last_error(void);
 int vl3d_version(void);
@@ -65,7 +65,7 @@ typedef struct vl3d_render_desc {
     int32_t H, W;
     int32_t row0, col0;
     int32_t coord_mode, border_mode, act_order, rgb_act, alpha_act;
-    int32_t stack_dtype;   /* VL3D_F32 | VL3D_F16 (grad_stack has the same dtype); VL3D_U8: vl3d_render_fwd_baked only */
+    int32_t stack_dtype;   /* VL3D_F32 | VL3D_F16 (grad_stack has the same dtype); VL3D_U8: vl3d_render_fwd_baked(_pool) only */
     float pixel_center;    /* 0 (utils_mpi) or 0.5 (pytorch3d pixel centres) */
     float sx, sy, ox, oy;  /* VL3D_COORD_AFFINE only */
     int32_t variant;       /* kernel selector for bitwise cross-checks between EXACT kernels; 0 = default.  Bits 0-3: backward (see
@@ -127,6 +127,22 @@ int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stack_dtype, in
 int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
                           const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
                           vl3d_stream_t stream);
+/*   vl3d_render_fwd_baked_pool (csrc/vl3d_render_baked_pool.hip): the same render from the baked POOL of a packed tile-culled model -- the
+ *     "Packed storage" block table below with RGBA8 texels behind it -- instead of a dense clip.  blocks [D][ceil(Hs/8)][ceil(Ws/8)] int32:
+ *     -1 (not stored) | slot << 1 | dynamic; pool: n_slots * 256 bytes, a slot = one 8 x 8 block of 4-byte texels, row-major; a static block
+ *     owns one slot, a dynamic block T_model consecutive ones (frame t at slot + t); 4-byte aligned.  A tap in a block without storage reads
+ *     `culled_rgba8` (r | g << 8 | b << 16 | a << 24).  The frames are frame0 .. frame0 + desc->T - 1 of the model's T_model frames: desc->T is
+ *     the length of the run, as for vl3d_render_fwd_baked, and T_model -- the count that bounds the run and that the table's dynamic blocks
+ *     were laid out for -- is an argument of its own, where the dense entry takes T_alloc.  desc otherwise as for vl3d_render_fwd_baked
+ *     (VL3D_U8, VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, uv_noise_seed = 0, variant = 0, Hs, Ws >= 2), no desc->cull_* window (the pool holds
+ *     whole planes); quad_keep [D][|QH|][|QW|] is REQUIRED (the table is built from it; negative grid: tile-exact layout), D <= 128,
+ *     cull_scratch of vl3d_render_cull_scratch_bytes().  Anything else: VL3D_EINVAL, nothing launched.  The table is trusted as
+ *     packed.PackedLayout builds it: every stored slot (+ T_model - 1 for a dynamic block) lies inside the pool.  Per covered (pixel, plane):
+ *     one table entry and one 8-byte load per texel row (two entries and two 4-byte loads where x0 % 8 == 7); static blocks are fetched once
+ *     per frame pair; uncovered pixels fetch nothing.  rgb / alpha: the bits of vl3d_render_fwd_baked on the unpacked texels. */
+int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0, int32_t T_model,
+                               const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
+                               void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream);
 
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).

@@ -2,9 +2,15 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
-and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked)."""
+and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
+
+The CULLED pair (--legs culled, or all): the dense baked render WITH a quad map against the pool render (render_frame_run_baked_pool) of the
+same texels, alternating in the same way.  The quad map: 35 x 63 quads per plane, one coherent blob per plane holding --keep (0.165) of the
+plane's quads -- the nearest to the blob's centre -- of which the innermost --dyn (0.3) are dynamic; the pool is scattered from the baked clip
+plane by plane, the dense leg's clip is the pool unpacked (texels without storage read culled_rgba8), the two outputs are compared bit for bit
+before the timing.  Prints the two times, their ratio and the bytes of the pool against the dense baked clip."""
 import argparse
 import json
 import os
@@ -22,6 +28,9 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled"])
+ap.add_argument("--keep", type=float, default=0.165)
+ap.add_argument("--dyn", type=float, default=0.3)
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 assert a.warm >= 1 and a.iters >= a.rounds >= 1
@@ -29,8 +38,9 @@ assert a.warm >= 1 and a.iters >= a.rounds >= 1
 import __graft_entry__ as ge  # noqa: E402
 ge.build()
 from videoloop3d_amd import synth  # noqa: E402
-from videoloop3d_amd.baked import bake_texels  # noqa: E402
-from videoloop3d_amd.render import RenderSpec, render_frame_run, render_frame_run_baked  # noqa: E402
+from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, scatter_plane_  # noqa: E402
+from videoloop3d_amd.packed import PackedLayout  # noqa: E402
+from videoloop3d_amd.render import RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool  # noqa: E402
 from videoloop3d_amd.utils_mpi import compute_homography, make_depths  # noqa: E402
 
 assert torch.cuda.is_available(), "profiles/baked_fwd.py measures on the MI355X"
@@ -43,36 +53,93 @@ stack = synth.make_plane_stack(D, T, H, W, seed=2, device=dev)
 baked = bake_texels(stack, "sigmoid", "sigmoid")
 spec = RenderSpec.mpv()
 out = (torch.empty((T, H, W, 3), device=dev), torch.empty((T, H, W), device=dev))
-legs = {"float": lambda: render_frame_run(stack, 0, T, homos, H, W, spec, out=out),
-        "baked": lambda: render_frame_run_baked(baked, 0, T, homos, H, W, spec, out=out)}
-bytes_px = {"float": 16 * D + 16, "baked": 4 * D + 16}
 
-for f in legs.values():
-    for _ in range(a.warm):
-        f()
-torch.cuda.synchronize()
-per = max(1, a.iters // a.rounds)
-ms = {k: [] for k in legs}
-for r in range(a.rounds):
-    for k in (("float", "baked") if r % 2 == 0 else ("baked", "float")):      # alternate the order as well
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(per):
-            legs[k]()
-        e1.record()
-        e1.synchronize()
-        ms[k].append(e0.elapsed_time(e1) / per)
-res = {"config": {"D": D, "T": T, "H": H, "W": W, "warm": a.warm, "timed_calls_per_leg": per * a.rounds, "rounds": a.rounds},
+
+def ab(legs):
+    """alternate the two legs round by round (and their order) under HIP events -> {leg: [ms per call of each round]}"""
+    names = list(legs)
+    for f in legs.values():
+        for _ in range(a.warm):
+            f()
+    torch.cuda.synchronize()
+    per = max(1, a.iters // a.rounds)
+    ms = {k: [] for k in legs}
+    for r in range(a.rounds):
+        for k in (names if r % 2 == 0 else names[::-1]):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(per):
+                legs[k]()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / per)
+    return ms, per
+
+
+res = {"config": {"D": D, "T": T, "H": H, "W": W, "warm": a.warm, "timed_calls_per_leg": max(1, a.iters // a.rounds) * a.rounds, "rounds": a.rounds,
+                  "legs": a.legs},
        "stack_GB": {"float": stack.numel() * 4 / 1e9, "baked": baked.numel() / 1e9}}
-for k in legs:
-    med, lo = statistics.median(ms[k]), min(ms[k])
-    res[k] = {"ms_median": med, "ms_min": lo, "ms_max": max(ms[k]), "Mpix_s": T * H * W / med / 1e3, "algorithmic_bytes_per_pixel": bytes_px[k],
-              "fraction_of_8TBs": T * H * W * bytes_px[k] / (med * 1e-3) / 8e12}
-    print(f"{k:5s} forward: {med:7.3f} ms (min {lo:.3f}, max {max(ms[k]):.3f} over {a.rounds} rounds of {per})  {res[k]['Mpix_s']:8.0f} Mpix/s  "
-          f"{bytes_px[k]} B/pixel -> {res[k]['fraction_of_8TBs']:.3f} of 8 TB/s")
-res["speedup"] = res["float"]["ms_median"] / res["baked"]["ms_median"]
-res["byte_ratio"] = bytes_px["float"] / bytes_px["baked"]
-print(f"baked is {res['speedup']:.2f}x the float forward (algorithmic byte ratio {res['byte_ratio']:.2f}x)")
+
+
+def report(k, ms, per, bytes_px):
+    med, lo = statistics.median(ms), min(ms)
+    res[k] = {"ms_median": med, "ms_min": lo, "ms_max": max(ms), "Mpix_s": T * H * W / med / 1e3}
+    line = f"{k:12s} forward: {med:7.3f} ms (min {lo:.3f}, max {max(ms):.3f} over {a.rounds} rounds of {per})  {res[k]['Mpix_s']:8.0f} Mpix/s"
+    if bytes_px:
+        res[k].update({"algorithmic_bytes_per_pixel": bytes_px, "fraction_of_8TBs": T * H * W * bytes_px / (med * 1e-3) / 8e12})
+        line += f"  {bytes_px} B/pixel -> {res[k]['fraction_of_8TBs']:.3f} of 8 TB/s"
+    print(line)
+
+
+if a.legs in ("all", "dense"):
+    ms, per = ab({"float": lambda: render_frame_run(stack, 0, T, homos, H, W, spec, out=out),
+                  "baked": lambda: render_frame_run_baked(baked, 0, T, homos, H, W, spec, out=out)})
+    report("float", ms["float"], per, 16 * D + 16)
+    report("baked", ms["baked"], per, 4 * D + 16)
+    res["speedup"] = res["float"]["ms_median"] / res["baked"]["ms_median"]
+    res["byte_ratio"] = (16 * D + 16) / (4 * D + 16)
+    print(f"baked is {res['speedup']:.2f}x the float forward (algorithmic byte ratio {res['byte_ratio']:.2f}x)")
+
+if a.legs in ("all", "culled"):
+    del stack
+    QH, QW = 35, 63                                       # 36 x 64 vertices
+    qy, qx = torch.meshgrid(torch.arange(QH, device=dev), torch.arange(QW, device=dev), indexing="ij")
+    n_keep = round(a.keep * QH * QW)
+    n_dyn = round(a.dyn * n_keep)
+    keep = torch.zeros((D, QH * QW), dtype=torch.bool, device=dev)
+    dyn = torch.zeros_like(keep)
+    for d in range(D):                                    # one coherent blob per plane: the quads nearest to its centre (in quad units of equal size on screen)
+        cy, cx = (7 * d + 3) % QH, (11 * d + 5) % QW
+        order = (((qy - cy) * (H / QH)) ** 2 + ((qx - cx) * (W / QW)) ** 2).flatten().argsort(stable=True)
+        keep[d, order[:n_keep]] = True
+        dyn[d, order[:n_dyn]] = True
+    keep, dyn = keep.view(D, QH, QW), dyn.view(D, QH, QW)
+    lay = PackedLayout(keep, dyn, T, H, W)
+    pool = torch.zeros((lay.n_slots * 64, 4), dtype=torch.uint8, device=dev)
+    for d in range(D):
+        scatter_plane_(lay, pool, d, baked[d])
+    del baked
+    qk = keep.to(torch.uint8).contiguous()
+    bp = BakedPool(pool, lay, qk, spec, "", None, culled_texel_rgba8("sigmoid", "sigmoid"))
+    dense = bp.unpack_frames(range(T))                    # the clip the dense leg reads: the SAME texels, culled_rgba8 where nothing is stored
+    out2 = (torch.empty_like(out[0]), torch.empty_like(out[1]))
+    render_frame_run_baked(dense, 0, T, homos, H, W, spec, out=out, quad_keep=qk)
+    render_frame_run_baked_pool(lay, pool, 0, T, homos, H, W, spec, out=out2, quad_keep=qk, culled_rgba8=bp.culled_rgba8)
+    same = torch.equal(out[0], out2[0]) and torch.equal(out[1], out2[1])
+    covered = float((out[1] > 0).float().mean())
+    del out2
+    res["culled_map"] = {"QH": QH, "QW": QW, "kept": float(keep.float().mean()), "dynamic_of_kept": float(dyn.sum()) / float(keep.sum()),
+                         "blocks_static": lay.n_static, "blocks_dynamic": lay.n_dynamic, "blocks_unstored": int((lay.blocks < 0).sum()),
+                         "pool_bytes": bp.nbytes, "dense_baked_bytes": dense.numel(), "outputs_bit_equal": same, "covered_pixels": covered}
+    print(f"culled map: {QH} x {QW} quads, {res['culled_map']['kept']:.3f} kept, {res['culled_map']['dynamic_of_kept']:.3f} of them dynamic; blocks "
+          f"static {lay.n_static} / dynamic {lay.n_dynamic} / unstored {res['culled_map']['blocks_unstored']}; pool {bp.nbytes / 1e9:.3f} GB against "
+          f"{dense.numel() / 1e9:.3f} GB dense baked ({dense.numel() / bp.nbytes:.1f}x); outputs bit-equal: {same}; covered pixels {covered:.3f}")
+    ms, per = ab({"baked_culled": lambda: render_frame_run_baked(dense, 0, T, homos, H, W, spec, out=out, quad_keep=qk),
+                  "baked_pool": lambda: render_frame_run_baked_pool(lay, pool, 0, T, homos, H, W, spec, out=out, quad_keep=qk, culled_rgba8=bp.culled_rgba8)})
+    report("baked_culled", ms["baked_culled"], per, 0)
+    report("baked_pool", ms["baked_pool"], per, 0)
+    res["pool_over_dense_culled"] = res["baked_pool"]["ms_median"] / res["baked_culled"]["ms_median"]
+    print(f"pool render is {res['pool_over_dense_culled']:.3f}x the dense culled baked render's time (bar: <= 1.05)")
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

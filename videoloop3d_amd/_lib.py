@@ -74,6 +74,7 @@ SIGNATURES = {
     "vl3d_render_fwd_frames_culled": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_bake_rgba8": ([_I64, _P, _I32, _I32, _I32, _P, _P], C.c_int),
     "vl3d_render_fwd_baked": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _I32, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),

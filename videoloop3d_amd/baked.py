@@ -8,7 +8,13 @@ atlases ACTIVATED, multiplied by 255, clipped and truncated to 8 bits; a player 
                                        vl3d_bake_rgba8 for device tensors, the same expression in torch for host tensors (the export runs there).
   bake(module) -> BakedMPV             the uint8 texels (D,T,Hs,Ws,4) of an MPMeshVid with its quad map, render geometry, background and
                                        camera: renders without the float stack (render.render_frame_run_baked), a quarter of its bytes.
+  bake_pool(module) -> BakedPool       the same for a tile-culled model, packed or not, WITHOUT a dense clip: RGBA8 blocks of 8 x 8 texels behind the
+                                       block table of packed.PackedLayout (static blocks once, dynamic blocks per frame, culled blocks not at all --
+                                       the static and the dynamic atlas of the viewer package), rendered by render.render_frame_run_baked_pool with
+                                       the bits of the dense baked render.  256 bytes per slot: a quarter of the float pool.
 """
+import copy
+
 import torch
 
 from . import _lib as L
@@ -50,7 +56,48 @@ class _Camera:
             setattr(self, name, getattr(module, name).detach().clone())
 
 
-class BakedMPV:
+class _Baked:
+    """what BakedMPV and BakedPool share: camera, background and the module's eval forward over runs of consecutive frames.  A subclass has
+    `device`, `frm_num`, `bg_color`, `camera` and `_run(frame0, n, homos, H, W, out)`: its render of a run of frames, read in place."""
+
+    def extrins_to_ref(self, tar_extrins):
+        """world-to-camera poses -> reference-camera-to-target transforms, as MPMeshVid.forward forms them (MPV.py:481)."""
+        return tar_extrins @ self.camera._on(tar_extrins.device, "ref_extrin")[None, ...].inverse().to(tar_extrins.dtype)
+
+    def background(self):
+        """the background colour of this call as a device tensor, or None (MPV.py:455-461: "" none, "random" one draw per call, "r#g#b")."""
+        if len(self.bg_color) == 0:
+            return None
+        if self.bg_color == "random":
+            return torch.rand(3).to(self.device)
+        return torch.tensor([float(v) for v in self.bg_color.split('#')], dtype=torch.float32, device=self.device)
+
+    @torch.no_grad()
+    def render(self, H, W, extrins, intrins, ts=None):
+        """the module's eval forward on the baked texels: one camera (extrins [1,4,4] world-to-camera, intrins [1,3,3]), frames `ts` (default:
+        the whole clip) -> (rgb [T',3,H,W] over the background, alpha [T',H,W])."""
+        extrins, intrins = torch.as_tensor(extrins), torch.as_tensor(intrins)
+        tl = list(range(self.frm_num)) if ts is None else [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        dev = self.device
+        homos = self.camera.plane_homographies(self.extrins_to_ref(extrins), intrins).to(dev)
+        rgb = torch.empty((len(tl), H, W, 3), dtype=torch.float32, device=dev)
+        alpha = torch.empty((len(tl), H, W), dtype=torch.float32, device=dev)
+        i = 0
+        while i < len(tl):      # runs of consecutive frames are read where they lie in the clip
+            j = i + 1
+            while j < len(tl) and tl[j] == tl[j - 1] + 1:
+                j += 1
+            if not (0 <= tl[i] and tl[j - 1] < self.frm_num):
+                raise IndexError(f"frame index {tl[i]} .. {tl[j - 1]} outside the clip of {self.frm_num} frames")
+            self._run(tl[i], j - i, homos, H, W, (rgb[i:j], alpha[i:j]))
+            i = j
+        bg = self.background()
+        if bg is not None:
+            rgb = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
+        return rgb.permute(0, 3, 1, 2), alpha
+
+
+class BakedMPV(_Baked):
     """bake(module)'s product.  texels [D,T,Hs,Ws,4] uint8 on the device, quad_keep [D,QH,QW] uint8 or None, spec (render.RenderSpec: pixel
     centre, texel scale / offset, tile-exact layout), bg_color, camera (plane_homographies, ref_extrin)."""
 
@@ -66,42 +113,118 @@ class BakedMPV:
     def frm_num(self):
         return int(self.texels.shape[1])
 
-    def extrins_to_ref(self, tar_extrins):
-        """world-to-camera poses -> reference-camera-to-target transforms, as MPMeshVid.forward forms them (MPV.py:481)."""
-        return tar_extrins @ self.camera._on(tar_extrins.device, "ref_extrin")[None, ...].inverse().to(tar_extrins.dtype)
+    @property
+    def device(self):
+        return self.texels.device
 
-    def background(self):
-        """the background colour of this call as a device tensor, or None (MPV.py:455-461: "" none, "random" one draw per call, "r#g#b")."""
-        if len(self.bg_color) == 0:
-            return None
-        if self.bg_color == "random":
-            return torch.rand(3).to(self.texels.device)
-        return torch.tensor([float(v) for v in self.bg_color.split('#')], dtype=torch.float32, device=self.texels.device)
+    def _run(self, frame0, n, homos, H, W, out):
+        from .render import render_frame_run_baked
+        return render_frame_run_baked(self.texels, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep)
+
+
+class BakedPool(_Baked):
+    """bake_pool(module)'s product: the playback model of a tile-culled model without a dense clip.  pool [n_slots * 64, 4] uint8 on the device
+    (8 x 8-texel blocks, row-major), layout (packed.PackedLayout: the block table -1 | slot << 1 | dynamic), quad_keep [D,QH,QW] uint8, spec,
+    bg_color, camera as in BakedMPV; culled_rgba8: the texel (r | g << 8 | b << 16 | a << 24) a block without storage reads as -- the bake of
+    (0, 0, 0, tiles.CULLED_ALPHA) under the model's activations.
+    Its render is the dense baked render of `unpack_frames`, bit for bit.  Against bake() of the DENSE model that holds only where the dense
+    stack agrees with what the pool stores: static quads with the same texels in every frame (the pool keeps frame 0) and culled texels at
+    (0, 0, 0, CULLED_ALPHA).  Other values in culled texels show at ~1e-7 in the float render -- a sample on a tile border can tap the
+    neighbouring tile with such a weight -- and not in the uint8 frames (docs/kernels/K9_baked_playback.md, "Culled texels")."""
+
+    def __init__(self, pool, layout, quad_keep, spec, bg_color, camera, culled_rgba8):
+        self.pool, self.layout, self.quad_keep, self.spec, self.bg_color, self.camera = pool, layout, quad_keep, spec, bg_color, camera
+        self.culled_rgba8 = int(culled_rgba8)
+
+    @property
+    def nbytes(self):
+        """bytes of the pool (256 per slot) plus the block table."""
+        return self.pool.numel() * self.pool.element_size() + self.layout.blocks.numel() * self.layout.blocks.element_size()
+
+    @property
+    def frm_num(self):
+        return int(self.layout.T)
+
+    @property
+    def device(self):
+        return self.pool.device
+
+    def _run(self, frame0, n, homos, H, W, out):
+        from .render import render_frame_run_baked_pool
+        return render_frame_run_baked_pool(self.layout, self.pool, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
+                                           culled_rgba8=self.culled_rgba8)
 
     @torch.no_grad()
-    def render(self, H, W, extrins, intrins, ts=None):
-        """the module's eval forward on the baked texels: one camera (extrins [1,4,4] world-to-camera, intrins [1,3,3]), frames `ts` (default:
-        the whole clip) -> (rgb [T',3,H,W] over the background, alpha [T',H,W])."""
-        from .render import render_frame_run_baked
-        extrins, intrins = torch.as_tensor(extrins), torch.as_tensor(intrins)
-        tl = list(range(self.frm_num)) if ts is None else [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
-        dev = self.texels.device
-        homos = self.camera.plane_homographies(self.extrins_to_ref(extrins), intrins).to(dev)
-        rgb = torch.empty((len(tl), H, W, 3), dtype=torch.float32, device=dev)
-        alpha = torch.empty((len(tl), H, W), dtype=torch.float32, device=dev)
-        i = 0
-        while i < len(tl):      # runs of consecutive frames are read where they lie in the clip
-            j = i + 1
-            while j < len(tl) and tl[j] == tl[j - 1] + 1:
-                j += 1
-            if not (0 <= tl[i] and tl[j - 1] < self.frm_num):
-                raise IndexError(f"frame index {tl[i]} .. {tl[j - 1]} outside the clip of {self.frm_num} frames")
-            render_frame_run_baked(self.texels, tl[i], j - i, homos, H, W, self.spec, out=(rgb[i:j], alpha[i:j]), quad_keep=self.quad_keep)
-            i = j
-        bg = self.background()
-        if bg is not None:
-            rgb = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
-        return rgb.permute(0, 3, 1, 2), alpha
+    def unpack_frames(self, frames):
+        """-> (D, len(frames), Hs, Ws, 4) uint8: the frames of the dense baked clip this pool stands for; texels of blocks without storage
+        hold culled_rgba8.  Plain torch (tests, export): the render does not go through it."""
+        frames = [int(t) for t in frames]
+        lay = self.layout
+        if frames and (min(frames) < 0 or max(frames) >= lay.T):
+            raise IndexError(f"frame index out of range [0, {lay.T})")
+        fill = torch.tensor([(self.culled_rgba8 >> (8 * k)) & 0xff for k in range(4)], dtype=torch.uint8, device=self.device)
+        out = torch.empty((lay.D, len(frames), lay.Hs, lay.Ws, 4), dtype=torch.uint8, device=self.device)
+        for d in range(lay.D):
+            base, fs, ok = lay._plane_index(d)
+            for i, t in enumerate(frames):
+                out[d, i] = torch.where(ok[..., None], self.pool[base + t * fs], fill)
+        return out
+
+
+@torch.no_grad()
+def scatter_plane_(layout, pool, d, plane):
+    """plane d of a dense baked clip, (T,Hs,Ws,4) uint8, -> the baked pool [n_slots * 64, 4] through the block table: static blocks take frame
+    0, texels of blocks without storage are dropped (packed.PackedLayout.pack_plane_ for uint8 texels).  Plain torch: conversion."""
+    base, fs, ok = layout._plane_index(d)
+    for t in range(layout.T):
+        sel = ok & ((fs > 0) | (t == 0))
+        pool[(base + t * fs)[sel]] = plane[t][sel]
+
+
+def culled_texel_rgba8(rgb_act, alpha_act):
+    """the texel a block without storage reads as: the bake (host rule) of (0, 0, 0, tiles.CULLED_ALPHA) under the activations, as the word
+    r | g << 8 | b << 16 | a << 24 (BakedPool.culled_rgba8, the `culled_rgba8` of vl3d_render_fwd_baked_pool)."""
+    from .tiles import CULLED_ALPHA
+    b = bake_texels(torch.tensor([[0.0, 0.0, 0.0, CULLED_ALPHA]], dtype=torch.float32), rgb_act, alpha_act)[0].tolist()
+    return b[0] | b[1] << 8 | b[2] << 16 | b[3] << 24
+
+
+@torch.no_grad()
+def bake_pool(module):
+    """Tile-culled MPMeshVid -> BakedPool, without a dense uint8 clip and without a float pool of its own.
+      a packed model: ONE bake launch over its pool; the layout is the module's (the table cloned);
+      a sparsified dense model (either tile layout): the layout pack_() would build from its quad maps, then plane by plane bake the
+        plane's (T,Hs,Ws,4) texels and scatter them through the table (static blocks take frame 0, the dense model's convention) -- the bytes
+        bake_pool gives after module.pack_().
+    A model that is not sparse (nothing to cull: bake() is its playback model), an `atlas_exact` model and a model on the host are refused."""
+    from .packed import TS, PackedLayout
+    module = getattr(module, "module", module)
+    if getattr(module, "atlas_exact", False):
+        raise RuntimeError("bake_pool: atlas_exact models sample the reference's atlas cells; the baked render is built for the planar convention")
+    if not (getattr(module, "is_sparse", False) and getattr(module, "quad_keep", None) is not None and getattr(module, "quad_dyn", None) is not None):
+        raise RuntimeError("bake_pool: the model is not sparse -- no quad maps, nothing to cull: bake() gives its playback model")
+    param = module._param() if hasattr(module, "_param") else None
+    if param is None or not hasattr(module, "frm_num"):
+        raise RuntimeError("bake_pool: an MPMeshVid (its dense (D,T,Hs,Ws,4) stack, or the pool of pack_())")
+    if not param.is_cuda:
+        raise RuntimeError("bake_pool: the model is on the host; the baked model lives and renders on the device (module.cuda() first)")
+    module._flush_deferred_updates()
+    dev = param.device
+    ra, aa = module.args.rgb_activate, module.args.alpha_activate
+    if module.packed is not None:
+        lay = copy.copy(module.packed)      # the module's layout with a table of its own: a later lod() / pack_() of the module does not reach it
+        lay.blocks, lay._index_cache = module.packed.blocks.clone(), {}
+        pool = bake_texels(module.stack_pool.data.view(-1, 4), ra, aa)
+    else:
+        stack = module.stack.data
+        lay = PackedLayout(module.quad_keep.to(dev), module.quad_dyn.to(dev), stack.shape[1], stack.shape[2], stack.shape[3], module.tile_own)
+        # texels of a stored block that lie past the plane's last row / column are never written: pack_() leaves them 0.0, which bakes to this
+        unset = bake_texels(torch.zeros((1, 4), dtype=torch.float32, device=dev), ra, aa)
+        pool = unset.repeat(lay.n_slots * TS * TS, 1)
+        for d in range(lay.D):
+            scatter_plane_(lay, pool, d, bake_texels(stack[d], ra, aa))      # (T,Hs,Ws,4) uint8: one plane at a time, never the clip
+    qk = module.quad_keep.to(torch.uint8).contiguous().clone()
+    return BakedPool(pool, lay, qk, module.spec, str(module.args.bg_color), _Camera(module), culled_texel_rgba8(ra, aa))
 
 
 @torch.no_grad()

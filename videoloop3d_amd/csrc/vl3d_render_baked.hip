@@ -12,14 +12,11 @@
 //     the 1 / 255 of the decode is folded into the four blend weights once per plane, and nothing is activated.  The launch shape is the float
 //     forward's: 64 x 8 pixels per workgroup, XCD remap, two frames per thread for T >= 2 (an odd tail frame composited twice, stored once).
 // Forward only: a baked model is not trained.
-#include "vl3d_render_core.h"
+#include "vl3d_baked_core.h"      // BakedTaps, chan<K>, blend<K>: shared with csrc/vl3d_render_baked_pool.hip
 
 using vl3d_render_detail::RenderArgs;
 
 namespace {
-
-typedef unsigned u2w __attribute__((ext_vector_type(2)));
-typedef u2w u2w_a4 __attribute__((aligned(4)));      // two 4-byte texels of a row: 4-byte aligned (x0 may be odd)
 
 // ---- bake ---------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float act_rt(int act, float v) {      // (the activation is uniform: a scalar branch)
@@ -60,18 +57,10 @@ __global__ __launch_bounds__(256) void bake_rgba8_k(int64_t n, const char *__res
 }
 
 // ---- render -------------------------------------------------------------------------------------------------------------------------------
-// the four taps of a sample: texels (x0, x0 + 1) of rows y0 and y0 + 1, one 8-byte load per row against a uniform plane base
-struct BakedTaps { u2w r0, r1; };
+// the taps of a dense clip: one 8-byte load per texel row against a uniform plane base
 __device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, const Taps2 &t, unsigned row_b) {
     const size_t o = (size_t)(t.off >> 2);      // make_taps2 gives the byte offset of 16-byte texels
     return BakedTaps{*reinterpret_cast<const u2w_a4 *>(plane + o), *reinterpret_cast<const u2w_a4 *>(plane + row_b + o)};
-}
-template <int K>
-__device__ __forceinline__ float chan(unsigned w) { return (float)((w >> (8 * K)) & 0xffu); }
-// bilinear blend of the decoded taps; w255 = the tent weights * (1 / 255).  Associated like shade2: tap 3 first, then 2, 1, 0.
-template <int K>
-__device__ __forceinline__ float blend(const BakedTaps &v, f4 w255) {
-    return fmaf(chan<K>(v.r0.x), w255[0], fmaf(chan<K>(v.r0.y), w255[1], fmaf(chan<K>(v.r1.x), w255[2], chan<K>(v.r1.y) * w255[3])));
 }
 
 template <int NF, bool CULL>

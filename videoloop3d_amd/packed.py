@@ -30,6 +30,7 @@ class PackedLayout:
         its border texels, Hs x Ws = QH th x QW tw): a block is stored when a kept tile overlaps it."""
         self.D, self.T, self.Hs, self.Ws = int(quad_keep.shape[0]), int(T), int(Hs), int(Ws)
         self.tile = (int(tile[0]), int(tile[1])) if (tile is not None and tile[0]) else None
+        self.quad_grid = (int(quad_keep.shape[1]), int(quad_keep.shape[2]))      # (QH, QW) the table was built from
         dev = quad_keep.device
         keep_t = tiles.quad_to_texel_mask(quad_keep.bool(), Hs, Ws, self.tile)                       # D,Hs,Ws: texels a kept quad can read
         dyn_t = tiles.quad_to_texel_mask((quad_keep & quad_dyn).bool(), Hs, Ws, self.tile)           # ... a dynamic quad can read

@@ -391,6 +391,66 @@ def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec
     return rgb, alpha
 
 
+def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8):
+    """render_frame_run_baked from the baked POOL of a packed tile-culled model (baked.BakedPool; vl3d_render_fwd_baked_pool): `layout` the
+    packed.PackedLayout whose block table addresses `pool` [n_slots * 64, 4] uint8 (8 x 8-texel blocks of baked RGBA8 texels), `quad_keep`
+    [D,QH,QW] the quad map the table was built from, `culled_rgba8` the texel (r | g << 8 | b << 16 | a << 24) a block without storage reads
+    as (BakedPool.culled_rgba8) -- both required, by keyword.  The kernel trusts the table: the layout's table and the quad map are checked
+    here against the layout's own dimensions.  Frames frame0 .. frame0 + nframes - 1 of the model's layout.T -> (rgb [n,H,W,3], alpha [n,H,W]) float32: the bits of
+    render_frame_run_baked on the unpacked texels, without the dense clip.  The planar convention only; forward only."""
+    L.check_cuda(pool, homos, layout.blocks)
+    if pool.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
+        raise RuntimeError("render_frame_run_baked_pool: baked texels have no backward (train the float model, then bake it)")
+    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
+        raise RuntimeError("render_frame_run_baked_pool: a contiguous uint8 pool [n_slots * 64, 4] of the layout (baked.bake_pool)")
+    if spec.coord_mode != "affine" or spec.border != "hardcut":
+        raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
+    if quad_keep is None:
+        raise RuntimeError("render_frame_run_baked_pool: the quad map the block table was built from (quad_keep [D,QH,QW]) is required")
+    D, T = layout.D, layout.T
+    if not (0 <= frame0 and nframes >= 1 and frame0 + nframes <= T):
+        raise RuntimeError(f"render_frame_run_baked_pool: frames {frame0} .. {frame0 + nframes - 1} leave the model's {T}")
+    if homos.shape != (D, 3, 3):
+        raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
+    L.check_cuda(quad_keep)
+    if quad_keep.dim() != 3 or quad_keep.shape[0] != D:
+        raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {D}, got {tuple(quad_keep.shape)}")
+    grid = getattr(layout, "quad_grid", None)      # (a layout object made before PackedLayout recorded its grid: nothing to compare with)
+    if grid is not None and tuple(quad_keep.shape[1:]) != tuple(grid):
+        raise RuntimeError(f"quad_keep is {tuple(quad_keep.shape[1:])} quads per plane, the layout's block table was built from {tuple(grid)}")
+    bl = layout.blocks
+    if bl.dtype != torch.int32 or not bl.is_contiguous() or tuple(bl.shape) != (D, -(-layout.Hs // 8), -(-layout.Ws // 8)) or bl.device != pool.device:
+        raise RuntimeError("render_frame_run_baked_pool: the layout's block table must be contiguous int32 [D, ceil(Hs/8), ceil(Ws/8)] on the pool's device")
+    if bool(getattr(spec, "tile", (0, 0))[0]) != (layout.tile is not None):
+        raise RuntimeError("render_frame_run_baked_pool: RenderSpec.tile and the layout's tile must both name the tile-exact layout, or neither")
+    homos = homos.detach().to(torch.float32).contiguous()
+    dev = pool.device
+    d = L.RenderDesc()
+    d.D, d.T, d.Hs, d.Ws, d.H, d.W = D, int(nframes), layout.Hs, layout.Ws, int(H), int(W)
+    d.coord_mode, d.border_mode, d.act_order = L.COORD[spec.coord_mode], L.BORDER[spec.border], L.ACT_ORDER[spec.act_order]
+    d.rgb_act, d.alpha_act = L.ACT[spec.rgb_act], L.ACT[spec.alpha_act]
+    d.stack_dtype = L.STACK_DTYPE["u8"]
+    d.pixel_center = float(spec.pixel_center)
+    d.sx, d.sy, d.ox, d.oy = float(spec.scale[0]), float(spec.scale[1]), float(spec.offset[0]), float(spec.offset[1])
+    d.variant = int(spec.variant)
+    d.uv_noise_seed = int(getattr(spec, "uv_noise_seed", 0)) & 0xFFFFFFFF
+    if out is None:
+        rgb = torch.empty((nframes, H, W, 3), dtype=torch.float32, device=dev)
+        alpha = torch.empty((nframes, H, W), dtype=torch.float32, device=dev)
+    else:
+        rgb, alpha = out
+        if tuple(rgb.shape) != (nframes, H, W, 3) or tuple(alpha.shape) != (nframes, H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
+            raise RuntimeError("render_frame_run_baked_pool: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
+    from .tiles import as_u8
+    qk = as_u8(quad_keep)
+    with torch.cuda.device(dev):
+        cull = torch.empty((int(L.lib().vl3d_render_cull_scratch_bytes(d)) + 3) // 4, dtype=torch.float32, device=dev)
+        L.check(L.lib().vl3d_render_fwd_baked_pool(d, L.ptr(layout.blocks), L.ptr(pool), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec),
+                                                   int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)),
+                "vl3d_render_fwd_baked_pool")
+    return rgb, alpha
+
+
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,
                   fused_adam=None):
     """stack (D,T,Hs,Ws,4) pre-activation fp32 (plane 0 = nearest), homos [D,3,3] (target pixel -> plane pixel).

@@ -167,11 +167,18 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
     one camera -- is rendered where it lies in the clip (render.render_frame_run: no gather of stack[:, ts]), straight into a chunk buffer
     that is converted to uint8 once (a sparsified model with its quad map; a packed one through its block table).  None when the model is
     not one this path serves (atlas_exact / CPU).  `baked` (baked.BakedMPV): the frames come from ITS uint8 texels, quad map, geometry,
-    camera and background through the same runs (render.render_frame_run_baked); the float model is not read."""
-    from .render import render_frame_run, render_frame_run_baked
+    camera and background through the same runs (render.render_frame_run_baked); the float model is not read.  A baked.BakedPool renders its
+    runs from the pool behind its block table (render.render_frame_run_baked_pool)."""
+    from .render import render_frame_run, render_frame_run_baked, render_frame_run_baked_pool
     if baked is not None:
         if baked.bg_color == "random":
             return None
+        if hasattr(baked, "pool"):
+            def run_pool(pool, t0, n, homos, H, W, spec, out=None, quad_keep=None):
+                return render_frame_run_baked_pool(baked.layout, pool, t0, n, homos, H, W, spec, out=out, quad_keep=quad_keep,
+                                                   culled_rgba8=baked.culled_rgba8)
+            return _in_place_runs(baked.camera, baked.pool, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
+                                  render_t, chunk, run_pool, T=baked.frm_num)
         return _in_place_runs(baked.camera, baked.texels, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
                               render_t, chunk, render_frame_run_baked)
     packed = getattr(module, "packed", None)
@@ -186,11 +193,12 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
                           render_frame_run)
 
 
-def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run):
+def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run, T=None):
     """the frame loop of _render_frames_in_place: `camera` gives the homographies (`plane_homographies`, `ref_extrin`), `run` renders a run of
-    consecutive frames of the dense clip `stack` in place (render_frame_run / render_frame_run_baked); `packed`: the pool's layout instead."""
+    consecutive frames of the dense clip `stack` in place (render_frame_run / render_frame_run_baked); `packed`: the pool's layout instead.
+    `T`: the clip's frame count where `stack` is not a (D,T,...) clip (a baked pool)."""
     from .render import render_planes_packed
-    n, T, dev = len(render_t), (packed.T if packed is not None else stack.shape[1]), stack.device
+    n, T, dev = len(render_t), (packed.T if packed is not None else (stack.shape[1] if T is None else T)), stack.device
     if packed is not None:      # a packed model reads its pool through the block table (vl3d_render_fwd_packed): the frame indices go up once
         from .tiles import CULLED_ALPHA
         t_dev = torch.as_tensor(render_t.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
@@ -241,7 +249,7 @@ def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64
     (`_render_frames_in_place`: 720p, D = 32, T = 50 along a spiral 1430 -> several thousand frames / s; `in_place=False` keeps the loop below).
     Otherwise runs of consecutive frames with one camera are rendered by ONE call of the module with `ts` a vector (at most `max_batch` frames:
     the frames of a call are resident together).
-    `baked` (baked.BakedMPV, the product of baked.bake(model)): the frames of the PLAYBACK model -- its 8-bit texels filtered after the
+    `baked` (baked.BakedMPV or baked.BakedPool, the product of baked.bake(model) / baked.bake_pool(model)): the frames of the PLAYBACK model -- its 8-bit texels filtered after the
     activation, what the exported viewer package shows -- through the same run logic; the float stack is not read."""
     module = getattr(nerf, "module", nerf)
     was_training = module.training
