@@ -38,7 +38,7 @@ assert a.warm >= 1 and a.iters >= a.rounds >= 1
 import __graft_entry__ as ge  # noqa: E402
 ge.build()
 from videoloop3d_amd import synth  # noqa: E402
-from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, scatter_plane_  # noqa: E402
+from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8  # noqa: E402
 from videoloop3d_amd.packed import PackedLayout  # noqa: E402
 from videoloop3d_amd.render import RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool  # noqa: E402
 from videoloop3d_amd.utils_mpi import compute_homography, make_depths  # noqa: E402
@@ -117,7 +117,7 @@ if a.legs in ("all", "culled"):
     lay = PackedLayout(keep, dyn, T, H, W)
     pool = torch.zeros((lay.n_slots * 64, 4), dtype=torch.uint8, device=dev)
     for d in range(D):
-        scatter_plane_(lay, pool, d, baked[d])
+        lay.pack_plane_(pool, d, baked[d])
     del baked
     qk = keep.to(torch.uint8).contiguous()
     bp = BakedPool(pool, lay, qk, spec, "", None, culled_texel_rgba8("sigmoid", "sigmoid"))

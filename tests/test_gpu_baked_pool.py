@@ -83,10 +83,7 @@ def _scatter_pool(lay, clip, fill):
     """dense uint8 clip [D,T,Hs,Ws,4] -> pool [n_slots * 64, 4] through the block table (static blocks take frame 0), plain torch."""
     pool = fill.repeat(lay.n_slots * 64, 1)
     for d in range(lay.D):
-        base, fs, ok = lay._plane_index(d)
-        for t in range(lay.T):
-            sel = ok & ((fs > 0) | (t == 0))
-            pool[(base + t * fs)[sel]] = clip[d, t][sel]
+        lay.pack_plane_(pool, d, clip[d])
     return pool
 
 
@@ -358,3 +355,47 @@ def test_determinism_and_guards(dev, scenes):
     with pytest.raises(RuntimeError, match="tile"):
         render_frame_run_baked_pool(lay, pool, 1, 3, scenes.homos, H, W, scenes.geo["exact"].spec, **kw)
     torch.cuda.synchronize()
+
+
+# ---- 7. the four culled forward entries share one quad-grid rule ---------------------------------------------------------------------------
+def test_culled_forward_entries_share_the_grid_rule(dev, scenes):
+    """vl3d_render_fwd_frames_culled, _fwd_packed, _fwd_baked and _fwd_baked_pool at the C ABI, on the `exact` (30 x 70 texels, 5 x 7 tiles) and
+    `shared` (40 x 72 texels, 5 x 9 quads) scenes: every entry refuses the same bad quad grids with VL3D_EINVAL -- mixed signs, a zero, a
+    tile-exact grid that does not divide the plane, a tile-exact grid of 1-texel tiles -- before anything is launched (the sentinel-filled
+    outputs stay untouched), and accepts the scene's own grid."""
+    from videoloop3d_amd import _lib as L
+    from videoloop3d_amd.render import _desc_dims, _qgrid
+    lib, stream, n, EINVAL, SENT = L.lib(), L.stream_ptr(dev), 3, 1, 123.0
+    frames = torch.arange(1, 1 + n, dtype=torch.int32, device=dev)
+    for name in ("exact", "shared"):
+        s = scenes.geo[name]
+        g, lay = s.g, s.bp.layout
+        QH, QW = _qgrid(s.qk, s.spec)
+        assert (QH < 0) == (name == "exact")
+        stack = synth.make_plane_stack(D, T_MODEL, g["Hs"], g["Ws"], seed=7, device=dev)
+        fpool = lay.new_pool(dev)
+        rgb = torch.full((n, H, W, 3), SENT, device=dev)
+        alpha = torch.full((n, H, W), SENT, device=dev)
+        d_f32 = _desc_dims(D, n, g["Hs"], g["Ws"], H, W, s.spec, L.STACK_DTYPE["f32"])
+        d_pk = _desc_dims(D, T_MODEL, g["Hs"], g["Ws"], H, W, s.spec, L.STACK_DTYPE["f32"])
+        d_u8 = _desc_dims(D, n, g["Hs"], g["Ws"], H, W, s.spec, L.STACK_DTYPE["u8"])
+        cull = torch.empty((int(lib.vl3d_render_cull_scratch_bytes(d_f32)) + 3) // 4, dtype=torch.float32, device=dev)
+        hom, qk, out = L.ptr(scenes.homos), L.ptr(s.qk), (L.ptr(rgb), L.ptr(alpha))
+        entries = {
+            "vl3d_render_fwd_frames_culled": lambda qh, qw: lib.vl3d_render_fwd_frames_culled(d_f32, L.ptr(stack), 1, T_MODEL, hom, qk, qh, qw,
+                                                                                              L.ptr(cull), *out, stream),
+            "vl3d_render_fwd_packed": lambda qh, qw: lib.vl3d_render_fwd_packed(d_pk, L.ptr(lay.blocks), L.ptr(fpool), L.ptr(frames), n, hom, qk, qh, qw,
+                                                                                0.0, *out, stream),
+            "vl3d_render_fwd_baked": lambda qh, qw: lib.vl3d_render_fwd_baked(d_u8, L.ptr(s.dense), 1, T_MODEL, hom, qk, qh, qw, L.ptr(cull), *out, stream),
+            "vl3d_render_fwd_baked_pool": lambda qh, qw: lib.vl3d_render_fwd_baked_pool(d_u8, L.ptr(lay.blocks), L.ptr(s.bp.pool), 1, T_MODEL, hom, qk,
+                                                                                        qh, qw, s.bp.culled_rgba8, L.ptr(cull), *out, stream),
+        }
+        bad = [(abs(QH), -abs(QW)), (0, abs(QW)), (-4, -7), (-30, -70)]
+        for entry, call in entries.items():
+            for qh, qw in bad:
+                assert call(qh, qw) == EINVAL, (name, entry, qh, qw)
+        torch.cuda.synchronize()
+        assert bool((rgb == SENT).all()) and bool((alpha == SENT).all())      # error returns: nothing was launched
+        for entry, call in entries.items():
+            assert call(QH, QW) == 0, (name, entry, lib.vl3d_last_error())
+        torch.cuda.synchronize()

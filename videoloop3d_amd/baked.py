@@ -162,23 +162,8 @@ class BakedPool(_Baked):
         lay = self.layout
         if frames and (min(frames) < 0 or max(frames) >= lay.T):
             raise IndexError(f"frame index out of range [0, {lay.T})")
-        fill = torch.tensor([(self.culled_rgba8 >> (8 * k)) & 0xff for k in range(4)], dtype=torch.uint8, device=self.device)
-        out = torch.empty((lay.D, len(frames), lay.Hs, lay.Ws, 4), dtype=torch.uint8, device=self.device)
-        for d in range(lay.D):
-            base, fs, ok = lay._plane_index(d)
-            for i, t in enumerate(frames):
-                out[d, i] = torch.where(ok[..., None], self.pool[base + t * fs], fill)
-        return out
-
-
-@torch.no_grad()
-def scatter_plane_(layout, pool, d, plane):
-    """plane d of a dense baked clip, (T,Hs,Ws,4) uint8, -> the baked pool [n_slots * 64, 4] through the block table: static blocks take frame
-    0, texels of blocks without storage are dropped (packed.PackedLayout.pack_plane_ for uint8 texels).  Plain torch: conversion."""
-    base, fs, ok = layout._plane_index(d)
-    for t in range(layout.T):
-        sel = ok & ((fs > 0) | (t == 0))
-        pool[(base + t * fs)[sel]] = plane[t][sel]
+        culled = [(self.culled_rgba8 >> (8 * k)) & 0xff for k in range(4)]
+        return torch.stack([lay.unpack_plane(self.pool, d, frames, culled=culled) for d in range(lay.D)], 0)
 
 
 def culled_texel_rgba8(rgb_act, alpha_act):
@@ -222,7 +207,7 @@ def bake_pool(module):
         unset = bake_texels(torch.zeros((1, 4), dtype=torch.float32, device=dev), ra, aa)
         pool = unset.repeat(lay.n_slots * TS * TS, 1)
         for d in range(lay.D):
-            scatter_plane_(lay, pool, d, bake_texels(stack[d], ra, aa))      # (T,Hs,Ws,4) uint8: one plane at a time, never the clip
+            lay.pack_plane_(pool, d, bake_texels(stack[d], ra, aa))      # (T,Hs,Ws,4) uint8: one plane at a time, never the clip
     qk = module.quad_keep.to(torch.uint8).contiguous().clone()
     return BakedPool(pool, lay, qk, module.spec, str(module.args.bg_color), _Camera(module), culled_texel_rgba8(ra, aa))
 

@@ -4,9 +4,9 @@
 // Replaces (reference, /root/reference): MPV.py:351-454 (planar geometry) ==
 // utils_mpi.py:159-176 (warp_homography) + utils_mpi.py:92-107 (overcompose), and their autograd.
 #include <string>
-#include "vl3d_render_core.h"
+#include "vl3d_render_args.h"
 
-using vl3d_render_detail::RenderArgs;
+using namespace vl3d_render_detail;
 
 namespace {
 
@@ -16,7 +16,6 @@ namespace {
 //   (AFFINE_PLANES, HARDCUT, POST)  MPV.py atlas-cell sampling: per-plane texel transform + quad extent   sigmoid/sigmoid
 //   (UTILS_MPI, ZEROS,   POST), (UTILS_MPI, HARDCUT, PRE)  cross-check conventions     sigmoid/sigmoid
 int dispatch(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s) {
-    using namespace vl3d_render_detail;
     const int c = d->coord_mode, b = d->border_mode, o = d->act_order;
     if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_ZEROS && o == VL3D_ACT_PRE) return conv_utils_zeros_pre(bwd, d, a, s);
     if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_ZEROS && o == VL3D_ACT_POST) return conv_utils_zeros_post(bwd, d, a, s);
@@ -49,58 +48,18 @@ int check_desc(const vl3d_render_desc *d) {
     return VL3D_OK;
 }
 
-RenderArgs make_args(const vl3d_render_desc *d) {
-    RenderArgs a{};
-    a.D = d->D; a.T = d->T; a.Hs = d->Hs; a.Ws = d->Ws; a.H = d->H; a.W = d->W;
-    a.Tstride = d->T;
-    a.row0 = d->row0; a.col0 = d->col0;
-    a.pc = d->pixel_center; a.sx = d->sx; a.sy = d->sy; a.ox = d->ox; a.oy = d->oy;
-    a.uv_seed = d->uv_noise_seed;
-    return a;
+// tile culling of the float render: the shared grid rules (vl3d_render_args.h) plus what only this unit's conventions need
+int check_cull(const vl3d_render_desc *desc, const uint8_t *quad_keep, int32_t QH, int32_t QW) {
+    if (!quad_keep) return VL3D_OK;
+    VL3D_REQUIRE(desc->coord_mode != VL3D_COORD_AFFINE_PLANES, "tile culling is not available with per-plane texel transforms");
+    const int rc = check_cull_grid(desc, QH, QW, "tile culling");
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(QH > 0 || (desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT),
+                 "tile-exact layout: the planar MPV / MPI convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
+    return VL3D_OK;
 }
 
 }  // namespace
-
-// the quad grid is laid over the whole plane; the stack may be a texel window of it (desc->cull_*: crop-aware training renders
-// from a compact copy of the window the crop can reach, videoloop3d_amd/optim.py)
-static void set_cull_geometry(RenderArgs &a, const vl3d_render_desc *desc, int32_t QH, int32_t QW) {
-    const bool win = desc->cull_Hs > 0 && desc->cull_Ws > 0;
-    a.q_Hs = win ? desc->cull_Hs : desc->Hs;
-    a.q_Ws = win ? desc->cull_Ws : desc->Ws;
-    a.q_x0 = win ? (float)desc->cull_col0 : 0.0f;
-    a.q_y0 = win ? (float)desc->cull_row0 : 0.0f;
-    a.q_th = a.q_tw = 0;
-    if (QH < 0 && QW < 0) {
-        // TILE-EXACT layout (include/vl3d.h): the plane is |QH| x |QW| tiles of th x tw texels, every quad owning its border row / column; the
-        // homography + (sx, ox) give LATTICE coordinates (a quad spans tw - 1 of them), the kernels add the quad index (make_taps_i)
-        a.QH = -QH; a.QW = -QW;
-        a.q_th = a.q_Hs / a.QH; a.q_tw = a.q_Ws / a.QW;
-        a.q_inv_cw = 1.0f / (float)(a.q_tw > 1 ? a.q_tw - 1 : 1);
-        a.q_inv_ch = 1.0f / (float)(a.q_th > 1 ? a.q_th - 1 : 1);
-        return;
-    }
-    a.QH = QH; a.QW = QW;
-    a.q_inv_cw = (float)QW / (float)(a.q_Ws > 1 ? a.q_Ws - 1 : 1);
-    a.q_inv_ch = (float)QH / (float)(a.q_Hs > 1 ? a.q_Hs - 1 : 1);
-}
-
-static int check_cull(const vl3d_render_desc *desc, const uint8_t *quad_keep, int32_t QH, int32_t QW) {
-    if (!quad_keep) return VL3D_OK;
-    VL3D_REQUIRE(desc->coord_mode != VL3D_COORD_AFFINE_PLANES, "tile culling is not available with per-plane texel transforms");
-    VL3D_REQUIRE((QH > 0 && QW > 0) || (QH < 0 && QW < 0), "tile culling: empty quad grid (both positive, or both negative for the tile-exact layout)");
-    if (QH < 0) {
-        const int pH = desc->cull_Hs > 0 ? desc->cull_Hs : desc->Hs, pW = desc->cull_Ws > 0 ? desc->cull_Ws : desc->Ws;
-        VL3D_REQUIRE(pH % (-QH) == 0 && pW % (-QW) == 0 && pH / (-QH) >= 2 && pW / (-QW) >= 2,
-                     "tile-exact layout: the plane must be |QH| x |QW| whole tiles of at least 2 x 2 texels");
-        VL3D_REQUIRE(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT,
-                     "tile-exact layout: the planar MPV / MPI convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
-    }
-    VL3D_REQUIRE((desc->cull_Hs == 0 && desc->cull_Ws == 0) ||
-                     (desc->cull_row0 >= 0 && desc->cull_col0 >= 0 && desc->cull_row0 + desc->Hs <= desc->cull_Hs && desc->cull_col0 + desc->Ws <= desc->cull_Ws),
-                 "tile culling: the stack window (cull_row0, cull_col0) + (Hs, Ws) leaves the plane (cull_Hs, cull_Ws)");
-    VL3D_REQUIRE(desc->D <= 128, "tile culling supports at most 128 planes");
-    return VL3D_OK;
-}
 
 extern "C" int64_t vl3d_render_cull_scratch_bytes(const vl3d_render_desc *desc) {
     if (!desc || desc->H <= 0 || desc->W <= 0) return 0;
@@ -117,7 +76,7 @@ static int render_fwd_impl(const vl3d_render_desc *desc, const void *stack, cons
     rc = check_cull(desc, quad_keep, QH, QW);
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(!quad_keep || cull_scratch, "tile culling: the forward needs vl3d_render_cull_scratch_bytes() of scratch");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums;
     a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
     set_cull_geometry(a, desc, QH, QW); a.cull_masks = (const unsigned long long *)cull_scratch;
@@ -214,7 +173,7 @@ extern "C" int vl3d_render_fwd_reg(const vl3d_render_desc *desc, const void *sta
     VL3D_REQUIRE(stack && homos && rgb && alpha && sums && reg_state, "null pointer passed to vl3d_render_fwd_reg");
     VL3D_REQUIRE(desc->D <= 128, "the layer regularisers support at most 128 planes (coverage masks)");
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums; a.reg_sums = sums;
     set_reg_state(a, desc, reg_state);
     a.g_f16 = desc->stack_dtype == VL3D_F16;
@@ -247,7 +206,7 @@ extern "C" int vl3d_render_fwd_mask(const vl3d_render_desc *desc, const void *st
     VL3D_REQUIRE((sums == nullptr) == (reg_state == nullptr), "vl3d_render_fwd_mask: sums and reg_state come together (both NULL: no layer regularisers)");
     VL3D_REQUIRE(!sums || desc->D <= 128, "the layer regularisers support at most 128 planes (coverage masks)");
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums;
     a.mask = mask; a.label = label;
     a.fwd_variant = (desc->variant >> 8) & 0xf;
@@ -274,7 +233,7 @@ extern "C" int vl3d_render_bwd_mask(const vl3d_render_desc *desc, const void *st
     VL3D_REQUIRE(stack && mask && homos && rgb && alpha && grad_rgb && grad_label && grad_stack && grad_mask, "null pointer passed to vl3d_render_bwd_mask");
     VL3D_REQUIRE(!grad_reg || reg_state, "vl3d_render_bwd_mask: grad_reg needs the reg_state the forward with regularisers filled");
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     if (grad_reg) set_reg_state(a, desc, reg_state);
     a.stack = (const float *)stack; a.homos = homos;
     a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
@@ -321,7 +280,7 @@ extern "C" int vl3d_render_fwd_reg_culled(const vl3d_render_desc *desc, const vo
     rc = check_cull(desc, quad_keep, QH, QW);
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums; a.reg_sums = sums;
     a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
     set_cull_geometry(a, desc, QH, QW);
@@ -344,7 +303,7 @@ static int render_reg_fwd_impl(const vl3d_render_desc *desc, const void *stack, 
     rc = check_cull(desc, quad_keep, QH, QW);
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = (const float *)stack; a.homos = homos; a.reg_sums = sums;
     a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
     set_cull_geometry(a, desc, QH, QW);
@@ -389,7 +348,7 @@ static int render_bwd_impl(const vl3d_render_desc *desc, const void *stack, cons
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack, "null pointer passed to vl3d_render_bwd");
     VL3D_REQUIRE(!grad_reg || reg_state, "vl3d_render_bwd: grad_reg needs the reg_state the forward with regularisers filled");
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     if (grad_reg) set_reg_state(a, desc, reg_state);
     a.stack = (const float *)stack; a.homos = homos;
     a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
@@ -480,7 +439,7 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
                                     adam->exp_avg, adam->exp_avg_sq, adam->last_step, adam->hist, adam->lr, adam->beta1, adam->beta2, adam->eps,
                                     adam->step, qk, adam->quad_dyn, adam->QH, adam->QW, adam->plane_boxes, adam->blocks, nullptr, adam->boxes_scratch, s);
     if (rc != VL3D_OK) return rc;
-    RenderArgs a = make_args(desc);
+    RenderArgs a = render_args_of(desc);
     if (grad_reg) set_reg_state(a, desc, reg_state);
     a.stack = (const float *)stack; a.homos = homos;
     a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);

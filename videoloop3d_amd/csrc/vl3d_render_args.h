@@ -1,0 +1,65 @@
+// From a render descriptor to the kernels' arguments, host side: the one place where vl3d_render_desc becomes RenderArgs and where the
+// quad grid of a tile-culled model is checked and turned into the kernels' quotients.  Every render entry point (vl3d_render.hip, _packed,
+// _baked, _baked_pool, _plane_rows, _label) starts from these; what an entry adds -- its own refusals, the frame offset of a run, g_f16 --
+// stays at the entry.
+#pragma once
+#include <string>
+#include "vl3d_render_core.h"
+
+namespace vl3d_render_detail {
+
+// dims, window, pixel centre, texel transform and jitter seed; every pointer and option zero.  Tstride = T: an entry that reads a run of
+// frames of a longer clip sets its own.
+inline RenderArgs render_args_of(const vl3d_render_desc *d) {
+    RenderArgs a{};
+    a.D = d->D; a.T = d->T; a.Hs = d->Hs; a.Ws = d->Ws; a.H = d->H; a.W = d->W;
+    a.Tstride = d->T;
+    a.row0 = d->row0; a.col0 = d->col0;
+    a.pc = d->pixel_center; a.sx = d->sx; a.sy = d->sy; a.ox = d->ox; a.oy = d->oy;
+    a.uv_seed = d->uv_noise_seed;
+    return a;
+}
+
+// the quad grid is laid over the whole plane; the stack may be a texel window of it (desc->cull_*: crop-aware training renders
+// from a compact copy of the window the crop can reach, videoloop3d_amd/optim.py)
+inline void set_cull_geometry(RenderArgs &a, const vl3d_render_desc *desc, int32_t QH, int32_t QW) {
+    const bool win = desc->cull_Hs > 0 && desc->cull_Ws > 0;
+    a.q_Hs = win ? desc->cull_Hs : desc->Hs;
+    a.q_Ws = win ? desc->cull_Ws : desc->Ws;
+    a.q_x0 = win ? (float)desc->cull_col0 : 0.0f;
+    a.q_y0 = win ? (float)desc->cull_row0 : 0.0f;
+    a.q_th = a.q_tw = 0;
+    if (QH < 0 && QW < 0) {
+        // TILE-EXACT layout (include/vl3d.h): the plane is |QH| x |QW| tiles of th x tw texels, every quad owning its border row / column; the
+        // homography + (sx, ox) give LATTICE coordinates (a quad spans tw - 1 of them), the kernels add the quad index (make_taps_i)
+        a.QH = -QH; a.QW = -QW;
+        a.q_th = a.q_Hs / a.QH; a.q_tw = a.q_Ws / a.QW;
+        a.q_inv_cw = 1.0f / (float)(a.q_tw > 1 ? a.q_tw - 1 : 1);
+        a.q_inv_ch = 1.0f / (float)(a.q_th > 1 ? a.q_th - 1 : 1);
+        return;
+    }
+    a.QH = QH; a.QW = QW;
+    a.q_inv_cw = (float)QW / (float)(a.q_Ws > 1 ? a.q_Ws - 1 : 1);
+    a.q_inv_ch = (float)QH / (float)(a.q_Hs > 1 ? a.q_Hs - 1 : 1);
+}
+
+// the rules every culled entry shares, `who` in front of the message: the signs of the grid, whole tiles of at least 2 x 2 texels in the
+// tile-exact layout (of the plane the grid lies over: cull_Hs / cull_Ws when set), the stack window inside that plane, two 64-bit plane masks
+inline int check_cull_grid(const vl3d_render_desc *desc, int32_t QH, int32_t QW, const char *who) {
+    const char *bad = nullptr;
+    const int pH = desc->cull_Hs > 0 ? desc->cull_Hs : desc->Hs, pW = desc->cull_Ws > 0 ? desc->cull_Ws : desc->Ws;
+    if (!((QH > 0 && QW > 0) || (QH < 0 && QW < 0)))
+        bad = "bad quad grid (both positive, or both negative for the tile-exact layout)";
+    else if (QH < 0 && !(pH % (-QH) == 0 && pW % (-QW) == 0 && pH / (-QH) >= 2 && pW / (-QW) >= 2))
+        bad = "bad quad grid (tile-exact layout: the plane must be |QH| x |QW| whole tiles of at least 2 x 2 texels)";
+    else if (!((desc->cull_Hs == 0 && desc->cull_Ws == 0) ||
+               (desc->cull_row0 >= 0 && desc->cull_col0 >= 0 && desc->cull_row0 + desc->Hs <= desc->cull_Hs && desc->cull_col0 + desc->Ws <= desc->cull_Ws)))
+        bad = "the stack window (cull_row0, cull_col0) + (Hs, Ws) leaves the plane (cull_Hs, cull_Ws)";
+    else if (desc->D > 128)
+        bad = "tile culling supports at most 128 planes";
+    if (!bad) return VL3D_OK;
+    vl3d_set_error((std::string(who) + ": " + bad).c_str());
+    return VL3D_EINVAL;
+}
+
+}  // namespace vl3d_render_detail

@@ -12,9 +12,10 @@
 //     the 1 / 255 of the decode is folded into the four blend weights once per plane, and nothing is activated.  The launch shape is the float
 //     forward's: 64 x 8 pixels per workgroup, XCD remap, two frames per thread for T >= 2 (an odd tail frame composited twice, stored once).
 // Forward only: a baked model is not trained.
-#include "vl3d_baked_core.h"      // BakedTaps, chan<K>, blend<K>: shared with csrc/vl3d_render_baked_pool.hip
+#include "vl3d_baked_core.h"      // taps, decode, blend, composite step and pixel store: shared with csrc/vl3d_render_baked_pool.hip
+#include "vl3d_render_args.h"
 
-using vl3d_render_detail::RenderArgs;
+using namespace vl3d_render_detail;
 
 namespace {
 
@@ -65,7 +66,6 @@ __device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, 
 
 template <int NF, bool CULL>
 __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y) {
-    static_assert(NF == 1 || NF == 2, "one frame or a frame pair per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_x = b % tiles_x, rest = b / tiles_x;
     const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;
@@ -84,21 +84,8 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
 #pragma unroll
     for (int f = 0; f < NF; ++f) { Tr[f] = 1.0f; cr[f] = cg[f] = cb[f] = A[f] = 0.0f; }
     BakedTaps vA[NF], vB[NF];
-    // The fused multiply-adds are spelt out and nothing else may be contracted: left to -ffp-contract=fast, hipcc fuses cb += w * c in the
-    // frame-pair kernel and not in the one-frame kernel (where it packs the add with A += w instead), and a frame would depend, in its last
-    // bit, on the length of the run it is rendered in.
-    auto composite = [&](const Taps2 &t, const BakedTaps *v) {
-#pragma clang fp contract(off)
-        const f4 w255 = t.w * (1.0f / 255.0f);      // the decode's 1 / 255, once per plane for every channel and frame
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            const float al = blend<3>(v[f], w255) * t.cov;      // uncovered: a = 0 -> the plane drops out of the composite
-            const float w = al * Tr[f];
-            cr[f] = fmaf(w, blend<0>(v[f], w255), cr[f]); cg[f] = fmaf(w, blend<1>(v[f], w255), cg[f]); cb[f] = fmaf(w, blend<2>(v[f], w255), cb[f]);
-            A[f] += w;
-            Tr[f] *= (1.0f - al);
-        }
-    };
+    struct Owner;      // a type of this kernel instantiation alone: its own copy of the composite (vl3d_baked_core.h)
+    const BakedComposite<NF, Owner> composite(Tr, cr, cg, cb, A);
     auto fetch = [&](int d, Taps2 &t, BakedTaps *v) {
         float h[VL3D_HN];
         load_uniform(a.homos + VL3D_HS * d, h);
@@ -110,26 +97,17 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     };
     Taps2 tA, tB;
     if constexpr (CULL) {
-        // the workgroup's plane list (cull_fwd_plan_k): two 64-bit words in SGPRs, scalar bit scans; a pixel inside a culled quad is uncovered
-        // (make_taps2), so walking only the listed planes changes no result
-        const unsigned long long *mk = a.cull_masks + (size_t)(tile_y * tiles_x + tile_x) * 2;
-        unsigned long long m0 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[0];
-        unsigned long long m1 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[1];
-        auto next = [&]() {
-            int d = -1;
-            if (m0) { d = __builtin_ctzll(m0); m0 &= m0 - 1; }
-            else if (m1) { d = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
-            return d;
-        };
-        int dA = next();
+        // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps2)
+        PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
+        int dA = list.next();
         if (dA >= 0) {
             fetch(dA, tA, vA);
             for (;;) {
-                const int dB = next();
+                const int dB = list.next();
                 fetch(dB < 0 ? dA : dB, tB, vB);      // unconditional prefetch (re-reads the current plane past the end)
                 composite(tA, vA);
                 if (dB < 0) break;
-                const int dC = next();
+                const int dC = list.next();
                 fetch(dC < 0 ? dB : dC, tA, vA);
                 composite(tB, vB);
                 if (dC < 0) break;
@@ -149,16 +127,7 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
             if (d + 2 >= a.D) break;
         }
     }
-    size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
-    a.rgb[pix * 3 + 0] = cr[0]; a.rgb[pix * 3 + 1] = cg[0]; a.rgb[pix * 3 + 2] = cb[0];
-    a.alpha[pix] = A[0];
-    if constexpr (NF == 2) {
-        if (has1) {
-            pix += (size_t)a.H * a.W;
-            a.rgb[pix * 3 + 0] = cr[1]; a.rgb[pix * 3 + 1] = cg[1]; a.rgb[pix * 3 + 2] = cb[1];
-            a.alpha[pix] = A[1];
-        }
-    }
+    composite.store(a, t0, x, y, has1);
 }
 
 template <int NF>
@@ -166,10 +135,7 @@ void launch_baked(const RenderArgs &a, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
     if (a.quad_keep) {      // tile culling: the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
-        auto *masks = const_cast<unsigned long long *>(a.cull_masks);
-        (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
-        const int n = tiles_x * tiles_y * a.D;
-        hipLaunchKernelGGL((cull_fwd_plan_k<VL3D_COORD_AFFINE>), dim3((n + 255) / 256), dim3(256), 0, s, a, 8, tiles_x, tiles_y, masks);
+        launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
         hipLaunchKernelGGL((render_fwd_baked_k<NF, true>), grid, block, 0, s, a, tiles_x, tiles_y);
         return;
     }
@@ -213,39 +179,17 @@ extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t
     VL3D_REQUIRE(baked && homos && rgb && alpha, "vl3d_render_fwd_baked: null pointer");
     VL3D_REQUIRE(((uintptr_t)baked & 3) == 0, "vl3d_render_fwd_baked: the texels must be 4-byte aligned");
     VL3D_REQUIRE(T_alloc > 0 && frame0 >= 0 && frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
-    RenderArgs a{};
-    a.D = desc->D; a.T = desc->T; a.Hs = desc->Hs; a.Ws = desc->Ws; a.H = desc->H; a.W = desc->W;
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above)
     a.Tstride = T_alloc;
-    a.row0 = desc->row0; a.col0 = desc->col0;
-    a.pc = desc->pixel_center; a.sx = desc->sx; a.sy = desc->sy; a.ox = desc->ox; a.oy = desc->oy;
     a.stack = reinterpret_cast<const float *>(baked + (size_t)frame0 * desc->Hs * desc->Ws * 4);
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
     if (quad_keep) {
-        VL3D_REQUIRE((QH > 0 && QW > 0) || (QH < 0 && QW < 0), "vl3d_render_fwd_baked: empty quad grid (both positive, or both negative for the tile-exact layout)");
-        VL3D_REQUIRE(desc->D <= 128, "tile culling supports at most 128 planes");
+        const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked");
+        if (rc != VL3D_OK) return rc;
         VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
-        const bool win = desc->cull_Hs > 0 && desc->cull_Ws > 0;
-        VL3D_REQUIRE((desc->cull_Hs == 0 && desc->cull_Ws == 0) ||
-                         (win && desc->cull_row0 >= 0 && desc->cull_col0 >= 0 && desc->cull_row0 + desc->Hs <= desc->cull_Hs && desc->cull_col0 + desc->Ws <= desc->cull_Ws),
-                     "vl3d_render_fwd_baked: the stack window (cull_row0, cull_col0) + (Hs, Ws) leaves the plane (cull_Hs, cull_Ws)");
         a.quad_keep = quad_keep;
         a.cull_masks = (const unsigned long long *)cull_scratch;
-        a.q_Hs = win ? desc->cull_Hs : desc->Hs;
-        a.q_Ws = win ? desc->cull_Ws : desc->Ws;
-        a.q_x0 = win ? (float)desc->cull_col0 : 0.0f;
-        a.q_y0 = win ? (float)desc->cull_row0 : 0.0f;
-        if (QH < 0) {      // tile-exact layout (include/vl3d.h): |QH| x |QW| tiles, every quad owning its border texels
-            VL3D_REQUIRE(a.q_Hs % (-QH) == 0 && a.q_Ws % (-QW) == 0 && a.q_Hs / (-QH) >= 2 && a.q_Ws / (-QW) >= 2,
-                         "tile-exact layout: the plane must be |QH| x |QW| whole tiles of at least 2 x 2 texels");
-            a.QH = -QH; a.QW = -QW;
-            a.q_th = a.q_Hs / a.QH; a.q_tw = a.q_Ws / a.QW;
-            a.q_inv_cw = 1.0f / (float)(a.q_tw - 1);
-            a.q_inv_ch = 1.0f / (float)(a.q_th > 1 ? a.q_th - 1 : 1);
-        } else {
-            a.QH = QH; a.QW = QW;
-            a.q_inv_cw = (float)QW / (float)(a.q_Ws - 1);
-            a.q_inv_ch = (float)QH / (float)(a.q_Hs - 1);
-        }
+        set_cull_geometry(a, desc, QH, QW);
     }
     if (desc->T >= 2) launch_baked<2>(a, (hipStream_t)stream);
     else launch_baked<1>(a, (hipStream_t)stream);

@@ -6,8 +6,8 @@
 // a dynamic block T consecutive ones) -- the static and the dynamic atlas of the viewer package, a quarter of the float pool.
 //   * coverage and taps: make_taps_i / plane_cull of vl3d_render_core.h with the arguments the dense baked kernel passes to make_taps2
 //     (which is make_taps_i plus a byte offset), the workgroups' plane lists by cull_fwd_plan_k;
-//   * decode, blend, composite: chan / blend of vl3d_baked_core.h and the dense kernel's composite, text for text -- the image is the dense
-//     baked render of the unpacked texels, bit for bit;
+//   * decode, blend, composite, pixel store: chan / blend / BakedComposite of vl3d_baked_core.h, the dense kernel's own -- the image is the
+//     dense baked render of the unpacked texels, bit for bit;
 //   * fetch: per texel row one 4-byte table entry (shared by the 64 texels of a block) and ONE 8-byte load of texels (x0, x0 + 1) when they
 //     lie in one block (x0 % 8 != 7), else a second entry and two 4-byte loads across the seam.  A static block is fetched once for both
 //     frames of a pair, a dynamic block at `frame` and `frame + 1`; a tap in a block without storage is `culled_rgba8` from a register; a
@@ -15,8 +15,9 @@
 // Launch shape of the dense baked kernel: 64 x 8 pixels per workgroup, XCD remap, frame pairs for T >= 2 (an odd tail frame composited twice
 // and stored once), the next plane's taps fetched before the current plane is composited (two register sets).  Forward only.
 #include "vl3d_baked_core.h"
+#include "vl3d_render_args.h"
 
-using vl3d_render_detail::RenderArgs;
+using namespace vl3d_render_detail;
 
 namespace {
 
@@ -50,7 +51,6 @@ __device__ __forceinline__ void pool_load(const PoolSrc &p, int e, unsigned in_b
 
 template <int NF>
 __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, PoolSrc p, int tiles_x, int tiles_y) {
-    static_assert(NF == 1 || NF == 2, "one frame or a frame pair per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_x = b % tiles_x, rest = b / tiles_x;
     const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;
@@ -65,20 +65,8 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
 #pragma unroll
     for (int f = 0; f < NF; ++f) { Tr[f] = 1.0f; cr[f] = cg[f] = cb[f] = A[f] = 0.0f; }
     BakedTaps vA[NF], vB[NF];
-    // the dense baked kernel's composite (csrc/vl3d_render_baked.hip), text for text: the fused multiply-adds are spelt out and nothing else
-    // may be contracted, so that a frame has the same bits in a pair, alone, and in the dense render
-    auto composite = [&](const TapsI &t, const BakedTaps *v) {
-#pragma clang fp contract(off)
-        const f4 w255 = t.w * (1.0f / 255.0f);      // the decode's 1 / 255, once per plane for every channel and frame
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            const float al = blend<3>(v[f], w255) * t.cov;      // uncovered: a = 0 -> the plane drops out of the composite
-            const float w = al * Tr[f];
-            cr[f] = fmaf(w, blend<0>(v[f], w255), cr[f]); cg[f] = fmaf(w, blend<1>(v[f], w255), cg[f]); cb[f] = fmaf(w, blend<2>(v[f], w255), cb[f]);
-            A[f] += w;
-            Tr[f] *= (1.0f - al);
-        }
-    };
+    struct Owner;      // a type of this kernel instantiation alone: its own copy of the composite (vl3d_baked_core.h)
+    const BakedComposite<NF, Owner> composite(Tr, cr, cg, cb, A);
     auto fetch = [&](int d, TapsI &t, BakedTaps *v) {
         float h[VL3D_HN];
         load_uniform(a.homos + VL3D_HS * d, h);
@@ -115,45 +103,28 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
         }
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
+    // (an uncovered pixel's composite step changes no bit of the state -- see fetch --: skipped)
     auto composite_if = [&](const TapsI &t, const BakedTaps *v) {
         if (t.cov != 0.0f) composite(t, v);
     };
-    // the workgroup's plane list (cull_fwd_plan_k): two 64-bit words in SGPRs, scalar bit scans; a pixel inside a culled quad is uncovered
-    // (make_taps_i), so walking only the listed planes changes no result
-    const unsigned long long *mk = a.cull_masks + (size_t)(tile_y * tiles_x + tile_x) * 2;
-    unsigned long long m0 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[0];
-    unsigned long long m1 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[1];
-    auto next = [&]() {
-        int d = -1;
-        if (m0) { d = __builtin_ctzll(m0); m0 &= m0 - 1; }
-        else if (m1) { d = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
-        return d;
-    };
+    // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps_i)
+    PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
     TapsI tA, tB;
-    const int dA = next();
+    const int dA = list.next();
     if (dA >= 0) {
         fetch(dA, tA, vA);
         for (;;) {      // two register sets: the next listed plane is fetched before the current one is composited; nothing is fetched past the end
-            const int dB = next();
+            const int dB = list.next();
             if (dB >= 0) fetch(dB, tB, vB);
             composite_if(tA, vA);
             if (dB < 0) break;
-            const int dC = next();
+            const int dC = list.next();
             if (dC >= 0) fetch(dC, tA, vA);
             composite_if(tB, vB);
             if (dC < 0) break;
         }
     }
-    size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
-    a.rgb[pix * 3 + 0] = cr[0]; a.rgb[pix * 3 + 1] = cg[0]; a.rgb[pix * 3 + 2] = cb[0];
-    a.alpha[pix] = A[0];
-    if constexpr (NF == 2) {
-        if (has1) {
-            pix += (size_t)a.H * a.W;
-            a.rgb[pix * 3 + 0] = cr[1]; a.rgb[pix * 3 + 1] = cg[1]; a.rgb[pix * 3 + 2] = cb[1];
-            a.alpha[pix] = A[1];
-        }
-    }
+    composite.store(a, t0, x, y, has1);
 }
 
 template <int NF>
@@ -161,10 +132,7 @@ void launch_baked_pool(const RenderArgs &a, const PoolSrc &p, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
     // the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
-    auto *masks = const_cast<unsigned long long *>(a.cull_masks);
-    (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
-    const int n = tiles_x * tiles_y * a.D;
-    hipLaunchKernelGGL((cull_fwd_plan_k<VL3D_COORD_AFFINE>), dim3((n + 255) / 256), dim3(256), 0, s, a, 8, tiles_x, tiles_y, masks);
+    launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
     hipLaunchKernelGGL((render_fwd_baked_pool_k<NF>), grid, block, 0, s, a, p, tiles_x, tiles_y);
 }
 
@@ -188,28 +156,14 @@ extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const in
     VL3D_REQUIRE(((uintptr_t)pool & 3) == 0 && ((uintptr_t)blocks & 3) == 0, "vl3d_render_fwd_baked_pool: the pool and the block table must be 4-byte aligned");
     VL3D_REQUIRE(T_model > 0 && frame0 >= 0 && (int64_t)frame0 + desc->T <= T_model,
                  "vl3d_render_fwd_baked_pool: the run of frames leaves the model's T_model frames");
-    VL3D_REQUIRE((QH > 0 && QW > 0) || (QH < 0 && QW < 0 && desc->Hs % (-QH) == 0 && desc->Ws % (-QW) == 0 && desc->Hs / (-QH) >= 2 && desc->Ws / (-QW) >= 2),
-                 "vl3d_render_fwd_baked_pool: bad quad grid (both positive, or both negative for the tile-exact layout: whole tiles of at least 2 x 2 texels)");
-    VL3D_REQUIRE(desc->D <= 128, "tile culling supports at most 128 planes");
     VL3D_REQUIRE(desc->cull_Hs == 0 && desc->cull_Ws == 0, "vl3d_render_fwd_baked_pool: the pool holds whole planes (no desc->cull_* window)");
-    RenderArgs a{};
-    a.D = desc->D; a.T = desc->T; a.Hs = desc->Hs; a.Ws = desc->Ws; a.H = desc->H; a.W = desc->W;
-    a.row0 = desc->row0; a.col0 = desc->col0;
-    a.pc = desc->pixel_center; a.sx = desc->sx; a.sy = desc->sy; a.ox = desc->ox; a.oy = desc->oy;
+    const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked_pool");
+    if (rc != VL3D_OK) return rc;
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a.Tstride is not read: the pool has no frame stride)
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
     a.quad_keep = quad_keep;
     a.cull_masks = (const unsigned long long *)cull_scratch;
-    a.q_Hs = desc->Hs; a.q_Ws = desc->Ws; a.q_x0 = 0.0f; a.q_y0 = 0.0f;
-    if (QH < 0) {      // tile-exact layout (include/vl3d.h): |QH| x |QW| tiles, every quad owning its border texels
-        a.QH = -QH; a.QW = -QW;
-        a.q_th = a.q_Hs / a.QH; a.q_tw = a.q_Ws / a.QW;
-        a.q_inv_cw = 1.0f / (float)(a.q_tw - 1);
-        a.q_inv_ch = 1.0f / (float)(a.q_th > 1 ? a.q_th - 1 : 1);
-    } else {
-        a.QH = QH; a.QW = QW;
-        a.q_inv_cw = (float)QW / (float)(a.q_Ws - 1);
-        a.q_inv_ch = (float)QH / (float)(a.q_Hs - 1);
-    }
+    set_cull_geometry(a, desc, QH, QW);
     const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, frame0, culled_rgba8};
     if (desc->T >= 2) launch_baked_pool<2>(a, p, (hipStream_t)stream);
     else launch_baked_pool<1>(a, p, (hipStream_t)stream);

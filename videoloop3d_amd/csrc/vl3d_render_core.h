@@ -818,6 +818,33 @@ __global__ __launch_bounds__(256) void cull_fwd_plan_k(RenderArgs a, int TY, int
     if (box_touches_kept_quad(a, d, tnx, txx, tny, txy)) atomicOr(masks + (size_t)tile * 2 + (d >> 6), 1ull << (d & 63));
 }
 
+// clear a.cull_masks and run the plan for a forward of tiles_x x tiles_y workgroups of 64 x TY pixels, on the forward's stream
+template <int COORD>
+void launch_cull_fwd_plan(const RenderArgs &a, int TY, int tiles_x, int tiles_y, hipStream_t s) {
+    auto *masks = const_cast<unsigned long long *>(a.cull_masks);
+    (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
+    const int n = tiles_x * tiles_y * a.D;
+    hipLaunchKernelGGL((cull_fwd_plan_k<COORD>), dim3((n + 255) / 256), dim3(256), 0, s, a, TY, tiles_x, tiles_y, masks);
+}
+
+// A workgroup's plane list as the plan wrote it: two 64-bit words read through the constant address space (SGPRs, scalar bit scans).
+// next(): the nearest plane not yet handed out, -1 when the list is exhausted.  A plane that is not listed has no kept quad under any of the
+// workgroup's pixels -- every sample of it is uncovered --, so walking only the list changes no result.
+struct PlaneList {
+    unsigned long long m0, m1;
+    __device__ __forceinline__ PlaneList(const unsigned long long *cull_masks, int tile) {
+        typedef const __attribute__((address_space(4))) unsigned long long *cu64_p;
+        const cu64_p mk = (cu64_p)(cull_masks + (size_t)tile * 2);
+        m0 = mk[0]; m1 = mk[1];
+    }
+    __device__ __forceinline__ int next() {
+        int d = -1;
+        if (m0) { d = __builtin_ctzll(m0); m0 &= m0 - 1; }
+        else if (m1) { d = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
+        return d;
+    }
+};
+
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, int TY, bool SWZ, bool F16, bool CULL = false, bool MASK = false>
 __global__ __launch_bounds__(64 * TY) void render_fwd2_k(RenderArgs a, int tiles_x, int tiles_y) {
     static_assert(!(MASK && (CULL || F16)), "the loop-mask channel: dense fp32 stage-1 stacks");
@@ -851,15 +878,7 @@ __global__ __launch_bounds__(64 * TY) void render_fwd2_k(RenderArgs a, int tiles
     if constexpr (CULL) {
         // tile culling: walk only the planes whose bit is set for this workgroup (two 64-bit words in SGPRs, scalar bit scans);
         // the skipped planes' taps are all culled texels (alpha exactly 0), so the result is bit-identical to walking them
-        const unsigned long long *mk = a.cull_masks + (size_t)(tile_y * tiles_x + tile_x) * 2;
-        unsigned long long m0 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[0];
-        unsigned long long m1 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[1];
-        auto next = [&]() {
-            int d = -1;
-            if (m0) { d = __builtin_ctzll(m0); m0 &= m0 - 1; }
-            else if (m1) { d = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
-            return d;
-        };
+        PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
         auto fetch = [&](int d, Taps2 &t, tapv_t *v) {
             float h[VL3D_HN];
             load_uniform(a.homos + VL3D_HS * d, h);
@@ -867,16 +886,16 @@ __global__ __launch_bounds__(64 * TY) void render_fwd2_k(RenderArgs a, int tiles
             load_taps2<F16>(plane + (size_t)d * plane_stride_b, t, st, v);
             asm volatile("" ::: "memory");
         };
-        int dA = next();
+        int dA = list.next();
         if (dA >= 0) {
             Taps2 tA, tB;
             fetch(dA, tA, vA);
             for (;;) {
-                const int dB = next();
+                const int dB = list.next();
                 fetch(dB < 0 ? dA : dB, tB, vB);      // unconditional prefetch (re-reads the current plane past the end)
                 VL3D_COMPOSITE(tA, vA, mA)
                 if (dB < 0) break;
-                const int dC = next();
+                const int dC = list.next();
                 fetch(dC < 0 ? dB : dC, tA, vA);
                 VL3D_COMPOSITE(tB, vB, mB)
                 if (dC < 0) break;
@@ -963,15 +982,7 @@ __global__ __launch_bounds__(64 * TY, VL3D_FWD2X_MIN_WAVES) void render_fwd2x_k(
     if constexpr (CULL) {
         // the workgroup's plane list (cull_fwd_plan_k): two 64-bit words in SGPRs, scalar bit scans; a skipped plane's taps are all culled
         // texels (alpha exactly 0), so the result is bit-identical to walking it
-        const unsigned long long *mk = a.cull_masks + (size_t)(tile_y * tiles_x + tile_x) * 2;
-        unsigned long long m0 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[0];
-        unsigned long long m1 = ((const __attribute__((address_space(4))) unsigned long long *)mk)[1];
-        auto next = [&]() {
-            int d = -1;
-            if (m0) { d = __builtin_ctzll(m0); m0 &= m0 - 1; }
-            else if (m1) { d = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
-            return d;
-        };
+        PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
         auto fetch = [&](int d, Taps2 &t, tapv_t *v0, tapv_t *v1) {
             float h[VL3D_HN];
             load_uniform(a.homos + VL3D_HS * d, h);
@@ -980,16 +991,16 @@ __global__ __launch_bounds__(64 * TY, VL3D_FWD2X_MIN_WAVES) void render_fwd2x_k(
             load_taps2<F16>(plane1 + (size_t)d * plane_stride_b, t, st, v1);
             asm volatile("" ::: "memory");
         };
-        int dA = next();
+        int dA = list.next();
         if (dA >= 0) {
             Taps2 tA, tB;
             fetch(dA, tA, vA0, vA1);
             for (;;) {
-                const int dB = next();
+                const int dB = list.next();
                 fetch(dB < 0 ? dA : dB, tB, vB0, vB1);      // unconditional prefetch (re-reads the current plane past the end)
                 VL3D_COMPOSITE2(tA, vA0, vA1)
                 if (dB < 0) break;
-                const int dC = next();
+                const int dC = list.next();
                 fetch(dC < 0 ? dB : dC, tA, vA0, vA1);
                 VL3D_COMPOSITE2(tB, vB0, vB1)
                 if (dC < 0) break;
@@ -1044,10 +1055,7 @@ void launch_fwd2x(const RenderArgs &a, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + TY - 1) / TY;
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + 1) / 2))), block(64 * TY);
     if (a.quad_keep && a.cull_masks) {       // tile culling: plan (frame independent; the workgroups are render_fwd2_k's 64 x 8 tiles), then the plane-list kernel
-        auto *masks = const_cast<unsigned long long *>(a.cull_masks);
-        (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
-        const int n = tiles_x * tiles_y * a.D;
-        hipLaunchKernelGGL((cull_fwd_plan_k<COORD>), dim3((n + 255) / 256), dim3(256), 0, s, a, TY, tiles_x, tiles_y, masks);
+        launch_cull_fwd_plan<COORD>(a, TY, tiles_x, tiles_y, s);
         hipLaunchKernelGGL((render_fwd2x_k<COORD, BORDER, ORDER, RACT, AACT, TY, F16, true>), grid, block, 0, s, a, tiles_x, tiles_y);
         return;
     }
@@ -1058,10 +1066,7 @@ template <int COORD, int BORDER, int ORDER, int RACT, int AACT, int TY, bool SWZ
 void launch_fwd2(const RenderArgs &a, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + TY - 1) / TY;
     if (a.quad_keep && a.cull_masks) {       // tile culling: plan (frame independent), then the plane-list kernel
-        auto *masks = const_cast<unsigned long long *>(a.cull_masks);
-        (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
-        const int n = tiles_x * tiles_y * a.D;
-        hipLaunchKernelGGL((cull_fwd_plan_k<COORD>), dim3((n + 255) / 256), dim3(256), 0, s, a, TY, tiles_x, tiles_y, masks);
+        launch_cull_fwd_plan<COORD>(a, TY, tiles_x, tiles_y, s);
         hipLaunchKernelGGL((render_fwd2_k<COORD, BORDER, ORDER, RACT, AACT, TY, SWZ, F16, true>), dim3((unsigned)(tiles_x * tiles_y * a.T)),
                            dim3(64 * TY), 0, s, a, tiles_x, tiles_y);
         return;

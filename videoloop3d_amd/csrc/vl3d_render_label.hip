@@ -9,9 +9,9 @@
 // (the rasteriser's, in the reference).  The gradient reaches the mask texture only (alphas detached, MPI.py:577-579): global atomics at the four
 // unjittered taps.  Off in every shipped configuration (config_parser.py:48): built for completeness of MPI.py's semantics, not for speed.
 #include <string>
-#include "vl3d_render_core.h"
+#include "vl3d_render_args.h"
 
-using vl3d_render_detail::RenderArgs;
+using namespace vl3d_render_detail;
 
 namespace {
 
@@ -80,15 +80,6 @@ int check(const vl3d_render_desc *d, const char *who) {
     return VL3D_OK;
 }
 
-RenderArgs args_of(const vl3d_render_desc *d) {
-    RenderArgs a{};
-    a.D = d->D; a.T = d->T; a.Hs = d->Hs; a.Ws = d->Ws; a.H = d->H; a.W = d->W; a.Tstride = d->T;
-    a.row0 = d->row0; a.col0 = d->col0;
-    a.pc = d->pixel_center; a.sx = d->sx; a.sy = d->sy; a.ox = d->ox; a.oy = d->oy;
-    a.uv_seed = d->uv_noise_seed;
-    return a;
-}
-
 }  // namespace
 
 extern "C" int vl3d_label_noise_fwd(const vl3d_render_desc *desc, const float *stack, const float *mask, const float *homos, float *label,
@@ -96,7 +87,7 @@ extern "C" int vl3d_label_noise_fwd(const vl3d_render_desc *desc, const float *s
     int rc = check(desc, "vl3d_label_noise_fwd");
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(stack && mask && homos && label, "null pointer passed to vl3d_label_noise_fwd");
-    RenderArgs a = args_of(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = stack; a.mask = mask; a.homos = homos; a.label = label;
     hipLaunchKernelGGL(label_noise_k<false>, dim3((desc->W + 63) / 64, (desc->H + 3) / 4, desc->T), dim3(256), 0, (hipStream_t)stream, a, desc->alpha_act);
     VL3D_CHECK_LAUNCH();
@@ -108,7 +99,7 @@ extern "C" int vl3d_label_noise_bwd(const vl3d_render_desc *desc, const float *s
     int rc = check(desc, "vl3d_label_noise_bwd");
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(stack && mask && homos && grad_label && grad_mask, "null pointer passed to vl3d_label_noise_bwd");
-    RenderArgs a = args_of(desc);
+    RenderArgs a = render_args_of(desc);
     a.stack = stack; a.mask = mask; a.homos = homos; a.g_label = grad_label; a.g_mask = grad_mask;
     VL3D_HIP(hipMemsetAsync(grad_mask, 0, (size_t)desc->D * desc->T * desc->Hs * desc->Ws * sizeof(float), (hipStream_t)stream));
     hipLaunchKernelGGL(label_noise_k<true>, dim3((desc->W + 63) / 64, (desc->H + 3) / 4, desc->T), dim3(256), 0, (hipStream_t)stream, a, desc->alpha_act);

@@ -9,9 +9,9 @@
 // blended, activated and composited by the dense kernels' own shade2 / composite sequence: the image is the dense culled render's,
 // bit for bit, without the (D, n, Hs, Ws, 4) stack an evaluation render used to unpack first.
 // Forward only: training renders from the compact window copy the crop-aware optimiser's catch-up builds anyway (csrc/vl3d_optim.hip).
-#include "vl3d_render_core.h"
+#include "vl3d_render_args.h"
 
-using vl3d_render_detail::RenderArgs;
+using namespace vl3d_render_detail;
 
 namespace {
 
@@ -91,28 +91,18 @@ extern "C" int vl3d_render_fwd_packed(const vl3d_render_desc *desc, const int32_
     VL3D_REQUIRE(desc->D > 0 && desc->D <= 128 && desc->T > 0 && desc->Hs > 0 && desc->Ws > 0 && desc->H > 0 && desc->W > 0 && n > 0,
                  "vl3d_render_fwd_packed: non-positive dims (or more than 128 planes)");
     VL3D_REQUIRE(blocks && pool && frames && homos && quad_keep && rgb && alpha, "vl3d_render_fwd_packed: null pointer");
-    VL3D_REQUIRE((QH > 0 && QW > 0) || (QH < 0 && QW < 0 && desc->Hs % (-QH) == 0 && desc->Ws % (-QW) == 0 && desc->Hs / (-QH) >= 2 && desc->Ws / (-QW) >= 2),
-                 "vl3d_render_fwd_packed: bad quad grid (tile-exact layout: whole tiles of at least 2 x 2 texels)");
+    vl3d_render_desc whole = *desc;      // the pool holds whole planes: the quad grid lies over (Hs, Ws), desc->cull_* is not read
+    whole.cull_row0 = whole.cull_col0 = whole.cull_Hs = whole.cull_Ws = 0;
+    const int rc = check_cull_grid(&whole, QH, QW, "vl3d_render_fwd_packed");
+    if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT && desc->act_order == VL3D_ACT_POST,
                  "vl3d_render_fwd_packed: the planar MPV convention (affine, hardcut, post) only");
     VL3D_REQUIRE(desc->stack_dtype == VL3D_F32, "vl3d_render_fwd_packed: the pool holds fp32 texels");
     VL3D_REQUIRE((int64_t)desc->H * desc->W * n < (1ll << 40), "vl3d_render_fwd_packed: output too large");
-    RenderArgs a{};
-    a.D = desc->D; a.T = desc->T; a.Hs = desc->Hs; a.Ws = desc->Ws; a.H = desc->H; a.W = desc->W;
-    a.row0 = desc->row0; a.col0 = desc->col0;
-    a.pc = desc->pixel_center; a.sx = desc->sx; a.sy = desc->sy; a.ox = desc->ox; a.oy = desc->oy;
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed, a.Tstride: not read by this unit's kernel -- a packed model renders without jitter)
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
-    a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
-    a.q_Hs = desc->Hs; a.q_Ws = desc->Ws; a.q_x0 = 0.0f; a.q_y0 = 0.0f;
-    if (QH < 0) {      // tile-exact layout (include/vl3d.h): |QH| x |QW| tiles, each quad owning its border texels
-        a.QH = -QH; a.QW = -QW;
-        a.q_th = desc->Hs / a.QH; a.q_tw = desc->Ws / a.QW;
-        a.q_inv_cw = 1.0f / (float)(a.q_tw - 1);
-        a.q_inv_ch = 1.0f / (float)(a.q_th - 1);
-    } else {
-        a.q_inv_cw = (float)QW / (float)(a.q_Ws > 1 ? a.q_Ws - 1 : 1);
-        a.q_inv_ch = (float)QH / (float)(a.q_Hs > 1 ? a.q_Hs - 1 : 1);
-    }
+    a.quad_keep = quad_keep;
+    set_cull_geometry(a, &whole, QH, QW);
     PackedSrc p{blocks, reinterpret_cast<const float4 *>(pool), frames, (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, culled_alpha};
     hipStream_t s = (hipStream_t)stream;
 #define VL3D_CASE(R, A)                                                   \

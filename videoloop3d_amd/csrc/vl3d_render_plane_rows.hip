@@ -7,7 +7,7 @@
 // magnitudes only by luck.  The origin is uniform per plane: it is read through the constant address space (one scalar load per plane,
 // an SGPR operand of the offset arithmetic).  A translation unit of its own, so that the headline kernels of vl3d_render_c*.hip compile
 // exactly as before (their schedules are pinned by tests/test_kernel_schedule_canary.py).
-#include "vl3d_render_core.h"
+#include "vl3d_render_args.h"
 
 using vl3d_render_detail::RenderArgs;
 
@@ -380,16 +380,6 @@ int check_plane_rows_desc(const vl3d_render_desc *d, const int32_t *plane_row0, 
     return VL3D_OK;
 }
 
-RenderArgs plane_rows_args(const vl3d_render_desc *d) {
-    RenderArgs a{};
-    a.D = d->D; a.T = d->T; a.Hs = d->Hs; a.Ws = d->Ws; a.H = d->H; a.W = d->W;
-    a.Tstride = d->T;
-    a.row0 = d->row0; a.col0 = d->col0;
-    a.pc = d->pixel_center; a.sx = d->sx; a.sy = d->sy; a.ox = d->ox; a.oy = d->oy;
-    a.g_f16 = d->stack_dtype == VL3D_F16;
-    return a;
-}
-
 }  // namespace
 
 extern "C" int vl3d_render_fwd_plane_rows(const vl3d_render_desc *desc, const void *stack, const int32_t *plane_row0, int32_t R, const float *homos,
@@ -397,7 +387,8 @@ extern "C" int vl3d_render_fwd_plane_rows(const vl3d_render_desc *desc, const vo
     int rc = check_plane_rows_desc(desc, plane_row0, R);
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(stack && homos && rgb && alpha, "null pointer passed to vl3d_render_fwd_plane_rows");
-    RenderArgs a = plane_rows_args(desc);
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0: check_plane_rows_desc)
+    a.g_f16 = desc->stack_dtype == VL3D_F16;
     a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha;
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + 1) / 2))), block(64 * 8);
@@ -421,7 +412,8 @@ extern "C" int vl3d_render_bwd_plane_rows(const vl3d_render_desc *desc, const vo
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack, "null pointer passed to vl3d_render_bwd_plane_rows");
     const bool f16 = desc->stack_dtype == VL3D_F16;
-    RenderArgs a = plane_rows_args(desc);
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0: check_plane_rows_desc)
+    a.g_f16 = f16;
     a.stack = (const float *)stack; a.homos = homos;
     a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
     a.g_rgb = grad_rgb; a.g_alpha = grad_alpha; a.g_stack = (float *)grad_stack;

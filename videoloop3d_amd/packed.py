@@ -85,9 +85,10 @@ class PackedLayout:
 
     @torch.no_grad()
     def pack_plane_(self, pool, d, plane):
-        """plane (T,Hs,Ws,4) of the dense model -> the pool (static blocks take frame 0; texels of blocks without storage are dropped)."""
+        """plane (T,Hs,Ws,4) of the dense model -> the pool, in the pool's dtype (float texels, or the uint8 texels of a baked pool): static
+        blocks take frame 0; texels of blocks without storage are dropped."""
         base, fs, ok = self._plane_index(d)
-        plane = plane.to(pool.device, torch.float32)
+        plane = plane.to(pool.device, pool.dtype)
         for t in range(self.T):
             sel = ok & ((fs > 0) | (t == 0))
             pool[(base + t * fs)[sel]] = plane[t][sel]

@@ -44,26 +44,56 @@ def _qgrid(quad_keep, spec):
     return (-QH, -QW) if getattr(spec, "tile", (0, 0))[0] else (QH, QW)
 
 
-def _desc(stack, H, W, spec, row0, col0, cull_window=None, grad_flags=0):
-    D, T, Hs, Ws, C4 = stack.shape
-    assert C4 == 4, "plane stack must be (D,T,Hs,Ws,4)"
+def _desc_dims(D, T, Hs, Ws, H, W, spec, stack_dtype=0, row0=0, col0=0):
+    """the render descriptor of `spec` for a model given by its dimensions (a stack, or the block table of a packed model)."""
     d = L.RenderDesc()
-    d.D, d.T, d.Hs, d.Ws, d.H, d.W = D, T, Hs, Ws, int(H), int(W)
+    d.D, d.T, d.Hs, d.Ws, d.H, d.W = int(D), int(T), int(Hs), int(Ws), int(H), int(W)
     d.row0, d.col0 = int(row0), int(col0)
     d.coord_mode = L.COORD[spec.coord_mode]
     d.border_mode = L.BORDER[spec.border]
     d.act_order = L.ACT_ORDER[spec.act_order]
     d.rgb_act, d.alpha_act = L.ACT[spec.rgb_act], L.ACT[spec.alpha_act]
-    d.stack_dtype = 1 if stack.dtype == torch.float16 else 0
+    d.stack_dtype = int(stack_dtype)
     d.pixel_center = float(spec.pixel_center)
     d.sx, d.sy = float(spec.scale[0]), float(spec.scale[1])
     d.ox, d.oy = float(spec.offset[0]), float(spec.offset[1])
     d.variant = int(spec.variant)
     d.uv_noise_seed = int(getattr(spec, "uv_noise_seed", 0)) & 0xFFFFFFFF
+    return d
+
+
+def _desc(stack, H, W, spec, row0, col0, cull_window=None, grad_flags=0):
+    D, T, Hs, Ws, C4 = stack.shape
+    assert C4 == 4, "plane stack must be (D,T,Hs,Ws,4)"
+    d = _desc_dims(D, T, Hs, Ws, H, W, spec, 1 if stack.dtype == torch.float16 else 0, row0, col0)
     if cull_window is not None:        # the stack is the texel window (y0, x0) of a (Hs_plane, Ws_plane) plane the quad grid lies over
         d.cull_row0, d.cull_col0, d.cull_Hs, d.cull_Ws = (int(v) for v in cull_window)
     d.grad_flags = int(grad_flags)
     return d
+
+
+def _out_buffers(out, n, H, W, device, who):
+    """(rgb [n,H,W,3], alpha [n,H,W]) float32: fresh, or the caller's `out` pair checked."""
+    if out is None:
+        return (torch.empty((n, H, W, 3), dtype=torch.float32, device=device), torch.empty((n, H, W), dtype=torch.float32, device=device))
+    rgb, alpha = out
+    if tuple(rgb.shape) != (n, H, W, 3) or tuple(alpha.shape) != (n, H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
+        raise RuntimeError(f"{who}: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
+    return rgb, alpha
+
+
+def _quad_map(quad_keep, D):
+    """the quad map [D,QH,QW] of a tile-culled model as the uint8 tensor the ABI reads."""
+    L.check_cuda(quad_keep)
+    if quad_keep.dim() != 3 or quad_keep.shape[0] != D:
+        raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {D}, got {tuple(quad_keep.shape)}")
+    from .tiles import as_u8
+    return as_u8(quad_keep)
+
+
+def _cull_scratch(desc, device):
+    """the plane masks of a culled forward (vl3d_render_cull_scratch_bytes); call under torch.cuda.device(device)."""
+    return torch.empty((int(L.lib().vl3d_render_cull_scratch_bytes(desc)) + 3) // 4, dtype=torch.float32, device=device)
 
 
 # scratch (plan) buffer of the most recent backward: element 0 viewed as int32 is 1 when the LDS-staged
@@ -84,11 +114,7 @@ class _RenderPlanes(torch.autograd.Function):
                                         and fused_adam.fuses(stack, spec)) else None
         ctx.leaf = stack if ctx.fused_adam is not None else None
         if quad_keep is not None:
-            L.check_cuda(quad_keep)
-            if quad_keep.dim() != 3 or quad_keep.shape[0] != stack.shape[0]:
-                raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {stack.shape[0]}, got {tuple(quad_keep.shape)}")
-            from .tiles import as_u8
-            quad_keep = as_u8(quad_keep)
+            quad_keep = _quad_map(quad_keep, stack.shape[0])
         if stack.dtype not in (torch.float32, torch.float16):
             raise RuntimeError("plane stack must be float32 or float16 (arithmetic is fp32 either way)")
         if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
@@ -103,8 +129,7 @@ class _RenderPlanes(torch.autograd.Function):
                 raise RuntimeError("tile culling is not available with per-plane texel transforms")
         elif homos.shape != (D, 3, 3):
             raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
-        rgb = torch.empty((T, H, W, 3), dtype=torch.float32, device=stack.device)
-        alpha = torch.empty((T, H, W), dtype=torch.float32, device=stack.device)
+        rgb, alpha = _out_buffers(None, T, H, W, stack.device, "render_planes")
         ctx.nothing_to_render = T == 0 or H == 0 or W == 0
         if ctx.nothing_to_render:
             # an empty `ts` / zero-area crop: grid_sample + cumprod of the reference return empty tensors (MPV.py:425-454); the
@@ -137,8 +162,7 @@ class _RenderPlanes(torch.autograd.Function):
                 L.check(L.lib().vl3d_render_fwd(desc, L.ptr(stack), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.ptr(asum),
                                                 L.stream_ptr(stack.device)), "vl3d_render_fwd")
             else:
-                ncull = int(L.lib().vl3d_render_cull_scratch_bytes(desc))
-                cull = torch.empty((ncull + 3) // 4, dtype=torch.float32, device=stack.device)
+                cull = _cull_scratch(desc, stack.device)
                 L.check(L.lib().vl3d_render_fwd_culled(desc, L.ptr(stack), L.ptr(homos), L.ptr(quad_keep), *_qgrid(quad_keep, spec), L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.ptr(asum),
                                                        L.stream_ptr(stack.device)), "vl3d_render_fwd_culled")
         ctx.save_for_backward(stack, homos, rgb, alpha)
@@ -319,25 +343,14 @@ def render_frame_run(stack, frame0, nframes, homos, H, W, spec: RenderSpec = Ren
     homos = homos.detach().to(torch.float32).contiguous()
     desc = _desc(stack, H, W, spec, 0, 0)
     desc.T = int(nframes)
-    if out is None:
-        rgb = torch.empty((nframes, H, W, 3), dtype=torch.float32, device=stack.device)
-        alpha = torch.empty((nframes, H, W), dtype=torch.float32, device=stack.device)
-    else:
-        rgb, alpha = out
-        if tuple(rgb.shape) != (nframes, H, W, 3) or tuple(alpha.shape) != (nframes, H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
-            raise RuntimeError("render_frame_run: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
+    rgb, alpha = _out_buffers(out, nframes, H, W, stack.device, "render_frame_run")
     with torch.cuda.device(stack.device):
         if quad_keep is None:
             L.check(L.lib().vl3d_render_fwd_frames(desc, L.ptr(stack), int(frame0), int(T), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(stack.device)),
                     "vl3d_render_fwd_frames")
         else:
-            L.check_cuda(quad_keep)
-            if quad_keep.dim() != 3 or quad_keep.shape[0] != D:
-                raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {D}, got {tuple(quad_keep.shape)}")
-            from .tiles import as_u8
-            qk = as_u8(quad_keep)
-            ncull = int(L.lib().vl3d_render_cull_scratch_bytes(desc))
-            cull = torch.empty((ncull + 3) // 4, dtype=torch.float32, device=stack.device)
+            qk = _quad_map(quad_keep, D)
+            cull = _cull_scratch(desc, stack.device)
             L.check(L.lib().vl3d_render_fwd_frames_culled(desc, L.ptr(stack), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec),
                                                           L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(stack.device)), "vl3d_render_fwd_frames_culled")
     return rgb, alpha
@@ -368,24 +381,14 @@ def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec
     desc.T = int(nframes)
     desc.stack_dtype = L.STACK_DTYPE["u8"]
     dev = baked.device
-    if out is None:
-        rgb = torch.empty((nframes, H, W, 3), dtype=torch.float32, device=dev)
-        alpha = torch.empty((nframes, H, W), dtype=torch.float32, device=dev)
-    else:
-        rgb, alpha = out
-        if tuple(rgb.shape) != (nframes, H, W, 3) or tuple(alpha.shape) != (nframes, H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
-            raise RuntimeError("render_frame_run_baked: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
+    rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked")
     qk, grid, cull = None, (0, 0), None
     if quad_keep is not None:
-        L.check_cuda(quad_keep)
-        if quad_keep.dim() != 3 or quad_keep.shape[0] != D:
-            raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {D}, got {tuple(quad_keep.shape)}")
-        from .tiles import as_u8
-        qk = as_u8(quad_keep)
+        qk = _quad_map(quad_keep, D)
         grid = _qgrid(qk, spec)
     with torch.cuda.device(dev):
         if qk is not None:
-            cull = torch.empty((int(L.lib().vl3d_render_cull_scratch_bytes(desc)) + 3) // 4, dtype=torch.float32, device=dev)
+            cull = _cull_scratch(desc, dev)
         L.check(L.lib().vl3d_render_fwd_baked(desc, L.ptr(baked), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *grid, L.ptr(cull), L.ptr(rgb),
                                               L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked")
     return rgb, alpha
@@ -412,9 +415,7 @@ def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec
         raise RuntimeError(f"render_frame_run_baked_pool: frames {frame0} .. {frame0 + nframes - 1} leave the model's {T}")
     if homos.shape != (D, 3, 3):
         raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
-    L.check_cuda(quad_keep)
-    if quad_keep.dim() != 3 or quad_keep.shape[0] != D:
-        raise RuntimeError(f"quad_keep must be [D,QH,QW] with D = {D}, got {tuple(quad_keep.shape)}")
+    qk = _quad_map(quad_keep, D)
     grid = getattr(layout, "quad_grid", None)      # (a layout object made before PackedLayout recorded its grid: nothing to compare with)
     if grid is not None and tuple(quad_keep.shape[1:]) != tuple(grid):
         raise RuntimeError(f"quad_keep is {tuple(quad_keep.shape[1:])} quads per plane, the layout's block table was built from {tuple(grid)}")
@@ -425,26 +426,10 @@ def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec
         raise RuntimeError("render_frame_run_baked_pool: RenderSpec.tile and the layout's tile must both name the tile-exact layout, or neither")
     homos = homos.detach().to(torch.float32).contiguous()
     dev = pool.device
-    d = L.RenderDesc()
-    d.D, d.T, d.Hs, d.Ws, d.H, d.W = D, int(nframes), layout.Hs, layout.Ws, int(H), int(W)
-    d.coord_mode, d.border_mode, d.act_order = L.COORD[spec.coord_mode], L.BORDER[spec.border], L.ACT_ORDER[spec.act_order]
-    d.rgb_act, d.alpha_act = L.ACT[spec.rgb_act], L.ACT[spec.alpha_act]
-    d.stack_dtype = L.STACK_DTYPE["u8"]
-    d.pixel_center = float(spec.pixel_center)
-    d.sx, d.sy, d.ox, d.oy = float(spec.scale[0]), float(spec.scale[1]), float(spec.offset[0]), float(spec.offset[1])
-    d.variant = int(spec.variant)
-    d.uv_noise_seed = int(getattr(spec, "uv_noise_seed", 0)) & 0xFFFFFFFF
-    if out is None:
-        rgb = torch.empty((nframes, H, W, 3), dtype=torch.float32, device=dev)
-        alpha = torch.empty((nframes, H, W), dtype=torch.float32, device=dev)
-    else:
-        rgb, alpha = out
-        if tuple(rgb.shape) != (nframes, H, W, 3) or tuple(alpha.shape) != (nframes, H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
-            raise RuntimeError("render_frame_run_baked_pool: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
-    from .tiles import as_u8
-    qk = as_u8(quad_keep)
+    d = _desc_dims(D, nframes, layout.Hs, layout.Ws, H, W, spec, L.STACK_DTYPE["u8"])
+    rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked_pool")
     with torch.cuda.device(dev):
-        cull = torch.empty((int(L.lib().vl3d_render_cull_scratch_bytes(d)) + 3) // 4, dtype=torch.float32, device=dev)
+        cull = _cull_scratch(d, dev)
         L.check(L.lib().vl3d_render_fwd_baked_pool(d, L.ptr(layout.blocks), L.ptr(pool), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec),
                                                    int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)),
                 "vl3d_render_fwd_baked_pool")
@@ -562,28 +547,17 @@ def render_planes_packed(layout, pool, frames, homos, H, W, spec: RenderSpec, qu
     homos = homos.detach().to(torch.float32).contiguous()
     if homos.shape != (layout.D, 3, 3):
         raise RuntimeError(f"homos must be [D,3,3] = [{layout.D},3,3], got {tuple(homos.shape)}")
-    d = L.RenderDesc()
-    d.D, d.T, d.Hs, d.Ws, d.H, d.W = layout.D, layout.T, layout.Hs, layout.Ws, int(H), int(W)
-    d.coord_mode, d.border_mode, d.act_order = L.COORD["affine"], L.BORDER["hardcut"], L.ACT_ORDER["post"]
-    d.rgb_act, d.alpha_act = L.ACT[spec.rgb_act], L.ACT[spec.alpha_act]
-    d.pixel_center = float(spec.pixel_center)
-    d.sx, d.sy, d.ox, d.oy = float(spec.scale[0]), float(spec.scale[1]), float(spec.offset[0]), float(spec.offset[1])
+    d = _desc_dims(layout.D, layout.T, layout.Hs, layout.Ws, H, W, spec)      # (the planar convention: checked above)
+    d.variant, d.uv_noise_seed = 0, 0
     dev = pool.device
-    from .tiles import as_u8
-    qk = as_u8(quad_keep)
+    qk = _quad_map(quad_keep, layout.D)
     if frames_dev is not None:
         if frames_dev.dtype != torch.int32 or frames_dev.numel() != len(frames) or not frames_dev.is_contiguous() or frames_dev.device != dev:
             raise RuntimeError("render_planes_packed: frames_dev must be the contiguous int32 device copy of `frames`")
         ft = frames_dev
     else:
         ft = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
-    if out is None:
-        rgb = torch.empty((len(frames), H, W, 3), dtype=torch.float32, device=dev)
-        alpha = torch.empty((len(frames), H, W), dtype=torch.float32, device=dev)
-    else:
-        rgb, alpha = out
-        if tuple(rgb.shape) != (len(frames), H, W, 3) or tuple(alpha.shape) != (len(frames), H, W) or not rgb.is_contiguous() or not alpha.is_contiguous():
-            raise RuntimeError("render_planes_packed: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W])")
+    rgb, alpha = _out_buffers(out, len(frames), H, W, dev, "render_planes_packed")
     with torch.cuda.device(dev):
         L.check(L.lib().vl3d_render_fwd_packed(d, L.ptr(layout.blocks), L.ptr(pool), L.ptr(ft), len(frames), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec), float(culled_alpha), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_packed")
     return rgb, alpha
