@@ -144,6 +144,32 @@ int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *bloc
                                const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
                                void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream);
 
+/* Baked playback along a CAMERA PATH (csrc/vl3d_render_baked.hip, csrc/vl3d_render_baked_pool.hip): N = desc->T output frames, each with
+ * its own camera and its own frame of the clip -- the spiral of scripts/script_render_video.py:47-85, pose i showing loop frame i % T -- in
+ * one plan launch plus one render launch, where the entries above take one camera per call.
+ *   homos (n_cams, D, 3, 3): the homographies of the path's distinct cameras, 1 <= n_cams <= 65535.
+ *   frame_cam, frame_t: DEVICE int32[N]; output frame i is camera frame_cam[i] showing frame frame_t[i] of the clip (of the model's T_model
+ *     frames for the pool).  The host side cannot read them: the wrapper (render.render_path_baked / _pool) checks 0 <= frame_cam[i] <
+ *     n_cams and 0 <= frame_t[i] < T_alloc (T_model) before it uploads them, as it checks the frames_dev of vl3d_render_fwd_packed; the
+ *     kernels check them again -- a workgroup whose camera or frame is out of range returns before any load or store and its pixels stay
+ *     unwritten --, so no index read from device memory forms an address outside the clip, the pool or the masks.
+ *   cull_scratch: vl3d_render_path_cull_scratch_bytes(desc, n_cams) bytes -- two 64-bit plane masks per (camera, 64 x 8 pixel workgroup),
+ *     [n_cams][ceil(H/8) * ceil(W/64)][2], rebuilt every call by ONE memset and ONE plan launch over (camera, tile, plane).  Required with
+ *     quad_keep (always for the pool).
+ *   rgb (N,H,W,3), alpha (N,H,W): frame i holds the bits of the one-camera entry called for frame frame_t[i] alone with camera
+ *     frame_cam[i]'s homographies (one frame per thread: the one-frame kernels' own text).
+ * desc and every refusal are those of vl3d_render_fwd_baked / _pool (same messages, same order); in addition n_cams outside [1, 65535], a
+ * NULL index pointer, T_alloc / T_model < 1 and ceil(W/64) * ceil(H/8) * N > 2^31 - 1 return VL3D_EINVAL with nothing launched.  Forward
+ * only; no host synchronisation. */
+int64_t vl3d_render_path_cull_scratch_bytes(const vl3d_render_desc *desc, int32_t n_cams);
+int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
+                               const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                               void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
+                                    const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
+                                    const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch, float *rgb,
+                                    float *alpha, vl3d_stream_t stream);
+
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).
  * grad_alpha_sums (optional): (T,H,W,2) gradient w.r.t. alpha_sums of the forward.

@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -10,7 +10,14 @@ The CULLED pair (--legs culled, or all): the dense baked render WITH a quad map 
 same texels, alternating in the same way.  The quad map: 35 x 63 quads per plane, one coherent blob per plane holding --keep (0.165) of the
 plane's quads -- the nearest to the blob's centre -- of which the innermost --dyn (0.3) are dynamic; the pool is scattered from the baked clip
 plane by plane, the dense leg's clip is the pool unpacked (texels without storage read culled_rgba8), the two outputs are compared bit for bit
-before the timing.  Prints the two times, their ratio and the bytes of the pool against the dense baked clip."""
+before the timing.  Prints the two times, their ratio and the bytes of the pool against the dense baked clip.
+
+The PATH leg (--legs path; not part of `all`): a spiral of --poses (120) cameras, pose i showing frame i % T, on three storages -- the dense baked
+clip, the culled clip and the pool of the culled pair's map.  (a) the per-frame loop: one render_frame_run_baked / _pool call per pose (one
+memset, one plan and one one-frame render launch each: what render_frames(baked=) issued along a spiral before the path render), the
+yardstick; (b) ONE render_path_baked / _pool call.  The outputs are compared bit for bit first; then (a) and (b) alternate round by round
+under HIP events that span the whole path.  Prints ms per frame of both (median, min .. max over the rounds) and their ratio; the condition is
+path median <= loop median on every storage."""
 import argparse
 import json
 import os
@@ -28,7 +35,8 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path"])
+ap.add_argument("--poses", type=int, default=120)
 ap.add_argument("--keep", type=float, default=0.165)
 ap.add_argument("--dyn", type=float, default=0.3)
 ap.add_argument("--out", default="")
@@ -40,7 +48,8 @@ ge.build()
 from videoloop3d_amd import synth  # noqa: E402
 from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8  # noqa: E402
 from videoloop3d_amd.packed import PackedLayout  # noqa: E402
-from videoloop3d_amd.render import RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool  # noqa: E402
+from videoloop3d_amd.render import (RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool, render_path_baked,  # noqa: E402
+                                    render_path_baked_pool)
 from videoloop3d_amd.utils_mpi import compute_homography, make_depths  # noqa: E402
 
 assert torch.cuda.is_available(), "profiles/baked_fwd.py measures on the MI355X"
@@ -100,8 +109,8 @@ if a.legs in ("all", "dense"):
     res["byte_ratio"] = (16 * D + 16) / (4 * D + 16)
     print(f"baked is {res['speedup']:.2f}x the float forward (algorithmic byte ratio {res['byte_ratio']:.2f}x)")
 
-if a.legs in ("all", "culled"):
-    del stack
+def culled_model(baked):
+    """the culled pair's model from the baked clip: (layout, pool, quad map uint8, BakedPool, the pool unpacked as a dense clip)"""
     QH, QW = 35, 63                                       # 36 x 64 vertices
     qy, qx = torch.meshgrid(torch.arange(QH, device=dev), torch.arange(QW, device=dev), indexing="ij")
     n_keep = round(a.keep * QH * QW)
@@ -118,19 +127,27 @@ if a.legs in ("all", "culled"):
     pool = torch.zeros((lay.n_slots * 64, 4), dtype=torch.uint8, device=dev)
     for d in range(D):
         lay.pack_plane_(pool, d, baked[d])
-    del baked
     qk = keep.to(torch.uint8).contiguous()
     bp = BakedPool(pool, lay, qk, spec, "", None, culled_texel_rgba8("sigmoid", "sigmoid"))
     dense = bp.unpack_frames(range(T))                    # the clip the dense leg reads: the SAME texels, culled_rgba8 where nothing is stored
+    res["culled_map"] = {"QH": QH, "QW": QW, "kept": float(keep.float().mean()), "dynamic_of_kept": float(dyn.sum()) / float(keep.sum()),
+                         "blocks_static": lay.n_static, "blocks_dynamic": lay.n_dynamic, "blocks_unstored": int((lay.blocks < 0).sum()),
+                         "pool_bytes": bp.nbytes, "dense_baked_bytes": dense.numel()}
+    return lay, pool, qk, bp, dense
+
+
+if a.legs in ("all", "culled"):
+    del stack
+    lay, pool, qk, bp, dense = culled_model(baked)
+    del baked
+    QH, QW = res["culled_map"]["QH"], res["culled_map"]["QW"]
     out2 = (torch.empty_like(out[0]), torch.empty_like(out[1]))
     render_frame_run_baked(dense, 0, T, homos, H, W, spec, out=out, quad_keep=qk)
     render_frame_run_baked_pool(lay, pool, 0, T, homos, H, W, spec, out=out2, quad_keep=qk, culled_rgba8=bp.culled_rgba8)
     same = torch.equal(out[0], out2[0]) and torch.equal(out[1], out2[1])
     covered = float((out[1] > 0).float().mean())
     del out2
-    res["culled_map"] = {"QH": QH, "QW": QW, "kept": float(keep.float().mean()), "dynamic_of_kept": float(dyn.sum()) / float(keep.sum()),
-                         "blocks_static": lay.n_static, "blocks_dynamic": lay.n_dynamic, "blocks_unstored": int((lay.blocks < 0).sum()),
-                         "pool_bytes": bp.nbytes, "dense_baked_bytes": dense.numel(), "outputs_bit_equal": same, "covered_pixels": covered}
+    res["culled_map"].update({"outputs_bit_equal": same, "covered_pixels": covered})
     print(f"culled map: {QH} x {QW} quads, {res['culled_map']['kept']:.3f} kept, {res['culled_map']['dynamic_of_kept']:.3f} of them dynamic; blocks "
           f"static {lay.n_static} / dynamic {lay.n_dynamic} / unstored {res['culled_map']['blocks_unstored']}; pool {bp.nbytes / 1e9:.3f} GB against "
           f"{dense.numel() / 1e9:.3f} GB dense baked ({dense.numel() / bp.nbytes:.1f}x); outputs bit-equal: {same}; covered pixels {covered:.3f}")
@@ -140,6 +157,53 @@ if a.legs in ("all", "culled"):
     report("baked_pool", ms["baked_pool"], per, 0)
     res["pool_over_dense_culled"] = res["baked_pool"]["ms_median"] / res["baked_culled"]["ms_median"]
     print(f"pool render is {res['pool_over_dense_culled']:.3f}x the dense culled baked render's time (bar: <= 1.05)")
+
+if a.legs == "path":
+    import math
+    del stack, out
+    N = a.poses
+    hs = []
+    for i in range(N):                                    # the spiral of examples/playback.py around the benchmark camera's rotation
+        ang = 2 * math.pi * i / N
+        e = tar_e.clone()
+        e[:3, 3] = torch.tensor([0.05 * math.cos(ang), 0.03 * math.sin(ang), 0.01 * math.sin(2 * ang)])
+        hs.append(compute_homography(ref_e[None], Kr[None], e[None], Kt[None], torch.tensor([0., 0., 1.]).expand(1, D, 3),
+                                     make_depths(D, 1.0, 100.0).flip(0)[None])[0])
+    path_homos = torch.stack(hs).float().to(dev)          # [N, D, 3, 3]
+    cam, ts = list(range(N)), [i % T for i in range(N)]
+    o_loop = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    o_path = (torch.empty_like(o_loop[0]), torch.empty_like(o_loop[1]))
+    lay, pool, qk, bp, dense = culled_model(baked)
+    kwp = dict(quad_keep=qk, culled_rgba8=bp.culled_rgba8)
+
+    def loop_of(one):
+        def f():
+            for i in range(N):
+                one(ts[i], path_homos[i], (o_loop[0][i:i + 1], o_loop[1][i:i + 1]))
+        return f
+    storages = {
+        "dense": (loop_of(lambda t, h, o: render_frame_run_baked(baked, t, 1, h, H, W, spec, out=o)),
+                  lambda: render_path_baked(baked, cam, ts, path_homos, H, W, spec, out=o_path)),
+        "culled": (loop_of(lambda t, h, o: render_frame_run_baked(dense, t, 1, h, H, W, spec, out=o, quad_keep=qk)),
+                   lambda: render_path_baked(dense, cam, ts, path_homos, H, W, spec, out=o_path, quad_keep=qk)),
+        "pool": (loop_of(lambda t, h, o: render_frame_run_baked_pool(lay, pool, t, 1, h, H, W, spec, out=o, **kwp)),
+                 lambda: render_path_baked_pool(lay, pool, cam, ts, path_homos, H, W, spec, out=o_path, **kwp)),
+    }
+    res["path"] = {"poses": N}
+    for name, (loop, path) in storages.items():
+        o_loop[0].fill_(-1.0), o_path[0].fill_(-2.0)
+        loop()
+        path()
+        same = torch.equal(o_loop[0], o_path[0]) and torch.equal(o_loop[1], o_path[1])
+        ms, per = ab({"loop": loop, "path": path})
+        ml, mp = statistics.median(ms["loop"]), statistics.median(ms["path"])
+        res["path"][name] = {"outputs_bit_equal": same, "covered_pixels": float((o_path[1] > 0).float().mean()),
+                             "loop_ms_per_frame": {"median": ml / N, "min": min(ms["loop"]) / N, "max": max(ms["loop"]) / N},
+                             "path_ms_per_frame": {"median": mp / N, "min": min(ms["path"]) / N, "max": max(ms["path"]) / N},
+                             "path_over_loop": mp / ml, "condition_path_le_loop": bool(mp <= ml)}
+        print(f"path [{name:6s}] bit-equal {same}; loop {ml / N:.4f} ms/frame ({min(ms['loop']) / N:.4f} .. {max(ms['loop']) / N:.4f}), "
+              f"path {mp / N:.4f} ms/frame ({min(ms['path']) / N:.4f} .. {max(ms['path']) / N:.4f}) over {a.rounds} rounds of {per} paths of {N}; "
+              f"path / loop {mp / ml:.3f} -> {'ok' if mp <= ml else 'MISSED'}")
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

@@ -56,9 +56,24 @@ class _Camera:
             setattr(self, name, getattr(module, name).detach().clone())
 
 
+def path_cameras(camera, view_extrins, view_intrins):
+    """the DISTINCT cameras of a path: (view_extrins [N,4,4] world-to-camera, view_intrins [N,3,3], host float tensors) -> (cam_of: for every
+    pose the index of its camera, in order of first appearance; homos [C,D,3,3] on the host: `camera.plane_homographies` of each distinct
+    camera -- the module's own code object, called pose by pose: the bits of its forward).  Poses are equal when their bytes are."""
+    ref_inv = camera._on(view_extrins.device, "ref_extrin")[None, ...].inverse().to(view_extrins.dtype)
+    cams, cam_of = {}, []
+    for i in range(len(view_extrins)):
+        key = (view_extrins[i].numpy().tobytes(), view_intrins[i].numpy().tobytes())
+        if key not in cams:
+            cams[key] = (len(cams), camera.plane_homographies(view_extrins[i:i + 1] @ ref_inv, view_intrins[i:i + 1]))
+        cam_of.append(cams[key][0])
+    return cam_of, torch.stack([h for _, h in sorted(cams.values(), key=lambda c: c[0])])
+
+
 class _Baked:
     """what BakedMPV and BakedPool share: camera, background and the module's eval forward over runs of consecutive frames.  A subclass has
-    `device`, `frm_num`, `bg_color`, `camera` and `_run(frame0, n, homos, H, W, out)`: its render of a run of frames, read in place."""
+    `device`, `frm_num`, `bg_color`, `camera`, `_run(frame0, n, homos, H, W, out)`: its render of a run of frames, read in place, and
+    `_path(frame_cam, frame_t, homos [C,D,3,3], H, W, out)`: its render of a camera path."""
 
     def extrins_to_ref(self, tar_extrins):
         """world-to-camera poses -> reference-camera-to-target transforms, as MPMeshVid.forward forms them (MPV.py:481)."""
@@ -97,6 +112,24 @@ class _Baked:
         return rgb.permute(0, 3, 1, 2), alpha
 
 
+    @torch.no_grad()
+    def render_path(self, H, W, extrins, intrins, ts):
+        """a camera path in one plan launch plus one render launch (render.render_path_baked / _pool): N poses (extrins [N,4,4] world-to-camera,
+        intrins [N,3,3]), output frame i showing frame ts[i] of the clip -> (rgb [N,3,H,W] over the background, alpha [N,H,W]); frame i has
+        the bits of render(H, W, extrins[i:i+1], intrins[i:i+1], ts[i:i+1])."""
+        extrins = torch.as_tensor(extrins, dtype=torch.float32).cpu()
+        intrins = torch.as_tensor(intrins, dtype=torch.float32).cpu()
+        tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        if not (len(extrins) == len(intrins) == len(tl)):
+            raise RuntimeError(f"render_path: one pose and one frame per output frame ({len(extrins)} extrins, {len(intrins)} intrins, {len(tl)} frames)")
+        cam_of, homos = path_cameras(self.camera, extrins, intrins)
+        rgb, alpha = self._path(cam_of, tl, homos.pin_memory().to(self.device, non_blocking=True), H, W, None)
+        bg = self.background()
+        if bg is not None:
+            rgb = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
+        return rgb.permute(0, 3, 1, 2), alpha
+
+
 class BakedMPV(_Baked):
     """bake(module)'s product.  texels [D,T,Hs,Ws,4] uint8 on the device, quad_keep [D,QH,QW] uint8 or None, spec (render.RenderSpec: pixel
     centre, texel scale / offset, tile-exact layout), bg_color, camera (plane_homographies, ref_extrin)."""
@@ -120,6 +153,10 @@ class BakedMPV(_Baked):
     def _run(self, frame0, n, homos, H, W, out):
         from .render import render_frame_run_baked
         return render_frame_run_baked(self.texels, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep)
+
+    def _path(self, frame_cam, frame_t, homos, H, W, out, cull_scratch=None):
+        from .render import render_path_baked
+        return render_path_baked(self.texels, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep, cull_scratch=cull_scratch)
 
 
 class BakedPool(_Baked):
@@ -153,6 +190,11 @@ class BakedPool(_Baked):
         from .render import render_frame_run_baked_pool
         return render_frame_run_baked_pool(self.layout, self.pool, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
                                            culled_rgba8=self.culled_rgba8)
+
+    def _path(self, frame_cam, frame_t, homos, H, W, out, cull_scratch=None):
+        from .render import render_path_baked_pool
+        return render_path_baked_pool(self.layout, self.pool, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
+                                      culled_rgba8=self.culled_rgba8, cull_scratch=cull_scratch)
 
     @torch.no_grad()
     def unpack_frames(self, frames):

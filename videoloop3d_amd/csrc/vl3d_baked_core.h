@@ -4,6 +4,7 @@
 // the composite state of one frame or a frame pair with its step, and the pixel store.  Each unit keeps its fetch, its kernel skeleton and
 // its entry point; the plane list of a tile-culled model is PlaneList of vl3d_render_core.h, as in the float forward.
 #pragma once
+#include <type_traits>
 #include "vl3d_render_core.h"
 
 namespace {
@@ -19,6 +20,22 @@ __device__ __forceinline__ float chan(unsigned w) { return (float)((w >> (8 * K)
 template <int K>
 __device__ __forceinline__ float blend(const BakedTaps &v, f4 w255) {
     return fmaf(chan<K>(v.r0.x), w255[0], fmaf(chan<K>(v.r0.y), w255[1], fmaf(chan<K>(v.r1.x), w255[2], chan<K>(v.r1.y) * w255[3])));
+}
+
+// A camera path (vl3d_render_fwd_baked_path / _pool_path): output frame i of the launch has its own camera frame_cam[i] and its own frame
+// frame_t[i] of the clip, both device int32[N].  NoPath: the kernels' one-camera form, (frame, camera) from the block index and the launch
+// arguments -- an empty argument, so that the two forms are one kernel text.
+struct NoPath {};
+struct PathIdx {
+    const int *frame_cam, *frame_t;
+    int n_cams, n_t;      // cameras of the homographies / masks, frames of the clip (T_alloc; T_model of a pool)
+};
+// (cam, t) of output frame i as workgroup-uniform scalar loads; false -- the workgroup returns before any other load or store -- unless
+// cam is in [0, n_cams) and t in [0, n_t): no index read from device memory ever forms an address outside the clip, the pool or the masks
+__device__ __forceinline__ bool path_frame(const PathIdx &p, int i, int &cam, int &t) {
+    cam = ((cint_p)p.frame_cam)[i];
+    t = ((cint_p)p.frame_t)[i];
+    return (unsigned)cam < (unsigned)p.n_cams && (unsigned)t < (unsigned)p.n_t;
 }
 
 // Front-to-back composite of a pixel's NF frames (one, or a frame pair) over the kernel's own accumulators: transmittance, colour and alpha

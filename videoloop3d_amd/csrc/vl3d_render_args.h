@@ -62,4 +62,7 @@ inline int check_cull_grid(const vl3d_render_desc *desc, int32_t QH, int32_t QW,
     return VL3D_EINVAL;
 }
 
+// a camera path (vl3d_render_fwd_baked_path / _pool_path; csrc/vl3d_render_baked.hip): n_cams in [1, 65535], index pointers, tiles x frames
+int check_path(const vl3d_render_desc *desc, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t, const char *who);
+
 }  // namespace vl3d_render_detail

@@ -64,12 +64,26 @@ __device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, 
     return BakedTaps{*reinterpret_cast<const u2w_a4 *>(plane + o), *reinterpret_cast<const u2w_a4 *>(plane + row_b + o)};
 }
 
-template <int NF, bool CULL>
-__global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y) {
+// PATH = NoPath: frames t0 .. of the run a.stack starts at, one camera (a.homos, a.cull_masks of one plan).
+// PATH = PathIdx (vl3d_render_fwd_baked_path): the block index's outermost factor is the OUTPUT frame i; the workgroup reads its camera and
+// its frame of the clip (path_frame: scalar loads, range-checked) and from them forms its homography, mask and texel bases.  One frame per
+// thread: from there on the one-frame kernel.
+template <int NF, bool CULL, typename PATH = NoPath>
+__global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y, PATH path) {
+    constexpr bool IS_PATH = !std::is_same<PATH, NoPath>::value;
+    static_assert(!IS_PATH || NF == 1, "a camera path renders one frame per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_x = b % tiles_x, rest = b / tiles_x;
-    const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;
+    const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;      // (a path: the output frame)
     const bool has1 = NF == 2 && t0 + 1 < a.T;      // odd T: the last pair composites frame t0 twice and stores it once
+    int tile = tile_y * tiles_x + tile_x, src_t = t0;
+    const float *homos = a.homos;
+    if constexpr (IS_PATH) {
+        int cam;
+        if (!path_frame(path, t0, cam, src_t)) return;      // uniform: nothing loaded, nothing stored
+        homos += (size_t)cam * a.D * VL3D_HS;
+        tile += cam * tiles_x * tiles_y;
+    }
     const int x = tile_x * 64 + (threadIdx.x & 63);
     const int y = tile_y * 8 + (threadIdx.x >> 6);
     if (x >= a.W || y >= a.H) return;
@@ -78,7 +92,7 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     const size_t frame_b = (size_t)a.Hs * a.Ws * 4;
     const size_t plane_stride_b = (size_t)a.Tstride * frame_b;
     const char *base[NF];
-    base[0] = reinterpret_cast<const char *>(a.stack) + (size_t)t0 * frame_b;
+    base[0] = reinterpret_cast<const char *>(a.stack) + (size_t)src_t * frame_b;
     if constexpr (NF == 2) base[1] = base[0] + (has1 ? frame_b : 0);
     float Tr[NF], cr[NF], cg[NF], cb[NF], A[NF];
 #pragma unroll
@@ -88,7 +102,7 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     const BakedComposite<NF, Owner> composite(Tr, cr, cg, cb, A);
     auto fetch = [&](int d, Taps2 &t, BakedTaps *v) {
         float h[VL3D_HN];
-        load_uniform(a.homos + VL3D_HS * d, h);
+        load_uniform(homos + VL3D_HS * d, h);
         if constexpr (CULL) t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
         else t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
 #pragma unroll
@@ -98,7 +112,7 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     Taps2 tA, tB;
     if constexpr (CULL) {
         // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps2)
-        PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
+        PlaneList list(a.cull_masks, tile);
         int dA = list.next();
         if (dA >= 0) {
             fetch(dA, tA, vA);
@@ -136,10 +150,22 @@ void launch_baked(const RenderArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
     if (a.quad_keep) {      // tile culling: the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
         launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
-        hipLaunchKernelGGL((render_fwd_baked_k<NF, true>), grid, block, 0, s, a, tiles_x, tiles_y);
+        hipLaunchKernelGGL((render_fwd_baked_k<NF, true>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{});
         return;
     }
-    hipLaunchKernelGGL((render_fwd_baked_k<NF, false>), grid, block, 0, s, a, tiles_x, tiles_y);
+    hipLaunchKernelGGL((render_fwd_baked_k<NF, false>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{});
+}
+
+// a camera path: a.T output frames, one plan launch for all cameras (a culled model), one render launch
+void launch_baked_path(const RenderArgs &a, const PathIdx &path, hipStream_t s) {
+    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
+    const dim3 grid((unsigned)(tiles_x * tiles_y * a.T)), block(512);
+    if (a.quad_keep) {
+        launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
+        hipLaunchKernelGGL((render_fwd_baked_k<1, true, PathIdx>), grid, block, 0, s, a, tiles_x, tiles_y, path);
+        return;
+    }
+    hipLaunchKernelGGL((render_fwd_baked_k<1, false, PathIdx>), grid, block, 0, s, a, tiles_x, tiles_y, path);
 }
 
 bool known_act(int act) { return act >= VL3D_ACT_NONE && act <= VL3D_ACT_ABS; }
@@ -162,9 +188,8 @@ extern "C" int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stac
     return VL3D_OK;
 }
 
-extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
-                                     vl3d_stream_t stream) {
+// what vl3d_render_fwd_baked and vl3d_render_fwd_baked_path refuse alike, in two parts around the entry's own rule about its frames
+static int baked_check_desc(const vl3d_render_desc *desc, const uint8_t *baked, const float *homos, const float *rgb, const float *alpha) {
     VL3D_REQUIRE(desc != nullptr, "null render desc");
     VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked: no kernel variants (desc->variant = 0)");
     VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked: non-positive render dims");
@@ -178,21 +203,69 @@ extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t
     VL3D_REQUIRE(desc->uv_noise_seed == 0, "vl3d_render_fwd_baked: add_uv_noise is a training switch (uv_noise_seed = 0)");
     VL3D_REQUIRE(baked && homos && rgb && alpha, "vl3d_render_fwd_baked: null pointer");
     VL3D_REQUIRE(((uintptr_t)baked & 3) == 0, "vl3d_render_fwd_baked: the texels must be 4-byte aligned");
+    return VL3D_OK;
+}
+static int baked_set_cull(RenderArgs &a, const vl3d_render_desc *desc, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch) {
+    if (!quad_keep) return VL3D_OK;
+    const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked");
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
+    a.quad_keep = quad_keep;
+    a.cull_masks = (const unsigned long long *)cull_scratch;
+    set_cull_geometry(a, desc, QH, QW);
+    return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
+                                     vl3d_stream_t stream) {
+    int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(T_alloc > 0 && frame0 >= 0 && frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
     RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above)
     a.Tstride = T_alloc;
     a.stack = reinterpret_cast<const float *>(baked + (size_t)frame0 * desc->Hs * desc->Ws * 4);
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
-    if (quad_keep) {
-        const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked");
-        if (rc != VL3D_OK) return rc;
-        VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
-        a.quad_keep = quad_keep;
-        a.cull_masks = (const unsigned long long *)cull_scratch;
-        set_cull_geometry(a, desc, QH, QW);
-    }
+    rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);
+    if (rc != VL3D_OK) return rc;
     if (desc->T >= 2) launch_baked<2>(a, (hipStream_t)stream);
     else launch_baked<1>(a, (hipStream_t)stream);
+    VL3D_CHECK_LAUNCH();
+    return VL3D_OK;
+}
+
+// two 64-bit plane masks per (camera, 64 x 8 pixel workgroup): [n_cams][tiles_y * tiles_x][2]
+extern "C" int64_t vl3d_render_path_cull_scratch_bytes(const vl3d_render_desc *desc, int32_t n_cams) {
+    if (!desc || desc->H <= 0 || desc->W <= 0 || n_cams <= 0) return 0;
+    return (int64_t)n_cams * ((desc->W + 63) / 64) * ((desc->H + 7) / 8) * 16;
+}
+
+// what the two path entries add to their one-camera entries' refusals (`who` in front of the message)
+int vl3d_render_detail::check_path(const vl3d_render_desc *desc, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t, const char *who) {
+    const char *bad = nullptr;
+    if (!(n_cams >= 1 && n_cams <= 65535)) bad = "n_cams must be in [1, 65535]";
+    else if (!frame_cam || !frame_t) bad = "null pointer (frame_cam, frame_t: device int32[desc->T])";
+    else if ((int64_t)((desc->W + 63) / 64) * ((desc->H + 7) / 8) * desc->T > 0x7fffffffll) bad = "tiles x frames exceed the grid";
+    if (!bad) return VL3D_OK;
+    vl3d_set_error((std::string(who) + ": " + bad).c_str());
+    return VL3D_EINVAL;
+}
+
+extern "C" int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
+                                          const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                          void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
+    int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_baked_path: a clip of T_alloc >= 1 frames");
+    rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_path");
+    if (rc != VL3D_OK) return rc;
+    RenderArgs a = render_args_of(desc);      // a.T: the output frames of the path
+    a.Tstride = T_alloc;
+    a.stack = reinterpret_cast<const float *>(baked);
+    a.homos = homos; a.rgb = rgb; a.alpha = alpha;
+    rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);      // (cull_scratch: vl3d_render_path_cull_scratch_bytes)
+    if (rc != VL3D_OK) return rc;
+    launch_baked_path(a, PathIdx{frame_cam, frame_t, n_cams, T_alloc}, (hipStream_t)stream);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
 }

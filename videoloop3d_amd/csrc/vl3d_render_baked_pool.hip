@@ -49,17 +49,29 @@ __device__ __forceinline__ void pool_load(const PoolSrc &p, int e, unsigned in_b
     }
 }
 
-template <int NF>
-__global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, PoolSrc p, int tiles_x, int tiles_y) {
+// PATH = NoPath: frames p.frame0 + t0 .. of one camera.  PATH = PathIdx (vl3d_render_fwd_baked_pool_path): the block index's outermost factor is
+// the OUTPUT frame; camera and frame of the model come from path_frame (scalar loads, range-checked), as in the dense path kernel.
+template <int NF, typename PATH = NoPath>
+__global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, PoolSrc p, int tiles_x, int tiles_y, PATH path) {
+    constexpr bool IS_PATH = !std::is_same<PATH, NoPath>::value;
+    static_assert(!IS_PATH || NF == 1, "a camera path renders one frame per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_x = b % tiles_x, rest = b / tiles_x;
-    const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;
+    const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;      // (a path: the output frame)
     const bool has1 = NF == 2 && t0 + 1 < a.T;      // odd T: the last pair composites frame t0 twice and stores it once
+    int tile = tile_y * tiles_x + tile_x, src_t = p.frame0 + t0;
+    const float *homos = a.homos;
+    if constexpr (IS_PATH) {
+        int cam;
+        if (!path_frame(path, t0, cam, src_t)) return;      // uniform: nothing loaded, nothing stored
+        homos += (size_t)cam * a.D * VL3D_HS;
+        tile += cam * tiles_x * tiles_y;
+    }
     const int x = tile_x * 64 + (threadIdx.x & 63);
     const int y = tile_y * 8 + (threadIdx.x >> 6);
     if (x >= a.W || y >= a.H) return;
     const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
-    const size_t frame_b = (size_t)(p.frame0 + t0) * SLOT_B;
+    const size_t frame_b = (size_t)src_t * SLOT_B;
     const size_t bplane_n = (size_t)p.tiles_y * p.tiles_x;
     float Tr[NF], cr[NF], cg[NF], cb[NF], A[NF];
 #pragma unroll
@@ -69,7 +81,7 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
     const BakedComposite<NF, Owner> composite(Tr, cr, cg, cb, A);
     auto fetch = [&](int d, TapsI &t, BakedTaps *v) {
         float h[VL3D_HN];
-        load_uniform(a.homos + VL3D_HS * d, h);
+        load_uniform(homos + VL3D_HS * d, h);
         t = make_taps_i<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
 #pragma unroll
         for (int f = 0; f < NF; ++f) v[f] = BakedTaps{u2w{0u, 0u}, u2w{0u, 0u}};
@@ -108,7 +120,7 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
         if (t.cov != 0.0f) composite(t, v);
     };
     // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps_i)
-    PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
+    PlaneList list(a.cull_masks, tile);
     TapsI tA, tB;
     const int dA = list.next();
     if (dA >= 0) {
@@ -133,14 +145,22 @@ void launch_baked_pool(const RenderArgs &a, const PoolSrc &p, hipStream_t s) {
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
     // the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
     launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
-    hipLaunchKernelGGL((render_fwd_baked_pool_k<NF>), grid, block, 0, s, a, p, tiles_x, tiles_y);
+    hipLaunchKernelGGL((render_fwd_baked_pool_k<NF>), grid, block, 0, s, a, p, tiles_x, tiles_y, NoPath{});
+}
+
+// a camera path: a.T output frames, one plan launch for all cameras, one render launch
+void launch_baked_pool_path(const RenderArgs &a, const PoolSrc &p, const PathIdx &path, hipStream_t s) {
+    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
+    const dim3 grid((unsigned)(tiles_x * tiles_y * a.T)), block(512);
+    launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
+    hipLaunchKernelGGL((render_fwd_baked_pool_k<1, PathIdx>), grid, block, 0, s, a, p, tiles_x, tiles_y, path);
 }
 
 }  // namespace
 
-extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
-                                          int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                          uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
+// what vl3d_render_fwd_baked_pool and vl3d_render_fwd_baked_pool_path refuse alike, in two parts around the entry's own rule about its frames
+static int pool_check_desc(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, const float *homos, const uint8_t *quad_keep,
+                           const void *cull_scratch, const float *rgb, const float *alpha) {
     VL3D_REQUIRE(desc != nullptr, "null render desc");
     VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked_pool: no kernel variants (desc->variant = 0)");
     VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked_pool: non-positive render dims");
@@ -154,19 +174,52 @@ extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const in
     VL3D_REQUIRE(blocks && pool && homos && quad_keep && cull_scratch && rgb && alpha,
                  "vl3d_render_fwd_baked_pool: null pointer (the quad map and vl3d_render_cull_scratch_bytes() of scratch are required)");
     VL3D_REQUIRE(((uintptr_t)pool & 3) == 0 && ((uintptr_t)blocks & 3) == 0, "vl3d_render_fwd_baked_pool: the pool and the block table must be 4-byte aligned");
-    VL3D_REQUIRE(T_model > 0 && frame0 >= 0 && (int64_t)frame0 + desc->T <= T_model,
-                 "vl3d_render_fwd_baked_pool: the run of frames leaves the model's T_model frames");
+    return VL3D_OK;
+}
+static int pool_set_args(RenderArgs &a, const vl3d_render_desc *desc, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                         void *cull_scratch, float *rgb, float *alpha) {
     VL3D_REQUIRE(desc->cull_Hs == 0 && desc->cull_Ws == 0, "vl3d_render_fwd_baked_pool: the pool holds whole planes (no desc->cull_* window)");
     const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked_pool");
     if (rc != VL3D_OK) return rc;
-    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a.Tstride is not read: the pool has no frame stride)
+    a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a.Tstride is not read: the pool has no frame stride)
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
     a.quad_keep = quad_keep;
     a.cull_masks = (const unsigned long long *)cull_scratch;
     set_cull_geometry(a, desc, QH, QW);
+    return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
+                                          int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                          uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
+    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(T_model > 0 && frame0 >= 0 && (int64_t)frame0 + desc->T <= T_model,
+                 "vl3d_render_fwd_baked_pool: the run of frames leaves the model's T_model frames");
+    RenderArgs a;
+    rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
     const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, frame0, culled_rgba8};
     if (desc->T >= 2) launch_baked_pool<2>(a, p, (hipStream_t)stream);
     else launch_baked_pool<1>(a, p, (hipStream_t)stream);
+    VL3D_CHECK_LAUNCH();
+    return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked_pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
+                                               const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
+                                               const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
+                                               float *rgb, float *alpha, vl3d_stream_t stream) {
+    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(T_model > 0, "vl3d_render_fwd_baked_pool_path: a model of T_model >= 1 frames");
+    rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_pool_path");
+    if (rc != VL3D_OK) return rc;
+    RenderArgs a;      // a.T: the output frames of the path; cull_scratch: vl3d_render_path_cull_scratch_bytes
+    rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, 0, culled_rgba8};
+    launch_baked_pool_path(a, p, PathIdx{frame_cam, frame_t, n_cams, T_model}, (hipStream_t)stream);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
 }

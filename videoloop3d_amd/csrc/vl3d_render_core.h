@@ -800,13 +800,19 @@ __device__ __forceinline__ int xcd_remap(int b, int nb) {
 
 // forward plan of the tile culling: one thread per (64 x TY pixel workgroup, plane) projects the workgroup's corners and sets
 // the plane's bit when the footprint touches a kept quad.  Frame independent, once per call.
-template <int COORD>
+// CAMS (a camera path, vl3d_render_fwd_baked_path): the same thread for every camera c = blockIdx.y of gridDim.y, with camera c's
+// homographies a.homos + c * D * VL3D_HS and camera c's masks [C][tiles_y * tiles_x][2].
+template <int COORD, bool CAMS = false>
 __global__ __launch_bounds__(256) void cull_fwd_plan_k(RenderArgs a, int TY, int tiles_x, int tiles_y, unsigned long long *masks) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= tiles_x * tiles_y * a.D) return;
     const int d = i % a.D, tile = i / a.D, tile_x = tile % tiles_x, tile_y = tile / tiles_x;
     const int x0 = tile_x * 64, x1 = min(x0 + 63, a.W - 1), y0 = tile_y * TY, y1 = min(y0 + TY - 1, a.H - 1);
     const float *h = a.homos + VL3D_HS * d;
+    if constexpr (CAMS) {
+        h += (size_t)blockIdx.y * a.D * VL3D_HS;
+        masks += (size_t)blockIdx.y * tiles_x * tiles_y * 2;
+    }
     float tnx = 1e30f, txx = -1e30f, tny = 1e30f, txy = -1e30f;
     for (int c = 0; c < 4; ++c) {
         const float cx = (float)a.col0 + a.pc + (float)((c & 1) ? x1 : x0), cy = (float)a.row0 + a.pc + (float)((c & 2) ? y1 : y0);
@@ -825,6 +831,14 @@ void launch_cull_fwd_plan(const RenderArgs &a, int TY, int tiles_x, int tiles_y,
     (void)hipMemsetAsync(masks, 0, (size_t)tiles_x * tiles_y * 16, s);
     const int n = tiles_x * tiles_y * a.D;
     hipLaunchKernelGGL((cull_fwd_plan_k<COORD>), dim3((n + 255) / 256), dim3(256), 0, s, a, TY, tiles_x, tiles_y, masks);
+}
+// ... for the n_cams cameras of a.homos (C, D, 3, 3), 1 <= n_cams <= 65535 (the grid's second axis): one memset and one launch for all plans
+template <int COORD>
+void launch_cull_fwd_plan_cams(const RenderArgs &a, int n_cams, int TY, int tiles_x, int tiles_y, hipStream_t s) {
+    auto *masks = const_cast<unsigned long long *>(a.cull_masks);
+    (void)hipMemsetAsync(masks, 0, (size_t)n_cams * tiles_x * tiles_y * 16, s);
+    const int n = tiles_x * tiles_y * a.D;
+    hipLaunchKernelGGL((cull_fwd_plan_k<COORD, true>), dim3((n + 255) / 256, n_cams), dim3(256), 0, s, a, TY, tiles_x, tiles_y, masks);
 }
 
 // A workgroup's plane list as the plan wrote it: two 64-bit words read through the constant address space (SGPRs, scalar bit scans).

@@ -436,6 +436,119 @@ def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec
     return rgb, alpha
 
 
+def _path_indices(frame_cam, frame_t, n_cams, T, device, who):
+    """the (camera, frame) indices of a camera path, range-checked on the host (the kernels cannot report a bad index: they skip its frame)
+    and uploaded in ONE pinned copy -> (N, int32 [2,N] on `device`: row 0 the cameras, row 1 the frames)."""
+    import numpy as np
+    cam, t = np.asarray(frame_cam).reshape(-1), np.asarray(frame_t).reshape(-1)
+    if len(cam) != len(t):
+        raise RuntimeError(f"{who}: frame_cam and frame_t name the same output frames ({len(cam)} cameras, {len(t)} frames)")
+    if len(cam) == 0:
+        raise RuntimeError(f"{who}: an empty path (N = 0 output frames)")
+    if cam.dtype.kind not in "iu" or t.dtype.kind not in "iu":
+        raise RuntimeError(f"{who}: frame_cam and frame_t are integer indices")
+    if int(cam.min()) < 0 or int(cam.max()) >= n_cams:
+        raise IndexError(f"{who}: camera index {int(cam.min())} .. {int(cam.max())} outside the {n_cams} cameras of homos")
+    if int(t.min()) < 0 or int(t.max()) >= T:
+        raise IndexError(f"{who}: frame index {int(t.min())} .. {int(t.max())} outside the clip of {T} frames")
+    idx = torch.from_numpy(np.stack([cam, t]).astype(np.int32)).pin_memory().to(device, non_blocking=True)
+    return len(cam), idx
+
+
+def _path_cull_scratch(desc, n_cams, device, cull_scratch, who):
+    """the plane masks of a path render, [n_cams][tiles][2] uint64 (vl3d_render_path_cull_scratch_bytes): the caller's buffer checked for
+    device, dtype and size, or a fresh one; call under torch.cuda.device(device)."""
+    need = int(L.lib().vl3d_render_path_cull_scratch_bytes(desc, int(n_cams)))
+    if cull_scratch is None:
+        return torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
+    if not isinstance(cull_scratch, torch.Tensor) or not cull_scratch.is_cuda or cull_scratch.device != device:
+        raise RuntimeError(f"{who}: cull_scratch must be a tensor on the model's device")
+    if cull_scratch.dtype != torch.int64 or not cull_scratch.is_contiguous() or cull_scratch.numel() * 8 < need:
+        raise RuntimeError(f"{who}: cull_scratch must be contiguous int64 of at least {need} bytes "
+                           f"(vl3d_render_path_cull_scratch_bytes: two 64-bit plane masks per camera and 64 x 8 pixel tile)")
+    return cull_scratch
+
+
+def render_path_baked(baked, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, cull_scratch=None):
+    """A camera path on the baked clip (vl3d_render_fwd_baked_path): N output frames in ONE plan launch plus ONE render launch, output frame i
+    being frame frame_t[i] of `baked` [D,T,Hs,Ws,4] uint8 seen by camera frame_cam[i] of `homos` [C,D,3,3] -- the spiral of the offline renderer,
+    where render_frame_run_baked takes one camera per call.  frame_cam / frame_t: host sequences or numpy arrays of N indices (checked here:
+    IndexError).  `cull_scratch`: an int64 buffer of vl3d_render_path_cull_scratch_bytes to hold the plane masks [C][tiles][2] across calls (a
+    tile-culled model; allocated per call when absent).  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal to
+    render_frame_run_baked(baked, frame_t[i], 1, homos[frame_cam[i]], ...).  Everything else as render_frame_run_baked."""
+    who = "render_path_baked"
+    L.check_cuda(baked, homos)
+    if baked.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
+        raise RuntimeError(f"{who}: baked texels have no backward (train the float model, then bake it)")
+    if baked.dtype != torch.uint8 or baked.dim() != 5 or baked.shape[4] != 4 or not baked.is_contiguous():
+        raise RuntimeError(f"{who}: a contiguous uint8 clip [D,T,Hs,Ws,4] (baked.bake_texels)")
+    if spec.coord_mode != "affine" or spec.border != "hardcut":
+        raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
+    D, T = baked.shape[:2]
+    if homos.dim() != 4 or tuple(homos.shape[1:]) != (D, 3, 3) or homos.shape[0] < 1:
+        raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
+    if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
+        raise RuntimeError("RenderSpec.tile (tile-exact layout) belongs to a tile-culled model: pass its quad_keep map")
+    dev = baked.device
+    C = int(homos.shape[0])
+    qk, grid, cull = None, (0, 0), None
+    if quad_keep is not None:
+        qk = _quad_map(quad_keep, D)
+        grid = _qgrid(qk, spec)
+    N, idx = _path_indices(frame_cam, frame_t, C, T, dev, who)
+    homos = homos.detach().to(torch.float32).contiguous()
+    desc = _desc(baked, H, W, spec, 0, 0)
+    desc.T = N
+    desc.stack_dtype = L.STACK_DTYPE["u8"]
+    rgb, alpha = _out_buffers(out, N, H, W, dev, who)
+    with torch.cuda.device(dev):
+        if qk is not None:
+            cull = _path_cull_scratch(desc, C, dev, cull_scratch, who)
+        L.check(L.lib().vl3d_render_fwd_baked_path(desc, L.ptr(baked), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk), *grid,
+                                                   L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked_path")
+    return rgb, alpha
+
+
+def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, cull_scratch=None):
+    """render_path_baked from the baked POOL (vl3d_render_fwd_baked_pool_path): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
+    render_frame_run_baked_pool takes them, the path as render_path_baked takes it.  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal
+    to render_frame_run_baked_pool(layout, pool, frame_t[i], 1, homos[frame_cam[i]], ...)."""
+    who = "render_path_baked_pool"
+    L.check_cuda(pool, homos, layout.blocks)
+    if pool.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
+        raise RuntimeError(f"{who}: baked texels have no backward (train the float model, then bake it)")
+    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
+        raise RuntimeError(f"{who}: a contiguous uint8 pool [n_slots * 64, 4] of the layout (baked.bake_pool)")
+    if spec.coord_mode != "affine" or spec.border != "hardcut":
+        raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
+    if quad_keep is None:
+        raise RuntimeError(f"{who}: the quad map the block table was built from (quad_keep [D,QH,QW]) is required")
+    D, T = layout.D, layout.T
+    if homos.dim() != 4 or tuple(homos.shape[1:]) != (D, 3, 3) or homos.shape[0] < 1:
+        raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
+    qk = _quad_map(quad_keep, D)
+    grid = getattr(layout, "quad_grid", None)
+    if grid is not None and tuple(quad_keep.shape[1:]) != tuple(grid):
+        raise RuntimeError(f"quad_keep is {tuple(quad_keep.shape[1:])} quads per plane, the layout's block table was built from {tuple(grid)}")
+    bl = layout.blocks
+    if bl.dtype != torch.int32 or not bl.is_contiguous() or tuple(bl.shape) != (D, -(-layout.Hs // 8), -(-layout.Ws // 8)) or bl.device != pool.device:
+        raise RuntimeError(f"{who}: the layout's block table must be contiguous int32 [D, ceil(Hs/8), ceil(Ws/8)] on the pool's device")
+    if bool(getattr(spec, "tile", (0, 0))[0]) != (layout.tile is not None):
+        raise RuntimeError(f"{who}: RenderSpec.tile and the layout's tile must both name the tile-exact layout, or neither")
+    dev = pool.device
+    C = int(homos.shape[0])
+    N, idx = _path_indices(frame_cam, frame_t, C, T, dev, who)
+    homos = homos.detach().to(torch.float32).contiguous()
+    d = _desc_dims(D, N, layout.Hs, layout.Ws, H, W, spec, L.STACK_DTYPE["u8"])
+    rgb, alpha = _out_buffers(out, N, H, W, dev, who)
+    with torch.cuda.device(dev):
+        cull = _path_cull_scratch(d, C, dev, cull_scratch, who)
+        L.check(L.lib().vl3d_render_fwd_baked_pool_path(d, L.ptr(bl), L.ptr(pool), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk),
+                                                        *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha),
+                                                        L.stream_ptr(dev)), "vl3d_render_fwd_baked_pool_path")
+    return rgb, alpha
+
+
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,
                   fused_adam=None):
     """stack (D,T,Hs,Ws,4) pre-activation fp32 (plane 0 = nearest), homos [D,3,3] (target pixel -> plane pixel).

@@ -161,6 +161,25 @@ def to8b(x):
     return (255 * x.clamp(0, 1)).to(torch.uint8)
 
 
+def path_segments(cam_of, render_t, chunk):
+    """How render_frames(baked=) launches a selection of n output frames (cam_of[i]: the index of frame i's camera, render_t[i]: its frame of
+    the clip) in chunks of at most `chunk` frames -> [(kind, i, j)], one segment per chunk, frames i .. j - 1:
+      "run"   the chunk is exactly one run -- one camera, consecutive frames of the clip: the frame-pair call (render_frame_run_baked);
+      "path"  anything else -- the camera changes or the frame order breaks somewhere inside the chunk: ONE path call
+              (render_path_baked: one plan launch and one render launch for the chunk, where runs would be one call per break).
+    Pure: no device, no model.  The frames are bit-equal either way; this decides how the work is launched."""
+    n = len(render_t)
+    if len(cam_of) != n:
+        raise ValueError(f"path_segments: {len(cam_of)} cameras for {n} frames")
+    chunk = max(1, min(int(chunk), n)) if n else 1
+    segs = []
+    for c0 in range(0, n, chunk):
+        c1 = min(n, c0 + chunk)
+        one_run = all(cam_of[j] == cam_of[c0] and int(render_t[j]) == int(render_t[j - 1]) + 1 for j in range(c0 + 1, c1))
+        segs.append(("run" if one_run else "path", c0, c1))
+    return segs
+
+
 def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, chunk, baked=None):
     """render_frames for a dense model on the device: the plane homographies of every DISTINCT camera of the path are formed up front (the
     module's own `plane_homographies`, the same bits as its forward) and uploaded in ONE copy, every frame -- or run of consecutive frames of
@@ -168,7 +187,8 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
     that is converted to uint8 once (a sparsified model with its quad map; a packed one through its block table).  None when the model is
     not one this path serves (atlas_exact / CPU).  `baked` (baked.BakedMPV): the frames come from ITS uint8 texels, quad map, geometry,
     camera and background through the same runs (render.render_frame_run_baked); the float model is not read.  A baked.BakedPool renders its
-    runs from the pool behind its block table (render.render_frame_run_baked_pool)."""
+    runs from the pool behind its block table (render.render_frame_run_baked_pool).  Chunks of a baked model that are not one run go through
+    its path render (`path_segments`, `baked._path`)."""
     from .render import render_frame_run, render_frame_run_baked, render_frame_run_baked_pool
     if baked is not None:
         if baked.bg_color == "random":
@@ -178,9 +198,9 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
                 return render_frame_run_baked_pool(baked.layout, pool, t0, n, homos, H, W, spec, out=out, quad_keep=quad_keep,
                                                    culled_rgba8=baked.culled_rgba8)
             return _in_place_runs(baked.camera, baked.pool, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
-                                  render_t, chunk, run_pool, T=baked.frm_num)
+                                  render_t, chunk, run_pool, T=baked.frm_num, path=baked._path)
         return _in_place_runs(baked.camera, baked.texels, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
-                              render_t, chunk, render_frame_run_baked)
+                              render_t, chunk, render_frame_run_baked, path=baked._path)
     packed = getattr(module, "packed", None)
     stack = module.stack_pool.data if packed is not None else getattr(module, "stack", None)
     if (stack is None or not stack.is_cuda or not stack.is_contiguous() or module.atlas_exact or module.training
@@ -193,33 +213,32 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
                           render_frame_run)
 
 
-def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run, T=None):
+def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run, T=None, path=None):
     """the frame loop of _render_frames_in_place: `camera` gives the homographies (`plane_homographies`, `ref_extrin`), `run` renders a run of
     consecutive frames of the dense clip `stack` in place (render_frame_run / render_frame_run_baked); `packed`: the pool's layout instead.
-    `T`: the clip's frame count where `stack` is not a (D,T,...) clip (a baked pool)."""
+    `T`: the clip's frame count where `stack` is not a (D,T,...) clip (a baked pool).  `path` (a baked model's `_path`): a chunk that is not
+    one run -- path_segments -- is ONE call of it, every frame with its own camera, instead of one `run` per frame."""
+    from .baked import path_cameras
     from .render import render_planes_packed
     n, T, dev = len(render_t), (packed.T if packed is not None else (stack.shape[1] if T is None else T)), stack.device
     if packed is not None:      # a packed model reads its pool through the block table (vl3d_render_fwd_packed): the frame indices go up once
         from .tiles import CULLED_ALPHA
         t_dev = torch.as_tensor(render_t.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-    ref_inv = camera._on(view_extrins.device, "ref_extrin")[None, ...].inverse().to(view_extrins.dtype)
-    cams, cam_of = {}, []
-    for i in range(n):
-        key = (view_extrins[i].numpy().tobytes(), view_intrins[i].numpy().tobytes())
-        if key not in cams:
-            cams[key] = (len(cams), camera.plane_homographies(view_extrins[i:i + 1] @ ref_inv, view_intrins[i:i + 1]))
-        cam_of.append(cams[key][0])
-    homos = torch.stack([h for _, h in sorted(cams.values(), key=lambda c: c[0])]).pin_memory().to(dev, non_blocking=True)      # [cameras, D, 3, 3]
+    cam_of, homos = path_cameras(camera, view_extrins[:n], view_intrins[:n])
+    homos = homos.pin_memory().to(dev, non_blocking=True)      # [cameras, D, 3, 3]
     bg = None
     if len(bg_color) > 0:                                                                    # MPV.py:455-461
         bg = torch.tensor([float(v) for v in bg_color.split('#')], dtype=torch.float32, device=dev)
     out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
     chunk = max(1, min(int(chunk), n))
     rgb, alpha = torch.empty((chunk, H, W, 3), dtype=torch.float32, device=dev), torch.empty((chunk, H, W), dtype=torch.float32, device=dev)
-    c0 = 0
-    while c0 < n:
-        c1 = min(n, c0 + chunk)
-        i = c0
+    for kind, c0, c1 in path_segments(cam_of, render_t, chunk):
+        m = c1 - c0
+        by_path = kind == "path" and path is not None
+        if by_path:
+            lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras: a slice of the path's (a spiral: exactly its own)
+            path([c - lo for c in cam_of[c0:c1]], render_t[c0:c1], homos[lo:hi], H, W, (rgb[:m], alpha[:m]))
+        i = c1 if by_path else c0
         while i < c1:
             j = i + 1      # a run: one camera, consecutive frames of the clip
             while j < c1 and cam_of[j] == cam_of[i] and render_t[j] == render_t[j - 1] + 1:
@@ -233,12 +252,10 @@ def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins
             else:
                 run(stack, t0, j - i, homos[cam_of[i]], H, W, spec, out=(rgb[i - c0:j - c0], alpha[i - c0:j - c0]), quad_keep=qk)
             i = j
-        m = c1 - c0
         x = rgb[:m]
         if bg is not None:
             x = x * alpha[:m, ..., None] + bg[None, None, None] * (-alpha[:m, ..., None] + 1)
         out[c0:c1] = to8b(x)
-        c0 = c1
     return out
 
 
@@ -250,7 +267,9 @@ def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64
     Otherwise runs of consecutive frames with one camera are rendered by ONE call of the module with `ts` a vector (at most `max_batch` frames:
     the frames of a call are resident together).
     `baked` (baked.BakedMPV or baked.BakedPool, the product of baked.bake(model) / baked.bake_pool(model)): the frames of the PLAYBACK model -- its 8-bit texels filtered after the
-    activation, what the exported viewer package shows -- through the same run logic; the float stack is not read."""
+    activation, what the exported viewer package shows -- through the same run logic; the float stack is not read.  A chunk of `max_batch`
+    frames that is not one run (a spiral: every frame its own camera) is ONE path call (render.render_path_baked / _pool: one plan launch and one
+    render launch for the chunk; `path_segments`), with the bits of the per-frame calls."""
     module = getattr(nerf, "module", nerf)
     was_training = module.training
     nerf.eval()
