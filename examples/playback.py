@@ -3,7 +3,8 @@
 synthetic weights and a synthetic quad map), render the same spiral from the float model, from the baked one and from the baked POOL
 (`baked.bake_pool`: static blocks once, dynamic blocks per frame, culled blocks not at all -- no dense clip) -- frames / s of
 `render_video.render_frames` for each (the two baked models along the spiral through the path render: one plan launch and one render launch
-per chunk of 64 poses, `calls` in the output), bytes of the three textures, PSNR between the float and the baked frames, and whether the pool's
+per chunk of 64 poses, `calls` in the output, the launch storing the uint8 frames itself -- `route`: no float frames, no torch epilogue),
+bytes of the three textures, PSNR between the float and the baked frames, and whether the pool's
 frames equal the dense baked frames --, then write the viewer package (geometry.obj, static.png,
 dynamic/%04d.png, meta.json).  `--full`: 720p, D = 32, T = 50."""
 import argparse
@@ -70,6 +71,7 @@ def run(full=False, outdir=None, dev="cuda:0"):
         if kw:      # how render_frames launched the spiral: every pose its own camera -> one path call per chunk
             kinds = [k for k, _, _ in RV.path_segments(list(range(N)), rt, 64)]
             out[name]["calls"] = {k: kinds.count(k) for k in sorted(set(kinds))}
+            out[name]["route"] = "render_display: uint8 frames stored by the render launches (frames8=)"
     mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
     out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
     out["pool_frames_equal_baked_frames"] = bool(torch.equal(frames["baked_pool"], frames["baked"]))

@@ -170,6 +170,34 @@ int vl3d_render_fwd_baked_pool_path(const vl3d_render_desc *desc, const int32_t 
                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch, float *rgb,
                                     float *alpha, vl3d_stream_t stream);
 
+/* Baked playback, DISPLAY output (csrc/vl3d_baked_core.h: DisplayOut): the four baked forwards above with the frame a viewer shows as their
+ * output -- frames (N, H, W, channels) uint8, N = desc->T, channels = 3 (RGB8) or 4 (RGBA8) -- written by the render launch itself; no
+ * fp32 rgb / alpha exists.  Per pixel, every operation rounded on its own (the order of the torch statement it replaces, so the bytes are
+ * those of that statement applied to the float entry's output):
+ *     bg != NULL:  x_k = c_k * A + bg[k] * ((-A) + 1)      (MPV.py:455-461; c, A: the float entry's rgb and alpha)
+ *     bg == NULL:  x_k = c_k
+ *     byte k = (uint8) trunc(255 * min(max(x_k, 0), 1))    (utils.py to8b);   byte 3 (channels == 4) = trunc(255 * min(max(A, 0), 1)),
+ *                                                           never composited over the background
+ *   bg: a HOST pointer to 3 floats, read by the call (it travels in the kernel arguments), or NULL for no background.
+ * Every argument in front of `frames` and every refusal are the float sibling's (same checks, same messages); in addition channels outside
+ * {3, 4}, frames NULL, frames not 4-byte aligned for channels == 4 and a non-finite bg component return VL3D_EINVAL with nothing launched.
+ * A path frame whose index is out of range keeps its bytes unwritten, as its floats are above.  RGB8 rows are stored lane-packed (a wave's
+ * 192 bytes as 48 dwords) where the 64-pixel row segment is full and 4-byte aligned, as bytes elsewhere; the environment variable
+ * VL3D_DISPLAY_STORE3=bytes selects byte stores everywhere -- a measurement hook (profiles/baked_fwd.py --legs display), same bytes. */
+int vl3d_render_fwd_baked_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                             const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, uint8_t *frames, int32_t channels,
+                             const float *bg, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_pool_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0, int32_t T_model,
+                                  const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
+                                  void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_path_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
+                                  const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                  void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_pool_path_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
+                                       const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
+                                       const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
+                                       uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream);
+
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).
  * grad_alpha_sums (optional): (T,H,W,2) gradient w.r.t. alpha_sums of the forward.

@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -17,7 +17,15 @@ clip, the culled clip and the pool of the culled pair's map.  (a) the per-frame 
 memset, one plan and one one-frame render launch each: what render_frames(baked=) issued along a spiral before the path render), the
 yardstick; (b) ONE render_path_baked / _pool call.  The outputs are compared bit for bit first; then (a) and (b) alternate round by round
 under HIP events that span the whole path.  Prints ms per frame of both (median, min .. max over the rounds) and their ratio; the condition is
-path median <= loop median on every storage."""
+path median <= loop median on every storage.
+
+The DISPLAY leg (--legs display; not part of `all`): the same spiral and storages, the uint8 frames a viewer shows as the product, without a
+background and over one.  (a) the yardstick, the route before the display output: ONE render_path_baked / _pool call into fp32 buffers, then
+the torch epilogue (baked.display_frames and the copy into the uint8 result); (b) ONE path call with `frames8=`: RGB8 with the lane-packed
+store, RGB8 with byte stores (VL3D_DISPLAY_STORE3=bytes), RGBA8.  Every (b) output is compared with (a)'s by torch.equal first (RGBA8: its
+colour bytes, and its alpha byte with display_frames'); then the four legs alternate round by round under HIP events that span the whole
+path.  Prints ms per frame (median, min .. max) and the ratio to (a); the condition is RGB8 (the store the library ships: packed) median <=
+(a) median for every storage and background."""
 import argparse
 import json
 import os
@@ -35,7 +43,7 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display"])
 ap.add_argument("--poses", type=int, default=120)
 ap.add_argument("--keep", type=float, default=0.165)
 ap.add_argument("--dyn", type=float, default=0.3)
@@ -46,7 +54,7 @@ assert a.warm >= 1 and a.iters >= a.rounds >= 1
 import __graft_entry__ as ge  # noqa: E402
 ge.build()
 from videoloop3d_amd import synth  # noqa: E402
-from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8  # noqa: E402
+from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, display_frames  # noqa: E402
 from videoloop3d_amd.packed import PackedLayout  # noqa: E402
 from videoloop3d_amd.render import (RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool, render_path_baked,  # noqa: E402
                                     render_path_baked_pool)
@@ -158,7 +166,7 @@ if a.legs in ("all", "culled"):
     res["pool_over_dense_culled"] = res["baked_pool"]["ms_median"] / res["baked_culled"]["ms_median"]
     print(f"pool render is {res['pool_over_dense_culled']:.3f}x the dense culled baked render's time (bar: <= 1.05)")
 
-if a.legs == "path":
+if a.legs in ("path", "display"):
     import math
     del stack, out
     N = a.poses
@@ -171,10 +179,12 @@ if a.legs == "path":
                                      make_depths(D, 1.0, 100.0).flip(0)[None])[0])
     path_homos = torch.stack(hs).float().to(dev)          # [N, D, 3, 3]
     cam, ts = list(range(N)), [i % T for i in range(N)]
-    o_loop = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
-    o_path = (torch.empty_like(o_loop[0]), torch.empty_like(o_loop[1]))
     lay, pool, qk, bp, dense = culled_model(baked)
     kwp = dict(quad_keep=qk, culled_rgba8=bp.culled_rgba8)
+
+if a.legs == "path":
+    o_loop = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    o_path = (torch.empty_like(o_loop[0]), torch.empty_like(o_loop[1]))
 
     def loop_of(one):
         def f():
@@ -204,6 +214,48 @@ if a.legs == "path":
         print(f"path [{name:6s}] bit-equal {same}; loop {ml / N:.4f} ms/frame ({min(ms['loop']) / N:.4f} .. {max(ms['loop']) / N:.4f}), "
               f"path {mp / N:.4f} ms/frame ({min(ms['path']) / N:.4f} .. {max(ms['path']) / N:.4f}) over {a.rounds} rounds of {per} paths of {N}; "
               f"path / loop {mp / ml:.3f} -> {'ok' if mp <= ml else 'MISSED'}")
+if a.legs == "display":
+    o_f = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    f_a, f_3, f_4 = (torch.empty((N, H, W, c), dtype=torch.uint8, device=dev) for c in (3, 3, 4))
+    paths = {"dense": lambda **o: render_path_baked(baked, cam, ts, path_homos, H, W, spec, **o),
+             "culled": lambda **o: render_path_baked(dense, cam, ts, path_homos, H, W, spec, quad_keep=qk, **o),
+             "pool": lambda **o: render_path_baked_pool(lay, pool, cam, ts, path_homos, H, W, spec, **kwp, **o)}
+    res["display"] = {"poses": N, "shipped_rgb8_store": "packed"}
+    for name, path in paths.items():
+        for bg in (None, (0.2, 0.4, 0.6)):
+            bg_dev = None if bg is None else torch.tensor(bg, dtype=torch.float32, device=dev)
+
+            def leg_a():      # the route before the display output: fp32 frames, the torch epilogue, the copy into the uint8 result
+                path(out=o_f)
+                f_a[:] = display_frames(o_f[0], o_f[1], bg_dev, 3)
+
+            def leg_b(store, frames):
+                def f():
+                    os.environ["VL3D_DISPLAY_STORE3"] = store
+                    path(frames8=frames, bg=bg)
+                return f
+            legs = {"a_float_then_torch": leg_a, "b_rgb8_packed": leg_b("packed", f_3), "b_rgb8_bytes": leg_b("bytes", f_3),
+                    "b_rgba8": leg_b("packed", f_4)}
+            leg_a()
+            same = {}
+            for k in ("b_rgb8_packed", "b_rgb8_bytes"):
+                f_3.fill_(0xAB)
+                legs[k]()
+                same[k] = torch.equal(f_3, f_a)
+            f_4.fill_(0xAB)
+            legs["b_rgba8"]()
+            same["b_rgba8"] = torch.equal(f_4[..., :3], f_a) and torch.equal(f_4[..., 3], display_frames(o_f[0], o_f[1], None, 4)[..., 3])
+            ms, per = ab(legs)
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            key = f"{name}{'_bg' if bg else ''}"
+            res["display"][key] = {"outputs_equal": same, "condition_rgb8_le_yardstick": bool(med["b_rgb8_packed"] <= med["a_float_then_torch"]),
+                                   "legs": {k: {"ms_per_frame_median": med[k] / N, "min": min(ms[k]) / N, "max": max(ms[k]) / N,
+                                                "over_yardstick": med[k] / med["a_float_then_torch"]} for k in legs}}
+            for k in legs:
+                verdict = "" if k != "b_rgb8_packed" else (" -> ok" if med[k] <= med["a_float_then_torch"] else " -> MISSED")
+                print(f"display [{name:6s} {'bg   ' if bg else 'no bg'}] {k:20s} {med[k] / N:.4f} ms/frame ({min(ms[k]) / N:.4f} .. {max(ms[k]) / N:.4f}) "
+                      f"{med[k] / med['a_float_then_torch']:.3f} of (a); equal to (a): {same.get(k, '-')}{verdict}", flush=True)
+    os.environ.pop("VL3D_DISPLAY_STORE3", None)
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

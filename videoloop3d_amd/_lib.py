@@ -78,6 +78,11 @@ SIGNATURES = {
     "vl3d_render_path_cull_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
     "vl3d_render_fwd_baked_path": ([C.POINTER(RenderDesc), _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_baked_pool_path": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked_u8": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked_pool_u8": ([C.POINTER(RenderDesc), _P, _P, _I32, _I32, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _I32, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked_path_u8": ([C.POINTER(RenderDesc), _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked_pool_path_u8": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _I32, _P, _P],
+                                           C.c_int),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),

@@ -12,6 +12,8 @@ atlases ACTIVATED, multiplied by 255, clipped and truncated to 8 bits; a player 
                                        block table of packed.PackedLayout (static blocks once, dynamic blocks per frame, culled blocks not at all --
                                        the static and the dynamic atlas of the viewer package), rendered by render.render_frame_run_baked_pool with
                                        the bits of the dense baked render.  256 bytes per slot: a quarter of the float pool.
+  display_frames(rgb, alpha, bg, C)    the ONE display rule: a float render -> the uint8 frames a viewer shows (over the background, to8b).
+  BakedMPV / BakedPool.render_display  poses in, uint8 frames out: the render kernels store that rule's bytes themselves (`frames8=`).
 """
 import copy
 
@@ -40,6 +42,22 @@ def bake_texels(t, rgb_act, alpha_act):
     with torch.cuda.device(t.device):
         L.check(L.lib().vl3d_bake_rgba8(t.numel() // 4, L.ptr(t), L.STACK_DTYPE["f16" if t.dtype == torch.float16 else "f32"], L.ACT[rgb_act],
                                         L.ACT[alpha_act], L.ptr(out), L.stream_ptr(t.device)), "vl3d_bake_rgba8")
+    return out
+
+
+def display_frames(rgb, alpha, bg=None, channels=3):
+    """The display rule in torch: rgb [N,H,W,3], alpha [N,H,W] float32 -> uint8 [N,H,W,channels].  Over `bg` (3 floats or a tensor of 3, or
+    None) as MPV.py:455-461 composites, then to8b (utils.py: (255 * clip(x, 0, 1)).astype(uint8), truncating); channels == 4 appends the alpha
+    byte, to8b of alpha itself, never composited.  The `frames8=` sink of the baked renders (vl3d_render_fwd_baked*_u8) stores these bytes."""
+    if channels not in (3, 4):
+        raise ValueError(f"display_frames: channels must be 3 (RGB8) or 4 (RGBA8), got {channels}")
+    x = rgb
+    if bg is not None:
+        bg = torch.as_tensor(bg, dtype=torch.float32).to(rgb.device)
+        x = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
+    out = (255 * x.clamp(0, 1)).to(torch.uint8)
+    if channels == 4:
+        out = torch.cat([out, (255 * alpha.clamp(0, 1)).to(torch.uint8)[..., None]], dim=-1)
     return out
 
 
@@ -73,7 +91,7 @@ def path_cameras(camera, view_extrins, view_intrins):
 class _Baked:
     """what BakedMPV and BakedPool share: camera, background and the module's eval forward over runs of consecutive frames.  A subclass has
     `device`, `frm_num`, `bg_color`, `camera`, `_run(frame0, n, homos, H, W, out)`: its render of a run of frames, read in place, and
-    `_path(frame_cam, frame_t, homos [C,D,3,3], H, W, out)`: its render of a camera path."""
+    `_path(frame_cam, frame_t, homos [C,D,3,3], H, W, out)`: its render of a camera path; both take `frames8=`, `bg=` for the display frames."""
 
     def extrins_to_ref(self, tar_extrins):
         """world-to-camera poses -> reference-camera-to-target transforms, as MPMeshVid.forward forms them (MPV.py:481)."""
@@ -129,6 +147,48 @@ class _Baked:
             rgb = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
         return rgb.permute(0, 3, 1, 2), alpha
 
+    def display_bg(self):
+        """bg_color parsed for the display frames: 3 floats, or None; "random" -- one draw per call, a float composite -- is refused."""
+        if self.bg_color == "random":
+            raise RuntimeError('render_display: bg_color "random" is one draw per call; the display frames carry a fixed colour (use render)')
+        return [float(v) for v in self.bg_color.split('#')] if len(self.bg_color) > 0 else None
+
+    @torch.no_grad()
+    def render_display(self, H, W, extrins, intrins, ts, channels=3, out=None, max_batch=64):
+        """Poses in, the frames a viewer shows out: N poses (extrins [N,4,4] world-to-camera, intrins [N,3,3]), output frame i showing frame
+        ts[i] of the clip -> uint8 [N,H,W,channels] on the device (`out`: written in place), display_frames of render / render_path byte
+        for byte, stored by the render launches themselves (`frames8=`): no float frame exists.  Equal poses share a camera (path_cameras);
+        chunks of at most `max_batch` frames are launched as render_video.path_segments says -- one run call for a chunk that is one run,
+        else one path call."""
+        from .render_video import path_segments
+        extrins = torch.as_tensor(extrins, dtype=torch.float32).cpu()
+        intrins = torch.as_tensor(intrins, dtype=torch.float32).cpu()
+        tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        n, dev = len(tl), self.device
+        if not (len(extrins) == len(intrins) == n):
+            raise RuntimeError(f"render_display: one pose and one frame per output frame ({len(extrins)} extrins, {len(intrins)} intrins, {n} frames)")
+        if channels not in (3, 4):
+            raise ValueError(f"render_display: channels must be 3 (RGB8) or 4 (RGBA8), got {channels}")
+        bg = self.display_bg()
+        if out is None:
+            out = torch.empty((n, H, W, channels), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, channels) or not out.is_contiguous() or out.device != dev:
+            raise RuntimeError(f"render_display: `out` must be contiguous uint8 [{n},{H},{W},{channels}] on the model's device")
+        if n == 0:
+            return out
+        cam_of, homos = path_cameras(self.camera, extrins, intrins)
+        if dev.type == "cuda":
+            homos = homos.pin_memory().to(dev, non_blocking=True)      # [cameras, D, 3, 3], one copy
+        for kind, c0, c1 in path_segments(cam_of, tl, max_batch):
+            if kind == "run":
+                if not (0 <= tl[c0] and tl[c1 - 1] < self.frm_num):
+                    raise IndexError(f"frame index {tl[c0]} .. {tl[c1 - 1]} outside the clip of {self.frm_num} frames")
+                self._run(tl[c0], c1 - c0, homos[cam_of[c0]], H, W, None, frames8=out[c0:c1], bg=bg)
+            else:
+                lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras: a slice of the path's (a spiral: exactly its own)
+                self._path([c - lo for c in cam_of[c0:c1]], tl[c0:c1], homos[lo:hi], H, W, None, frames8=out[c0:c1], bg=bg)
+        return out
+
 
 class BakedMPV(_Baked):
     """bake(module)'s product.  texels [D,T,Hs,Ws,4] uint8 on the device, quad_keep [D,QH,QW] uint8 or None, spec (render.RenderSpec: pixel
@@ -150,13 +210,14 @@ class BakedMPV(_Baked):
     def device(self):
         return self.texels.device
 
-    def _run(self, frame0, n, homos, H, W, out):
+    def _run(self, frame0, n, homos, H, W, out, **display):
         from .render import render_frame_run_baked
-        return render_frame_run_baked(self.texels, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep)
+        return render_frame_run_baked(self.texels, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep, **display)
 
-    def _path(self, frame_cam, frame_t, homos, H, W, out, cull_scratch=None):
+    def _path(self, frame_cam, frame_t, homos, H, W, out, cull_scratch=None, **display):
         from .render import render_path_baked
-        return render_path_baked(self.texels, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep, cull_scratch=cull_scratch)
+        return render_path_baked(self.texels, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep, cull_scratch=cull_scratch,
+                                 **display)
 
 
 class BakedPool(_Baked):
@@ -186,15 +247,15 @@ class BakedPool(_Baked):
     def device(self):
         return self.pool.device
 
-    def _run(self, frame0, n, homos, H, W, out):
+    def _run(self, frame0, n, homos, H, W, out, **display):
         from .render import render_frame_run_baked_pool
         return render_frame_run_baked_pool(self.layout, self.pool, frame0, n, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
-                                           culled_rgba8=self.culled_rgba8)
+                                           culled_rgba8=self.culled_rgba8, **display)
 
-    def _path(self, frame_cam, frame_t, homos, H, W, out, cull_scratch=None):
+    def _path(self, frame_cam, frame_t, homos, H, W, out, cull_scratch=None, **display):
         from .render import render_path_baked_pool
         return render_path_baked_pool(self.layout, self.pool, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
-                                      culled_rgba8=self.culled_rgba8, cull_scratch=cull_scratch)
+                                      culled_rgba8=self.culled_rgba8, cull_scratch=cull_scratch, **display)
 
     @torch.no_grad()
     def unpack_frames(self, frames):

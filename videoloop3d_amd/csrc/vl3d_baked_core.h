@@ -4,6 +4,10 @@
 // the composite state of one frame or a frame pair with its step, and the pixel store.  Each unit keeps its fetch, its kernel skeleton and
 // its entry point; the plane list of a tile-culled model is PlaneList of vl3d_render_core.h, as in the float forward.
 #pragma once
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
 #include <type_traits>
 #include "vl3d_render_core.h"
 
@@ -38,6 +42,76 @@ __device__ __forceinline__ bool path_frame(const PathIdx &p, int i, int &cam, in
     return (unsigned)cam < (unsigned)p.n_cams && (unsigned)t < (unsigned)p.n_t;
 }
 
+// Where a composited pixel goes.  FloatOut: a.rgb / a.alpha, fp32 -- an empty argument, so that the two sinks are one kernel text (as NoPath
+// beside PathIdx).  DisplayOut (vl3d_render_fwd_baked*_u8): the frame a viewer shows, frames (N,H,W,channels) uint8, over the background
+// bg when has_bg; pack3: the lane-packed RGB8 store instead of three byte stores per lane.  bg travels in the kernel arguments.
+struct FloatOut {};
+struct DisplayOut {
+    uint8_t *frames;
+    float bg[3];
+    int has_bg, channels, pack3;
+};
+// What the four _u8 entries add to their float siblings' refusals (`who` in front of the message), and their sink.  bg: a HOST pointer to 3
+// floats or null, read here -- no device read for it.  The RGB8 store is the lane-packed one; VL3D_DISPLAY_STORE3=bytes is the measurement
+// hook of profiles/baked_fwd.py --legs display for the byte stores (read per call: the legs alternate inside one process).
+inline int display_out_of(uint8_t *frames, int32_t channels, const float *bg, const char *who, DisplayOut &out) {
+    const char *bad = nullptr;
+    if (channels != 3 && channels != 4) bad = "channels must be 3 (RGB8) or 4 (RGBA8)";
+    else if (!frames) bad = "null pointer (frames)";
+    else if (channels == 4 && ((uintptr_t)frames & 3) != 0) bad = "RGBA8 frames must be 4-byte aligned";
+    else if (bg && !(std::isfinite(bg[0]) && std::isfinite(bg[1]) && std::isfinite(bg[2]))) bad = "the background colour must be finite";
+    if (bad) {
+        vl3d_set_error((std::string(who) + ": " + bad).c_str());
+        return VL3D_EINVAL;
+    }
+    const char *store3 = std::getenv("VL3D_DISPLAY_STORE3");
+    out = DisplayOut{frames, {bg ? bg[0] : 0.0f, bg ? bg[1] : 0.0f, bg ? bg[2] : 0.0f}, bg != nullptr, channels,
+                     !(store3 && std::strcmp(store3, "bytes") == 0)};
+    return VL3D_OK;
+}
+// to8b of the reference's utils.py, (255 * clip(x, 0, 1)).astype(uint8): every operation rounded on its own, the conversion truncates
+__device__ __forceinline__ unsigned display_byte(float x) {
+#pragma clang fp contract(off)
+    return (unsigned)(255.0f * fminf(fmaxf(x, 0.0f), 1.0f));
+}
+// the display rule of one pixel -> r | g << 8 | b << 16 | a << 24.  Over a background (MPV.py:455-461) x = c * A + bg * (-A + 1) in torch's
+// order -- two products, the complement and one sum, none fused -- so that the bytes equal to8b of the float render's; the alpha byte is
+// never composited.
+__device__ __forceinline__ unsigned display_word(const DisplayOut &o, float r, float g, float b, float A) {
+#pragma clang fp contract(off)
+    if (o.has_bg) {
+        const float om = (-A) + 1.0f;
+        const float r1 = r * A, g1 = g * A, b1 = b * A;
+        const float r2 = o.bg[0] * om, g2 = o.bg[1] * om, b2 = o.bg[2] * om;
+        r = r1 + r2; g = g1 + g2; b = b1 + b2;
+    }
+    return display_byte(r) | display_byte(g) << 8 | display_byte(b) << 16 | display_byte(A) << 24;
+}
+// pixel `pix` (of N * H * W) of the display frames; x0w: the first column of the wave's 64-pixel row segment, W the row length.
+// channels == 4: one aligned dword per lane.  channels == 3: three byte stores per lane, or (pack3) the wave's 192 contiguous bytes as 48
+// dwords -- dword j = 3 q + m holds bytes of pixels 4 q + m and 4 q + m + 1, fetched from their lanes by two cross-lane reads -- when the
+// segment is a full 64 pixels and starts 4-byte aligned: a wave-uniform condition under which every lane of the wave is here (no lane left
+// at the x >= W return), so the cross-lane reads see live lanes; otherwise the byte stores.
+__device__ __forceinline__ void display_store(const DisplayOut &o, size_t pix, int x0w, int W, unsigned w) {
+    if (o.channels == 4) {
+        reinterpret_cast<unsigned *>(o.frames)[pix] = w;
+        return;
+    }
+    uint8_t *p = o.frames + pix * 3;
+    if (o.pack3) {
+        const int lane = (int)(threadIdx.x & 63);
+        uint8_t *seg = p - (size_t)lane * 3;      // the wave's first byte: the same address in every lane
+        const int fast = __builtin_amdgcn_readfirstlane((int)(x0w + 64 <= W && ((uintptr_t)seg & 3) == 0));
+        if (fast) {
+            const int q = lane / 3, m = lane - q * 3;      // (lanes 48 .. 63 read lanes they do not need and store nothing)
+            const unsigned wa = (unsigned)__shfl((int)w, (4 * q + m) & 63), wb = (unsigned)__shfl((int)w, (4 * q + m + 1) & 63);
+            if (lane < 48) reinterpret_cast<unsigned *>(seg)[lane] = ((wa & 0xffffffu) >> (8 * m)) | (wb << (24 - 8 * m));
+            return;
+        }
+    }
+    p[0] = (uint8_t)w; p[1] = (uint8_t)(w >> 8); p[2] = (uint8_t)(w >> 16);
+}
+
 // Front-to-back composite of a pixel's NF frames (one, or a frame pair) over the kernel's own accumulators: transmittance, colour and alpha
 // per frame, five plain arrays the kernel declares and clears (T = 1, the rest 0) and this struct steps and stores -- a by-reference closure
 // with a name.  OWNER is a type local to the kernel that uses it: like the lambda it replaces, every kernel instantiation gets a copy of its
@@ -67,7 +141,15 @@ struct BakedComposite {
         }
     }
     // pixel (x, y) of frame t0, then of frame t0 + 1 under has1 (odd T: the last pair composites frame t0 twice and stores it once)
-    __device__ __forceinline__ void store(const RenderArgs &a, int t0, int x, int y, bool has1) const {
+    __device__ __forceinline__ void store(const RenderArgs &a, const DisplayOut &o, int t0, int x, int y, bool has1) const {
+        const size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
+        const int x0w = x - (int)(threadIdx.x & 63);
+        display_store(o, pix, x0w, a.W, display_word(o, cr[0], cg[0], cb[0], A[0]));
+        if constexpr (NF == 2) {
+            if (has1) display_store(o, pix + (size_t)a.H * a.W, x0w, a.W, display_word(o, cr[1], cg[1], cb[1], A[1]));
+        }
+    }
+    __device__ __forceinline__ void store(const RenderArgs &a, const FloatOut &, int t0, int x, int y, bool has1) const {
         size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
         a.rgb[pix * 3 + 0] = cr[0]; a.rgb[pix * 3 + 1] = cg[0]; a.rgb[pix * 3 + 2] = cb[0];
         a.alpha[pix] = A[0];

@@ -68,8 +68,10 @@ __device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, 
 // PATH = PathIdx (vl3d_render_fwd_baked_path): the block index's outermost factor is the OUTPUT frame i; the workgroup reads its camera and
 // its frame of the clip (path_frame: scalar loads, range-checked) and from them forms its homography, mask and texel bases.  One frame per
 // thread: from there on the one-frame kernel.
-template <int NF, bool CULL, typename PATH = NoPath>
-__global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y, PATH path) {
+// OUT = FloatOut: rgb / alpha fp32 at a.rgb / a.alpha.  OUT = DisplayOut (vl3d_render_fwd_baked_u8 / _path_u8): the 8-bit display frame over
+// the background, written by the same launch (vl3d_baked_core.h); everything in front of the store is the one text.
+template <int NF, bool CULL, typename PATH = NoPath, typename OUT = FloatOut>
+__global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y, PATH path, OUT out) {
     constexpr bool IS_PATH = !std::is_same<PATH, NoPath>::value;
     static_assert(!IS_PATH || NF == 1, "a camera path renders one frame per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
@@ -141,31 +143,32 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
             if (d + 2 >= a.D) break;
         }
     }
-    composite.store(a, t0, x, y, has1);
+    composite.store(a, out, t0, x, y, has1);
 }
 
-template <int NF>
-void launch_baked(const RenderArgs &a, hipStream_t s) {
+template <int NF, typename OUT>
+void launch_baked(const RenderArgs &a, const OUT &out, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
     if (a.quad_keep) {      // tile culling: the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
         launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
-        hipLaunchKernelGGL((render_fwd_baked_k<NF, true>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{});
+        hipLaunchKernelGGL((render_fwd_baked_k<NF, true, NoPath, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{}, out);
         return;
     }
-    hipLaunchKernelGGL((render_fwd_baked_k<NF, false>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{});
+    hipLaunchKernelGGL((render_fwd_baked_k<NF, false, NoPath, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{}, out);
 }
 
 // a camera path: a.T output frames, one plan launch for all cameras (a culled model), one render launch
-void launch_baked_path(const RenderArgs &a, const PathIdx &path, hipStream_t s) {
+template <typename OUT>
+void launch_baked_path(const RenderArgs &a, const PathIdx &path, const OUT &out, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * a.T)), block(512);
     if (a.quad_keep) {
         launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
-        hipLaunchKernelGGL((render_fwd_baked_k<1, true, PathIdx>), grid, block, 0, s, a, tiles_x, tiles_y, path);
+        hipLaunchKernelGGL((render_fwd_baked_k<1, true, PathIdx, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, out);
         return;
     }
-    hipLaunchKernelGGL((render_fwd_baked_k<1, false, PathIdx>), grid, block, 0, s, a, tiles_x, tiles_y, path);
+    hipLaunchKernelGGL((render_fwd_baked_k<1, false, PathIdx, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, out);
 }
 
 bool known_act(int act) { return act >= VL3D_ACT_NONE && act <= VL3D_ACT_ABS; }
@@ -188,8 +191,9 @@ extern "C" int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stac
     return VL3D_OK;
 }
 
-// what vl3d_render_fwd_baked and vl3d_render_fwd_baked_path refuse alike, in two parts around the entry's own rule about its frames
-static int baked_check_desc(const vl3d_render_desc *desc, const uint8_t *baked, const float *homos, const float *rgb, const float *alpha) {
+// what vl3d_render_fwd_baked, vl3d_render_fwd_baked_path and their _u8 forms refuse alike, in two parts around the entry's own rule about
+// its frames (rgb, alpha: the outputs -- a _u8 entry passes its frames for both)
+static int baked_check_desc(const vl3d_render_desc *desc, const uint8_t *baked, const float *homos, const void *rgb, const void *alpha) {
     VL3D_REQUIRE(desc != nullptr, "null render desc");
     VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked: no kernel variants (desc->variant = 0)");
     VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked: non-positive render dims");
@@ -216,22 +220,41 @@ static int baked_set_cull(RenderArgs &a, const vl3d_render_desc *desc, const uin
     return VL3D_OK;
 }
 
-extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
-                                     vl3d_stream_t stream) {
-    int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
+// a run of frames into either sink: OUT = FloatOut with rgb / alpha, OUT = DisplayOut (checked by the entry) with rgb = alpha = its frames
+template <typename OUT>
+static int baked_run(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha, const OUT &out,
+                     vl3d_stream_t stream) {
     VL3D_REQUIRE(T_alloc > 0 && frame0 >= 0 && frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
     RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above)
     a.Tstride = T_alloc;
     a.stack = reinterpret_cast<const float *>(baked + (size_t)frame0 * desc->Hs * desc->Ws * 4);
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
-    rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);
+    const int rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);
     if (rc != VL3D_OK) return rc;
-    if (desc->T >= 2) launch_baked<2>(a, (hipStream_t)stream);
-    else launch_baked<1>(a, (hipStream_t)stream);
+    if (desc->T >= 2) launch_baked<2>(a, out, (hipStream_t)stream);
+    else launch_baked<1>(a, out, (hipStream_t)stream);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
+                                     vl3d_stream_t stream) {
+    const int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    return baked_run(desc, baked, frame0, T_alloc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha, FloatOut{}, stream);
+}
+
+extern "C" int vl3d_render_fwd_baked_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
+                                        const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, uint8_t *frames, int32_t channels,
+                                        const float *bg, vl3d_stream_t stream) {
+    int rc = baked_check_desc(desc, baked, homos, frames, frames);
+    if (rc != VL3D_OK) return rc;
+    DisplayOut out;
+    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_u8", out);
+    if (rc != VL3D_OK) return rc;
+    return baked_run(desc, baked, frame0, T_alloc, homos, quad_keep, QH, QW, cull_scratch, nullptr, nullptr, out, stream);
 }
 
 // two 64-bit plane masks per (camera, 64 x 8 pixel workgroup): [n_cams][tiles_y * tiles_x][2]
@@ -251,13 +274,13 @@ int vl3d_render_detail::check_path(const vl3d_render_desc *desc, int32_t n_cams,
     return VL3D_EINVAL;
 }
 
-extern "C" int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
-                                          const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                          void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
-    int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
+// a camera path into either sink (as baked_run)
+template <typename OUT>
+static int baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
+                      const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
+                      float *rgb, float *alpha, const OUT &out, vl3d_stream_t stream) {
     VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_baked_path: a clip of T_alloc >= 1 frames");
-    rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_path");
+    int rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_path");
     if (rc != VL3D_OK) return rc;
     RenderArgs a = render_args_of(desc);      // a.T: the output frames of the path
     a.Tstride = T_alloc;
@@ -265,7 +288,27 @@ extern "C" int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const ui
     a.homos = homos; a.rgb = rgb; a.alpha = alpha;
     rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);      // (cull_scratch: vl3d_render_path_cull_scratch_bytes)
     if (rc != VL3D_OK) return rc;
-    launch_baked_path(a, PathIdx{frame_cam, frame_t, n_cams, T_alloc}, (hipStream_t)stream);
+    launch_baked_path(a, PathIdx{frame_cam, frame_t, n_cams, T_alloc}, out, (hipStream_t)stream);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
+                                          const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                          void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
+    const int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    return baked_path(desc, baked, T_alloc, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, cull_scratch, rgb, alpha, FloatOut{}, stream);
+}
+
+extern "C" int vl3d_render_fwd_baked_path_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                                             int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH,
+                                             int32_t QW, void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg,
+                                             vl3d_stream_t stream) {
+    int rc = baked_check_desc(desc, baked, homos, frames, frames);
+    if (rc != VL3D_OK) return rc;
+    DisplayOut out;
+    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_path_u8", out);
+    if (rc != VL3D_OK) return rc;
+    return baked_path(desc, baked, T_alloc, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, cull_scratch, nullptr, nullptr, out, stream);
 }

@@ -51,8 +51,9 @@ __device__ __forceinline__ void pool_load(const PoolSrc &p, int e, unsigned in_b
 
 // PATH = NoPath: frames p.frame0 + t0 .. of one camera.  PATH = PathIdx (vl3d_render_fwd_baked_pool_path): the block index's outermost factor is
 // the OUTPUT frame; camera and frame of the model come from path_frame (scalar loads, range-checked), as in the dense path kernel.
-template <int NF, typename PATH = NoPath>
-__global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, PoolSrc p, int tiles_x, int tiles_y, PATH path) {
+// OUT: FloatOut, or the DisplayOut of the _u8 entries (vl3d_baked_core.h), as in the dense kernel.
+template <int NF, typename PATH = NoPath, typename OUT = FloatOut>
+__global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, PoolSrc p, int tiles_x, int tiles_y, PATH path, OUT out) {
     constexpr bool IS_PATH = !std::is_same<PATH, NoPath>::value;
     static_assert(!IS_PATH || NF == 1, "a camera path renders one frame per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
@@ -136,31 +137,33 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
             if (dC < 0) break;
         }
     }
-    composite.store(a, t0, x, y, has1);
+    composite.store(a, out, t0, x, y, has1);
 }
 
-template <int NF>
-void launch_baked_pool(const RenderArgs &a, const PoolSrc &p, hipStream_t s) {
+template <int NF, typename OUT>
+void launch_baked_pool(const RenderArgs &a, const PoolSrc &p, const OUT &out, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
     // the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
     launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
-    hipLaunchKernelGGL((render_fwd_baked_pool_k<NF>), grid, block, 0, s, a, p, tiles_x, tiles_y, NoPath{});
+    hipLaunchKernelGGL((render_fwd_baked_pool_k<NF, NoPath, OUT>), grid, block, 0, s, a, p, tiles_x, tiles_y, NoPath{}, out);
 }
 
 // a camera path: a.T output frames, one plan launch for all cameras, one render launch
-void launch_baked_pool_path(const RenderArgs &a, const PoolSrc &p, const PathIdx &path, hipStream_t s) {
+template <typename OUT>
+void launch_baked_pool_path(const RenderArgs &a, const PoolSrc &p, const PathIdx &path, const OUT &out, hipStream_t s) {
     const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
     const dim3 grid((unsigned)(tiles_x * tiles_y * a.T)), block(512);
     launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
-    hipLaunchKernelGGL((render_fwd_baked_pool_k<1, PathIdx>), grid, block, 0, s, a, p, tiles_x, tiles_y, path);
+    hipLaunchKernelGGL((render_fwd_baked_pool_k<1, PathIdx, OUT>), grid, block, 0, s, a, p, tiles_x, tiles_y, path, out);
 }
 
 }  // namespace
 
-// what vl3d_render_fwd_baked_pool and vl3d_render_fwd_baked_pool_path refuse alike, in two parts around the entry's own rule about its frames
+// what vl3d_render_fwd_baked_pool, vl3d_render_fwd_baked_pool_path and their _u8 forms refuse alike, in two parts around the entry's own rule
+// about its frames (rgb, alpha: the outputs -- a _u8 entry passes its frames for both)
 static int pool_check_desc(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, const float *homos, const uint8_t *quad_keep,
-                           const void *cull_scratch, const float *rgb, const float *alpha) {
+                           const void *cull_scratch, const void *rgb, const void *alpha) {
     VL3D_REQUIRE(desc != nullptr, "null render desc");
     VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked_pool: no kernel variants (desc->variant = 0)");
     VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked_pool: non-positive render dims");
@@ -189,37 +192,77 @@ static int pool_set_args(RenderArgs &a, const vl3d_render_desc *desc, const floa
     return VL3D_OK;
 }
 
-extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
-                                          int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                          uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
-    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
+// a run of frames / a camera path into either sink: OUT = FloatOut with rgb / alpha, OUT = DisplayOut (checked by the entry) without
+template <typename OUT>
+static int pool_run(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0, int32_t T_model, const float *homos,
+                    const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha,
+                    const OUT &out, vl3d_stream_t stream) {
     VL3D_REQUIRE(T_model > 0 && frame0 >= 0 && (int64_t)frame0 + desc->T <= T_model,
                  "vl3d_render_fwd_baked_pool: the run of frames leaves the model's T_model frames");
     RenderArgs a;
-    rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
+    const int rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
     if (rc != VL3D_OK) return rc;
     const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, frame0, culled_rgba8};
-    if (desc->T >= 2) launch_baked_pool<2>(a, p, (hipStream_t)stream);
-    else launch_baked_pool<1>(a, p, (hipStream_t)stream);
+    if (desc->T >= 2) launch_baked_pool<2>(a, p, out, (hipStream_t)stream);
+    else launch_baked_pool<1>(a, p, out, (hipStream_t)stream);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
+}
+template <typename OUT>
+static int pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos, int32_t n_cams,
+                     const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
+                     void *cull_scratch, float *rgb, float *alpha, const OUT &out, vl3d_stream_t stream) {
+    VL3D_REQUIRE(T_model > 0, "vl3d_render_fwd_baked_pool_path: a model of T_model >= 1 frames");
+    int rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_pool_path");
+    if (rc != VL3D_OK) return rc;
+    RenderArgs a;      // a.T: the output frames of the path; cull_scratch: vl3d_render_path_cull_scratch_bytes
+    rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, 0, culled_rgba8};
+    launch_baked_pool_path(a, p, PathIdx{frame_cam, frame_t, n_cams, T_model}, out, (hipStream_t)stream);
+    VL3D_CHECK_LAUNCH();
+    return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
+                                          int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                          uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
+    const int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
+    if (rc != VL3D_OK) return rc;
+    return pool_run(desc, blocks, pool, frame0, T_model, homos, quad_keep, QH, QW, culled_rgba8, cull_scratch, rgb, alpha, FloatOut{}, stream);
+}
+
+extern "C" int vl3d_render_fwd_baked_pool_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
+                                             int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                             uint32_t culled_rgba8, void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg,
+                                             vl3d_stream_t stream) {
+    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, frames, frames);
+    if (rc != VL3D_OK) return rc;
+    DisplayOut out;
+    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_pool_u8", out);
+    if (rc != VL3D_OK) return rc;
+    return pool_run(desc, blocks, pool, frame0, T_model, homos, quad_keep, QH, QW, culled_rgba8, cull_scratch, nullptr, nullptr, out, stream);
 }
 
 extern "C" int vl3d_render_fwd_baked_pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
                                                const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
                                                const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
                                                float *rgb, float *alpha, vl3d_stream_t stream) {
-    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
+    const int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
     if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(T_model > 0, "vl3d_render_fwd_baked_pool_path: a model of T_model >= 1 frames");
-    rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_pool_path");
+    return pool_path(desc, blocks, pool, T_model, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, culled_rgba8, cull_scratch, rgb, alpha,
+                     FloatOut{}, stream);
+}
+
+extern "C" int vl3d_render_fwd_baked_pool_path_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
+                                                  const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
+                                                  const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
+                                                  uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream) {
+    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, frames, frames);
     if (rc != VL3D_OK) return rc;
-    RenderArgs a;      // a.T: the output frames of the path; cull_scratch: vl3d_render_path_cull_scratch_bytes
-    rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
+    DisplayOut out;
+    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_pool_path_u8", out);
     if (rc != VL3D_OK) return rc;
-    const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, 0, culled_rgba8};
-    launch_baked_pool_path(a, p, PathIdx{frame_cam, frame_t, n_cams, T_model}, (hipStream_t)stream);
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
+    return pool_path(desc, blocks, pool, T_model, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, culled_rgba8, cull_scratch, nullptr, nullptr,
+                     out, stream);
 }

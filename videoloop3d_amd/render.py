@@ -82,6 +82,26 @@ def _out_buffers(out, n, H, W, device, who):
     return rgb, alpha
 
 
+def _display_out(out, frames8, bg, n, H, W, device, who):
+    """the display sink of a baked render (vl3d_render_fwd_baked*_u8): `frames8` uint8 [n,H,W,3|4] contiguous on `device`, `bg` a sequence of 3
+    floats or None -> (channels, bg as a host float[3] or None).  `out=` (the float sink) with `frames8=` is a ValueError; alignment of RGBA8
+    frames and a non-finite background are the entry's refusals."""
+    if out is not None:
+        raise ValueError(f"{who}: `out=` (float32 rgb / alpha) and `frames8=` (uint8 display frames) name two different outputs: pass one")
+    if not isinstance(frames8, torch.Tensor) or not frames8.is_cuda or frames8.device != device:
+        raise RuntimeError(f"{who}: `frames8` must be a tensor on the model's device")
+    if (frames8.dtype != torch.uint8 or frames8.dim() != 4 or tuple(frames8.shape[:3]) != (n, H, W) or frames8.shape[3] not in (3, 4)
+            or not frames8.is_contiguous()):
+        raise RuntimeError(f"{who}: `frames8` must be contiguous uint8 [n,H,W,3] (RGB8) or [n,H,W,4] (RGBA8) = [{n},{H},{W},3|4], "
+                           f"got {tuple(frames8.shape)} {frames8.dtype}")
+    if bg is not None:
+        bg = [float(v) for v in bg]
+        if len(bg) != 3:
+            raise RuntimeError(f"{who}: `bg` is a colour of 3 floats, got {len(bg)}")
+        bg = (L.C.c_float * 3)(*bg)
+    return int(frames8.shape[3]), bg
+
+
 def _quad_map(quad_keep, D):
     """the quad map [D,QH,QW] of a tile-culled model as the uint8 tensor the ABI reads."""
     L.check_cuda(quad_keep)
@@ -356,13 +376,18 @@ def render_frame_run(stack, frame0, nframes, homos, H, W, spec: RenderSpec = Ren
     return rgb, alpha
 
 
-def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, quad_keep=None):
+def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, frames8=None, bg=None):
     """render_frame_run on the BAKED texels of a playback model (videoloop3d_amd/baked.py; vl3d_render_fwd_baked): `baked` [D,T,Hs,Ws,4] uint8 --
     activated, times 255, truncated (baked.bake_texels) -- filtered bilinearly AFTER the activation, as a player filters the exported 8-bit
     atlases; nothing is activated behind the blend, so spec.rgb_act / alpha_act / act_order are not read.  Coverage (hard cut, culled quads,
     tile-exact layout) is decided by the float kernels' own code.  The planar convention only (RenderSpec.mpv()); forward only -- a baked
-    model is not trained: inputs that require a gradient are refused.  -> (rgb [n,H,W,3], alpha [n,H,W]) float32."""
+    model is not trained: inputs that require a gradient are refused.  -> (rgb [n,H,W,3], alpha [n,H,W]) float32.
+    `frames8` (uint8 [n,H,W,3|4] on the device): the DISPLAY frames instead -- baked.display_frames(rgb, alpha, bg, channels), byte for byte,
+    written by the render launch (vl3d_render_fwd_baked_u8); no float output exists and `frames8` is returned.  `bg`: the background
+    colour, 3 floats, or None."""
     L.check_cuda(baked, homos)
+    if bg is not None and frames8 is None:
+        raise ValueError("render_frame_run_baked: `bg` belongs to the display frames (`frames8=`)")
     if baked.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
         raise RuntimeError("render_frame_run_baked: baked texels have no backward (train the float model, then bake it)")
     if baked.dtype != torch.uint8 or baked.dim() != 5 or baked.shape[4] != 4 or not baked.is_contiguous():
@@ -381,7 +406,10 @@ def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec
     desc.T = int(nframes)
     desc.stack_dtype = L.STACK_DTYPE["u8"]
     dev = baked.device
-    rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked")
+    if frames8 is not None:
+        channels, bg = _display_out(out, frames8, bg, nframes, H, W, dev, "render_frame_run_baked")
+    else:
+        rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked")
     qk, grid, cull = None, (0, 0), None
     if quad_keep is not None:
         qk = _quad_map(quad_keep, D)
@@ -389,19 +417,27 @@ def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec
     with torch.cuda.device(dev):
         if qk is not None:
             cull = _cull_scratch(desc, dev)
+        if frames8 is not None:
+            L.check(L.lib().vl3d_render_fwd_baked_u8(desc, L.ptr(baked), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *grid, L.ptr(cull),
+                                                     L.ptr(frames8), channels, bg, L.stream_ptr(dev)), "vl3d_render_fwd_baked_u8")
+            return frames8
         L.check(L.lib().vl3d_render_fwd_baked(desc, L.ptr(baked), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *grid, L.ptr(cull), L.ptr(rgb),
                                               L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked")
     return rgb, alpha
 
 
-def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8):
+def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, frames8=None,
+                                bg=None):
     """render_frame_run_baked from the baked POOL of a packed tile-culled model (baked.BakedPool; vl3d_render_fwd_baked_pool): `layout` the
     packed.PackedLayout whose block table addresses `pool` [n_slots * 64, 4] uint8 (8 x 8-texel blocks of baked RGBA8 texels), `quad_keep`
     [D,QH,QW] the quad map the table was built from, `culled_rgba8` the texel (r | g << 8 | b << 16 | a << 24) a block without storage reads
     as (BakedPool.culled_rgba8) -- both required, by keyword.  The kernel trusts the table: the layout's table and the quad map are checked
     here against the layout's own dimensions.  Frames frame0 .. frame0 + nframes - 1 of the model's layout.T -> (rgb [n,H,W,3], alpha [n,H,W]) float32: the bits of
-    render_frame_run_baked on the unpacked texels, without the dense clip.  The planar convention only; forward only."""
+    render_frame_run_baked on the unpacked texels, without the dense clip.  The planar convention only; forward only.  `frames8`, `bg`: the
+    display frames instead, as render_frame_run_baked takes them (vl3d_render_fwd_baked_pool_u8)."""
     L.check_cuda(pool, homos, layout.blocks)
+    if bg is not None and frames8 is None:
+        raise ValueError("render_frame_run_baked_pool: `bg` belongs to the display frames (`frames8=`)")
     if pool.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
         raise RuntimeError("render_frame_run_baked_pool: baked texels have no backward (train the float model, then bake it)")
     if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
@@ -427,9 +463,17 @@ def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec
     homos = homos.detach().to(torch.float32).contiguous()
     dev = pool.device
     d = _desc_dims(D, nframes, layout.Hs, layout.Ws, H, W, spec, L.STACK_DTYPE["u8"])
-    rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked_pool")
+    if frames8 is not None:
+        channels, bg = _display_out(out, frames8, bg, nframes, H, W, dev, "render_frame_run_baked_pool")
+    else:
+        rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked_pool")
     with torch.cuda.device(dev):
         cull = _cull_scratch(d, dev)
+        if frames8 is not None:
+            L.check(L.lib().vl3d_render_fwd_baked_pool_u8(d, L.ptr(layout.blocks), L.ptr(pool), int(frame0), int(T), L.ptr(homos), L.ptr(qk),
+                                                          *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(frames8), channels, bg,
+                                                          L.stream_ptr(dev)), "vl3d_render_fwd_baked_pool_u8")
+            return frames8
         L.check(L.lib().vl3d_render_fwd_baked_pool(d, L.ptr(layout.blocks), L.ptr(pool), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec),
                                                    int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)),
                 "vl3d_render_fwd_baked_pool")
@@ -469,15 +513,18 @@ def _path_cull_scratch(desc, n_cams, device, cull_scratch, who):
     return cull_scratch
 
 
-def render_path_baked(baked, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, cull_scratch=None):
+def render_path_baked(baked, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, cull_scratch=None, frames8=None, bg=None):
     """A camera path on the baked clip (vl3d_render_fwd_baked_path): N output frames in ONE plan launch plus ONE render launch, output frame i
     being frame frame_t[i] of `baked` [D,T,Hs,Ws,4] uint8 seen by camera frame_cam[i] of `homos` [C,D,3,3] -- the spiral of the offline renderer,
     where render_frame_run_baked takes one camera per call.  frame_cam / frame_t: host sequences or numpy arrays of N indices (checked here:
     IndexError).  `cull_scratch`: an int64 buffer of vl3d_render_path_cull_scratch_bytes to hold the plane masks [C][tiles][2] across calls (a
     tile-culled model; allocated per call when absent).  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal to
-    render_frame_run_baked(baked, frame_t[i], 1, homos[frame_cam[i]], ...).  Everything else as render_frame_run_baked."""
+    render_frame_run_baked(baked, frame_t[i], 1, homos[frame_cam[i]], ...).  Everything else as render_frame_run_baked, `frames8` / `bg` (the
+    display frames uint8 [N,H,W,3|4] instead: vl3d_render_fwd_baked_path_u8) included."""
     who = "render_path_baked"
     L.check_cuda(baked, homos)
+    if bg is not None and frames8 is None:
+        raise ValueError(f"{who}: `bg` belongs to the display frames (`frames8=`)")
     if baked.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
         raise RuntimeError(f"{who}: baked texels have no backward (train the float model, then bake it)")
     if baked.dtype != torch.uint8 or baked.dim() != 5 or baked.shape[4] != 4 or not baked.is_contiguous():
@@ -500,21 +547,32 @@ def render_path_baked(baked, frame_cam, frame_t, homos, H, W, spec: RenderSpec, 
     desc = _desc(baked, H, W, spec, 0, 0)
     desc.T = N
     desc.stack_dtype = L.STACK_DTYPE["u8"]
-    rgb, alpha = _out_buffers(out, N, H, W, dev, who)
+    if frames8 is not None:
+        channels, bg = _display_out(out, frames8, bg, N, H, W, dev, who)
+    else:
+        rgb, alpha = _out_buffers(out, N, H, W, dev, who)
     with torch.cuda.device(dev):
         if qk is not None:
             cull = _path_cull_scratch(desc, C, dev, cull_scratch, who)
+        if frames8 is not None:
+            L.check(L.lib().vl3d_render_fwd_baked_path_u8(desc, L.ptr(baked), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk), *grid,
+                                                          L.ptr(cull), L.ptr(frames8), channels, bg, L.stream_ptr(dev)), "vl3d_render_fwd_baked_path_u8")
+            return frames8
         L.check(L.lib().vl3d_render_fwd_baked_path(desc, L.ptr(baked), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk), *grid,
                                                    L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked_path")
     return rgb, alpha
 
 
-def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, cull_scratch=None):
+def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, cull_scratch=None,
+                           frames8=None, bg=None):
     """render_path_baked from the baked POOL (vl3d_render_fwd_baked_pool_path): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
     render_frame_run_baked_pool takes them, the path as render_path_baked takes it.  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal
-    to render_frame_run_baked_pool(layout, pool, frame_t[i], 1, homos[frame_cam[i]], ...)."""
+    to render_frame_run_baked_pool(layout, pool, frame_t[i], 1, homos[frame_cam[i]], ...).  `frames8`, `bg`: the display frames instead
+    (vl3d_render_fwd_baked_pool_path_u8)."""
     who = "render_path_baked_pool"
     L.check_cuda(pool, homos, layout.blocks)
+    if bg is not None and frames8 is None:
+        raise ValueError(f"{who}: `bg` belongs to the display frames (`frames8=`)")
     if pool.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
         raise RuntimeError(f"{who}: baked texels have no backward (train the float model, then bake it)")
     if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
@@ -540,9 +598,18 @@ def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: 
     N, idx = _path_indices(frame_cam, frame_t, C, T, dev, who)
     homos = homos.detach().to(torch.float32).contiguous()
     d = _desc_dims(D, N, layout.Hs, layout.Ws, H, W, spec, L.STACK_DTYPE["u8"])
-    rgb, alpha = _out_buffers(out, N, H, W, dev, who)
+    if frames8 is not None:
+        channels, bg = _display_out(out, frames8, bg, N, H, W, dev, who)
+    else:
+        rgb, alpha = _out_buffers(out, N, H, W, dev, who)
     with torch.cuda.device(dev):
         cull = _path_cull_scratch(d, C, dev, cull_scratch, who)
+        if frames8 is not None:
+            L.check(L.lib().vl3d_render_fwd_baked_pool_path_u8(d, L.ptr(bl), L.ptr(pool), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]),
+                                                               L.ptr(qk), *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull),
+                                                               L.ptr(frames8), channels, bg, L.stream_ptr(dev)),
+                    "vl3d_render_fwd_baked_pool_path_u8")
+            return frames8
         L.check(L.lib().vl3d_render_fwd_baked_pool_path(d, L.ptr(bl), L.ptr(pool), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk),
                                                         *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha),
                                                         L.stream_ptr(dev)), "vl3d_render_fwd_baked_pool_path")

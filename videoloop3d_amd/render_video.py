@@ -185,22 +185,16 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
     module's own `plane_homographies`, the same bits as its forward) and uploaded in ONE copy, every frame -- or run of consecutive frames of
     one camera -- is rendered where it lies in the clip (render.render_frame_run: no gather of stack[:, ts]), straight into a chunk buffer
     that is converted to uint8 once (a sparsified model with its quad map; a packed one through its block table).  None when the model is
-    not one this path serves (atlas_exact / CPU).  `baked` (baked.BakedMPV): the frames come from ITS uint8 texels, quad map, geometry,
-    camera and background through the same runs (render.render_frame_run_baked); the float model is not read.  A baked.BakedPool renders its
-    runs from the pool behind its block table (render.render_frame_run_baked_pool).  Chunks of a baked model that are not one run go through
-    its path render (`path_segments`, `baked._path`)."""
-    from .render import render_frame_run, render_frame_run_baked, render_frame_run_baked_pool
+    not one this path serves (atlas_exact / CPU).  `baked` (baked.BakedMPV / baked.BakedPool): the frames come from ITS uint8 texels (its
+    pool), quad map, geometry, camera and background, and leave its render launches as the uint8 frames themselves (`render_display`: a
+    chunk that is one run is one frame-pair call, any other chunk one path call -- `path_segments` --, each writing its slice of the result
+    through `frames8=`); the float model is not read and no float frame is allocated."""
+    from .render import render_frame_run
     if baked is not None:
         if baked.bg_color == "random":
             return None
-        if hasattr(baked, "pool"):
-            def run_pool(pool, t0, n, homos, H, W, spec, out=None, quad_keep=None):
-                return render_frame_run_baked_pool(baked.layout, pool, t0, n, homos, H, W, spec, out=out, quad_keep=quad_keep,
-                                                   culled_rgba8=baked.culled_rgba8)
-            return _in_place_runs(baked.camera, baked.pool, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
-                                  render_t, chunk, run_pool, T=baked.frm_num, path=baked._path)
-        return _in_place_runs(baked.camera, baked.texels, None, baked.quad_keep, baked.spec, baked.bg_color, H, W, view_extrins, view_intrins,
-                              render_t, chunk, render_frame_run_baked, path=baked._path)
+        n = len(render_t)
+        return baked.render_display(H, W, view_extrins[:n], view_intrins[:n], render_t, channels=3, max_batch=chunk)
     packed = getattr(module, "packed", None)
     stack = module.stack_pool.data if packed is not None else getattr(module, "stack", None)
     if (stack is None or not stack.is_cuda or not stack.is_contiguous() or module.atlas_exact or module.training
@@ -213,14 +207,13 @@ def _render_frames_in_place(module, H, W, view_extrins, view_intrins, render_t, 
                           render_frame_run)
 
 
-def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run, T=None, path=None):
-    """the frame loop of _render_frames_in_place: `camera` gives the homographies (`plane_homographies`, `ref_extrin`), `run` renders a run of
-    consecutive frames of the dense clip `stack` in place (render_frame_run / render_frame_run_baked); `packed`: the pool's layout instead.
-    `T`: the clip's frame count where `stack` is not a (D,T,...) clip (a baked pool).  `path` (a baked model's `_path`): a chunk that is not
-    one run -- path_segments -- is ONE call of it, every frame with its own camera, instead of one `run` per frame."""
-    from .baked import path_cameras
+def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins, view_intrins, render_t, chunk, run):
+    """the frame loop of _render_frames_in_place for the float model: `camera` gives the homographies (`plane_homographies`, `ref_extrin`), `run`
+    renders a run of consecutive frames of the dense clip `stack` in place (render_frame_run); `packed`: the pool's layout instead.  A chunk
+    of float frames becomes uint8 by baked.display_frames, the rule the baked renders store themselves."""
+    from .baked import display_frames, path_cameras
     from .render import render_planes_packed
-    n, T, dev = len(render_t), (packed.T if packed is not None else (stack.shape[1] if T is None else T)), stack.device
+    n, T, dev = len(render_t), (packed.T if packed is not None else stack.shape[1]), stack.device
     if packed is not None:      # a packed model reads its pool through the block table (vl3d_render_fwd_packed): the frame indices go up once
         from .tiles import CULLED_ALPHA
         t_dev = torch.as_tensor(render_t.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
@@ -232,13 +225,9 @@ def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins
     out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
     chunk = max(1, min(int(chunk), n))
     rgb, alpha = torch.empty((chunk, H, W, 3), dtype=torch.float32, device=dev), torch.empty((chunk, H, W), dtype=torch.float32, device=dev)
-    for kind, c0, c1 in path_segments(cam_of, render_t, chunk):
+    for _, c0, c1 in path_segments(cam_of, render_t, chunk):
         m = c1 - c0
-        by_path = kind == "path" and path is not None
-        if by_path:
-            lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras: a slice of the path's (a spiral: exactly its own)
-            path([c - lo for c in cam_of[c0:c1]], render_t[c0:c1], homos[lo:hi], H, W, (rgb[:m], alpha[:m]))
-        i = c1 if by_path else c0
+        i = c0
         while i < c1:
             j = i + 1      # a run: one camera, consecutive frames of the clip
             while j < c1 and cam_of[j] == cam_of[i] and render_t[j] == render_t[j - 1] + 1:
@@ -252,10 +241,7 @@ def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins
             else:
                 run(stack, t0, j - i, homos[cam_of[i]], H, W, spec, out=(rgb[i - c0:j - c0], alpha[i - c0:j - c0]), quad_keep=qk)
             i = j
-        x = rgb[:m]
-        if bg is not None:
-            x = x * alpha[:m, ..., None] + bg[None, None, None] * (-alpha[:m, ..., None] + 1)
-        out[c0:c1] = to8b(x)
+        out[c0:c1] = display_frames(rgb[:m], alpha[:m], bg, 3)
     return out
 
 
