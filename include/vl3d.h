@@ -108,95 +108,71 @@ int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stac
                                   const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
                                   vl3d_stream_t stream);
 
-/* Baked playback (csrc/vl3d_render_baked.hip).  The viewer package the reference exports (scripts/script_export_mesh.py:117-191) holds
- * ACTIVATED 8-bit atlases, and a player filters those texels bilinearly after the activation -- not the picture the float kernels above
- * compute (fp32 texels, interpolate, then activate).
+/* Baked playback (csrc/vl3d_render_baked.hip, csrc/vl3d_render_baked_pool.hip).  The viewer package the reference exports
+ * (scripts/script_export_mesh.py:117-191) holds ACTIVATED 8-bit atlases, and a player filters those texels bilinearly after the activation --
+ * not the picture the float kernels above compute (fp32 texels, interpolate, then activate).
  *   vl3d_bake_rgba8: the one bake rule, per channel u8 = uint8(trunc(clip(act(s) * 255, 0, 255))) -- act = rgb_act (VL3D_ACT_*) for channels
  *     0-2, alpha_act for channel 3; truncation, not rounding (script_export_mesh.py:130-138); straight RGBA, not premultiplied.  stack:
  *     n_texels rgba texels, fp32 (VL3D_F32) or fp16 (VL3D_F16), 16-byte aligned; out: n_texels * 4 bytes.
- *   vl3d_render_fwd_baked: frames frame0 .. frame0 + desc->T - 1 of a baked clip (D, T_alloc, Hs, Ws, 4) uint8, read in place.  Per covered
- *     (pixel, plane) the value is the bilinear blend of the four decoded taps u8 / 255 with NO activation behind it, composited front to back
- *     (SURVEY.md 9.3); rgb (T,H,W,3) and alpha (T,H,W) fp32 as vl3d_render_fwd_frames lays them out.  Sample position, hard cut, kept-quad
- *     test, tile-exact quad offset and tap weights are the float forward's own device functions: the two renders agree on every pixel's
- *     coverage.  desc: the planar convention only -- VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, pixel_center, sx / sy / ox / oy, stack_dtype =
- *     VL3D_U8, uv_noise_seed = 0, variant = 0, Hs, Ws >= 2 (act_order / rgb_act / alpha_act are not read: the texels are activated already);
- *     quad_keep NULL = a dense model, else vl3d_render_fwd_frames_culled's map, quad grid (negative: tile-exact layout), desc->cull_* window
- *     and cull_scratch (vl3d_render_cull_scratch_bytes).  Anything else: VL3D_EINVAL, nothing launched.  Forward only. */
+ *   The render, vl3d_render_fwd_baked / vl3d_render_fwd_baked_pool: desc->T output frames.  Per covered (pixel, plane) the value is the
+ *     bilinear blend of the four decoded taps u8 / 255 with NO activation behind it, composited front to back.  Sample
+ *     position, hard cut, kept-quad test, tile-exact quad offset and tap weights are the float forward's own device functions: the two
+ *     renders agree on every pixel's coverage.  desc: the planar convention only -- VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, pixel_center,
+ *     sx / sy / ox / oy, stack_dtype = VL3D_U8, uv_noise_seed = 0, variant = 0, Hs, Ws >= 2 (act_order / rgb_act / alpha_act are not read:
+ *     the texels are activated already).  Anything else, a NULL pointer, a misaligned source: VL3D_EINVAL, nothing launched.  Forward only;
+ *     no host synchronisation.  The two entries differ in the SOURCE; both take the SELECTION and the SINK as the two structs below.
+ *   Source.  vl3d_render_fwd_baked: a baked clip (D, T_alloc, Hs, Ws, 4) uint8, 4-byte aligned, read in place.  quad_keep NULL = a dense
+ *     model, else vl3d_render_fwd_frames_culled's map, quad grid (negative: tile-exact layout), desc->cull_* window and cull_scratch.
+ *     vl3d_render_fwd_baked_pool: the baked POOL of a packed tile-culled model -- the "Packed storage" block table below with RGBA8 texels
+ *     behind it.  blocks [D][ceil(Hs/8)][ceil(Ws/8)] int32: -1 (not stored) | slot << 1 | dynamic; pool: n_slots * 256 bytes, a slot = one
+ *     8 x 8 block of 4-byte texels, row-major; a static block owns one slot, a dynamic block T_model consecutive ones (frame t at slot + t);
+ *     both 4-byte aligned.  A tap in a block without storage reads `culled_rgba8` (r | g << 8 | b << 16 | a << 24).  No desc->cull_* window
+ *     (the pool holds whole planes); quad_keep [D][|QH|][|QW|] and cull_scratch are REQUIRED (the table is built from the map), D <= 128.
+ *     The table is trusted as packed.PackedLayout builds it: every stored slot (+ T_model - 1 for a dynamic block) lies inside the pool.  Per
+ *     covered (pixel, plane): one table entry and one 8-byte load per texel row (two entries and two 4-byte loads where x0 % 8 == 7); static
+ *     blocks are fetched once per frame pair; uncovered pixels fetch nothing.  The output has the bits of vl3d_render_fwd_baked on the
+ *     unpacked texels.
+ *   Selection (vl3d_baked_frames).  A RUN: frames frame0 .. frame0 + desc->T - 1 of the clip's T_alloc (the model's T_model) frames seen by
+ *     one camera, homos (D, 3, 3); frame_cam = frame_t = NULL, n_cams = 0; cull_scratch: vl3d_render_cull_scratch_bytes(desc).  A camera
+ *     PATH: output frame i is camera frame_cam[i] of homos (n_cams, D, 3, 3), 1 <= n_cams <= 65535, showing frame frame_t[i] -- the spiral of
+ *     scripts/script_render_video.py:47-85 -- in ONE plan launch plus ONE render launch; frame0 is not read; cull_scratch:
+ *     vl3d_render_path_cull_scratch_bytes(desc, n_cams), two 64-bit plane masks per (camera, 64 x 8 pixel workgroup).  Frame i of a path holds
+ *     the bits of the run of frame frame_t[i] alone under camera frame_cam[i].  The host side cannot read the indices: the wrapper
+ *     (render.render_path_baked / _pool) range-checks them before it uploads them, and the kernels check them again -- a workgroup whose
+ *     camera or frame is out of range returns before any load or store and its pixels stay unwritten.  VL3D_EINVAL: a struct that is neither
+ *     (one index pointer NULL, or n_cams != 0 without pointers), a run that leaves the clip, T_alloc / T_model < 1, n_cams outside
+ *     [1, 65535], ceil(W/64) * ceil(H/8) * desc->T > 2^31 - 1.
+ *   Sink (vl3d_baked_out), exactly one of two.  FLOAT: rgb (N,H,W,3) and alpha (N,H,W) fp32, N = desc->T, as vl3d_render_fwd_frames lays
+ *     them out; frames = bg = NULL.  DISPLAY: frames (N, H, W, channels) uint8, channels = 3 (RGB8) or 4 (RGBA8, 4-byte aligned), the frame a
+ *     viewer shows, written by the render launch itself (csrc/vl3d_baked_core.h: DisplayOut); rgb = alpha = NULL.  Per pixel, every
+ *     operation rounded on its own (the order of the torch statement it replaces; c, A: the float sink's rgb and alpha):
+ *         bg != NULL:  x_k = c_k * A + bg[k] * ((-A) + 1)      (MPV.py:455-461)          bg == NULL:  x_k = c_k
+ *         byte k = (uint8) trunc(255 * min(max(x_k, 0), 1))    (utils.py to8b);   byte 3 (channels == 4) = trunc(255 * min(max(A, 0), 1)),
+ *                                                               never composited over the background
+ *     bg: a HOST pointer to 3 finite floats, read by the call (it travels in the kernel arguments).  RGB8 rows are stored lane-packed (a
+ *     wave's 192 bytes as 48 dwords) where the 64-pixel row segment is full and 4-byte aligned, as bytes elsewhere; the environment variable
+ *     VL3D_DISPLAY_STORE3=bytes selects byte stores everywhere -- a measurement hook (profiles/baked_fwd.py --legs display), same bytes.
+ *     VL3D_EINVAL: both sinks or neither, a bg with the float sink, channels outside {3, 4}, misaligned RGBA8 frames, a non-finite bg. */
+typedef struct vl3d_baked_frames {
+    int32_t frame0;                        /* a run: its first frame */
+    int32_t n_cams;                        /* a path: the cameras of homos; 0 for a run */
+    const int32_t *frame_cam, *frame_t;    /* a path: device int32[desc->T]; both NULL for a run */
+} vl3d_baked_frames;
+typedef struct vl3d_baked_out {
+    float *rgb, *alpha;                    /* the float sink */
+    uint8_t *frames;                       /* the display sink ... */
+    int32_t channels;
+    const float *bg;                       /* ... its background: host float[3] or NULL */
+} vl3d_baked_out;
 int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stack_dtype, int32_t rgb_act, int32_t alpha_act, uint8_t *out,
                     vl3d_stream_t stream);
-int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                          const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
-                          vl3d_stream_t stream);
-/*   vl3d_render_fwd_baked_pool (csrc/vl3d_render_baked_pool.hip): the same render from the baked POOL of a packed tile-culled model -- the
- *     "Packed storage" block table below with RGBA8 texels behind it -- instead of a dense clip.  blocks [D][ceil(Hs/8)][ceil(Ws/8)] int32:
- *     -1 (not stored) | slot << 1 | dynamic; pool: n_slots * 256 bytes, a slot = one 8 x 8 block of 4-byte texels, row-major; a static block
- *     owns one slot, a dynamic block T_model consecutive ones (frame t at slot + t); 4-byte aligned.  A tap in a block without storage reads
- *     `culled_rgba8` (r | g << 8 | b << 16 | a << 24).  The frames are frame0 .. frame0 + desc->T - 1 of the model's T_model frames: desc->T is
- *     the length of the run, as for vl3d_render_fwd_baked, and T_model -- the count that bounds the run and that the table's dynamic blocks
- *     were laid out for -- is an argument of its own, where the dense entry takes T_alloc.  desc otherwise as for vl3d_render_fwd_baked
- *     (VL3D_U8, VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, uv_noise_seed = 0, variant = 0, Hs, Ws >= 2), no desc->cull_* window (the pool holds
- *     whole planes); quad_keep [D][|QH|][|QW|] is REQUIRED (the table is built from it; negative grid: tile-exact layout), D <= 128,
- *     cull_scratch of vl3d_render_cull_scratch_bytes().  Anything else: VL3D_EINVAL, nothing launched.  The table is trusted as
- *     packed.PackedLayout builds it: every stored slot (+ T_model - 1 for a dynamic block) lies inside the pool.  Per covered (pixel, plane):
- *     one table entry and one 8-byte load per texel row (two entries and two 4-byte loads where x0 % 8 == 7); static blocks are fetched once
- *     per frame pair; uncovered pixels fetch nothing.  rgb / alpha: the bits of vl3d_render_fwd_baked on the unpacked texels. */
-int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0, int32_t T_model,
-                               const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
-                               void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream);
-
-/* Baked playback along a CAMERA PATH (csrc/vl3d_render_baked.hip, csrc/vl3d_render_baked_pool.hip): N = desc->T output frames, each with
- * its own camera and its own frame of the clip -- the spiral of scripts/script_render_video.py:47-85, pose i showing loop frame i % T -- in
- * one plan launch plus one render launch, where the entries above take one camera per call.
- *   homos (n_cams, D, 3, 3): the homographies of the path's distinct cameras, 1 <= n_cams <= 65535.
- *   frame_cam, frame_t: DEVICE int32[N]; output frame i is camera frame_cam[i] showing frame frame_t[i] of the clip (of the model's T_model
- *     frames for the pool).  The host side cannot read them: the wrapper (render.render_path_baked / _pool) checks 0 <= frame_cam[i] <
- *     n_cams and 0 <= frame_t[i] < T_alloc (T_model) before it uploads them, as it checks the frames_dev of vl3d_render_fwd_packed; the
- *     kernels check them again -- a workgroup whose camera or frame is out of range returns before any load or store and its pixels stay
- *     unwritten --, so no index read from device memory forms an address outside the clip, the pool or the masks.
- *   cull_scratch: vl3d_render_path_cull_scratch_bytes(desc, n_cams) bytes -- two 64-bit plane masks per (camera, 64 x 8 pixel workgroup),
- *     [n_cams][ceil(H/8) * ceil(W/64)][2], rebuilt every call by ONE memset and ONE plan launch over (camera, tile, plane).  Required with
- *     quad_keep (always for the pool).
- *   rgb (N,H,W,3), alpha (N,H,W): frame i holds the bits of the one-camera entry called for frame frame_t[i] alone with camera
- *     frame_cam[i]'s homographies (one frame per thread: the one-frame kernels' own text).
- * desc and every refusal are those of vl3d_render_fwd_baked / _pool (same messages, same order); in addition n_cams outside [1, 65535], a
- * NULL index pointer, T_alloc / T_model < 1 and ceil(W/64) * ceil(H/8) * N > 2^31 - 1 return VL3D_EINVAL with nothing launched.  Forward
- * only; no host synchronisation. */
 int64_t vl3d_render_path_cull_scratch_bytes(const vl3d_render_desc *desc, int32_t n_cams);
-int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
-                               const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                               void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream);
-int vl3d_render_fwd_baked_pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
-                                    const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
-                                    const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch, float *rgb,
-                                    float *alpha, vl3d_stream_t stream);
-
-/* Baked playback, DISPLAY output (csrc/vl3d_baked_core.h: DisplayOut): the four baked forwards above with the frame a viewer shows as their
- * output -- frames (N, H, W, channels) uint8, N = desc->T, channels = 3 (RGB8) or 4 (RGBA8) -- written by the render launch itself; no
- * fp32 rgb / alpha exists.  Per pixel, every operation rounded on its own (the order of the torch statement it replaces, so the bytes are
- * those of that statement applied to the float entry's output):
- *     bg != NULL:  x_k = c_k * A + bg[k] * ((-A) + 1)      (MPV.py:455-461; c, A: the float entry's rgb and alpha)
- *     bg == NULL:  x_k = c_k
- *     byte k = (uint8) trunc(255 * min(max(x_k, 0), 1))    (utils.py to8b);   byte 3 (channels == 4) = trunc(255 * min(max(A, 0), 1)),
- *                                                           never composited over the background
- *   bg: a HOST pointer to 3 floats, read by the call (it travels in the kernel arguments), or NULL for no background.
- * Every argument in front of `frames` and every refusal are the float sibling's (same checks, same messages); in addition channels outside
- * {3, 4}, frames NULL, frames not 4-byte aligned for channels == 4 and a non-finite bg component return VL3D_EINVAL with nothing launched.
- * A path frame whose index is out of range keeps its bytes unwritten, as its floats are above.  RGB8 rows are stored lane-packed (a wave's
- * 192 bytes as 48 dwords) where the 64-pixel row segment is full and 4-byte aligned, as bytes elsewhere; the environment variable
- * VL3D_DISPLAY_STORE3=bytes selects byte stores everywhere -- a measurement hook (profiles/baked_fwd.py --legs display), same bytes. */
-int vl3d_render_fwd_baked_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                             const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, uint8_t *frames, int32_t channels,
-                             const float *bg, vl3d_stream_t stream);
-int vl3d_render_fwd_baked_pool_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0, int32_t T_model,
-                                  const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
-                                  void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream);
-int vl3d_render_fwd_baked_path_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
-                                  const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                  void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream);
-int vl3d_render_fwd_baked_pool_path_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
-                                       const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
-                                       const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
-                                       uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream);
+int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                          const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
+                          const vl3d_baked_out *out, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos,
+                               const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
+                               void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream);
 
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).

@@ -43,6 +43,8 @@ def test_struct_layout_matches_header(built):
     assert ctypes.sizeof(built.RenderDesc) == 104
     assert ctypes.sizeof(built.LossDesc) == 96
     assert ctypes.sizeof(built.Stage1ObjectiveDesc) == 64      # 4 x int32 + 12 x float
+    assert ctypes.sizeof(built.BakedFrames) == 24              # 2 x int32 + 2 pointers
+    assert ctypes.sizeof(built.BakedOut) == 40                 # 3 pointers + int32 + pad + pointer
 
 
 def test_cpu_tensor_is_rejected_loudly(built):

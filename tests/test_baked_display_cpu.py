@@ -1,6 +1,6 @@
 """The display output of the baked playback model, off the device: the display rule in torch (videoloop3d_amd/baked.display_frames) against
-numpy statements of the reference's `to8b` and of its background composite, the four `_u8` entry points by name (header, library, binding),
-and how `render_display` launches a selection -- `render_video.path_segments`: a chunk that is one run makes one run call, any other chunk one
+numpy statements of the reference's `to8b` and of its background composite, the two baked render entries with their selection and sink
+structs (header, library, binding) and what they refuse about the two structs, and how `render_display` launches a selection -- `render_video.path_segments`: a chunk that is one run makes one run call, any other chunk one
 path call, each carrying its uint8 slice of the result -- on a stubbed backend.  No GPU."""
 import ctypes
 import os
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U8_ENTRIES = ["vl3d_render_fwd_baked_u8", "vl3d_render_fwd_baked_pool_u8", "vl3d_render_fwd_baked_path_u8", "vl3d_render_fwd_baked_pool_path_u8"]
+ENTRIES = ["vl3d_render_fwd_baked", "vl3d_render_fwd_baked_pool"]
 
 
 # ---- 1. the display rule -------------------------------------------------------------------------------------------------------------------
@@ -79,22 +79,68 @@ def test_display_frames_over_a_background(bg):
 
 
 # ---- 2. the entry points, by name ----------------------------------------------------------------------------------------------------------
-def test_u8_entries_are_declared_exported_and_bound():
+def test_baked_entries_take_selection_and_sink_structs():
     import __graft_entry__ as g
     g.build()
     from videoloop3d_amd import _lib as L
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vl3d.h")).read(), flags=re.S)
     lib = ctypes.CDLL(L.LIB_PATH)
-    for name in U8_ENTRIES:
+    for name in ENTRIES:
         assert re.search(r"\bint\s+" + name + r"\s*\(", header), f"{name} is not declared in include/vl3d.h"
         assert hasattr(lib, name), f"{name} is not exported by the library"
-        sibling = name[:-len("_u8")]
         argtypes, restype = L.SIGNATURES[name]
-        # the sibling's arguments with (float *rgb, float *alpha) replaced by (uint8_t *frames, int32_t channels, const float *bg)
-        sib = L.SIGNATURES[sibling][0]
-        assert restype is ctypes.c_int and argtypes == sib[:-3] + [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p] + sib[-1:]
-        decl = re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1)
-        assert "uint8_t *frames, int32_t channels" in re.sub(r"\s+", " ", decl) and "const float *bg" in decl and "float *rgb" not in decl
+        # (..., const vl3d_baked_out *out, stream), one selection struct in front of the quad map; no positional rgb / alpha / frames
+        assert restype is ctypes.c_int and argtypes[-2] is ctypes.POINTER(L.BakedOut) and argtypes.count(ctypes.POINTER(L.BakedFrames)) == 1
+        decl = re.sub(r"\s+", " ", re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1))
+        assert "const vl3d_baked_frames *sel" in decl and "const vl3d_baked_out *out" in decl
+        assert "float *rgb" not in decl and "uint8_t *frames" not in decl and "frame_cam" not in decl
+    # the sink and the selection are fields: the display frames with their channel count and background, the path's cameras and indices
+    assert [f[0] for f in L.BakedOut._fields_] == ["rgb", "alpha", "frames", "channels", "bg"]
+    assert [f[0] for f in L.BakedFrames._fields_] == ["frame0", "n_cams", "frame_cam", "frame_t"]
+    # the eight entries the two replace are gone from header, library and binding
+    for old in ("_path", "_pool_path", "_u8", "_pool_u8", "_path_u8", "_pool_path_u8"):
+        name = "vl3d_render_fwd_baked" + old
+        assert name not in L.SIGNATURES and not hasattr(lib, name) and not re.search(r"\b" + name + r"\s*\(", header), name
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_selection_and_sink_refusals(entry):
+    """a `sel` that is neither a run nor a path, an `out` that names both sinks or neither, a background with the float sink: VL3D_EINVAL with a
+    message of its own, from either entry.  The refusals come before anything touches a device: the pointers are placeholders nothing reads."""
+    import __graft_entry__ as g
+    g.build()
+    from videoloop3d_amd import _lib as L
+    lib = L.lib()
+    d = L.RenderDesc()
+    d.D, d.T, d.Hs, d.Ws, d.H, d.W = 2, 3, 8, 8, 4, 6
+    d.coord_mode, d.border_mode, d.stack_dtype = L.COORD["affine"], L.BORDER["hardcut"], L.STACK_DTYPE["u8"]
+    p = 64      # a non-null, aligned placeholder
+    bg = (ctypes.c_float * 3)(0.2, 0.4, 0.6)
+    run, fl = L.BakedFrames(frame0=1), L.BakedOut(rgb=p, alpha=p)
+
+    def call(sel, out):
+        if entry == "vl3d_render_fwd_baked":
+            return lib.vl3d_render_fwd_baked(d, p, 5, p, sel, p, 2, 2, p, out, None)
+        return lib.vl3d_render_fwd_baked_pool(d, p, p, 5, p, sel, p, 2, 2, 0, p, out, None)
+
+    def refused(fragment, sel, out):
+        assert call(sel, out) == 1, fragment
+        msg = lib.vl3d_last_error()
+        assert msg.startswith(entry.encode() + b": ") and fragment in msg, msg
+    for sel in (L.BakedFrames(frame_cam=p), L.BakedFrames(frame_t=p), L.BakedFrames(n_cams=2), L.BakedFrames(n_cams=1, frame_cam=p)):
+        refused(b"neither a run", sel, fl)
+    refused(b"both sinks", run, L.BakedOut(rgb=p, alpha=p, frames=p, channels=3))
+    refused(b"both sinks", run, L.BakedOut(alpha=p, frames=p, channels=4))
+    refused(b"null pointer (out", run, L.BakedOut())
+    refused(b"null pointer (out", run, L.BakedOut(rgb=p))
+    refused(b"null pointer (out", run, L.BakedOut(channels=3, bg=ctypes.addressof(bg)))
+    refused(b"background", run, L.BakedOut(rgb=p, alpha=p, bg=ctypes.addressof(bg)))
+    refused(b"null pointer (sel)", None, fl)
+    refused(b"null pointer (out)", run, None)
+    # the refusals a path had before it was a struct keep their text
+    refused(b"n_cams must be in [1, 65535]", L.BakedFrames(n_cams=0, frame_cam=p, frame_t=p), fl)
+    refused(b"n_cams must be in [1, 65535]", L.BakedFrames(n_cams=65536, frame_cam=p, frame_t=p), fl)
+    refused(b"leaves the", L.BakedFrames(frame0=3), fl)      # frames 3 .. 5 of 5
 
 
 # ---- 3. how render_display launches a selection --------------------------------------------------------------------------------------------

@@ -12,13 +12,13 @@ import numpy as np
 import pytest
 import torch
 
+import baked_models as BM
+from baked_models import D, H, HS, QH, QW, T_ALLOC, W, WS
 from videoloop3d_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-D, T_ALLOC, F0, NF = 4, 5, 1, 3
-HS, WS, QH, QW = 40, 72, 5, 9
-H, W = 37, 70
+F0, NF = 1, 3
 # the activation pairs the product's dispatch table lists (csrc/vl3d_render_packed.hip, conv_affine_hardcut_post_*)
 ACT_PAIRS = [("sigmoid", "sigmoid"), ("none", "none"), ("none", "sigmoid"), ("clamp", "sigmoid"), ("relu", "sigmoid"), ("abs", "sigmoid"),
              ("clamp", "clamp"), ("sigmoid", "clamp"), ("none", "clamp")]
@@ -40,20 +40,6 @@ def _homographies():
     return compute_homography(ref_e[None], Kr[None], tar_e[None], Kt[None], torch.tensor([0., 0., 1.]).expand(1, D, 3), depths[None])[0].float()
 
 
-def _specs():
-    """layout -> RenderSpec with identity activations.  The plane pixels of the 37 x 70 view are scaled by (1.06, 1.1) and moved by (-1.0, -0.5)
-    onto the 40 x 72-texel planes: every plane leaves the frame on the left and at the top (the near ones, with ~2 px of parallax, furthest),
-    the far ones on the right and at the bottom as well -- hard-cut edges inside the view on all four sides, at other pixels for every plane."""
-    from videoloop3d_amd.render import RenderSpec
-    sc, off = (1.06, 1.1), (-1.0, -0.5)
-    dense = RenderSpec.mpv(rgb_act="none", alpha_act="none", scale=sc, offset=off)
-    # tile-exact: 5 x 9 tiles of 8 x 8 texels; the lattice a quad spans 7 units of is 36 x 64 points over the same plane extent
-    lat = (63.0 / 71.0, 35.0 / 39.0)
-    exact = dataclasses.replace(RenderSpec.mpv(rgb_act="none", alpha_act="none", scale=(sc[0] * lat[0], sc[1] * lat[1]),
-                                               offset=(off[0] * lat[0], off[1] * lat[1])), tile=(8, 8))
-    return {"dense": dense, "shared": dense, "exact": exact}
-
-
 @pytest.fixture(scope="module")
 def scene(dev):
     """the baked clip (hash-random texels through the bake kernel), the homographies, a quad map with about half of the quads and no quad of
@@ -69,7 +55,7 @@ def scene(dev):
     homos = _homographies().to(dev)
     decoded = baked.float() / 255
     ref = {}
-    for layout, spec in _specs().items():
+    for layout, spec in BM.specs().items():
         qk = None if layout == "dense" else keep
         rgb, alpha = render_frame_run(decoded, F0, NF, homos, H, W, spec, quad_keep=qk)
         ref[layout] = (rgb.clone(), alpha.clone())
@@ -121,7 +107,7 @@ def test_baked_render_matches_the_float_kernels(dev, scene, layout):
     interpolation is then immaterial, and the float kernels are pinned to goldens G2 / G17 / G19.  1e-5 max abs on EVERY pixel, rgb and alpha
     (the forward tolerance of tests/test_gpu_render.py): coverage comes from the same device functions in both renders."""
     from videoloop3d_amd.render import render_frame_run_baked
-    spec = _specs()[layout]
+    spec = BM.specs()[layout]
     qk = None if layout == "dense" else scene.keep
     rgb, alpha = render_frame_run_baked(scene.baked, F0, NF, scene.homos, H, W, spec, quad_keep=qk)
     rgb_f, alpha_f = scene.ref[layout]
@@ -176,7 +162,7 @@ def _fp64_render(baked, homos, spec, frames):
 
 def test_baked_render_matches_a_plain_fp64_statement(dev, scene):
     from videoloop3d_amd.render import render_frame_run_baked
-    spec = _specs()["dense"]
+    spec = BM.specs()["dense"]
     rgb, alpha = render_frame_run_baked(scene.baked, F0, NF, scene.homos, H, W, spec)
     rgb64, a64, inside = _fp64_render(scene.baked, scene.homos, spec, list(range(F0, F0 + NF)))
     assert int(inside.sum()) > H * W // 2
@@ -191,7 +177,7 @@ def test_baked_render_matches_a_plain_fp64_statement(dev, scene):
 def test_determinism_and_guards(dev, scene):
     from videoloop3d_amd import _lib as L
     from videoloop3d_amd.render import RenderSpec, _desc, render_frame_run_baked
-    specs = _specs()
+    specs = BM.specs()
     for layout in ("dense", "exact"):
         qk = None if layout == "dense" else scene.keep
         a = render_frame_run_baked(scene.baked, F0, NF, scene.homos, H, W, specs[layout], quad_keep=qk)
@@ -208,7 +194,8 @@ def test_determinism_and_guards(dev, scene):
         return d
 
     def baked_rc(d):
-        return lib.vl3d_render_fwd_baked(d, L.ptr(scene.baked), F0, T_ALLOC, L.ptr(scene.homos), None, 0, 0, None, L.ptr(rgb), L.ptr(alpha), stream)
+        return lib.vl3d_render_fwd_baked(d, L.ptr(scene.baked), T_ALLOC, L.ptr(scene.homos), BM.run_sel(F0), None, 0, 0, None, BM.float_out(rgb, alpha),
+                                         stream)
     EINVAL = 1
     assert baked_rc(desc(specs["dense"], "u8")) == 0
     # the float entry points refuse baked texels (error returns, before any launch)
@@ -238,35 +225,11 @@ def test_determinism_and_guards(dev, scene):
 
 
 # ---- 5. module level -------------------------------------------------------------------------------------------------------------------
-def _tile_exact_model(dev, bg_color):
-    """a tiny sparsified MPMeshVid in the tile-exact layout: 6 planes, 6 frames, 4 x 6 tiles of 8 x 8 texels per plane, about half of the quads
-    kept (plane 3 none), a third of the kept ones dynamic -- loaded through init_from_mpi like a checkpoint of this package."""
-    from videoloop3d_amd.MPV import MPMeshVid
-    Hm, Wm, Dm, Tm, qh, qw, th, tw = 36, 64, 6, 6, 4, 6, 8, 8
-    K = np.array([[0.9 * Wm, 0, Wm / 2], [0, 0.9 * Wm, Hm / 2], [0, 0, 1]])
-    args = types.SimpleNamespace(mpv_frm_num=Tm, mpv_isloop=True, mpi_h_scale=1.1, mpi_w_scale=1.1, mpi_d=Dm, atlas_grid_h=2, init_std=0.5,
-                                 rgb_mlp_type="direct", rgb_activate="sigmoid", alpha_activate="sigmoid", bg_color=bg_color, scale_invariant=True,
-                                 fp16=False, swd_patch_size=3, swd_patcht_size=3, swd_stride=2, swd_stridet=1, sparsity_loss_weight=0.0,
-                                 rgb_smooth_loss_weight=0.0, a_smooth_loss_weight=0.0, density_loss_weight=0.0, d_smooth_loss_weight=0.0,
-                                 optimizer="adam", lrate=0.1, lrate_decay=30, mpi_h_verts=qh + 1, mpi_w_verts=qw + 1)
-    model = MPMeshVid(args, Hm, Wm, np.eye(4), K, 1.0, 100.0)
-    keep = synth.hash_uniform((Dm, qh, qw), seed=21) < 0.55
-    keep[3] = False
-    dyn = keep & (synth.hash_uniform((Dm, qh, qw), seed=22) < 0.35)
-    stack = synth.make_plane_stack(Dm, Tm, qh * th, qw * tw, seed=5, alpha_bias=0.0) * 0.8
-    model.init_from_mpi({"ref_extrin": model.ref_extrin, "ref_intrin": model.ref_intrin, "planedepth": model.planedepth, "stack": stack,
-                         "quad_keep": keep, "quad_dyn": dyn, "self.is_sparse": True, "self.has_dyn": True, "self.tile_own": (th, tw),
-                         "self.tile_full": (th, tw)})
-    model = model.to(dev).eval()
-    assert model.is_sparse and model.tile_own == (th, tw) and model.spec.tile == (th, tw) and model.stack.shape == (Dm, Tm, qh * th, qw * tw, 4)
-    return model, Hm, Wm, K
-
-
 def test_module_bake_and_render_frames(dev):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd.baked import BakedMPV, bake
     from videoloop3d_amd.render import render_frame_run
-    model, Hm, Wm, K = _tile_exact_model(dev, "0.2#0.4#0.6")
+    model, Hm, Wm, K = BM.tile_exact_model(dev, "0.2#0.4#0.6")
     baked = bake(model)
     assert isinstance(baked, BakedMPV) and baked.texels.dtype == torch.uint8 and baked.texels.shape == model.stack.shape
     assert baked.nbytes * 4 == model.stack.numel() * model.stack.element_size()
@@ -305,7 +268,7 @@ def test_module_bake_and_render_frames(dev):
     model.pack_()
     with pytest.raises(RuntimeError, match="packed"):
         bake(model)
-    cpu_model, _, _, _ = _tile_exact_model(torch.device("cpu"), "")
+    cpu_model, _, _, _ = BM.tile_exact_model(torch.device("cpu"), "")
     with pytest.raises(RuntimeError, match="host"):
         bake(cpu_model)
     cpu_model.atlas_exact = True

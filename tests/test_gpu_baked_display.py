@@ -1,4 +1,4 @@
-"""The display output of the baked playback model on the MI355X (vl3d_render_fwd_baked_u8 / _pool_u8 / _path_u8 / _pool_path_u8; `frames8=` of
+"""The display output of the baked playback model on the MI355X (the display sink of vl3d_render_fwd_baked / _pool: vl3d_baked_out.frames; `frames8=` of
 render.render_frame_run_baked / _pool, render_path_baked / _pool; BakedMPV / BakedPool.render_display; render_frames(baked=)): the render
 launches store the uint8 frame a viewer shows.  The yardstick in every case is the existing FLOAT entry followed by baked.display_frames -- the
 torch statement the kernels' store replaces -- and the comparison is torch.equal on every byte, no pixel excluded.
@@ -15,20 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+import baked_models as BM
 from videoloop3d_amd import synth
-
-
-def _helpers(name):
-    """the tiny models of a sibling test file, executed as a private copy (not as the test module pytest collects)"""
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location("_baked_display_" + name, os.path.join(os.path.dirname(os.path.abspath(__file__)), name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-TB, TP = _helpers("test_gpu_baked"), _helpers("test_gpu_baked_pool")
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +91,7 @@ def models(dev):
             lay = PackedLayout(keep.to(dev), dyn.to(dev), T_CLIP, g["Hs"], g["Ws"], g["tile"])
             e = lay.blocks
             assert int((e < 0).sum()) > 0 and int(((e >= 0) & ((e & 1) == 0)).sum()) > 0 and int(((e >= 0) & ((e & 1) == 1)).sum()) > 0
-            pool = TP._scatter_pool(lay, clip, torch.zeros((1, 4), dtype=torch.uint8, device=dev))
+            pool = BM.scatter_pool(lay, clip, torch.zeros((1, 4), dtype=torch.uint8, device=dev))
             kw = dict(quad_keep=qk, culled_rgba8=0)      # sigmoid(CULLED_ALPHA) bakes to alpha 0
             m.lay, m.pool = lay, pool
             m.run = lambda t0, n, homos, H, W, spec, kw=kw, lay=lay, pool=pool, **o: R.render_frame_run_baked_pool(lay, pool, t0, n, homos, H, W, spec, **kw, **o)
@@ -165,7 +153,7 @@ def test_path_stores_the_display_bytes(dev, models, layout, size, monkeypatch):
                 monkeypatch.setenv("VL3D_DISPLAY_STORE3", store)
                 got = m.path(CAM, TS, homos, H, W, spec, frames8=_frames8(N, H, W, C, dev), bg=bg)
                 assert torch.equal(got, want), (layout, size, bg, C, store, int((got != want).sum()))
-            # ... and equal to the _u8 RUN call of each frame alone
+            # ... and equal to the display RUN call of each frame alone
             for i in range(N):
                 one = m.run(TS[i], 1, homos[CAM[i]], H, W, spec, frames8=_frames8(1, H, W, C, dev), bg=bg)
                 assert torch.equal(one[0], got[i]), (layout, size, bg, C, i)
@@ -191,12 +179,12 @@ def test_out_of_range_path_frames_are_left_unwritten(dev, models, layout):
     buf = _frames8(N, H, W, 3, dev)
     bgc = (L.C.c_float * 3)(*bg)
     grid = R._qgrid(m.qk, spec)
+    sel, sink = BM.path_sel(3, idx), BM.display_out(buf, 3, bgc)
     if layout == "pool":
-        rc = lib.vl3d_render_fwd_baked_pool_path_u8(d, L.ptr(m.lay.blocks), L.ptr(m.pool), T_CLIP, L.ptr(homos), 3, L.ptr(idx[0]), L.ptr(idx[1]),
-                                                    L.ptr(m.qk), *grid, 0, L.ptr(cull), L.ptr(buf), 3, bgc, stream)
+        rc = lib.vl3d_render_fwd_baked_pool(d, L.ptr(m.lay.blocks), L.ptr(m.pool), T_CLIP, L.ptr(homos), sel, L.ptr(m.qk), *grid, 0, L.ptr(cull), sink,
+                                            stream)
     else:
-        rc = lib.vl3d_render_fwd_baked_path_u8(d, L.ptr(m.clip), T_CLIP, L.ptr(homos), 3, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(m.qk), *grid,
-                                               L.ptr(cull), L.ptr(buf), 3, bgc, stream)
+        rc = lib.vl3d_render_fwd_baked(d, L.ptr(m.clip), T_CLIP, L.ptr(homos), sel, L.ptr(m.qk), *grid, L.ptr(cull), sink, stream)
     assert rc == 0, lib.vl3d_last_error()
     torch.cuda.synchronize()
     for i in range(N):
@@ -208,7 +196,8 @@ def test_out_of_range_path_frames_are_left_unwritten(dev, models, layout):
 
 # ---- 4. render_frames(baked=) --------------------------------------------------------------------------------------------------------------
 class _CountingLib:
-    """the loaded library with every call's symbol recorded"""
+    """the loaded library with every call's symbol recorded -- and, for the two baked render entries, the sink the call names: (symbol,
+    out.frames set, out.rgb or out.alpha set)"""
 
     def __init__(self, lib, calls):
         self._lib, self._calls = lib, calls
@@ -217,7 +206,11 @@ class _CountingLib:
         fn = getattr(self._lib, name)
 
         def counted(*a):
-            self._calls.append(name)
+            if name in ("vl3d_render_fwd_baked", "vl3d_render_fwd_baked_pool"):
+                sink = a[-2]      # (..., const vl3d_baked_out *out, stream)
+                self._calls.append((name, bool(sink.frames), bool(sink.rgb) or bool(sink.alpha)))
+            else:
+                self._calls.append((name,))
             return fn(*a)
         return counted
 
@@ -228,10 +221,10 @@ def test_render_frames_writes_display_frames_directly(dev, kind, monkeypatch):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd.baked import bake, bake_pool, display_frames
     if kind == "mpv":
-        model, Hm, Wm, K = TB._tile_exact_model(dev, "0.2#0.4#0.6")
+        model, Hm, Wm, K = BM.tile_exact_model(dev, "0.2#0.4#0.6")
         baked = bake(model)
     else:
-        model, Hm, Wm, K = TP._model(dev, "0.2#0.4#0.6", True)
+        model, Hm, Wm, K = BM.pool_model(dev, "0.2#0.4#0.6", True)
         baked = bake_pool(model)
     Tm, n = baked.frm_num, 7
     ext = np.tile(np.eye(4, dtype=np.float32)[None], (n, 1, 1))
@@ -254,9 +247,10 @@ def test_render_frames_writes_display_frames_directly(dev, kind, monkeypatch):
             frames = RV.render_frames(model, Hm, Wm, e, k, t, max_batch=max_batch, baked=baked)
             assert frames.dtype == torch.uint8 and frames.shape == (len(t), Hm, Wm, 3)
             assert torch.equal(frames, ref), (name, max_batch, int((frames != ref).sum()))
-            renders = [c for c in calls if c.startswith("vl3d_render_fwd")]
+            renders = [c for c in calls if c[0].startswith("vl3d_render_fwd")]
             print(f"[{kind}] {name}, chunks of {max_batch}: {renders}")
-            assert len(renders) >= 1 and all(c.endswith("_u8") for c in renders)      # no float render entry on this route
+            # no float render on this route: every render call is a baked entry whose sink is out.frames, out.rgb and out.alpha NULL
+            assert len(renders) >= 1 and all(len(c) == 3 and c[1] and not c[2] for c in renders)
     assert float(want.float().std()) > 1.0
     # render_display: RGBA8 and a caller's buffer
     rgba = baked.render_display(Hm, Wm, ext, intr, rt, channels=4)
@@ -307,50 +301,43 @@ def test_refusals(dev, models):
             m.run(F0, n, homos[0], H, W, spec, frames8=buf3.float())
         with pytest.raises(RuntimeError, match="frames8"):
             m.run(F0, n - 1, homos[0], H, W, spec, frames8=buf3)
-        # the C entries: channels, a null frames pointer, and the quad grids their siblings refuse, with the siblings' own messages
+        # the C entries: channels, a null frames pointer, and the quad grids the float sink refuses, with the float sink's own messages
         g = m.g
         d = R._desc_dims(D, n, g["Hs"], g["Ws"], H, W, spec, L.STACK_DTYPE["u8"])
         QH, QW = R._qgrid(m.qk, spec)
         cull = torch.zeros(int(lib.vl3d_render_path_cull_scratch_bytes(d, 3)) // 8, dtype=torch.int64, device=dev)
         idx = torch.tensor([CAM[:n], TS[:n]], dtype=torch.int32).to(dev)
         rgb, alpha = torch.full((n, H, W, 3), 123.0, device=dev), torch.full((n, H, W), 123.0, device=dev)
-        fl, u8 = (L.ptr(rgb), L.ptr(alpha)), (L.ptr(buf3), 3, None)
         hom, qk, sc = L.ptr(homos), L.ptr(m.qk), L.ptr(cull)
+        sels = {"run": BM.run_sel(F0), "path": BM.path_sel(3, idx)}
+        sinks = {"float": BM.float_out(rgb, alpha), "display": BM.display_out(buf3, 3)}
         if layout == "pool":
             bl, po = L.ptr(m.lay.blocks), L.ptr(m.pool)
-            entries = {
-                "vl3d_render_fwd_baked_pool": lambda qh, qw, o: lib.vl3d_render_fwd_baked_pool(d, bl, po, F0, T_CLIP, hom, qk, qh, qw, 0, sc, *o, stream),
-                "vl3d_render_fwd_baked_pool_u8": lambda qh, qw, o: lib.vl3d_render_fwd_baked_pool_u8(d, bl, po, F0, T_CLIP, hom, qk, qh, qw, 0, sc, *o, stream),
-                "vl3d_render_fwd_baked_pool_path": lambda qh, qw, o: lib.vl3d_render_fwd_baked_pool_path(d, bl, po, T_CLIP, hom, 3, L.ptr(idx[0]), L.ptr(idx[1]),
-                                                                                                       qk, qh, qw, 0, sc, *o, stream),
-                "vl3d_render_fwd_baked_pool_path_u8": lambda qh, qw, o: lib.vl3d_render_fwd_baked_pool_path_u8(d, bl, po, T_CLIP, hom, 3, L.ptr(idx[0]),
-                                                                                                             L.ptr(idx[1]), qk, qh, qw, 0, sc, *o, stream)}
+
+            def call(sel, qh, qw, sink):
+                return lib.vl3d_render_fwd_baked_pool(d, bl, po, T_CLIP, hom, sel, qk, qh, qw, 0, sc, sink, stream)
         else:
             cl = L.ptr(m.clip)
-            entries = {
-                "vl3d_render_fwd_baked": lambda qh, qw, o: lib.vl3d_render_fwd_baked(d, cl, F0, T_CLIP, hom, qk, qh, qw, sc, *o, stream),
-                "vl3d_render_fwd_baked_u8": lambda qh, qw, o: lib.vl3d_render_fwd_baked_u8(d, cl, F0, T_CLIP, hom, qk, qh, qw, sc, *o, stream),
-                "vl3d_render_fwd_baked_path": lambda qh, qw, o: lib.vl3d_render_fwd_baked_path(d, cl, T_CLIP, hom, 3, L.ptr(idx[0]), L.ptr(idx[1]), qk, qh, qw,
-                                                                                             sc, *o, stream),
-                "vl3d_render_fwd_baked_path_u8": lambda qh, qw, o: lib.vl3d_render_fwd_baked_path_u8(d, cl, T_CLIP, hom, 3, L.ptr(idx[0]), L.ptr(idx[1]), qk,
-                                                                                                   qh, qw, sc, *o, stream)}
+
+            def call(sel, qh, qw, sink):
+                return lib.vl3d_render_fwd_baked(d, cl, T_CLIP, hom, sel, qk, qh, qw, sc, sink, stream)
+        # (source: this layout's entry) x (selection) x (sink): all eight combinations over the two layouts
         bad = [(abs(QH), -abs(QW)), (0, abs(QW)), (-4, -7), (-g["Hs"], -g["Ws"])]
-        for name, call in entries.items():
-            if not name.endswith("_u8"):
-                continue
-            for qh, qw in bad:
-                assert entries[name[:-3]](qh, qw, fl) == EINVAL, (name, qh, qw)
+        for sname, sel in sels.items():
+            for qh, qw in bad:      # the display-sink call refuses with the float-sink call's exact message
+                assert call(sel, qh, qw, sinks["float"]) == EINVAL, (layout, sname, qh, qw)
                 theirs = lib.vl3d_last_error()
-                assert call(qh, qw, u8) == EINVAL, (name, qh, qw)
-                assert lib.vl3d_last_error() == theirs and b"bad quad grid" in theirs, (name, theirs)
+                assert call(sel, qh, qw, sinks["display"]) == EINVAL, (layout, sname, qh, qw)
+                assert lib.vl3d_last_error() == theirs and b"bad quad grid" in theirs, (layout, sname, theirs)
             for C in (0, 2, 5):
-                assert call(QH, QW, (L.ptr(buf3), C, None)) == EINVAL and b"channels" in lib.vl3d_last_error()
-            assert call(QH, QW, (None, 3, None)) == EINVAL and b"null pointer" in lib.vl3d_last_error()
+                assert call(sel, QH, QW, BM.display_out(buf3, C)) == EINVAL and b"channels" in lib.vl3d_last_error()
+            assert call(sel, QH, QW, BM.display_out(None, 3)) == EINVAL and b"null pointer" in lib.vl3d_last_error()
         torch.cuda.synchronize()
         assert bool((buf3 == SENT).all()) and bool((buf4 == SENT).all()) and bool((raw == SENT).all())      # nothing was launched
         assert bool((rgb == 123.0).all()) and bool((alpha == 123.0).all())
-        for name, call in entries.items():
-            assert call(QH, QW, u8 if name.endswith("_u8") else fl) == 0, (name, lib.vl3d_last_error())
+        for sname, sel in sels.items():
+            for kname, sink in sinks.items():
+                assert call(sel, QH, QW, sink) == 0, (layout, sname, kname, lib.vl3d_last_error())
         torch.cuda.synchronize()
     # a random background is a draw per call: the display frames refuse it and point at render
     mpv = BakedMPV(models["shared"].clip, models["shared"].qk, _spec(GEOM["shared"], W), "random", None)

@@ -1,5 +1,5 @@
-"""The baked playback model along a camera path on the MI355X (render.render_path_baked / render_path_baked_pool; vl3d_render_fwd_baked_path /
-_pool_path): N output frames, each with its own camera and its own frame of the clip, in one plan launch plus one render launch.  The
+"""The baked playback model along a camera path on the MI355X (render.render_path_baked / render_path_baked_pool; the path selection
+of vl3d_render_fwd_baked / _pool): N output frames, each with its own camera and its own frame of the clip, in one plan launch plus one render launch.  The
 one-camera one-frame kernels (pinned by tests/test_gpu_baked.py and tests/test_gpu_baked_pool.py) are the oracle and the comparison is EXACT:
 a frame has the same bits alone, in an even run and in an odd run (the composite is spelt out with contraction off), so every path frame must
 be torch.equal to render_frame_run_baked(baked, t_i, 1, homos[cam_i], ...) -- no tolerance.
@@ -14,24 +14,12 @@ import numpy as np
 import pytest
 import torch
 
+import baked_models as BM
 from videoloop3d_amd import synth
-
-
-def _helpers(name):
-    """the shapes, specs and tiny models of a sibling test file, executed as a private copy (not as the test module pytest collects)"""
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location("_baked_path_" + name, os.path.join(os.path.dirname(os.path.abspath(__file__)), name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-TB, TP = _helpers("test_gpu_baked"), _helpers("test_gpu_baked_pool")
 
 pytestmark = pytest.mark.gpu
 
-D, T, H, W = TB.D, TB.T_ALLOC, TB.H, TB.W
+D, T, H, W = BM.D, BM.T_ALLOC, BM.H, BM.W
 PATH = [(0, 1), (1, 1), (2, 4), (0, 0), (1, 3), (1, 4), (2, 2)]
 CAM = [c for c, _ in PATH]
 TS = [t for _, t in PATH]
@@ -78,17 +66,17 @@ def scene(dev):
     the reference, computed once and never modified."""
     from videoloop3d_amd.baked import bake_texels
     from videoloop3d_amd.render import render_frame_run_baked
-    baked = bake_texels(synth.make_plane_stack(D, T, TB.HS, TB.WS, seed=7, device=dev, alpha_bias=-0.5), "sigmoid", "sigmoid")
-    keep = synth.hash_uniform((D, TB.QH, TB.QW), seed=11) < 0.5
+    baked = bake_texels(synth.make_plane_stack(D, T, BM.HS, BM.WS, seed=7, device=dev, alpha_bias=-0.5), "sigmoid", "sigmoid")
+    keep = synth.hash_uniform((D, BM.QH, BM.QW), seed=11) < 0.5
     keep[2] = False
     keep = keep.to(torch.uint8).to(dev)
-    sparse = torch.zeros((D, TB.QH, TB.QW), dtype=torch.uint8)      # plane d keeps only quad column 2 d + 1, plane 2 nothing
+    sparse = torch.zeros((D, BM.QH, BM.QW), dtype=torch.uint8)      # plane d keeps only quad column 2 d + 1, plane 2 nothing
     for d in range(D):
         if d != 2:
             sparse[d, :, 2 * d + 1] = 1
     sparse = sparse.to(dev)
     homos = _homographies().to(dev)
-    specs = TB._specs()
+    specs = BM.specs()
 
     def singles(layout, qk):
         return [tuple(x.clone() for x in render_frame_run_baked(baked, TS[i], 1, homos[CAM[i]], H, W, specs[layout], quad_keep=qk)) for i in range(N)]
@@ -121,22 +109,22 @@ def test_path_frames_equal_their_single_frame_renders(dev, scene, layout):
 
 
 # ---- 2. the pool ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("geom", list(TP.GEOMS))
+@pytest.mark.parametrize("geom", list(BM.GEOMS))
 def test_pool_path_frames_equal_their_single_frame_renders(dev, scene, geom):
     """the pool of tests/test_gpu_baked_pool.py (hash-random texels behind the block table, static / dynamic / unstored blocks), both tile layouts"""
     from videoloop3d_amd.baked import BakedMPV, BakedPool, bake_texels
     from videoloop3d_amd.packed import PackedLayout
     from videoloop3d_amd.render import render_frame_run_baked_pool, render_path_baked_pool
-    g = TP.GEOMS[geom]
+    g = BM.GEOMS[geom]
     keep = synth.hash_uniform((D, g["QH"], g["QW"]), seed=11) < 0.5
     keep[2] = False
     dyn = keep & (synth.hash_uniform((D, g["QH"], g["QW"]), seed=12) < 1.0 / 3.0)
-    lay = PackedLayout(keep.to(dev), dyn.to(dev), TP.T_MODEL, g["Hs"], g["Ws"], g["tile"])
+    lay = PackedLayout(keep.to(dev), dyn.to(dev), BM.T_MODEL, g["Hs"], g["Ws"], g["tile"])
     e = lay.blocks
     assert int((e < 0).sum()) > 0 and int(((e >= 0) & ((e & 1) == 0)).sum()) > 0 and int(((e >= 0) & ((e & 1) == 1)).sum()) > 0
-    clip = bake_texels(synth.make_plane_stack(D, TP.T_MODEL, g["Hs"], g["Ws"], seed=7, device=dev, alpha_bias=-0.5), "sigmoid", "sigmoid")
-    pool = TP._scatter_pool(lay, clip, torch.zeros((1, 4), dtype=torch.uint8, device=dev))
-    spec, qk, culled = TP._spec(g), keep.to(torch.uint8).to(dev), 7 | 11 << 8 | 13 << 16 | 0 << 24
+    clip = bake_texels(synth.make_plane_stack(D, BM.T_MODEL, g["Hs"], g["Ws"], seed=7, device=dev, alpha_bias=-0.5), "sigmoid", "sigmoid")
+    pool = BM.scatter_pool(lay, clip, torch.zeros((1, 4), dtype=torch.uint8, device=dev))
+    spec, qk, culled = BM.pool_spec(g), keep.to(torch.uint8).to(dev), 7 | 11 << 8 | 13 << 16 | 0 << 24
     out = render_path_baked_pool(lay, pool, CAM, TS, scene.homos, H, W, spec, quad_keep=qk, culled_rgba8=culled)
     _assert_bit_equal(out, lambda i: render_frame_run_baked_pool(lay, pool, TS[i], 1, scene.homos[CAM[i]], H, W, spec, quad_keep=qk, culled_rgba8=culled))
     covered = float((out[1] > 0).float().mean())
@@ -149,7 +137,7 @@ def test_pool_path_frames_equal_their_single_frame_renders(dev, scene, geom):
     intr = torch.eye(3)[None].repeat(N, 1, 1)
     intr[:, 0, 0] = torch.tensor(CAM, dtype=torch.float32)      # (the stand-in camera reads its index here)
     bp = BakedPool(pool, lay, qk, spec, "0.2#0.4#0.6", cam, culled)
-    bm = BakedMPV(bp.unpack_frames(range(TP.T_MODEL)), qk, spec, "0.2#0.4#0.6", cam)
+    bm = BakedMPV(bp.unpack_frames(range(BM.T_MODEL)), qk, spec, "0.2#0.4#0.6", cam)
     rp, ap = bp.render_path(H, W, ext, intr, TS)
     rm, am = bm.render_path(H, W, ext, intr, TS)
     assert rp.shape == (N, 3, H, W) and ap.shape == (N, H, W)
@@ -168,7 +156,7 @@ def test_the_plan_is_per_camera(dev, scene, layout):
     from videoloop3d_amd import _lib as L
     from videoloop3d_amd.render import _desc_dims, render_path_baked
     spec = scene.specs[layout]
-    need = int(L.lib().vl3d_render_path_cull_scratch_bytes(_desc_dims(D, N, TB.HS, TB.WS, H, W, spec, L.STACK_DTYPE["u8"]), 3))
+    need = int(L.lib().vl3d_render_path_cull_scratch_bytes(_desc_dims(D, N, BM.HS, BM.WS, H, W, spec, L.STACK_DTYPE["u8"]), 3))
     assert need == 3 * TILES * 16
     scratch = torch.full((need // 8 + 3,), -1, dtype=torch.int64, device=dev)
     out = render_path_baked(scene.baked, CAM, TS, scene.homos, H, W, spec, quad_keep=scene.sparse, cull_scratch=scratch)
@@ -228,20 +216,20 @@ def test_refusals(dev, scene):
     with pytest.raises(RuntimeError, match="uint8"):
         call(baked=scene.baked.float())
     # the pool wrapper shares the index and scratch checks
-    g = TP.GEOMS["shared"]
+    g = BM.GEOMS["shared"]
     from videoloop3d_amd.packed import PackedLayout
     keep = synth.hash_uniform((D, g["QH"], g["QW"]), seed=11) < 0.5
-    lay = PackedLayout(keep.to(dev), torch.zeros_like(keep).to(dev), TP.T_MODEL, g["Hs"], g["Ws"], g["tile"])
+    lay = PackedLayout(keep.to(dev), torch.zeros_like(keep).to(dev), BM.T_MODEL, g["Hs"], g["Ws"], g["tile"])
     pool = torch.zeros((lay.n_slots * 64, 4), dtype=torch.uint8, device=dev)
     kw = dict(out=buf, quad_keep=keep.to(torch.uint8).to(dev), culled_rgba8=0)
     with pytest.raises(IndexError, match="frame index"):
-        render_path_baked_pool(lay, pool, CAM, TS[:-1] + [TP.T_MODEL], scene.homos, H, W, TP._spec(g), **kw)
+        render_path_baked_pool(lay, pool, CAM, TS[:-1] + [BM.T_MODEL], scene.homos, H, W, BM.pool_spec(g), **kw)
     with pytest.raises(IndexError, match="camera index"):
-        render_path_baked_pool(lay, pool, CAM[:-1] + [3], TS, scene.homos, H, W, TP._spec(g), **kw)
+        render_path_baked_pool(lay, pool, CAM[:-1] + [3], TS, scene.homos, H, W, BM.pool_spec(g), **kw)
     with pytest.raises(RuntimeError, match="cull_scratch"):
-        render_path_baked_pool(lay, pool, CAM, TS, scene.homos, H, W, TP._spec(g), cull_scratch=torch.zeros(1, dtype=torch.int64, device=dev), **kw)
+        render_path_baked_pool(lay, pool, CAM, TS, scene.homos, H, W, BM.pool_spec(g), cull_scratch=torch.zeros(1, dtype=torch.int64, device=dev), **kw)
     with pytest.raises(RuntimeError, match="quad map"):
-        render_path_baked_pool(lay, pool, CAM, TS, scene.homos, H, W, TP._spec(g), out=buf, quad_keep=None, culled_rgba8=0)
+        render_path_baked_pool(lay, pool, CAM, TS, scene.homos, H, W, BM.pool_spec(g), out=buf, quad_keep=None, culled_rgba8=0)
     torch.cuda.synchronize()
     assert bool((buf[0] == SENT).all()) and bool((buf[1] == SENT).all())      # nothing was launched
 
@@ -255,10 +243,10 @@ def test_render_frames_takes_the_path_render(dev, kind, monkeypatch):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd.baked import bake, bake_pool
     if kind == "mpv":
-        model, Hm, Wm, K = TB._tile_exact_model(dev, "0.2#0.4#0.6")
+        model, Hm, Wm, K = BM.tile_exact_model(dev, "0.2#0.4#0.6")
         baked, name = bake(model), "render_path_baked"
     else:
-        model, Hm, Wm, K = TP._model(dev, "0.2#0.4#0.6", True)
+        model, Hm, Wm, K = BM.pool_model(dev, "0.2#0.4#0.6", True)
         baked, name = bake_pool(model), "render_path_baked_pool"
     Tm = baked.frm_num
     n = 7

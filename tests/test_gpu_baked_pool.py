@@ -15,16 +15,13 @@ import numpy as np
 import pytest
 import torch
 
+import baked_models as BM
+from baked_models import GEOMS, D, H, T_MODEL, W
 from videoloop3d_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-D, T_MODEL = 4, 5
 RUNS = [(1, 3), (3, 1), (1, 2)]      # (frame0, n): the odd run, a single frame, the even run
-H, W = 37, 70
-SC, OFF = (1.06, 1.1), (-1.0, -0.5)      # plane pixel -> texel of a 40 x 72 plane (tests/test_gpu_baked.py)
-GEOMS = {"shared": dict(Hs=40, Ws=72, QH=5, QW=9, tile=None),
-         "exact": dict(Hs=30, Ws=70, QH=5, QW=7, tile=(6, 10))}
 
 
 @pytest.fixture(scope="module")
@@ -41,18 +38,6 @@ def _homographies():
     ref_e, Kr, tar_e, Kt = synth.make_cameras(H, W)
     depths = make_depths(D, 1.0, 100.0).flip(0)
     return compute_homography(ref_e[None], Kr[None], tar_e[None], Kt[None], torch.tensor([0., 0., 1.]).expand(1, D, 3), depths[None])[0].float()
-
-
-def _spec(g):
-    """the RenderSpec of a geometry: (a) texel coordinates of the 40 x 72 plane; (b) LATTICE coordinates -- a tile of th x tw texels spans
-    (th - 1) x (tw - 1) lattice units, so the 5 x 7 tiles of 6 x 10 are 26 x 64 lattice points over the same plane extent."""
-    from videoloop3d_amd.render import RenderSpec
-    if g["tile"] is None:
-        return RenderSpec.mpv(rgb_act="none", alpha_act="none", scale=SC, offset=OFF)
-    th, tw = g["tile"]
-    lat = ((g["QW"] * (tw - 1)) / 71.0, (g["QH"] * (th - 1)) / 39.0)
-    return dataclasses.replace(RenderSpec.mpv(rgb_act="none", alpha_act="none", scale=(SC[0] * lat[0], SC[1] * lat[1]),
-                                              offset=(OFF[0] * lat[0], OFF[1] * lat[1])), tile=(th, tw))
 
 
 def _base_taps(g, spec, homos, keep):
@@ -79,14 +64,6 @@ def _base_taps(g, spec, homos, keep):
     return torch.stack(cov), torch.stack(x0s)
 
 
-def _scatter_pool(lay, clip, fill):
-    """dense uint8 clip [D,T,Hs,Ws,4] -> pool [n_slots * 64, 4] through the block table (static blocks take frame 0), plain torch."""
-    pool = fill.repeat(lay.n_slots * 64, 1)
-    for d in range(lay.D):
-        lay.pack_plane_(pool, d, clip[d])
-    return pool
-
-
 @pytest.fixture(scope="module")
 def scenes(dev):
     """per geometry: the BakedPool of hash-random texels, its dense unpacking, and the DENSE baked kernel's render of that clip for the three
@@ -106,8 +83,8 @@ def scenes(dev):
         # the case cannot become trivial silently: static, dynamic and unstored blocks are all there
         assert int((e < 0).sum()) > 0 and int(((e >= 0) & ((e & 1) == 0)).sum()) > 0 and int(((e >= 0) & ((e & 1) == 1)).sum()) > 0
         clip = bake_texels(synth.make_plane_stack(D, T_MODEL, g["Hs"], g["Ws"], seed=7, device=dev, alpha_bias=-0.5), "sigmoid", "sigmoid")
-        pool = _scatter_pool(lay, clip, torch.zeros((1, 4), dtype=torch.uint8, device=dev))
-        spec = _spec(g)
+        pool = BM.scatter_pool(lay, clip, torch.zeros((1, 4), dtype=torch.uint8, device=dev))
+        spec = BM.pool_spec(g)
         qk = keep.to(torch.uint8).to(dev)
         bp = BakedPool(pool, lay, qk, spec, "", None, 7 | 11 << 8 | 13 << 16 | 0 << 24)      # (a culled texel with colour: it must never show)
         dense = bp.unpack_frames(range(T_MODEL))
@@ -148,42 +125,6 @@ def test_pool_render_equals_the_dense_baked_render(dev, scenes, geom):
 
 
 # ---- 2. pool contents, 3. module level ---------------------------------------------------------------------------------------------------
-def _model(dev, bg_color, exact=True):
-    """a tiny sparsified MPMeshVid, loaded through init_from_mpi like a checkpoint of this package: 6 planes, 6 frames, about half of the quads
-    kept (plane 3 none), a third of the kept ones dynamic.  exact: the tile-exact layout, 4 x 6 tiles of 8 x 8 texels (_tile_exact_model of
-    tests/test_gpu_baked.py); else the shared-border lattice on planes of 38 x 67 texels (ragged last blocks).  Texels no dynamic quad reads
-    hold frame 0 in every frame -- the dense model's convention for static texels -- and texels no kept quad reads hold (0, 0, 0,
-    tiles.CULLED_ALPHA), what PackedLayout.unpack_plane gives for them and BakedPool.culled_rgba8 bakes (the condition under which the pool and
-    bake() of the dense model hold the same texels everywhere a sample can tap: docs/kernels/K9_baked_playback.md, "Culled texels")."""
-    from videoloop3d_amd import tiles
-    from videoloop3d_amd.MPV import MPMeshVid
-    Hm, Wm, Dm, Tm, qh, qw, th, tw = 36, 64, 6, 6, 4, 6, 8, 8
-    hs, ws = (qh * th, qw * tw) if exact else (38, 67)
-    K = np.array([[0.9 * Wm, 0, Wm / 2], [0, 0.9 * Wm, Hm / 2], [0, 0, 1]])
-    args = types.SimpleNamespace(mpv_frm_num=Tm, mpv_isloop=True, mpi_h_scale=1.1, mpi_w_scale=1.1, mpi_d=Dm, atlas_grid_h=2, init_std=0.5,
-                                 rgb_mlp_type="direct", rgb_activate="sigmoid", alpha_activate="sigmoid", bg_color=bg_color, scale_invariant=True,
-                                 fp16=False, swd_patch_size=3, swd_patcht_size=3, swd_stride=2, swd_stridet=1, sparsity_loss_weight=0.0,
-                                 rgb_smooth_loss_weight=0.0, a_smooth_loss_weight=0.0, density_loss_weight=0.0, d_smooth_loss_weight=0.0,
-                                 optimizer="adam", lrate=0.1, lrate_decay=30, mpi_h_verts=qh + 1, mpi_w_verts=qw + 1)
-    model = MPMeshVid(args, Hm, Wm, np.eye(4), K, 1.0, 100.0)
-    keep = synth.hash_uniform((Dm, qh, qw), seed=21) < 0.55
-    keep[3] = False
-    dyn = keep & (synth.hash_uniform((Dm, qh, qw), seed=22) < 0.35)
-    stack = synth.make_plane_stack(Dm, Tm, hs, ws, seed=5, alpha_bias=0.0) * 0.8
-    dyn_t = tiles.quad_to_texel_mask(dyn, hs, ws, (th, tw) if exact else None)
-    stack = torch.where(dyn_t[:, None, :, :, None], stack, stack[:, :1])
-    keep_t = tiles.quad_to_texel_mask(keep, hs, ws, (th, tw) if exact else None)
-    stack = torch.where(keep_t[:, None, :, :, None], stack, torch.tensor([0.0, 0.0, 0.0, tiles.CULLED_ALPHA]))
-    sd = {"ref_extrin": model.ref_extrin, "ref_intrin": model.ref_intrin, "planedepth": model.planedepth, "stack": stack,
-          "quad_keep": keep, "quad_dyn": dyn, "self.is_sparse": True, "self.has_dyn": True}
-    if exact:
-        sd.update({"self.tile_own": (th, tw), "self.tile_full": (th, tw)})
-    model.init_from_mpi(sd)
-    model = model.to(dev).eval()
-    assert model.is_sparse and model.stack.shape == (Dm, Tm, hs, ws, 4) and (model.tile_own == (th, tw)) == exact
-    return model, Hm, Wm, K
-
-
 def _cameras(K):
     """three cameras (world-to-camera) over five output frames: a run of three on the first, then single frames (tests/test_gpu_baked.py)."""
     ext = np.tile(np.eye(4, dtype=np.float32)[None], (5, 1, 1))
@@ -195,7 +136,7 @@ def _cameras(K):
 @pytest.mark.parametrize("exact", [True, False], ids=["exact", "lattice"])
 def test_pool_contents(dev, exact):
     from videoloop3d_amd.baked import BakedPool, bake, bake_pool, bake_texels
-    model, _, _, _ = _model(dev, "", exact)
+    model, _, _, _ = BM.pool_model(dev, "", exact)
     dense_bake = bake(model)
     from_dense = bake_pool(model)                       # the unpacked sparsified model: plane by plane through the table
     assert isinstance(from_dense, BakedPool) and from_dense.pool.dtype == torch.uint8 and from_dense.pool.is_cuda
@@ -225,7 +166,7 @@ def test_module_bake_pool_and_render_frames(dev):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd.baked import bake, bake_pool
     for exact in (True, False):
-        model, Hm, Wm, K = _model(dev, "0.2#0.4#0.6", exact)
+        model, Hm, Wm, K = BM.pool_model(dev, "0.2#0.4#0.6", exact)
         dense_bake, pool_bake = bake(model), bake_pool(model)
         assert pool_bake.frm_num == dense_bake.frm_num == 6 and pool_bake.spec == model.spec and pool_bake.bg_color == "0.2#0.4#0.6"
         ext, intr, rt = _cameras(K)
@@ -254,11 +195,11 @@ def test_module_bake_pool_and_render_frames(dev):
 
 def test_bake_pool_refusals(dev):
     from videoloop3d_amd.baked import bake_pool
-    model, _, _, _ = _model(dev, "")
+    model, _, _, _ = BM.pool_model(dev, "")
     model.is_sparse = False
     with pytest.raises(RuntimeError, match="not sparse"):
         bake_pool(model)
-    cpu_model, _, _, _ = _model(torch.device("cpu"), "")
+    cpu_model, _, _, _ = BM.pool_model(torch.device("cpu"), "")
     with pytest.raises(RuntimeError, match="host"):
         bake_pool(cpu_model)
     cpu_model.atlas_exact = True
@@ -295,12 +236,12 @@ def test_determinism_and_guards(dev, scenes):
         return d
     cull = torch.empty((int(lib.vl3d_render_cull_scratch_bytes(desc())) + 3) // 4, dtype=torch.float32, device=dev)
     ARGS = dict(blocks=L.ptr(lay.blocks), pool=L.ptr(pool), frame0=1, T_model=T_MODEL, homos=L.ptr(scenes.homos), quad_keep=L.ptr(s.qk), QH=g["QH"],
-                QW=g["QW"], culled=s.bp.culled_rgba8, cull=L.ptr(cull), rgb=L.ptr(rgb), alpha=L.ptr(alpha))
+                QW=g["QW"], culled=s.bp.culled_rgba8, cull=L.ptr(cull), rgb=rgb, alpha=alpha)
 
     def rc(d, **over):
         a = dict(ARGS, **over)
-        return lib.vl3d_render_fwd_baked_pool(d, a["blocks"], a["pool"], a["frame0"], a["T_model"], a["homos"], a["quad_keep"], a["QH"], a["QW"],
-                                              a["culled"], a["cull"], a["rgb"], a["alpha"], stream)
+        return lib.vl3d_render_fwd_baked_pool(d, a["blocks"], a["pool"], a["T_model"], a["homos"], BM.run_sel(a["frame0"]), a["quad_keep"], a["QH"],
+                                              a["QW"], a["culled"], a["cull"], BM.float_out(a["rgb"], a["alpha"]), stream)
     EINVAL = 1
 
     def refused(fragment, d=None, **over):
@@ -308,8 +249,7 @@ def test_determinism_and_guards(dev, scenes):
         assert fragment in lib.vl3d_last_error(), lib.vl3d_last_error()
     for name in ("blocks", "pool", "homos", "quad_keep", "cull", "rgb", "alpha"):
         refused(b"null pointer", **{name: None})
-    assert lib.vl3d_render_fwd_baked_pool(None, *[ARGS[k] for k in ("blocks", "pool", "frame0", "T_model", "homos", "quad_keep", "QH", "QW", "culled",
-                                                                        "cull", "rgb", "alpha")], stream) == EINVAL
+    assert rc(None) == EINVAL
     refused(b"VL3D_U8", desc(dtype="f32"))
     refused(b"planar", desc(RenderSpec()))
     refused(b"uv_noise", desc(dataclasses.replace(s.spec, uv_noise_seed=5)))
@@ -381,14 +321,15 @@ def test_culled_forward_entries_share_the_grid_rule(dev, scenes):
         d_u8 = _desc_dims(D, n, g["Hs"], g["Ws"], H, W, s.spec, L.STACK_DTYPE["u8"])
         cull = torch.empty((int(lib.vl3d_render_cull_scratch_bytes(d_f32)) + 3) // 4, dtype=torch.float32, device=dev)
         hom, qk, out = L.ptr(scenes.homos), L.ptr(s.qk), (L.ptr(rgb), L.ptr(alpha))
+        sel, sink = BM.run_sel(1), BM.float_out(rgb, alpha)
         entries = {
             "vl3d_render_fwd_frames_culled": lambda qh, qw: lib.vl3d_render_fwd_frames_culled(d_f32, L.ptr(stack), 1, T_MODEL, hom, qk, qh, qw,
                                                                                               L.ptr(cull), *out, stream),
             "vl3d_render_fwd_packed": lambda qh, qw: lib.vl3d_render_fwd_packed(d_pk, L.ptr(lay.blocks), L.ptr(fpool), L.ptr(frames), n, hom, qk, qh, qw,
                                                                                 0.0, *out, stream),
-            "vl3d_render_fwd_baked": lambda qh, qw: lib.vl3d_render_fwd_baked(d_u8, L.ptr(s.dense), 1, T_MODEL, hom, qk, qh, qw, L.ptr(cull), *out, stream),
-            "vl3d_render_fwd_baked_pool": lambda qh, qw: lib.vl3d_render_fwd_baked_pool(d_u8, L.ptr(lay.blocks), L.ptr(s.bp.pool), 1, T_MODEL, hom, qk,
-                                                                                        qh, qw, s.bp.culled_rgba8, L.ptr(cull), *out, stream),
+            "vl3d_render_fwd_baked": lambda qh, qw: lib.vl3d_render_fwd_baked(d_u8, L.ptr(s.dense), T_MODEL, hom, sel, qk, qh, qw, L.ptr(cull), sink, stream),
+            "vl3d_render_fwd_baked_pool": lambda qh, qw: lib.vl3d_render_fwd_baked_pool(d_u8, L.ptr(lay.blocks), L.ptr(s.bp.pool), T_MODEL, hom, sel, qk,
+                                                                                        qh, qw, s.bp.culled_rgba8, L.ptr(cull), sink, stream),
         }
         bad = [(abs(QH), -abs(QW)), (0, abs(QW)), (-4, -7), (-30, -70)]
         for entry, call in entries.items():

@@ -58,6 +58,14 @@ class AdamWindow(C.Structure):
                 ("blocks", _P)]
 
 
+class BakedFrames(C.Structure):      # vl3d_baked_frames: a run (frame0) or a camera path (n_cams, frame_cam, frame_t) of a baked render
+    _fields_ = [("frame0", C.c_int32), ("n_cams", C.c_int32), ("frame_cam", _P), ("frame_t", _P)]
+
+
+class BakedOut(C.Structure):         # vl3d_baked_out: the float sink (rgb, alpha) or the display sink (frames, channels, bg)
+    _fields_ = [("rgb", _P), ("alpha", _P), ("frames", _P), ("channels", C.c_int32), ("bg", _P)]
+
+
 class Stage1ObjectiveDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("scale_invariant", C.c_int32),
                 ("w_img", C.c_float), ("w_loop", C.c_float), ("w_sparsity", C.c_float), ("w_density", C.c_float),
@@ -73,16 +81,10 @@ SIGNATURES = {
     "vl3d_render_fwd_frames": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_frames_culled": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_bake_rgba8": ([_I64, _P, _I32, _I32, _I32, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _I32, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_fwd_baked": ([C.POINTER(RenderDesc), _P, _I32, _P, C.POINTER(BakedFrames), _P, _I32, _I32, _P, C.POINTER(BakedOut), _P], C.c_int),
+    "vl3d_render_fwd_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, C.POINTER(BakedFrames), _P, _I32, _I32, C.c_uint32, _P,
+                                    C.POINTER(BakedOut), _P], C.c_int),
     "vl3d_render_path_cull_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
-    "vl3d_render_fwd_baked_path": ([C.POINTER(RenderDesc), _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked_pool_path": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked_u8": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked_pool_u8": ([C.POINTER(RenderDesc), _P, _P, _I32, _I32, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _I32, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked_path_u8": ([C.POINTER(RenderDesc), _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P], C.c_int),
-    "vl3d_render_fwd_baked_pool_path_u8": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, C.c_uint32, _P, _P, _I32, _P, _P],
-                                           C.c_int),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),

@@ -48,7 +48,7 @@ def bake_texels(t, rgb_act, alpha_act):
 def display_frames(rgb, alpha, bg=None, channels=3):
     """The display rule in torch: rgb [N,H,W,3], alpha [N,H,W] float32 -> uint8 [N,H,W,channels].  Over `bg` (3 floats or a tensor of 3, or
     None) as MPV.py:455-461 composites, then to8b (utils.py: (255 * clip(x, 0, 1)).astype(uint8), truncating); channels == 4 appends the alpha
-    byte, to8b of alpha itself, never composited.  The `frames8=` sink of the baked renders (vl3d_render_fwd_baked*_u8) stores these bytes."""
+    byte, to8b of alpha itself, never composited.  The `frames8=` sink of the baked renders (the display sink of vl3d_render_fwd_baked / _pool) stores these bytes."""
     if channels not in (3, 4):
         raise ValueError(f"display_frames: channels must be 3 (RGB8) or 4 (RGBA8), got {channels}")
     x = rgb

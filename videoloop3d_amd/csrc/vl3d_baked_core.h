@@ -26,7 +26,7 @@ __device__ __forceinline__ float blend(const BakedTaps &v, f4 w255) {
     return fmaf(chan<K>(v.r0.x), w255[0], fmaf(chan<K>(v.r0.y), w255[1], fmaf(chan<K>(v.r1.x), w255[2], chan<K>(v.r1.y) * w255[3])));
 }
 
-// A camera path (vl3d_render_fwd_baked_path / _pool_path): output frame i of the launch has its own camera frame_cam[i] and its own frame
+// A camera path (the path selection of vl3d_render_fwd_baked / _pool): output frame i of the launch has its own camera frame_cam[i] and its own frame
 // frame_t[i] of the clip, both device int32[N].  NoPath: the kernels' one-camera form, (frame, camera) from the block index and the launch
 // arguments -- an empty argument, so that the two forms are one kernel text.
 struct NoPath {};
@@ -43,7 +43,7 @@ __device__ __forceinline__ bool path_frame(const PathIdx &p, int i, int &cam, in
 }
 
 // Where a composited pixel goes.  FloatOut: a.rgb / a.alpha, fp32 -- an empty argument, so that the two sinks are one kernel text (as NoPath
-// beside PathIdx).  DisplayOut (vl3d_render_fwd_baked*_u8): the frame a viewer shows, frames (N,H,W,channels) uint8, over the background
+// beside PathIdx).  DisplayOut (the display sink, vl3d_baked_out.frames): the frame a viewer shows, frames (N,H,W,channels) uint8, over the background
 // bg when has_bg; pack3: the lane-packed RGB8 store instead of three byte stores per lane.  bg travels in the kernel arguments.
 struct FloatOut {};
 struct DisplayOut {
@@ -51,7 +51,7 @@ struct DisplayOut {
     float bg[3];
     int has_bg, channels, pack3;
 };
-// What the four _u8 entries add to their float siblings' refusals (`who` in front of the message), and their sink.  bg: a HOST pointer to 3
+// What the display sink adds to the float sink's refusals (`who` in front of the message), and the sink itself.  bg: a HOST pointer to 3
 // floats or null, read here -- no device read for it.  The RGB8 store is the lane-packed one; VL3D_DISPLAY_STORE3=bytes is the measurement
 // hook of profiles/baked_fwd.py --legs display for the byte stores (read per call: the legs alternate inside one process).
 inline int display_out_of(uint8_t *frames, int32_t channels, const float *bg, const char *who, DisplayOut &out) {

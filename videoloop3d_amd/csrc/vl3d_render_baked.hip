@@ -65,10 +65,10 @@ __device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, 
 }
 
 // PATH = NoPath: frames t0 .. of the run a.stack starts at, one camera (a.homos, a.cull_masks of one plan).
-// PATH = PathIdx (vl3d_render_fwd_baked_path): the block index's outermost factor is the OUTPUT frame i; the workgroup reads its camera and
+// PATH = PathIdx (a camera path, sel->frame_cam / frame_t): the block index's outermost factor is the OUTPUT frame i; the workgroup reads its camera and
 // its frame of the clip (path_frame: scalar loads, range-checked) and from them forms its homography, mask and texel bases.  One frame per
 // thread: from there on the one-frame kernel.
-// OUT = FloatOut: rgb / alpha fp32 at a.rgb / a.alpha.  OUT = DisplayOut (vl3d_render_fwd_baked_u8 / _path_u8): the 8-bit display frame over
+// OUT = FloatOut: rgb / alpha fp32 at a.rgb / a.alpha.  OUT = DisplayOut (out->frames): the 8-bit display frame over
 // the background, written by the same launch (vl3d_baked_core.h); everything in front of the store is the one text.
 template <int NF, bool CULL, typename PATH = NoPath, typename OUT = FloatOut>
 __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y, PATH path, OUT out) {
@@ -146,31 +146,6 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     composite.store(a, out, t0, x, y, has1);
 }
 
-template <int NF, typename OUT>
-void launch_baked(const RenderArgs &a, const OUT &out, hipStream_t s) {
-    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
-    const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
-    if (a.quad_keep) {      // tile culling: the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
-        launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
-        hipLaunchKernelGGL((render_fwd_baked_k<NF, true, NoPath, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{}, out);
-        return;
-    }
-    hipLaunchKernelGGL((render_fwd_baked_k<NF, false, NoPath, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, NoPath{}, out);
-}
-
-// a camera path: a.T output frames, one plan launch for all cameras (a culled model), one render launch
-template <typename OUT>
-void launch_baked_path(const RenderArgs &a, const PathIdx &path, const OUT &out, hipStream_t s) {
-    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
-    const dim3 grid((unsigned)(tiles_x * tiles_y * a.T)), block(512);
-    if (a.quad_keep) {
-        launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
-        hipLaunchKernelGGL((render_fwd_baked_k<1, true, PathIdx, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, out);
-        return;
-    }
-    hipLaunchKernelGGL((render_fwd_baked_k<1, false, PathIdx, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, out);
-}
-
 bool known_act(int act) { return act >= VL3D_ACT_NONE && act <= VL3D_ACT_ABS; }
 
 }  // namespace
@@ -191,124 +166,62 @@ extern "C" int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stac
     return VL3D_OK;
 }
 
-// what vl3d_render_fwd_baked, vl3d_render_fwd_baked_path and their _u8 forms refuse alike, in two parts around the entry's own rule about
-// its frames (rgb, alpha: the outputs -- a _u8 entry passes its frames for both)
-static int baked_check_desc(const vl3d_render_desc *desc, const uint8_t *baked, const float *homos, const void *rgb, const void *alpha) {
-    VL3D_REQUIRE(desc != nullptr, "null render desc");
-    VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked: no kernel variants (desc->variant = 0)");
-    VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked: non-positive render dims");
-    // a row's two taps are one 8-byte load, the two rows a constant step apart: planes of at least 2 x 2 texels
-    VL3D_REQUIRE(desc->Hs >= 2 && desc->Ws >= 2, "vl3d_render_fwd_baked: planes of at least 2 x 2 texels");
-    VL3D_REQUIRE(desc->Hs < (1 << 24) && desc->Ws < (1 << 24) && (int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32),
-                 "vl3d_render_fwd_baked: plane too large for 32-bit tap offsets");
-    VL3D_REQUIRE(desc->stack_dtype == VL3D_U8, "vl3d_render_fwd_baked: stack_dtype must be VL3D_U8 (the baked RGBA8 texels of vl3d_bake_rgba8)");
-    VL3D_REQUIRE(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT,
-                 "vl3d_render_fwd_baked: the planar MPV convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
-    VL3D_REQUIRE(desc->uv_noise_seed == 0, "vl3d_render_fwd_baked: add_uv_noise is a training switch (uv_noise_seed = 0)");
-    VL3D_REQUIRE(baked && homos && rgb && alpha, "vl3d_render_fwd_baked: null pointer");
-    VL3D_REQUIRE(((uintptr_t)baked & 3) == 0, "vl3d_render_fwd_baked: the texels must be 4-byte aligned");
-    return VL3D_OK;
-}
-static int baked_set_cull(RenderArgs &a, const vl3d_render_desc *desc, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch) {
-    if (!quad_keep) return VL3D_OK;
-    const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked");
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
-    a.quad_keep = quad_keep;
-    a.cull_masks = (const unsigned long long *)cull_scratch;
-    set_cull_geometry(a, desc, QH, QW);
-    return VL3D_OK;
-}
-
-// a run of frames into either sink: OUT = FloatOut with rgb / alpha, OUT = DisplayOut (checked by the entry) with rgb = alpha = its frames
-template <typename OUT>
-static int baked_run(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha, const OUT &out,
-                     vl3d_stream_t stream) {
-    VL3D_REQUIRE(T_alloc > 0 && frame0 >= 0 && frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
-    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above)
-    a.Tstride = T_alloc;
-    a.stack = reinterpret_cast<const float *>(baked + (size_t)frame0 * desc->Hs * desc->Ws * 4);
-    a.homos = homos; a.rgb = rgb; a.alpha = alpha;
-    const int rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);
-    if (rc != VL3D_OK) return rc;
-    if (desc->T >= 2) launch_baked<2>(a, out, (hipStream_t)stream);
-    else launch_baked<1>(a, out, (hipStream_t)stream);
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
-extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                                     const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
-                                     vl3d_stream_t stream) {
-    const int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
-    return baked_run(desc, baked, frame0, T_alloc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha, FloatOut{}, stream);
-}
-
-extern "C" int vl3d_render_fwd_baked_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t frame0, int32_t T_alloc, const float *homos,
-                                        const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, uint8_t *frames, int32_t channels,
-                                        const float *bg, vl3d_stream_t stream) {
-    int rc = baked_check_desc(desc, baked, homos, frames, frames);
-    if (rc != VL3D_OK) return rc;
-    DisplayOut out;
-    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_u8", out);
-    if (rc != VL3D_OK) return rc;
-    return baked_run(desc, baked, frame0, T_alloc, homos, quad_keep, QH, QW, cull_scratch, nullptr, nullptr, out, stream);
-}
-
 // two 64-bit plane masks per (camera, 64 x 8 pixel workgroup): [n_cams][tiles_y * tiles_x][2]
 extern "C" int64_t vl3d_render_path_cull_scratch_bytes(const vl3d_render_desc *desc, int32_t n_cams) {
     if (!desc || desc->H <= 0 || desc->W <= 0 || n_cams <= 0) return 0;
     return (int64_t)n_cams * ((desc->W + 63) / 64) * ((desc->H + 7) / 8) * 16;
 }
 
-// what the two path entries add to their one-camera entries' refusals (`who` in front of the message)
-int vl3d_render_detail::check_path(const vl3d_render_desc *desc, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t, const char *who) {
-    const char *bad = nullptr;
-    if (!(n_cams >= 1 && n_cams <= 65535)) bad = "n_cams must be in [1, 65535]";
-    else if (!frame_cam || !frame_t) bad = "null pointer (frame_cam, frame_t: device int32[desc->T])";
-    else if ((int64_t)((desc->W + 63) / 64) * ((desc->H + 7) / 8) * desc->T > 0x7fffffffll) bad = "tiles x frames exceed the grid";
-    if (!bad) return VL3D_OK;
-    vl3d_set_error((std::string(who) + ": " + bad).c_str());
-    return VL3D_EINVAL;
-}
-
-// a camera path into either sink (as baked_run)
-template <typename OUT>
-static int baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
-                      const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
-                      float *rgb, float *alpha, const OUT &out, vl3d_stream_t stream) {
-    VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_baked_path: a clip of T_alloc >= 1 frames");
-    int rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_path");
+// The one entry: the refusals, RenderArgs, then the plan launch of a tile-culled model (the float forward's plan over its 64 x 8 tiles: one
+// camera's, or all cameras' of a path in one launch) and the render launch on <NF, CULL, PATH, OUT> as `sel` and `out` name them.
+extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                                     const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
+                                     const vl3d_baked_out *out, vl3d_stream_t stream) {
+    const char *who = "vl3d_render_fwd_baked";
+    // a row's two taps are one 8-byte load, the two rows a constant step apart
+    int rc = check_baked_desc(desc, 1ll << 28, "plane too large for 32-bit tap offsets", who);
     if (rc != VL3D_OK) return rc;
-    RenderArgs a = render_args_of(desc);      // a.T: the output frames of the path
+    bool is_path = false;
+    if ((rc = check_baked_frames(desc, sel, is_path, who)) != VL3D_OK || (rc = check_baked_out(out, who)) != VL3D_OK) return rc;
+    VL3D_REQUIRE(baked && homos, "vl3d_render_fwd_baked: null pointer");
+    VL3D_REQUIRE(((uintptr_t)baked & 3) == 0, "vl3d_render_fwd_baked: the texels must be 4-byte aligned");
+    DisplayOut disp;
+    if (out->frames && (rc = display_out_of(out->frames, out->channels, out->bg, who, disp)) != VL3D_OK) return rc;
+    if (is_path) VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_baked: a clip of T_alloc >= 1 frames");
+    else VL3D_REQUIRE(T_alloc > 0 && sel->frame0 >= 0 && sel->frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a path: a.T is the count of its output frames)
     a.Tstride = T_alloc;
-    a.stack = reinterpret_cast<const float *>(baked);
-    a.homos = homos; a.rgb = rgb; a.alpha = alpha;
-    rc = baked_set_cull(a, desc, quad_keep, QH, QW, cull_scratch);      // (cull_scratch: vl3d_render_path_cull_scratch_bytes)
-    if (rc != VL3D_OK) return rc;
-    launch_baked_path(a, PathIdx{frame_cam, frame_t, n_cams, T_alloc}, out, (hipStream_t)stream);
+    a.stack = reinterpret_cast<const float *>(baked + (is_path ? 0 : (size_t)sel->frame0 * desc->Hs * desc->Ws * 4));
+    a.homos = homos; a.rgb = out->rgb; a.alpha = out->alpha;
+    if (quad_keep) {
+        if ((rc = check_cull_grid(desc, QH, QW, who)) != VL3D_OK) return rc;
+        VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
+        a.quad_keep = quad_keep;
+        a.cull_masks = (const unsigned long long *)cull_scratch;
+        set_cull_geometry(a, desc, QH, QW);
+    }
+    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
+    const hipStream_t s = (hipStream_t)stream;
+    auto launch = [&](auto nf, const auto &path, const auto &o) {
+        constexpr int NF = decltype(nf)::value;
+        using PATH = std::decay_t<decltype(path)>;
+        using OUT = std::decay_t<decltype(o)>;
+        const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
+        if (a.quad_keep) {
+            if constexpr (std::is_same<PATH, PathIdx>::value) launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
+            else launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
+            hipLaunchKernelGGL((render_fwd_baked_k<NF, true, PATH, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, o);
+            return;
+        }
+        hipLaunchKernelGGL((render_fwd_baked_k<NF, false, PATH, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, o);
+    };
+    const std::integral_constant<int, 1> one;      // frames per thread: pairs for a run of two or more, one along a path
+    const std::integral_constant<int, 2> two;
+    const PathIdx path{sel->frame_cam, sel->frame_t, sel->n_cams, T_alloc};
+    if (!is_path && !out->frames) desc->T >= 2 ? launch(two, NoPath{}, FloatOut{}) : launch(one, NoPath{}, FloatOut{});
+    else if (!is_path) desc->T >= 2 ? launch(two, NoPath{}, disp) : launch(one, NoPath{}, disp);
+    else if (!out->frames) launch(one, path, FloatOut{});
+    else launch(one, path, disp);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
-}
-
-extern "C" int vl3d_render_fwd_baked_path(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, int32_t n_cams,
-                                          const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                          void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
-    const int rc = baked_check_desc(desc, baked, homos, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
-    return baked_path(desc, baked, T_alloc, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, cull_scratch, rgb, alpha, FloatOut{}, stream);
-}
-
-extern "C" int vl3d_render_fwd_baked_path_u8(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
-                                             int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH,
-                                             int32_t QW, void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg,
-                                             vl3d_stream_t stream) {
-    int rc = baked_check_desc(desc, baked, homos, frames, frames);
-    if (rc != VL3D_OK) return rc;
-    DisplayOut out;
-    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_path_u8", out);
-    if (rc != VL3D_OK) return rc;
-    return baked_path(desc, baked, T_alloc, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, cull_scratch, nullptr, nullptr, out, stream);
 }

@@ -49,9 +49,9 @@ __device__ __forceinline__ void pool_load(const PoolSrc &p, int e, unsigned in_b
     }
 }
 
-// PATH = NoPath: frames p.frame0 + t0 .. of one camera.  PATH = PathIdx (vl3d_render_fwd_baked_pool_path): the block index's outermost factor is
+// PATH = NoPath: frames p.frame0 + t0 .. of one camera.  PATH = PathIdx (a camera path, sel->frame_cam / frame_t): the block index's outermost factor is
 // the OUTPUT frame; camera and frame of the model come from path_frame (scalar loads, range-checked), as in the dense path kernel.
-// OUT: FloatOut, or the DisplayOut of the _u8 entries (vl3d_baked_core.h), as in the dense kernel.
+// OUT: FloatOut, or the DisplayOut of out->frames (vl3d_baked_core.h), as in the dense kernel.
 template <int NF, typename PATH = NoPath, typename OUT = FloatOut>
 __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, PoolSrc p, int tiles_x, int tiles_y, PATH path, OUT out) {
     constexpr bool IS_PATH = !std::is_same<PATH, NoPath>::value;
@@ -140,129 +140,53 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
     composite.store(a, out, t0, x, y, has1);
 }
 
-template <int NF, typename OUT>
-void launch_baked_pool(const RenderArgs &a, const PoolSrc &p, const OUT &out, hipStream_t s) {
-    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
-    const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
-    // the float forward's plan (frame independent, its 64 x 8 tiles), then the plane-list kernel
-    launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
-    hipLaunchKernelGGL((render_fwd_baked_pool_k<NF, NoPath, OUT>), grid, block, 0, s, a, p, tiles_x, tiles_y, NoPath{}, out);
-}
-
-// a camera path: a.T output frames, one plan launch for all cameras, one render launch
-template <typename OUT>
-void launch_baked_pool_path(const RenderArgs &a, const PoolSrc &p, const PathIdx &path, const OUT &out, hipStream_t s) {
-    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
-    const dim3 grid((unsigned)(tiles_x * tiles_y * a.T)), block(512);
-    launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
-    hipLaunchKernelGGL((render_fwd_baked_pool_k<1, PathIdx, OUT>), grid, block, 0, s, a, p, tiles_x, tiles_y, path, out);
-}
-
 }  // namespace
 
-// what vl3d_render_fwd_baked_pool, vl3d_render_fwd_baked_pool_path and their _u8 forms refuse alike, in two parts around the entry's own rule
-// about its frames (rgb, alpha: the outputs -- a _u8 entry passes its frames for both)
-static int pool_check_desc(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, const float *homos, const uint8_t *quad_keep,
-                           const void *cull_scratch, const void *rgb, const void *alpha) {
-    VL3D_REQUIRE(desc != nullptr, "null render desc");
-    VL3D_REQUIRE(desc->variant == 0, "vl3d_render_fwd_baked_pool: no kernel variants (desc->variant = 0)");
-    VL3D_REQUIRE(desc->D > 0 && desc->T > 0 && desc->H > 0 && desc->W > 0, "vl3d_render_fwd_baked_pool: non-positive render dims");
-    // the base tap is clamped to (Ws - 2, Hs - 2) and its right / lower neighbours are read unconditionally: planes of at least 2 x 2 texels
-    VL3D_REQUIRE(desc->Hs >= 2 && desc->Ws >= 2, "vl3d_render_fwd_baked_pool: planes of at least 2 x 2 texels");
-    VL3D_REQUIRE(desc->Hs < (1 << 24) && desc->Ws < (1 << 24), "vl3d_render_fwd_baked_pool: plane too large");
-    VL3D_REQUIRE(desc->stack_dtype == VL3D_U8, "vl3d_render_fwd_baked_pool: stack_dtype must be VL3D_U8 (the baked RGBA8 texels of vl3d_bake_rgba8)");
-    VL3D_REQUIRE(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT,
-                 "vl3d_render_fwd_baked_pool: the planar MPV convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
-    VL3D_REQUIRE(desc->uv_noise_seed == 0, "vl3d_render_fwd_baked_pool: add_uv_noise is a training switch (uv_noise_seed = 0)");
-    VL3D_REQUIRE(blocks && pool && homos && quad_keep && cull_scratch && rgb && alpha,
+// The one entry: the refusals, RenderArgs and PoolSrc, then the plan launch (the float forward's plan over its 64 x 8 tiles: one camera's, or
+// all cameras' of a path in one launch) and the render launch on <NF, PATH, OUT> as `sel` and `out` name them.
+extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
+                                          const float *homos, const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                          uint32_t culled_rgba8, void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream) {
+    const char *who = "vl3d_render_fwd_baked_pool";
+    int rc = check_baked_desc(desc, INT64_MAX, "plane too large", who);
+    if (rc != VL3D_OK) return rc;
+    bool is_path = false;
+    if ((rc = check_baked_frames(desc, sel, is_path, who)) != VL3D_OK || (rc = check_baked_out(out, who)) != VL3D_OK) return rc;
+    VL3D_REQUIRE(blocks && pool && homos && quad_keep && cull_scratch,
                  "vl3d_render_fwd_baked_pool: null pointer (the quad map and vl3d_render_cull_scratch_bytes() of scratch are required)");
     VL3D_REQUIRE(((uintptr_t)pool & 3) == 0 && ((uintptr_t)blocks & 3) == 0, "vl3d_render_fwd_baked_pool: the pool and the block table must be 4-byte aligned");
-    return VL3D_OK;
-}
-static int pool_set_args(RenderArgs &a, const vl3d_render_desc *desc, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                         void *cull_scratch, float *rgb, float *alpha) {
+    DisplayOut disp;
+    if (out->frames && (rc = display_out_of(out->frames, out->channels, out->bg, who, disp)) != VL3D_OK) return rc;
+    if (is_path) VL3D_REQUIRE(T_model > 0, "vl3d_render_fwd_baked_pool: a model of T_model >= 1 frames");
+    else VL3D_REQUIRE(T_model > 0 && sel->frame0 >= 0 && (int64_t)sel->frame0 + desc->T <= T_model,
+                      "vl3d_render_fwd_baked_pool: the run of frames leaves the model's T_model frames");
     VL3D_REQUIRE(desc->cull_Hs == 0 && desc->cull_Ws == 0, "vl3d_render_fwd_baked_pool: the pool holds whole planes (no desc->cull_* window)");
-    const int rc = check_cull_grid(desc, QH, QW, "vl3d_render_fwd_baked_pool");
-    if (rc != VL3D_OK) return rc;
-    a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a.Tstride is not read: the pool has no frame stride)
-    a.homos = homos; a.rgb = rgb; a.alpha = alpha;
+    if ((rc = check_cull_grid(desc, QH, QW, who)) != VL3D_OK) return rc;
+    RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a.Tstride is not read: the pool has no frame stride)
+    a.homos = homos; a.rgb = out->rgb; a.alpha = out->alpha;
     a.quad_keep = quad_keep;
     a.cull_masks = (const unsigned long long *)cull_scratch;
     set_cull_geometry(a, desc, QH, QW);
-    return VL3D_OK;
-}
-
-// a run of frames / a camera path into either sink: OUT = FloatOut with rgb / alpha, OUT = DisplayOut (checked by the entry) without
-template <typename OUT>
-static int pool_run(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0, int32_t T_model, const float *homos,
-                    const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha,
-                    const OUT &out, vl3d_stream_t stream) {
-    VL3D_REQUIRE(T_model > 0 && frame0 >= 0 && (int64_t)frame0 + desc->T <= T_model,
-                 "vl3d_render_fwd_baked_pool: the run of frames leaves the model's T_model frames");
-    RenderArgs a;
-    const int rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
-    const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, frame0, culled_rgba8};
-    if (desc->T >= 2) launch_baked_pool<2>(a, p, out, (hipStream_t)stream);
-    else launch_baked_pool<1>(a, p, out, (hipStream_t)stream);
+    const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, is_path ? 0 : sel->frame0,
+                    culled_rgba8};
+    const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
+    const hipStream_t s = (hipStream_t)stream;
+    auto launch = [&](auto nf, const auto &path, const auto &o) {
+        constexpr int NF = decltype(nf)::value;
+        using PATH = std::decay_t<decltype(path)>;
+        using OUT = std::decay_t<decltype(o)>;
+        const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
+        if constexpr (std::is_same<PATH, PathIdx>::value) launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
+        else launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
+        hipLaunchKernelGGL((render_fwd_baked_pool_k<NF, PATH, OUT>), grid, block, 0, s, a, p, tiles_x, tiles_y, path, o);
+    };
+    const std::integral_constant<int, 1> one;      // frames per thread: pairs for a run of two or more, one along a path
+    const std::integral_constant<int, 2> two;
+    const PathIdx path{sel->frame_cam, sel->frame_t, sel->n_cams, T_model};
+    if (!is_path && !out->frames) desc->T >= 2 ? launch(two, NoPath{}, FloatOut{}) : launch(one, NoPath{}, FloatOut{});
+    else if (!is_path) desc->T >= 2 ? launch(two, NoPath{}, disp) : launch(one, NoPath{}, disp);
+    else if (!out->frames) launch(one, path, FloatOut{});
+    else launch(one, path, disp);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
-}
-template <typename OUT>
-static int pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos, int32_t n_cams,
-                     const int32_t *frame_cam, const int32_t *frame_t, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
-                     void *cull_scratch, float *rgb, float *alpha, const OUT &out, vl3d_stream_t stream) {
-    VL3D_REQUIRE(T_model > 0, "vl3d_render_fwd_baked_pool_path: a model of T_model >= 1 frames");
-    int rc = check_path(desc, n_cams, frame_cam, frame_t, "vl3d_render_fwd_baked_pool_path");
-    if (rc != VL3D_OK) return rc;
-    RenderArgs a;      // a.T: the output frames of the path; cull_scratch: vl3d_render_path_cull_scratch_bytes
-    rc = pool_set_args(a, desc, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
-    const PoolSrc p{blocks, reinterpret_cast<const char *>(pool), (desc->Hs + TSB - 1) / TSB, (desc->Ws + TSB - 1) / TSB, 0, culled_rgba8};
-    launch_baked_pool_path(a, p, PathIdx{frame_cam, frame_t, n_cams, T_model}, out, (hipStream_t)stream);
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
-extern "C" int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
-                                          int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                          uint32_t culled_rgba8, void *cull_scratch, float *rgb, float *alpha, vl3d_stream_t stream) {
-    const int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
-    return pool_run(desc, blocks, pool, frame0, T_model, homos, quad_keep, QH, QW, culled_rgba8, cull_scratch, rgb, alpha, FloatOut{}, stream);
-}
-
-extern "C" int vl3d_render_fwd_baked_pool_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t frame0,
-                                             int32_t T_model, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
-                                             uint32_t culled_rgba8, void *cull_scratch, uint8_t *frames, int32_t channels, const float *bg,
-                                             vl3d_stream_t stream) {
-    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, frames, frames);
-    if (rc != VL3D_OK) return rc;
-    DisplayOut out;
-    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_pool_u8", out);
-    if (rc != VL3D_OK) return rc;
-    return pool_run(desc, blocks, pool, frame0, T_model, homos, quad_keep, QH, QW, culled_rgba8, cull_scratch, nullptr, nullptr, out, stream);
-}
-
-extern "C" int vl3d_render_fwd_baked_pool_path(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
-                                               const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
-                                               const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
-                                               float *rgb, float *alpha, vl3d_stream_t stream) {
-    const int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, rgb, alpha);
-    if (rc != VL3D_OK) return rc;
-    return pool_path(desc, blocks, pool, T_model, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, culled_rgba8, cull_scratch, rgb, alpha,
-                     FloatOut{}, stream);
-}
-
-extern "C" int vl3d_render_fwd_baked_pool_path_u8(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
-                                                  const float *homos, int32_t n_cams, const int32_t *frame_cam, const int32_t *frame_t,
-                                                  const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch,
-                                                  uint8_t *frames, int32_t channels, const float *bg, vl3d_stream_t stream) {
-    int rc = pool_check_desc(desc, blocks, pool, homos, quad_keep, cull_scratch, frames, frames);
-    if (rc != VL3D_OK) return rc;
-    DisplayOut out;
-    rc = display_out_of(frames, channels, bg, "vl3d_render_fwd_baked_pool_path_u8", out);
-    if (rc != VL3D_OK) return rc;
-    return pool_path(desc, blocks, pool, T_model, homos, n_cams, frame_cam, frame_t, quad_keep, QH, QW, culled_rgba8, cull_scratch, nullptr, nullptr,
-                     out, stream);
 }

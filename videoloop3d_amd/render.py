@@ -3,6 +3,7 @@
 Host-side mirror of the chain MPV.py:351-454 (planar geometry) / utils_mpi.py:159-176 + 92-107 of the
 reference, behind a torch.autograd.Function.  The arithmetic lives in csrc/vl3d_render.hip.
 """
+import types
 from dataclasses import dataclass
 
 import torch
@@ -83,7 +84,7 @@ def _out_buffers(out, n, H, W, device, who):
 
 
 def _display_out(out, frames8, bg, n, H, W, device, who):
-    """the display sink of a baked render (vl3d_render_fwd_baked*_u8): `frames8` uint8 [n,H,W,3|4] contiguous on `device`, `bg` a sequence of 3
+    """the display sink of a baked render (vl3d_baked_out.frames): `frames8` uint8 [n,H,W,3|4] contiguous on `device`, `bg` a sequence of 3
     floats or None -> (channels, bg as a host float[3] or None).  `out=` (the float sink) with `frames8=` is a ValueError; alignment of RGBA8
     frames and a non-finite background are the entry's refusals."""
     if out is not None:
@@ -376,110 +377,6 @@ def render_frame_run(stack, frame0, nframes, homos, H, W, spec: RenderSpec = Ren
     return rgb, alpha
 
 
-def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, frames8=None, bg=None):
-    """render_frame_run on the BAKED texels of a playback model (videoloop3d_amd/baked.py; vl3d_render_fwd_baked): `baked` [D,T,Hs,Ws,4] uint8 --
-    activated, times 255, truncated (baked.bake_texels) -- filtered bilinearly AFTER the activation, as a player filters the exported 8-bit
-    atlases; nothing is activated behind the blend, so spec.rgb_act / alpha_act / act_order are not read.  Coverage (hard cut, culled quads,
-    tile-exact layout) is decided by the float kernels' own code.  The planar convention only (RenderSpec.mpv()); forward only -- a baked
-    model is not trained: inputs that require a gradient are refused.  -> (rgb [n,H,W,3], alpha [n,H,W]) float32.
-    `frames8` (uint8 [n,H,W,3|4] on the device): the DISPLAY frames instead -- baked.display_frames(rgb, alpha, bg, channels), byte for byte,
-    written by the render launch (vl3d_render_fwd_baked_u8); no float output exists and `frames8` is returned.  `bg`: the background
-    colour, 3 floats, or None."""
-    L.check_cuda(baked, homos)
-    if bg is not None and frames8 is None:
-        raise ValueError("render_frame_run_baked: `bg` belongs to the display frames (`frames8=`)")
-    if baked.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
-        raise RuntimeError("render_frame_run_baked: baked texels have no backward (train the float model, then bake it)")
-    if baked.dtype != torch.uint8 or baked.dim() != 5 or baked.shape[4] != 4 or not baked.is_contiguous():
-        raise RuntimeError("render_frame_run_baked: a contiguous uint8 clip [D,T,Hs,Ws,4] (baked.bake_texels)")
-    if spec.coord_mode != "affine" or spec.border != "hardcut":
-        raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
-    D, T = baked.shape[:2]
-    if not (0 <= frame0 and nframes >= 1 and frame0 + nframes <= T):
-        raise RuntimeError(f"render_frame_run_baked: frames {frame0} .. {frame0 + nframes - 1} leave the clip of {T}")
-    if homos.shape != (D, 3, 3):
-        raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
-    if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
-        raise RuntimeError("RenderSpec.tile (tile-exact layout) belongs to a tile-culled model: pass its quad_keep map")
-    homos = homos.detach().to(torch.float32).contiguous()
-    desc = _desc(baked, H, W, spec, 0, 0)
-    desc.T = int(nframes)
-    desc.stack_dtype = L.STACK_DTYPE["u8"]
-    dev = baked.device
-    if frames8 is not None:
-        channels, bg = _display_out(out, frames8, bg, nframes, H, W, dev, "render_frame_run_baked")
-    else:
-        rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked")
-    qk, grid, cull = None, (0, 0), None
-    if quad_keep is not None:
-        qk = _quad_map(quad_keep, D)
-        grid = _qgrid(qk, spec)
-    with torch.cuda.device(dev):
-        if qk is not None:
-            cull = _cull_scratch(desc, dev)
-        if frames8 is not None:
-            L.check(L.lib().vl3d_render_fwd_baked_u8(desc, L.ptr(baked), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *grid, L.ptr(cull),
-                                                     L.ptr(frames8), channels, bg, L.stream_ptr(dev)), "vl3d_render_fwd_baked_u8")
-            return frames8
-        L.check(L.lib().vl3d_render_fwd_baked(desc, L.ptr(baked), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *grid, L.ptr(cull), L.ptr(rgb),
-                                              L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked")
-    return rgb, alpha
-
-
-def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, frames8=None,
-                                bg=None):
-    """render_frame_run_baked from the baked POOL of a packed tile-culled model (baked.BakedPool; vl3d_render_fwd_baked_pool): `layout` the
-    packed.PackedLayout whose block table addresses `pool` [n_slots * 64, 4] uint8 (8 x 8-texel blocks of baked RGBA8 texels), `quad_keep`
-    [D,QH,QW] the quad map the table was built from, `culled_rgba8` the texel (r | g << 8 | b << 16 | a << 24) a block without storage reads
-    as (BakedPool.culled_rgba8) -- both required, by keyword.  The kernel trusts the table: the layout's table and the quad map are checked
-    here against the layout's own dimensions.  Frames frame0 .. frame0 + nframes - 1 of the model's layout.T -> (rgb [n,H,W,3], alpha [n,H,W]) float32: the bits of
-    render_frame_run_baked on the unpacked texels, without the dense clip.  The planar convention only; forward only.  `frames8`, `bg`: the
-    display frames instead, as render_frame_run_baked takes them (vl3d_render_fwd_baked_pool_u8)."""
-    L.check_cuda(pool, homos, layout.blocks)
-    if bg is not None and frames8 is None:
-        raise ValueError("render_frame_run_baked_pool: `bg` belongs to the display frames (`frames8=`)")
-    if pool.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
-        raise RuntimeError("render_frame_run_baked_pool: baked texels have no backward (train the float model, then bake it)")
-    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
-        raise RuntimeError("render_frame_run_baked_pool: a contiguous uint8 pool [n_slots * 64, 4] of the layout (baked.bake_pool)")
-    if spec.coord_mode != "affine" or spec.border != "hardcut":
-        raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
-    if quad_keep is None:
-        raise RuntimeError("render_frame_run_baked_pool: the quad map the block table was built from (quad_keep [D,QH,QW]) is required")
-    D, T = layout.D, layout.T
-    if not (0 <= frame0 and nframes >= 1 and frame0 + nframes <= T):
-        raise RuntimeError(f"render_frame_run_baked_pool: frames {frame0} .. {frame0 + nframes - 1} leave the model's {T}")
-    if homos.shape != (D, 3, 3):
-        raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
-    qk = _quad_map(quad_keep, D)
-    grid = getattr(layout, "quad_grid", None)      # (a layout object made before PackedLayout recorded its grid: nothing to compare with)
-    if grid is not None and tuple(quad_keep.shape[1:]) != tuple(grid):
-        raise RuntimeError(f"quad_keep is {tuple(quad_keep.shape[1:])} quads per plane, the layout's block table was built from {tuple(grid)}")
-    bl = layout.blocks
-    if bl.dtype != torch.int32 or not bl.is_contiguous() or tuple(bl.shape) != (D, -(-layout.Hs // 8), -(-layout.Ws // 8)) or bl.device != pool.device:
-        raise RuntimeError("render_frame_run_baked_pool: the layout's block table must be contiguous int32 [D, ceil(Hs/8), ceil(Ws/8)] on the pool's device")
-    if bool(getattr(spec, "tile", (0, 0))[0]) != (layout.tile is not None):
-        raise RuntimeError("render_frame_run_baked_pool: RenderSpec.tile and the layout's tile must both name the tile-exact layout, or neither")
-    homos = homos.detach().to(torch.float32).contiguous()
-    dev = pool.device
-    d = _desc_dims(D, nframes, layout.Hs, layout.Ws, H, W, spec, L.STACK_DTYPE["u8"])
-    if frames8 is not None:
-        channels, bg = _display_out(out, frames8, bg, nframes, H, W, dev, "render_frame_run_baked_pool")
-    else:
-        rgb, alpha = _out_buffers(out, nframes, H, W, dev, "render_frame_run_baked_pool")
-    with torch.cuda.device(dev):
-        cull = _cull_scratch(d, dev)
-        if frames8 is not None:
-            L.check(L.lib().vl3d_render_fwd_baked_pool_u8(d, L.ptr(layout.blocks), L.ptr(pool), int(frame0), int(T), L.ptr(homos), L.ptr(qk),
-                                                          *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(frames8), channels, bg,
-                                                          L.stream_ptr(dev)), "vl3d_render_fwd_baked_pool_u8")
-            return frames8
-        L.check(L.lib().vl3d_render_fwd_baked_pool(d, L.ptr(layout.blocks), L.ptr(pool), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec),
-                                                   int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)),
-                "vl3d_render_fwd_baked_pool")
-    return rgb, alpha
-
-
 def _path_indices(frame_cam, frame_t, n_cams, T, device, who):
     """the (camera, frame) indices of a camera path, range-checked on the host (the kernels cannot report a bad index: they skip its frame)
     and uploaded in ONE pinned copy -> (N, int32 [2,N] on `device`: row 0 the cameras, row 1 the frames)."""
@@ -513,66 +410,26 @@ def _path_cull_scratch(desc, n_cams, device, cull_scratch, who):
     return cull_scratch
 
 
-def render_path_baked(baked, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, cull_scratch=None, frames8=None, bg=None):
-    """A camera path on the baked clip (vl3d_render_fwd_baked_path): N output frames in ONE plan launch plus ONE render launch, output frame i
-    being frame frame_t[i] of `baked` [D,T,Hs,Ws,4] uint8 seen by camera frame_cam[i] of `homos` [C,D,3,3] -- the spiral of the offline renderer,
-    where render_frame_run_baked takes one camera per call.  frame_cam / frame_t: host sequences or numpy arrays of N indices (checked here:
-    IndexError).  `cull_scratch`: an int64 buffer of vl3d_render_path_cull_scratch_bytes to hold the plane masks [C][tiles][2] across calls (a
-    tile-culled model; allocated per call when absent).  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal to
-    render_frame_run_baked(baked, frame_t[i], 1, homos[frame_cam[i]], ...).  Everything else as render_frame_run_baked, `frames8` / `bg` (the
-    display frames uint8 [N,H,W,3|4] instead: vl3d_render_fwd_baked_path_u8) included."""
-    who = "render_path_baked"
+def _baked_dense(who, baked, homos, spec, quad_keep):
+    """the dense source of a baked render, validated: the clip [D,T,Hs,Ws,4] uint8 with its optional quad map -> (T, the source half of the call)"""
     L.check_cuda(baked, homos)
-    if bg is not None and frames8 is None:
-        raise ValueError(f"{who}: `bg` belongs to the display frames (`frames8=`)")
     if baked.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
         raise RuntimeError(f"{who}: baked texels have no backward (train the float model, then bake it)")
     if baked.dtype != torch.uint8 or baked.dim() != 5 or baked.shape[4] != 4 or not baked.is_contiguous():
         raise RuntimeError(f"{who}: a contiguous uint8 clip [D,T,Hs,Ws,4] (baked.bake_texels)")
     if spec.coord_mode != "affine" or spec.border != "hardcut":
         raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
-    D, T = baked.shape[:2]
-    if homos.dim() != 4 or tuple(homos.shape[1:]) != (D, 3, 3) or homos.shape[0] < 1:
-        raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
     if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
         raise RuntimeError("RenderSpec.tile (tile-exact layout) belongs to a tile-culled model: pass its quad_keep map")
-    dev = baked.device
-    C = int(homos.shape[0])
-    qk, grid, cull = None, (0, 0), None
-    if quad_keep is not None:
-        qk = _quad_map(quad_keep, D)
-        grid = _qgrid(qk, spec)
-    N, idx = _path_indices(frame_cam, frame_t, C, T, dev, who)
-    homos = homos.detach().to(torch.float32).contiguous()
-    desc = _desc(baked, H, W, spec, 0, 0)
-    desc.T = N
-    desc.stack_dtype = L.STACK_DTYPE["u8"]
-    if frames8 is not None:
-        channels, bg = _display_out(out, frames8, bg, N, H, W, dev, who)
-    else:
-        rgb, alpha = _out_buffers(out, N, H, W, dev, who)
-    with torch.cuda.device(dev):
-        if qk is not None:
-            cull = _path_cull_scratch(desc, C, dev, cull_scratch, who)
-        if frames8 is not None:
-            L.check(L.lib().vl3d_render_fwd_baked_path_u8(desc, L.ptr(baked), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk), *grid,
-                                                          L.ptr(cull), L.ptr(frames8), channels, bg, L.stream_ptr(dev)), "vl3d_render_fwd_baked_path_u8")
-            return frames8
-        L.check(L.lib().vl3d_render_fwd_baked_path(desc, L.ptr(baked), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk), *grid,
-                                                   L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(dev)), "vl3d_render_fwd_baked_path")
-    return rgb, alpha
+    D, T, Hs, Ws = baked.shape[:4]
+    qk = None if quad_keep is None else _quad_map(quad_keep, D)
+    return T, types.SimpleNamespace(entry="vl3d_render_fwd_baked", dims=(D, Hs, Ws), device=baked.device, qk=qk, head=(L.ptr(baked), int(T)), culled=())
 
 
-def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, cull_scratch=None,
-                           frames8=None, bg=None):
-    """render_path_baked from the baked POOL (vl3d_render_fwd_baked_pool_path): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
-    render_frame_run_baked_pool takes them, the path as render_path_baked takes it.  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal
-    to render_frame_run_baked_pool(layout, pool, frame_t[i], 1, homos[frame_cam[i]], ...).  `frames8`, `bg`: the display frames instead
-    (vl3d_render_fwd_baked_pool_path_u8)."""
-    who = "render_path_baked_pool"
+def _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8):
+    """the pool source of a baked render, validated: the kernel trusts the block table, so the table and the quad map are checked here against
+    the layout's own dimensions -> (T, the source half of the call)"""
     L.check_cuda(pool, homos, layout.blocks)
-    if bg is not None and frames8 is None:
-        raise ValueError(f"{who}: `bg` belongs to the display frames (`frames8=`)")
     if pool.requires_grad or (torch.is_grad_enabled() and homos.requires_grad):
         raise RuntimeError(f"{who}: baked texels have no backward (train the float model, then bake it)")
     if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
@@ -581,11 +438,9 @@ def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: 
         raise RuntimeError("a baked model renders in the planar MPV convention (RenderSpec.mpv())")
     if quad_keep is None:
         raise RuntimeError(f"{who}: the quad map the block table was built from (quad_keep [D,QH,QW]) is required")
-    D, T = layout.D, layout.T
-    if homos.dim() != 4 or tuple(homos.shape[1:]) != (D, 3, 3) or homos.shape[0] < 1:
-        raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
+    D = layout.D
     qk = _quad_map(quad_keep, D)
-    grid = getattr(layout, "quad_grid", None)
+    grid = getattr(layout, "quad_grid", None)      # (a layout object made before PackedLayout recorded its grid: nothing to compare with)
     if grid is not None and tuple(quad_keep.shape[1:]) != tuple(grid):
         raise RuntimeError(f"quad_keep is {tuple(quad_keep.shape[1:])} quads per plane, the layout's block table was built from {tuple(grid)}")
     bl = layout.blocks
@@ -593,27 +448,115 @@ def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: 
         raise RuntimeError(f"{who}: the layout's block table must be contiguous int32 [D, ceil(Hs/8), ceil(Ws/8)] on the pool's device")
     if bool(getattr(spec, "tile", (0, 0))[0]) != (layout.tile is not None):
         raise RuntimeError(f"{who}: RenderSpec.tile and the layout's tile must both name the tile-exact layout, or neither")
-    dev = pool.device
-    C = int(homos.shape[0])
-    N, idx = _path_indices(frame_cam, frame_t, C, T, dev, who)
+    return layout.T, types.SimpleNamespace(entry="vl3d_render_fwd_baked_pool", dims=(D, layout.Hs, layout.Ws), device=pool.device, qk=qk,
+                                           head=(L.ptr(bl), L.ptr(pool), int(layout.T)), culled=(int(culled_rgba8) & 0xFFFFFFFF,))
+
+
+def _baked_render(who, src, n, frame0, path, homos, H, W, spec, out, frames8, bg, cull_scratch=None):
+    """the one call of the four baked renders: `n` output frames of source `src` (_baked_dense / _baked_pool) -- the run from `frame0` under
+    homos [D,3,3], or the `path` (C, idx [2,n] on the device) under homos [C,D,3,3] -- into the float sink (`out`, or fresh buffers) or the
+    display sink (`frames8`, `bg`).  Fills vl3d_baked_frames and vl3d_baked_out and calls src.entry."""
+    dev = src.device
     homos = homos.detach().to(torch.float32).contiguous()
-    d = _desc_dims(D, N, layout.Hs, layout.Ws, H, W, spec, L.STACK_DTYPE["u8"])
+    desc = _desc_dims(src.dims[0], n, src.dims[1], src.dims[2], H, W, spec, L.STACK_DTYPE["u8"])
+    sel, sink = L.BakedFrames(frame0=int(frame0)), L.BakedOut()
+    if path is not None:
+        sel.n_cams, sel.frame_cam, sel.frame_t = path[0], path[1][0].data_ptr(), path[1][1].data_ptr()
     if frames8 is not None:
-        channels, bg = _display_out(out, frames8, bg, N, H, W, dev, who)
+        sink.channels, bgc = _display_out(out, frames8, bg, n, H, W, dev, who)
+        sink.frames, sink.bg, ret = frames8.data_ptr(), (None if bgc is None else L.C.addressof(bgc)), frames8
     else:
-        rgb, alpha = _out_buffers(out, N, H, W, dev, who)
+        ret = _out_buffers(out, n, H, W, dev, who)
+        sink.rgb, sink.alpha = ret[0].data_ptr(), ret[1].data_ptr()
     with torch.cuda.device(dev):
-        cull = _path_cull_scratch(d, C, dev, cull_scratch, who)
-        if frames8 is not None:
-            L.check(L.lib().vl3d_render_fwd_baked_pool_path_u8(d, L.ptr(bl), L.ptr(pool), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]),
-                                                               L.ptr(qk), *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull),
-                                                               L.ptr(frames8), channels, bg, L.stream_ptr(dev)),
-                    "vl3d_render_fwd_baked_pool_path_u8")
-            return frames8
-        L.check(L.lib().vl3d_render_fwd_baked_pool_path(d, L.ptr(bl), L.ptr(pool), int(T), L.ptr(homos), C, L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(qk),
-                                                        *_qgrid(qk, spec), int(culled_rgba8) & 0xFFFFFFFF, L.ptr(cull), L.ptr(rgb), L.ptr(alpha),
-                                                        L.stream_ptr(dev)), "vl3d_render_fwd_baked_pool_path")
-    return rgb, alpha
+        cull = None
+        if src.qk is not None:
+            cull = _cull_scratch(desc, dev) if path is None else _path_cull_scratch(desc, path[0], dev, cull_scratch, who)
+        grid = (0, 0) if src.qk is None else _qgrid(src.qk, spec)
+        L.check(getattr(L.lib(), src.entry)(desc, *src.head, L.ptr(homos), sel, L.ptr(src.qk), *grid, *src.culled, L.ptr(cull), sink,
+                                            L.stream_ptr(dev)), src.entry)
+    return ret
+
+
+def _check_run(who, frame0, nframes, T, homos, D, of):
+    """a run of one camera: frames inside the T of the source (`of`: how the message names it), homos [D,3,3]"""
+    if not (0 <= frame0 and nframes >= 1 and frame0 + nframes <= T):
+        raise RuntimeError(f"{who}: frames {frame0} .. {frame0 + nframes - 1} leave the {of} {T}")
+    if homos.shape != (D, 3, 3):
+        raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
+
+
+def _check_path(who, frame_cam, frame_t, T, homos, D, device):
+    """a camera path: homos [C,D,3,3], the indices range-checked and uploaded -> (n output frames, (C, idx [2,n] int32 on `device`))"""
+    if homos.dim() != 4 or tuple(homos.shape[1:]) != (D, 3, 3) or homos.shape[0] < 1:
+        raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
+    C = int(homos.shape[0])
+    n, idx = _path_indices(frame_cam, frame_t, C, T, device, who)
+    return n, (C, idx)
+
+
+def _check_bg(who, frames8, bg):
+    if bg is not None and frames8 is None:
+        raise ValueError(f"{who}: `bg` belongs to the display frames (`frames8=`)")
+
+
+def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, frames8=None, bg=None):
+    """render_frame_run on the BAKED texels of a playback model (videoloop3d_amd/baked.py; vl3d_render_fwd_baked): `baked` [D,T,Hs,Ws,4] uint8 --
+    activated, times 255, truncated (baked.bake_texels) -- filtered bilinearly AFTER the activation, as a player filters the exported 8-bit
+    atlases; nothing is activated behind the blend, so spec.rgb_act / alpha_act / act_order are not read.  Coverage (hard cut, culled quads,
+    tile-exact layout) is decided by the float kernels' own code.  The planar convention only (RenderSpec.mpv()); forward only -- a baked
+    model is not trained: inputs that require a gradient are refused.  -> (rgb [n,H,W,3], alpha [n,H,W]) float32.
+    `frames8` (uint8 [n,H,W,3|4] on the device): the DISPLAY frames instead -- baked.display_frames(rgb, alpha, bg, channels), byte for byte,
+    written by the render launch (the display sink of vl3d_baked_out); no float output exists and `frames8` is returned.  `bg`: the background
+    colour, 3 floats, or None."""
+    who = "render_frame_run_baked"
+    _check_bg(who, frames8, bg)
+    T, src = _baked_dense(who, baked, homos, spec, quad_keep)
+    _check_run(who, frame0, nframes, T, homos, src.dims[0], "clip of")
+    return _baked_render(who, src, int(nframes), frame0, None, homos, H, W, spec, out, frames8, bg)
+
+
+def render_frame_run_baked_pool(layout, pool, frame0, nframes, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, frames8=None,
+                                bg=None):
+    """render_frame_run_baked from the baked POOL of a packed tile-culled model (baked.BakedPool; vl3d_render_fwd_baked_pool): `layout` the
+    packed.PackedLayout whose block table addresses `pool` [n_slots * 64, 4] uint8 (8 x 8-texel blocks of baked RGBA8 texels), `quad_keep`
+    [D,QH,QW] the quad map the table was built from, `culled_rgba8` the texel (r | g << 8 | b << 16 | a << 24) a block without storage reads
+    as (BakedPool.culled_rgba8) -- both required, by keyword.  The kernel trusts the table: the layout's table and the quad map are checked
+    here against the layout's own dimensions.  Frames frame0 .. frame0 + nframes - 1 of the model's layout.T -> (rgb [n,H,W,3], alpha [n,H,W]) float32: the bits of
+    render_frame_run_baked on the unpacked texels, without the dense clip.  The planar convention only; forward only.  `frames8`, `bg`: the
+    display frames instead, as render_frame_run_baked takes them."""
+    who = "render_frame_run_baked_pool"
+    _check_bg(who, frames8, bg)
+    T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
+    _check_run(who, frame0, nframes, T, homos, src.dims[0], "model's")
+    return _baked_render(who, src, int(nframes), frame0, None, homos, H, W, spec, out, frames8, bg)
+
+
+def render_path_baked(baked, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, cull_scratch=None, frames8=None, bg=None):
+    """A camera path on the baked clip (vl3d_render_fwd_baked with a path selection): N output frames in ONE plan launch plus ONE render launch,
+    output frame i being frame frame_t[i] of `baked` [D,T,Hs,Ws,4] uint8 seen by camera frame_cam[i] of `homos` [C,D,3,3] -- the spiral of the offline
+    renderer, where render_frame_run_baked takes one camera per call.  frame_cam / frame_t: host sequences or numpy arrays of N indices (checked
+    here: IndexError).  `cull_scratch`: an int64 buffer of vl3d_render_path_cull_scratch_bytes to hold the plane masks [C][tiles][2] across calls (a
+    tile-culled model; allocated per call when absent).  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal to
+    render_frame_run_baked(baked, frame_t[i], 1, homos[frame_cam[i]], ...).  Everything else as render_frame_run_baked, `frames8` / `bg` (the
+    display frames uint8 [N,H,W,3|4] instead) included."""
+    who = "render_path_baked"
+    _check_bg(who, frames8, bg)
+    T, src = _baked_dense(who, baked, homos, spec, quad_keep)
+    n, path = _check_path(who, frame_cam, frame_t, T, homos, src.dims[0], src.device)
+    return _baked_render(who, src, n, 0, path, homos, H, W, spec, out, frames8, bg, cull_scratch)
+
+
+def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, cull_scratch=None,
+                           frames8=None, bg=None):
+    """render_path_baked from the baked POOL (vl3d_render_fwd_baked_pool with a path selection): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
+    render_frame_run_baked_pool takes them, the path as render_path_baked takes it.  -> (rgb [N,H,W,3], alpha [N,H,W]) float32, frame i bit-equal
+    to render_frame_run_baked_pool(layout, pool, frame_t[i], 1, homos[frame_cam[i]], ...).  `frames8`, `bg`: the display frames instead."""
+    who = "render_path_baked_pool"
+    _check_bg(who, frames8, bg)
+    T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
+    n, path = _check_path(who, frame_cam, frame_t, T, homos, src.dims[0], src.device)
+    return _baked_render(who, src, n, 0, path, homos, H, W, spec, out, frames8, bg, cull_scratch)
 
 
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,
