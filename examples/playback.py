@@ -6,7 +6,9 @@ synthetic weights and a synthetic quad map), render the same spiral from the flo
 per chunk of 64 poses, `calls` in the output, the launch storing the uint8 frames itself -- `route`: no float frames, no torch epilogue),
 bytes of the three textures, PSNR between the float and the baked frames, and whether the pool's
 frames equal the dense baked frames --, then write the viewer package (geometry.obj, static.png,
-dynamic/%04d.png, meta.json).  `--full`: 720p, D = 32, T = 50."""
+dynamic/%04d.png, meta.json), OPEN it again from the files alone (`baked.open_viewer_package`: no model, no arguments) and play the spiral
+from it: load time (PNG decode apart), frames / s, and the byte difference of its frames against the in-process pool's (this model's tiles
+share their borders, so the export resamples them: close, not equal).  `--full`: 720p, D = 32, T = 50."""
 import argparse
 import json
 import os
@@ -23,8 +25,8 @@ import torch
 def run(full=False, outdir=None, dev="cuda:0"):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth, tiles
-    from videoloop3d_amd.baked import bake, bake_pool
-    from videoloop3d_amd.export import save_viewer_package
+    from videoloop3d_amd.baked import bake, bake_pool, culled_texel_rgba8, open_viewer_package
+    from videoloop3d_amd.export import read_png, save_viewer_package
     from videoloop3d_amd.MPV import MPMeshVid
     dev = torch.device(dev)
     H, W, D, T, hv, wv, N = (720, 1280, 32, 50, 36, 64, 150) if full else (180, 320, 16, 12, 18, 32, 60)
@@ -82,6 +84,24 @@ def run(full=False, outdir=None, dev="cuda:0"):
         files = save_viewer_package(model, where, poses, intr[:8], np.array([1.0, 100.0]))
         out["package"] = {"seconds": time.perf_counter() - t0, "files": len(files), "MB": sum(os.path.getsize(f) for f in files) / 1e6,
                           "dir": outdir or "(temporary)"}
+        # the package alone: open it, play the spiral from it
+        sync(); t0 = time.perf_counter()
+        opened = open_viewer_package(where, dev, bg_color="", culled_rgba8=culled_texel_rgba8("sigmoid", "sigmoid"))
+        sync(); load_s = time.perf_counter() - t0
+        t0 = time.perf_counter()      # the decoding alone, on one thread: every PNG of the package once more
+        for f in files:
+            if f.endswith(".png"):
+                read_png(f)
+        decode_s = time.perf_counter() - t0
+        opened.render_display(H, W, ext[:4], intr[:4], rt[:4])      # untimed: allocator
+        sync(); t0 = time.perf_counter()
+        shown = opened.render_display(H, W, ext, intr, rt)
+        sync(); dt = time.perf_counter() - t0
+        diff = (shown.int() - frames["baked_pool"].to(shown.device).int()).abs()
+        out["opened"] = {"load_seconds": load_s, "png_decode_one_thread_seconds": decode_s, "pool_MB": opened.nbytes / 1e6,
+                         "tile": list(opened.layout.tile), "planes": opened.layout.D, "frames": N, "frames_per_s": N / dt, "ms_per_frame": dt / N * 1e3,
+                         "bytes_differing_from_in_process_pool": int((diff > 0).sum()), "bytes": diff.numel(), "max_level_difference": int(diff.max()),
+                         "mean_level_difference": float(diff.float().mean())}
     out["shape"] = f"{H}x{W}, D={D}, T={T}, planes {tuple(model.stack.shape[2:4])}, {float(keep.float().mean()):.0%} of the quads kept, {N} spiral frames"
     return out
 

@@ -174,6 +174,25 @@ int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *bloc
                                const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
                                void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream);
 
+/* A viewer package's atlases -> the baked pool (csrc/vl3d_pool_from_atlas.hip; baked.open_viewer_package).  A package IS a baked pool in another
+ * order: RGBA8 tiles of th x tw texels of the kept quads, static tiles once (static_atlas, As_h x As_w texels, row-major grid of
+ * As_w / tw tiles per row), dynamic tiles per frame (dyn_atlas, Ad_h x Ad_w: the atlas of frame `frame`), culled quads absent.  The
+ * destination is the pool of the TILE-EXACT layout of the quad maps (Hs = QH th, Ws = QW tw) behind its block table `blocks`
+ * [D][ceil(Hs/8)][ceil(Ws/8)] (vl3d_render_fwd_baked_pool above).  tile_src [D][QH][QW] int32 (device): -1 (culled) | k << 1 | dynamic, k the
+ * tile's index in its atlas.  One call writes frame `frame`: a static block (entry & 1 == 0) only when frame == 0, a dynamic block at slot +
+ * frame; each of a written block's 64 texels (y, x) is 0 past the plane, culled_rgba8 inside a culled tile, else the tile's texel
+ * atlas[(k / gw) th + y % th][(k % gw) tw + x % tw] -- a static tile inside a dynamic block in every frame.  One wave per block, one lane
+ * per texel: 64 dwords stored contiguously.  A block without storage (-1) returns before any other load.
+ * Bounds.  A k outside its atlas grid reads culled_rgba8 (the kernel compares it with the grid the sizes give; the wrapper range-checks
+ * the host copy of tile_src before it uploads it); an atlas pointer may be NULL with sizes 0 x 0 (a package without static, or without
+ * dynamic, quads).  The table is trusted as packed.PackedLayout builds it for T frames: every stored slot (+ T - 1 for a dynamic block) lies
+ * inside the pool.  VL3D_EINVAL, nothing launched: D, T, th, tw, QH, QW < 1, Hs != QH th, Ws != QW tw, frame outside [0, T), a NULL or
+ * misaligned (4 bytes) pointer, an atlas size that is not a multiple of the tile size, D * blocks per plane > 2^31 - 1. */
+int vl3d_pool_from_atlas_rgba8(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t th, int32_t tw, int32_t QH, int32_t QW,
+                               const int32_t *blocks, const int32_t *tile_src, const uint8_t *static_atlas, int32_t As_h, int32_t As_w,
+                               const uint8_t *dyn_atlas, int32_t Ad_h, int32_t Ad_w, int32_t frame, uint32_t culled_rgba8, uint8_t *pool,
+                               vl3d_stream_t stream);
+
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).
  * grad_alpha_sums (optional): (T,H,W,2) gradient w.r.t. alpha_sums of the forward.

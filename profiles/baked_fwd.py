@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|open] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -25,7 +25,15 @@ the torch epilogue (baked.display_frames and the copy into the uint8 result); (b
 store, RGB8 with byte stores (VL3D_DISPLAY_STORE3=bytes), RGBA8.  Every (b) output is compared with (a)'s by torch.equal first (RGBA8: its
 colour bytes, and its alpha byte with display_frames'); then the four legs alternate round by round under HIP events that span the whole
 path.  Prints ms per frame (median, min .. max) and the ratio to (a); the condition is RGB8 (the store the library ships: packed) median <=
-(a) median for every storage and background."""
+(a) median for every storage and background.
+
+The OPEN leg (--legs open; not part of `all`; allocates neither stack): the scatter of a viewer package's atlases into the baked pool
+(vl3d_pool_from_atlas_rgba8, baked.open_viewer_package).  The culled pair's quad map in the tile-exact layout (35 x 63 tiles of 21 x 21 texels:
+planes of 735 x 1323), synthetic RGBA8 atlases packed like export._pack_tiles (atlas_grid, row major), resident on the device.  (a) the
+yardstick, the only route to this pool without the kernel: per plane the atlases unpacked with torch gathers into (T,Hs,Ws,4) texels, then
+PackedLayout.pack_plane_; (b) the T scatter calls.  The two pools are compared with torch.equal first; then (a) and (b) alternate under HIP
+events.  Prints ms per pool and GB/s of pool written for both, their ratio (condition: (b) <= (a)), and -- separately -- the seconds
+export.read_png takes for ONE dynamic atlas of this size on one thread (incompressible synthetic texels: an upper bound on inflate time)."""
 import argparse
 import json
 import os
@@ -43,7 +51,7 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "open"])
 ap.add_argument("--poses", type=int, default=120)
 ap.add_argument("--keep", type=float, default=0.165)
 ap.add_argument("--dyn", type=float, default=0.3)
@@ -66,10 +74,11 @@ D, T, H, W = a.D, a.T, a.H, a.W
 ref_e, Kr, tar_e, Kt = synth.make_cameras(H, W)
 homos = compute_homography(ref_e[None], Kr[None], tar_e[None], Kt[None], torch.tensor([0., 0., 1.]).expand(1, D, 3),
                            make_depths(D, 1.0, 100.0).flip(0)[None])[0].to(dev)
-stack = synth.make_plane_stack(D, T, H, W, seed=2, device=dev)
-baked = bake_texels(stack, "sigmoid", "sigmoid")
 spec = RenderSpec.mpv()
-out = (torch.empty((T, H, W, 3), device=dev), torch.empty((T, H, W), device=dev))
+if a.legs != "open":
+    stack = synth.make_plane_stack(D, T, H, W, seed=2, device=dev)
+    baked = bake_texels(stack, "sigmoid", "sigmoid")
+    out = (torch.empty((T, H, W, 3), device=dev), torch.empty((T, H, W), device=dev))
 
 
 def ab(legs):
@@ -95,7 +104,7 @@ def ab(legs):
 
 res = {"config": {"D": D, "T": T, "H": H, "W": W, "warm": a.warm, "timed_calls_per_leg": max(1, a.iters // a.rounds) * a.rounds, "rounds": a.rounds,
                   "legs": a.legs},
-       "stack_GB": {"float": stack.numel() * 4 / 1e9, "baked": baked.numel() / 1e9}}
+       "stack_GB": {} if a.legs == "open" else {"float": stack.numel() * 4 / 1e9, "baked": baked.numel() / 1e9}}
 
 
 def report(k, ms, per, bytes_px):
@@ -117,8 +126,8 @@ if a.legs in ("all", "dense"):
     res["byte_ratio"] = (16 * D + 16) / (4 * D + 16)
     print(f"baked is {res['speedup']:.2f}x the float forward (algorithmic byte ratio {res['byte_ratio']:.2f}x)")
 
-def culled_model(baked):
-    """the culled pair's model from the baked clip: (layout, pool, quad map uint8, BakedPool, the pool unpacked as a dense clip)"""
+def culled_maps():
+    """the culled pair's quad maps: (keep, dyn) [D,35,63] bool on the device"""
     QH, QW = 35, 63                                       # 36 x 64 vertices
     qy, qx = torch.meshgrid(torch.arange(QH, device=dev), torch.arange(QW, device=dev), indexing="ij")
     n_keep = round(a.keep * QH * QW)
@@ -130,7 +139,13 @@ def culled_model(baked):
         order = (((qy - cy) * (H / QH)) ** 2 + ((qx - cx) * (W / QW)) ** 2).flatten().argsort(stable=True)
         keep[d, order[:n_keep]] = True
         dyn[d, order[:n_dyn]] = True
-    keep, dyn = keep.view(D, QH, QW), dyn.view(D, QH, QW)
+    return keep.view(D, QH, QW), dyn.view(D, QH, QW)
+
+
+def culled_model(baked):
+    """the culled pair's model from the baked clip: (layout, pool, quad map uint8, BakedPool, the pool unpacked as a dense clip)"""
+    keep, dyn = culled_maps()
+    QH, QW = keep.shape[1:]
     lay = PackedLayout(keep, dyn, T, H, W)
     pool = torch.zeros((lay.n_slots * 64, 4), dtype=torch.uint8, device=dev)
     for d in range(D):
@@ -256,6 +271,82 @@ if a.legs == "display":
                 print(f"display [{name:6s} {'bg   ' if bg else 'no bg'}] {k:20s} {med[k] / N:.4f} ms/frame ({min(ms[k]) / N:.4f} .. {max(ms[k]) / N:.4f}) "
                       f"{med[k] / med['a_float_then_torch']:.3f} of (a); equal to (a): {same.get(k, '-')}{verdict}", flush=True)
     os.environ.pop("VL3D_DISPLAY_STORE3", None)
+if a.legs == "open":
+    import tempfile
+    import time
+    from videoloop3d_amd.baked import atlas_tile_map, pool_from_atlas_
+    from videoloop3d_amd.export import atlas_grid, read_png, write_png
+    keep, dyn = culled_maps()
+    QH, QW = keep.shape[1:]
+    th = tw = 21                                          # 35 x 63 tiles of 21 x 21: planes of 735 x 1323 texels
+    Hs, Ws = QH * th, QW * tw
+    lay = PackedLayout(keep, dyn, T, Hs, Ws, (th, tw))
+    culled = culled_texel_rgba8("sigmoid", "sigmoid")
+    tile_src = torch.full((D * QH * QW,), -1, dtype=torch.int32)
+    grids, atlases = [], []
+    for mesh, mask in enumerate((keep & ~dyn, dyn)):      # tile k of a mesh = its k-th quad in (d, qy, qx) order, as export._pack_tiles numbers them
+        idx = mask.flatten().nonzero()[:, 0].cpu()
+        tile_src[idx] = (torch.arange(len(idx), dtype=torch.int32) << 1) | mesh
+        gh, gw, _ = atlas_grid(len(idx))
+        grids.append((gh, gw))
+        atlases.append(torch.randint(0, 256, ((T if mesh else 1), gh * th, gw * tw, 4), dtype=torch.uint8, device=dev))
+    static, dyn_all = atlases[0][0], atlases[1]
+    tile_src = tile_src.view(D, QH, QW)
+    tm = atlas_tile_map(tile_src, lay, tuple(static.shape[:2]), tuple(dyn_all.shape[1:3]))
+    pool_k = torch.full((lay.n_slots * 64, 4), 0xAB, dtype=torch.uint8, device=dev)
+    pool_t = torch.zeros_like(pool_k)
+    # the yardstick's gather indices, per plane [Hs,Ws]: the texel's index in its (flattened) atlas, its mesh, kept or not -- built once, like tile_src
+    yy, xx = torch.meshgrid(torch.arange(Hs, device=dev), torch.arange(Ws, device=dev), indexing="ij")
+    src_t = tm.dev[:, yy // th, xx // tw].long()          # D,Hs,Ws
+    k_t, mesh_t = (src_t >> 1).clamp_min(0), (src_t & 1).bool() & (src_t >= 0)
+    gw_t = torch.where(mesh_t, grids[1][1], grids[0][1])
+    aw_t = torch.where(mesh_t, dyn_all.shape[2], static.shape[1])
+    flat_t = ((k_t // gw_t) * th + yy % th) * aw_t + (k_t % gw_t) * tw + xx % tw
+    kept_t = src_t >= 0
+    del src_t, k_t, gw_t, aw_t
+    fill = torch.tensor([(culled >> (8 * k)) & 0xff for k in range(4)], dtype=torch.uint8, device=dev)
+    static_f, dyn_f = static.view(-1, 4), dyn_all.view(T, -1, 4)
+
+    def leg_torch():
+        for d in range(D):
+            s_idx = torch.where(mesh_t[d], 0, flat_t[d])
+            d_idx = torch.where(mesh_t[d], flat_t[d], 0)
+            plane = torch.where(mesh_t[d][None, ..., None], dyn_f[:, d_idx], static_f[s_idx][None])
+            plane = torch.where(kept_t[d][None, ..., None], plane, fill)
+            lay.pack_plane_(pool_t, d, plane)
+
+    def leg_kernel():
+        for t in range(T):
+            pool_from_atlas_(lay, pool_k, tm, static, dyn_all[t], t, culled)
+    leg_torch()
+    leg_kernel()
+    same = torch.equal(pool_k, pool_t)
+    ms, per = ab({"a_torch_pack_plane": leg_torch, "b_pool_from_atlas": leg_kernel})
+    pool_bytes = lay.n_slots * 256
+    res["open"] = {"tile": [th, tw], "planes": [Hs, Ws], "slots": lay.n_slots, "pool_bytes": pool_bytes, "blocks_static": lay.n_static,
+                   "blocks_dynamic": lay.n_dynamic, "static_atlas": list(static.shape[:2]), "dynamic_atlas": list(dyn_all.shape[1:3]),
+                   "pools_equal": same}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        res["open"][k] = {"ms_median": med, "ms_min": min(v), "ms_max": max(v), "GB_s_pool_written": pool_bytes / med / 1e6}
+        print(f"open {k:20s} {med:9.3f} ms per pool (min {min(v):.3f}, max {max(v):.3f} over {a.rounds} rounds of {per})  "
+              f"{pool_bytes / med / 1e6:8.1f} GB/s of pool written ({pool_bytes / 1e6:.1f} MB)")
+    ratio = statistics.median(ms["b_pool_from_atlas"]) / statistics.median(ms["a_torch_pack_plane"])
+    res["open"]["kernel_over_torch"] = ratio
+    print(f"open: pools equal {same}; kernel / torch route {ratio:.4f} -> {'ok' if ratio <= 1 else 'MISSED'} (condition: not slower than the torch route)")
+    with tempfile.TemporaryDirectory() as tmp:            # PNG decode, reported separately: one dynamic atlas, one thread
+        png = os.path.join(tmp, "0000.png")
+        write_png(png, dyn_all[0].cpu().numpy())
+        secs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            read_png(png)
+            secs.append(time.perf_counter() - t0)
+        res["open"]["png_decode"] = {"seconds_per_atlas_median": statistics.median(secs), "file_MB": os.path.getsize(png) / 1e6,
+                                     "texel_MB": dyn_all[0].numel() / 1e6, "frames": T}
+        print(f"open: read_png of one dynamic atlas ({dyn_all.shape[1]} x {dyn_all.shape[2]}, {os.path.getsize(png) / 1e6:.1f} MB file): "
+              f"{statistics.median(secs) * 1e3:.1f} ms on one thread; x {T} frames = {statistics.median(secs) * T:.2f} s of decoding against "
+              f"{statistics.median(ms['b_pool_from_atlas']):.3f} ms of scatter")
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

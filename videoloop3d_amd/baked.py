@@ -335,3 +335,131 @@ def bake(module):
     if module.is_sparse and getattr(module, "quad_keep", None) is not None:
         qk = module.quad_keep.to(torch.uint8).contiguous().clone()
     return BakedMPV(texels, qk, module.spec, str(module.args.bg_color), _Camera(module))
+
+
+# ---- a viewer package read back --------------------------------------------------------------------------------------------------
+class _PackageCamera(_Camera):
+    """the camera of an opened viewer package: what _Camera offers (the same `plane_homographies` code object), built from the package's
+    files.  The geometry lives in the reference camera's frame (ref_extrin = I); `ref_intrin_mpi` is the pinhole that maps a vertex's
+    (x / z, y / z) to LATTICE coordinates of the tile-exact layout -- column c of the vertex grid is lattice c (tw - 1), row r lattice r (th - 1)."""
+
+    def __init__(self, planedepth, step, origin, tile):
+        import types
+        self.args, self.mpi_d = types.SimpleNamespace(), int(len(planedepth))
+        fx, fy = (tile[1] - 1) / step[0], (tile[0] - 1) / step[1]
+        self.ref_extrin = torch.eye(4, dtype=torch.float64)
+        self.ref_intrin_mpi = torch.tensor([[fx, 0.0, -origin[0] * fx], [0.0, fy, -origin[1] * fy], [0.0, 0.0, 1.0]], dtype=torch.float64).float()
+        self.planedepth = torch.as_tensor(planedepth, dtype=torch.float32).clone()
+
+
+def package_camera(pk):
+    """export.read_viewer_package's dict -> (camera, spec) of the opened model: the plane-pixel grid is the tile lattice itself, so the spec is
+    RenderSpec.mpv with identity activations (the texels are baked), scale 1, offset 0 and the package's tile."""
+    import dataclasses
+    from .render import RenderSpec
+    spec = dataclasses.replace(RenderSpec.mpv(rgb_act="none", alpha_act="none", scale=(1.0, 1.0), offset=(0.0, 0.0)), tile=tuple(pk["tile"]))
+    return _PackageCamera(pk["planedepth"], pk["step"], pk["origin"], pk["tile"]), spec
+
+
+def atlas_tile_map(tile_src, layout, static_hw, dyn_hw):
+    """`tile_src` [D,QH,QW] int32 on the HOST (-1 | k << 1 | dynamic: export.read_viewer_package) checked against the layout and the two atlas
+    grids -- every k below (Ah / th) * (Aw / tw) of its atlas -- and uploaded to the layout's device -> what pool_from_atlas_ takes.  An atlas
+    of (0, 0) has no tiles."""
+    import types
+    if layout.tile is None:
+        raise RuntimeError("atlas_tile_map: the destination is a tile-exact PackedLayout (tile=(th, tw))")
+    th, tw = layout.tile
+    ts = torch.as_tensor(tile_src)
+    if ts.is_cuda or ts.dtype != torch.int32 or tuple(ts.shape) != (layout.D,) + tuple(layout.quad_grid):
+        raise RuntimeError(f"atlas_tile_map: tile_src must be int32 [D,QH,QW] = {(layout.D,) + tuple(layout.quad_grid)} on the host, got {tuple(ts.shape)} {ts.dtype}")
+    for mesh, (h, w) in enumerate((static_hw, dyn_hw)):
+        if h % th or w % tw or (h == 0) != (w == 0):
+            raise RuntimeError(f"atlas_tile_map: an atlas of {h} x {w} texels is no grid of {th} x {tw} tiles")
+        k = ts[(ts >= 0) & ((ts & 1) == mesh)] >> 1
+        n = (h // th) * (w // tw)
+        if k.numel() and int(k.max()) >= n:
+            raise RuntimeError(f"atlas_tile_map: tile index {int(k.max())} outside the {'dynamic' if mesh else 'static'} atlas grid of {n} tiles")
+    if int(ts.min()) < -1:
+        raise RuntimeError("atlas_tile_map: tile_src entries are -1 or k << 1 | dynamic")
+    return types.SimpleNamespace(dev=ts.contiguous().to(layout.blocks.device), static_hw=tuple(static_hw), dyn_hw=tuple(dyn_hw))
+
+
+def pool_from_atlas_(layout, pool, tiles_map, static_atlas, dyn_atlas, frame, culled_rgba8):
+    """vl3d_pool_from_atlas_rgba8: one frame of a viewer package's atlases into the baked pool, in place.  layout: the tile-exact PackedLayout
+    of the package's quad maps; pool [n_slots * 64, 4] uint8; tiles_map: atlas_tile_map's product; static_atlas [As_h,As_w,4] / dyn_atlas
+    [Ad_h,Ad_w,4] uint8 on the device (None for an atlas of (0, 0)), dyn_atlas the dynamic atlas of frame `frame`.  Static blocks are written
+    with frame 0 only."""
+    L.check_cuda(pool, layout.blocks, tiles_map.dev)
+    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
+        raise RuntimeError("pool_from_atlas_: a contiguous uint8 pool [n_slots * 64, 4] of the layout")
+    bl = layout.blocks
+    if bl.dtype != torch.int32 or not bl.is_contiguous() or tuple(bl.shape) != (layout.D, -(-layout.Hs // 8), -(-layout.Ws // 8)) or bl.device != pool.device:
+        raise RuntimeError("pool_from_atlas_: the layout's block table must be contiguous int32 [D, ceil(Hs/8), ceil(Ws/8)] on the pool's device")
+    if not 0 <= int(frame) < layout.T:
+        raise IndexError(f"pool_from_atlas_: frame {frame} outside the clip of {layout.T} frames")
+    for at, hw in ((static_atlas, tiles_map.static_hw), (dyn_atlas, tiles_map.dyn_hw)):
+        if hw == (0, 0):
+            if at is not None:
+                raise RuntimeError("pool_from_atlas_: an atlas without tiles is passed as None")
+            continue
+        if at is None or at.dtype != torch.uint8 or tuple(at.shape) != hw + (4,) or not at.is_contiguous() or at.device != pool.device:
+            raise RuntimeError(f"pool_from_atlas_: an atlas must be contiguous uint8 [{hw[0]},{hw[1]},4] on the pool's device")
+    (th, tw), (QH, QW) = layout.tile, layout.quad_grid
+    with torch.cuda.device(pool.device):
+        L.check(L.lib().vl3d_pool_from_atlas_rgba8(layout.D, layout.T, layout.Hs, layout.Ws, th, tw, QH, QW, L.ptr(bl), L.ptr(tiles_map.dev),
+                                                   L.ptr(static_atlas), *tiles_map.static_hw, L.ptr(dyn_atlas), *tiles_map.dyn_hw, int(frame),
+                                                   int(culled_rgba8) & 0xFFFFFFFF, L.ptr(pool), L.stream_ptr(pool.device)),
+                "vl3d_pool_from_atlas_rgba8")
+    return pool
+
+
+@torch.no_grad()
+def open_viewer_package(dir, device, bg_color="", culled_rgba8=0):
+    """A viewer package on disk (export.save_viewer_package: geometry.obj, static.png, dynamic/%04d.png, meta.json) -> BakedPool on `device`,
+    from the files alone.  export.read_viewer_package gives the quad maps, the tile of every quad and the camera; the pool is the tile-exact
+    PackedLayout of the quad maps.  The static atlas is uploaded once; every dynamic PNG is decoded on a thread pool of at most 16 workers,
+    uploaded through pinned memory (two halves of one buffer in turn, so the host copy of frame t + 1 overlaps the upload and scatter of frame
+    t) and scattered by one vl3d_pool_from_atlas_rgba8 call per frame: the dense clip never exists, on the host or on the device.  The plane-pixel grid of the returned model is the tile lattice itself: spec = RenderSpec.mpv("none", "none") with
+    tile = (th, tw), scale 1, offset 0; the camera's ref_intrin_mpi maps x / z to lattice coordinates (_PackageCamera).  `culled_rgba8`: the
+    texel a culled tile reads as (a package does not say; culled_texel_rgba8(...) of the model's activations reproduces bake_pool's bytes)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .export import read_png, read_viewer_package
+    from .packed import PackedLayout
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("open_viewer_package: the baked model lives and renders on the device (no CPU fallback)")
+    pk = read_viewer_package(dir)
+    (th, tw), T = pk["tile"], pk["frame_count"]
+    keep, dyn = pk["quad_keep"], pk["quad_dyn"]
+    D, QH, QW = keep.shape
+    lay = PackedLayout(keep.to(dev), dyn.to(dev), T, QH * th, QW * tw, (th, tw))
+    tiles_map = atlas_tile_map(pk["tile_src"], lay, *pk["atlas_hw"])
+    pool = torch.zeros((lay.n_slots * 64, 4), dtype=torch.uint8, device=dev)
+
+    def load(path, hw, rule):
+        img = read_png(path)
+        if img.shape != hw + (4,):
+            raise RuntimeError(f"open_viewer_package: {path} decodes to {img.shape}, expected {hw + (4,)} (rule: {rule})")
+        return img
+    s_hw, d_hw = tiles_map.static_hw, tiles_map.dyn_hw
+    static = None if s_hw == (0, 0) else torch.from_numpy(load(pk["static_path"], s_hw, "static.png is an RGBA atlas of the size its header states")).to(dev)
+    if d_hw == (0, 0):      # no dynamic quads: every block is static, one call
+        pool_from_atlas_(lay, pool, tiles_map, static, None, 0, culled_rgba8)
+    else:
+        rule = "every PNG in dynamic/ is an RGBA atlas of one size"
+        pinned = torch.empty((2,) + d_hw + (4,), dtype=torch.uint8).pin_memory()      # two halves in turn
+        atlas = torch.empty((2,) + d_hw + (4,), dtype=torch.uint8, device=dev)
+        left = [torch.cuda.Event(), torch.cuda.Event()]      # recorded behind the scatter that read a half: the half may be written again
+        with torch.cuda.device(dev), ThreadPoolExecutor(max_workers=max(1, min(16, T))) as ex:      # (zlib releases the interpreter lock)
+            for t0 in range(0, T, 16):      # 16 decoded atlases on the host at most, never the clip's
+                paths = pk["dynamic_paths"][t0:t0 + 16]
+                for t, img in enumerate(ex.map(load, paths, [d_hw] * len(paths), [rule] * len(paths)), t0):
+                    h = t & 1
+                    left[h].synchronize()      # (an event never recorded is complete)
+                    pinned[h].copy_(torch.from_numpy(img))
+                    atlas[h].copy_(pinned[h], non_blocking=True)
+                    pool_from_atlas_(lay, pool, tiles_map, static, atlas[h], t, culled_rgba8)
+                    left[h].record()
+        torch.cuda.current_stream(dev).synchronize()
+    camera, spec = package_camera(pk)
+    return BakedPool(pool, lay, keep.to(dev).to(torch.uint8).contiguous(), spec, str(bg_color), camera, culled_rgba8)

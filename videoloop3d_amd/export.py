@@ -328,3 +328,241 @@ def save_viewer_package(model, outdir, poses, intrins, bds, fps=25):
     with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(frames) + 1))) as ex:      # (zlib releases the interpreter lock)
         list(ex.map(write_png, [out[2]] + names, [static] + list(frames)))
     return out + names
+
+
+# ---- reading a viewer package back ----------------------------------------------------------------------------------------------
+def _png_chunks(path):
+    """(IHDR fields (w, h, depth, colour, compression, filter, interlace), concatenated IDAT bytes) of a PNG file, every chunk's CRC checked."""
+    b = open(path, "rb").read()
+    if b[:8] != b"\x89PNG\r\n\x1a\n":
+        raise RuntimeError(f"read_png: {path}: not a PNG file (signature)")
+    pos, idat, hdr, ended = 8, [], None, False
+    while pos + 12 <= len(b) and not ended:
+        n, tag = struct.unpack(">I", b[pos:pos + 4])[0], b[pos + 4:pos + 8]
+        if pos + 12 + n > len(b):
+            raise RuntimeError(f"read_png: {path}: chunk {tag!r} runs past the end of the file")
+        body = b[pos + 8:pos + 8 + n]
+        if struct.unpack(">I", b[pos + 8 + n:pos + 12 + n])[0] != zlib.crc32(tag + body) & 0xFFFFFFFF:
+            raise RuntimeError(f"read_png: {path}: CRC mismatch in chunk {tag!r}")
+        if tag == b"IHDR":
+            if n != 13:
+                raise RuntimeError(f"read_png: {path}: IHDR of {n} bytes")
+            hdr = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat.append(body)
+        ended = tag == b"IEND"
+        pos += 12 + n
+    if hdr is None or not ended:
+        raise RuntimeError(f"read_png: {path}: no IHDR or no IEND chunk")
+    return hdr, b"".join(idat)
+
+
+def _png_check_header(path, hdr):
+    w, h, depth, colour, comp, filt, interlace = hdr
+    if depth != 8:
+        raise RuntimeError(f"read_png: {path}: bit depth {depth}; 8-bit RGB / RGBA only")
+    if colour not in (2, 6):
+        raise RuntimeError(f"read_png: {path}: colour type {colour} (palette / grey); 8-bit RGB / RGBA only")
+    if interlace != 0 or comp != 0 or filt != 0:
+        raise RuntimeError(f"read_png: {path}: interlaced (or an unknown compression / filter method); non-interlaced only")
+    if w == 0 or h == 0:
+        raise RuntimeError(f"read_png: {path}: empty image")
+    return w, h, 4 if colour == 6 else 3
+
+
+def png_size(path):
+    """(H, W, channels) of an 8-bit RGB / RGBA PNG from its header, without inflating it."""
+    with open(path, "rb") as f:
+        b = f.read(33)
+    if len(b) < 33 or b[:8] != b"\x89PNG\r\n\x1a\n" or b[12:16] != b"IHDR":
+        raise RuntimeError(f"read_png: {path}: not a PNG file (signature / IHDR)")
+    if struct.unpack(">I", b[29:33])[0] != zlib.crc32(b[12:29]) & 0xFFFFFFFF:
+        raise RuntimeError(f"read_png: {path}: CRC mismatch in chunk b'IHDR'")
+    w, h, c = _png_check_header(path, struct.unpack(">IIBBBBB", b[16:29]))
+    return h, w, c
+
+
+def read_png(path):
+    """8-bit RGB / RGBA PNG, non-interlaced, any number of IDAT chunks, all five filter types -> uint8 [H,W,3|4] (zlib + numpy: the inverse of
+    write_png, and of any encoder's output in those formats).  Rows of filter type 0, 1 and 2 are undone with array operations (Sub is a
+    running sum per channel, Up an add of the row above); Average and Paeth rows -- which write_png never emits -- take a plain loop per byte.
+    A CRC mismatch, another bit depth, a palette and interlace are refused."""
+    hdr, idat = _png_chunks(path)
+    w, h, c = _png_check_header(path, hdr)
+    try:
+        raw = zlib.decompress(idat)
+    except zlib.error as e:
+        raise RuntimeError(f"read_png: {path}: {e}")
+    if len(raw) != h * (1 + w * c):
+        raise RuntimeError(f"read_png: {path}: {len(raw)} bytes of image data for {h} rows of {1 + w * c}")
+    rows = np.frombuffer(raw, dtype=np.uint8).reshape(h, 1 + w * c)
+    ftype, data = rows[:, 0], rows[:, 1:]
+    if not ftype.any():                                                                  # what write_png writes: nothing to undo
+        return data.reshape(h, w, c).copy()
+    if int(ftype.max()) > 4:
+        raise RuntimeError(f"read_png: {path}: filter type {int(ftype.max())}")
+    out = data.copy()
+    sub = ftype == 1                                                                     # Sub: independent of the row above, all such rows at once
+    if sub.any():
+        out[sub] = np.cumsum(data[sub].reshape(-1, w, c), axis=1, dtype=np.uint8).reshape(-1, w * c)
+    zero = np.zeros(w * c, dtype=np.uint8)
+    for y in np.nonzero(ftype >= 2)[0].tolist():
+        up = out[y - 1] if y > 0 else zero
+        if ftype[y] == 2:
+            out[y] = data[y] + up                                                        # (uint8 arithmetic wraps modulo 256)
+            continue
+        cur, upl, fl = bytearray(w * c), up.tolist(), data[y].tolist()
+        for i in range(w * c):
+            a = cur[i - c] if i >= c else 0
+            if ftype[y] == 3:
+                pred = (a + upl[i]) >> 1
+            else:
+                bb, cc = upl[i], (upl[i - c] if i >= c else 0)
+                p = a + bb - cc
+                pa, pb, pc = abs(p - a), abs(p - bb), abs(p - cc)
+                pred = a if (pa <= pb and pa <= pc) else (bb if pb <= pc else cc)
+            cur[i] = (fl[i] + pred) & 0xFF
+        out[y] = np.frombuffer(bytes(cur), dtype=np.uint8)
+    return out.reshape(h, w, c)
+
+
+def _progression(q, what, where):
+    """the values q (x / z or y / z of every vertex) on ONE arithmetic progression -> (step, origin, index of every value).  The step is the
+    smallest positive difference between distinct values (values closer than 1e-4 of a first estimate are one grid line with float32 rounding),
+    refitted over the whole span; the origin is the smallest value."""
+    s = np.sort(q)
+    diffs = np.diff(s)
+    span = s[-1] - s[0]
+    big = diffs[diffs > 1e-6 * max(span, np.abs(s).max(), 1e-30)]
+    if len(big) == 0:
+        raise RuntimeError(f"read_viewer_package: {where}: the {what} of all vertices are one value: no vertex grid (rule: x / z and y / z lie on an arithmetic progression)")
+    step = float(big.min())
+    origin = float(s[0])
+    n = int(round(span / step))
+    step = span / n                                      # refit: the whole span over its number of steps
+    idx = np.rint((q - origin) / step)
+    off = np.abs(q - (origin + idx * step)).max() / step
+    if off > 1e-3:
+        raise RuntimeError(f"read_viewer_package: {where}: a vertex lies {off:.3g} steps off the arithmetic progression of the {what} "
+                           "(rule: x / z and y / z of all vertices lie on one arithmetic progression per axis)")
+    return step, origin, idx.astype(np.int64)
+
+
+def read_viewer_package(dir):
+    """The viewer package save_viewer_package writes, read back from its four artefacts alone -- no checkpoint, no training arguments:
+    meta.json, geometry.obj (`v x y z r g b`, `vt u v`, `f a/b c/d e/f`; vertex colour (1,0,0) = static mesh, (0,1,0) = dynamic mesh; two
+    consecutive faces over the same four uv corners = one quad) and the sizes of static.png / dynamic/%04d.png.  The PNGs' texels are NOT read
+    here (baked.open_viewer_package decodes them on a thread pool).  -> dict:
+      planedepth [D] float32 (the distinct vertex depths, ascending);  step, origin: (x, y) of the progression x / z, y / z of the vertex grid
+      (gen_mpi_vertices: a linspace grid through a pinhole);  quad_keep, quad_dyn [D,QH,QW] bool over the bounding box of the quads present;
+      tile_src [D,QH,QW] int32 = -1 (culled) | k << 1 | dynamic, k the tile's row-major index in its atlas;  tile (th, tw);
+      grid_w (static, dynamic atlas grid widths; 0 for an empty mesh), atlas_hw ((As_h, As_w), (Ad_h, Ad_w); (0, 0) for an empty mesh),
+      static_path, dynamic_paths, frame_count, fps, meta.
+    Whatever does not fit the layout is refused with the rule it breaks."""
+    import json
+    who = f"read_viewer_package: {dir}"
+    for name in ("meta.json", "geometry.obj", "static.png"):
+        if not os.path.isfile(os.path.join(dir, name)):
+            raise RuntimeError(f"{who}: {name} is missing (rule: a package is meta.json, geometry.obj, static.png and dynamic/%04d.png)")
+    meta = json.load(open(os.path.join(dir, "meta.json")))
+    want = ("fps", "fov", "frame_count", "near", "far", "up", "lookat", "limit")
+    if sorted(meta) != sorted(want):
+        raise RuntimeError(f"{who}: meta.json holds {sorted(meta)} (rule: the keys of the package's meta.json are {sorted(want)})")
+    T = int(meta["frame_count"])
+    # ---- the PNGs: names, count, sizes
+    ddir = os.path.join(dir, "dynamic")
+    have = sorted(f for f in os.listdir(ddir) if f.endswith(".png")) if os.path.isdir(ddir) else []
+    if T < 1 or have != [f"{i:04d}.png" for i in range(T)]:
+        raise RuntimeError(f"{who}: dynamic/ holds {len(have)} PNG files, meta.json says frame_count = {T} "
+                           "(rule: dynamic/0000.png .. one file per frame, their count equal to frame_count)")
+    dyn_paths = [os.path.join(ddir, f) for f in have]
+    sizes = {png_size(p) for p in dyn_paths}
+    if len(sizes) != 1:
+        raise RuntimeError(f"{who}: the dynamic frames have the sizes {sorted(sizes)} (rule: every PNG in dynamic/ has one size)")
+    static_path = os.path.join(dir, "static.png")
+    hw = {0: png_size(static_path), 1: sizes.pop()}
+    if hw[0][2] != 4 or hw[1][2] != 4:
+        raise RuntimeError(f"{who}: the atlases must be RGBA (rule: straight RGBA8 tiles)")
+    # ---- geometry.obj
+    v, vt, f = [], [], []
+    for line in open(os.path.join(dir, "geometry.obj")):
+        p = line.split()
+        if not p:
+            continue
+        if p[0] == "v" and len(p) == 7:
+            v.append([float(x) for x in p[1:]])
+        elif p[0] == "vt" and len(p) == 3:
+            vt.append([float(x) for x in p[1:]])
+        elif p[0] == "f" and len(p) == 4:
+            f.append([[int(i) for i in c.split("/")] for c in p[1:]])
+        else:
+            raise RuntimeError(f"{who}: geometry.obj line {line.strip()!r} (rule: `v x y z r g b`, `vt u v`, `f a/b c/d e/f`)")
+    if not f or len(f) % 2:
+        raise RuntimeError(f"{who}: {len(f)} faces (rule: two consecutive faces form one quad)")
+    v, vt, f = np.array(v, dtype=np.float64), np.array(vt, dtype=np.float64), np.array(f, dtype=np.int64) - 1
+    if f.min() < 0 or f[..., 0].max() >= len(v) or f[..., 1].max() >= len(vt):
+        raise RuntimeError(f"{who}: a face index outside the vertex / uv lists")
+    red, green = (v[:, 3:] == [1, 0, 0]).all(1), (v[:, 3:] == [0, 1, 0]).all(1)
+    if not (red | green).all():
+        raise RuntimeError(f"{who}: a vertex colour that is neither (1,0,0) nor (0,1,0) (rule: vertex colour marks the static / the dynamic mesh)")
+    z = v[:, 2]
+    if (z == 1).all():
+        raise RuntimeError(f"{who}: every vertex has z == 1: geometry written with normalize_verts carries no plane depths "
+                           "(rule: the plane of a vertex is its z)")
+    if not (z > 0).all():
+        raise RuntimeError(f"{who}: a vertex with z <= 0 (rule: the plane of a vertex is its z)")
+    planedepth = np.unique(z.astype(np.float32))
+    d_of_v = np.searchsorted(planedepth, z.astype(np.float32))
+    sx, ox, ix = _progression(v[:, 0] / z, "x / z", dir)
+    sy, oy, iy = _progression(v[:, 1] / z, "y / z", dir)
+    # ---- quads: faces (2i, 2i + 1) = triangles (c0, c1, c3), (c3, c2, c0) of the corners c0 .. c3
+    f1, f2 = f[0::2], f[1::2]
+    if not ((f2[:, 0] == f1[:, 2]).all() and (f2[:, 2] == f1[:, 0]).all()):
+        raise RuntimeError(f"{who}: faces 2i and 2i + 1 do not share their diagonal (rule: two consecutive faces with the same four uv corners form one quad)")
+    qv = np.concatenate([f1[..., 0], f2[:, 1:2, 0]], axis=1)            # n,4 vertex ids: c0, c1, c3, c2
+    quv = vt[np.concatenate([f1[..., 1], f2[:, 1:2, 1]], axis=1)]       # n,4,2
+    is_dyn = green[qv[:, 0]]
+    if not ((green[qv] == is_dyn[:, None]).all() and (d_of_v[qv] == d_of_v[qv[:, :1]]).all()):
+        raise RuntimeError(f"{who}: a quad whose vertices differ in colour or depth (rule: a quad lies in one plane of one mesh)")
+    qx, qy, qd = ix[qv].min(1), iy[qv].min(1), d_of_v[qv[:, 0]]
+    if not ((ix[qv].max(1) - qx == 1).all() and (iy[qv].max(1) - qy == 1).all()):
+        raise RuntimeError(f"{who}: a quad that does not span one step of the vertex grid per axis (rule: the grid index of a vertex is round((q - origin) / step))")
+    D, QH, QW = len(planedepth), int(qy.max()) + 1, int(qx.max()) + 1
+    flat = (qd * QH + qy) * QW + qx
+    if len(np.unique(flat)) != len(flat):
+        raise RuntimeError(f"{who}: two quads at one (plane, row, column) (rule: a quad is static or dynamic, once)")
+    # ---- tiles: invert normalize_uv on the first uv corner (texel centres of an Ah x Aw atlas, v flipped)
+    tile, grid_w, k_of = None, [0, 0], np.zeros(len(flat), dtype=np.int64)
+    for mesh, name in ((0, "static.png"), (1, "dynamic/%04d.png")):
+        sel = is_dyn == bool(mesh)
+        if not sel.any():
+            hw[mesh] = (0, 0, 4)                                        # an empty mesh: its atlas file is 1 x 1 and ignored
+            continue
+        Ah, Aw = hw[mesh][:2]
+        uv = quv[sel]
+        du, dv = uv[..., 0].max(1) - uv[..., 0].min(1), uv[..., 1].max(1) - uv[..., 1].min(1)
+        tw, th = int(round(float(np.median(du)) * Aw)) + 1, int(round(float(np.median(dv)) * Ah)) + 1      # uv extent of a quad = (tw - 1) / Aw
+        if tile is not None and tile != (th, tw):
+            raise RuntimeError(f"{who}: static tiles of {tile}, dynamic tiles of {(th, tw)} texels (rule: both atlases agree on the tile size)")
+        tile = (th, tw)
+        if th < 2 or tw < 2 or Ah % th or Aw % tw:
+            raise RuntimeError(f"{who}: {name} is {Ah} x {Aw}, the tiles are {th} x {tw} (rule: the atlas size is a multiple of the tile size)")
+        col, row = uv[:, 0, 0] * Aw - 0.5, Ah - 0.5 - uv[:, 0, 1] * Ah
+        ci, ri = np.rint(col).astype(np.int64), np.rint(row).astype(np.int64)
+        ok = (np.abs(du * Aw + 1 - tw) < 1e-2) & (np.abs(dv * Ah + 1 - th) < 1e-2) & (np.abs(col - ci) < 1e-2) & (np.abs(row - ri) < 1e-2) \
+            & (ci % tw == 0) & (ri % th == 0) & (ci >= 0) & (ri >= 0) & (ci < Aw) & (ri < Ah) \
+            & (np.abs(uv[:, 0, 0] - uv[..., 0].min(1)) < 1e-9) & (np.abs(uv[:, 0, 1] - uv[..., 1].max(1)) < 1e-9)
+        if not ok.all():
+            raise RuntimeError(f"{who}: the uv corners of a quad do not name a tile of {name} (rule: the first uv corner, through the inverse of "
+                               "normalize_uv, is the first texel of tile k; a quad spans (tw - 1) / Aw)")
+        grid_w[mesh] = Aw // tw
+        k_of[sel] = (ri // th) * grid_w[mesh] + ci // tw
+    keep = np.zeros(D * QH * QW, dtype=bool)
+    dyn = np.zeros(D * QH * QW, dtype=bool)
+    src = np.full(D * QH * QW, -1, dtype=np.int32)
+    keep[flat], dyn[flat], src[flat] = True, is_dyn, (k_of << 1 | is_dyn).astype(np.int32)
+    return {"planedepth": planedepth, "step": (sx, sy), "origin": (ox, oy),
+            "quad_keep": torch.from_numpy(keep.reshape(D, QH, QW)), "quad_dyn": torch.from_numpy(dyn.reshape(D, QH, QW)),
+            "tile_src": torch.from_numpy(src.reshape(D, QH, QW)), "tile": tile, "grid_w": tuple(grid_w),
+            "atlas_hw": (tuple(hw[0][:2]), tuple(hw[1][:2])), "static_path": static_path, "dynamic_paths": dyn_paths,
+            "frame_count": T, "fps": meta["fps"], "meta": meta}
