@@ -200,18 +200,45 @@ int vl3d_pool_from_atlas_rgba8(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int
  * cfg5 shards only fit with an 8-byte gradient texel).
  * scratch: caller-owned device buffer of vl3d_render_bwd_scratch_bytes(desc) bytes (plan written and read on
  * `stream`, no host sync); with scratch == NULL the universal global-atomics kernel is used.
- * desc->variant: 0 auto (LDS-staged owner-computes kernel when its on-device feasibility plan allows, atomics
- * kernel otherwise), 1 force atomics, 3 owner-computes kernel, one frame per thread in 64 x 16-pixel regions (2: the 8-row regions of
- * round 1, no longer built, selects 3), 4 = 3 with the 3x3 gather everywhere (reference for the 2x2 gather of no-minification tiles, which
- * must equal it bit for bit), 5 = one frame per thread in 32 x 16-pixel regions (the shipped planar convention with fp32 stacks; = 3
- * elsewhere), 6 / 7 = two frames per thread in 32 x 16 / 64 x 12-pixel regions wherever 0 takes frame pairs (dense stacks at the frame's
- * resolution, T >= 2, no layer regularisers; = 3 elsewhere): 0 picks between the two by measurement.  All of them produce the same
- * gradient bits. */
+ * desc->variant bits 0-3 (the rules, in order, with their measurements: choose_bwd(), csrc/vl3d_render_bwd_choice.h):
+ *   0  auto: the owner-computes kernels (LDS-staged, no atomics) when the on-device feasibility plan allows, the atomics kernel
+ *      otherwise.  T >= 2, dense, sigmoid / sigmoid: two frames per thread -- in 64 x 12-pixel regions without layer regularisers where
+ *      the stack is no larger than the frame (+7 %) along one axis at least, in 32 x 16 regions with them (not under VL3D_COORD_UTILS_MPI).
+ *      T = 1, no regularisers, the shipped planar convention (affine, hardcut, post, sigmoid / sigmoid, fp32): one frame per thread in flat
+ *      64 x 8 regions.  A quad map under VL3D_GRAD_CULLED_UNWRITTEN, same convention: one frame per thread in 32 x 16 regions.  Everything
+ *      else: one frame per thread in 64 x 16 regions.
+ *   1  the atomics kernel alone (also: scratch NULL or short, uv_noise_seed != 0)
+ *   2  one frame per thread in flat 64 x 8 regions at any T (shipped planar convention, dense, no regularisers; = 3 elsewhere)
+ *   3  one frame per thread in 64 x 16 regions, the owner table built one texel per thread
+ *   4  = 3 with the 3x3 gather everywhere (reference for the 2x2 gather of no-minification tiles, which must equal it bit for bit)
+ *   5  one frame per thread in 32 x 16 regions (shipped planar convention; = 3 elsewhere)
+ *   6 / 7  two frames per thread in 32 x 16 / 64 x 12 regions wherever 0 takes frame pairs WITHOUT regularisers; = 3 elsewhere
+ *   every other value = 3.  All of them produce the same gradient bits.
+ * vl3d_render_bwd_mask: 3 / 4 the 64 x 16 regions, 1 atomics, every other value flat 64 x 8 regions (its default).  vl3d_render_bwd_adam: a
+ * dense model (variant 0 only) rides the 32 x 16 frame pairs; a tile-culled one 32 x 16 one-frame regions, 64 x 16 with variant 3. */
 int64_t vl3d_render_bwd_scratch_bytes(const vl3d_render_desc *desc);
 int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float *homos,
                     const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha,
                     const float *grad_reg, const void *reg_state, const float *grad_alpha_sums, float *grad_stack, void *scratch,
                     int64_t scratch_bytes, vl3d_stream_t stream);
+
+/* Which kernel a backward call runs, without running it: the value the entry points themselves compute (the same two functions, no device
+ * touched, nothing enqueued).  entry: which entry point; has_quad_keep / has_reg_grads (grad_reg or grad_alpha_sums non-NULL) / scratch_bytes:
+ * as the call would pass them (scratch_bytes 0 = scratch NULL); fused_step: vl3d_render_bwd_adam (entry VL3D_BWD_ENTRY_ADAM) only.  Refusals
+ * are the entry's own descriptor refusals (VL3D_EINVAL / VL3D_EUNSUPPORTED) -- all but two it cannot see: the quad grid's rules (QH, QW are
+ * not passed) and an activation pair its convention is not built for.  width x rows: the workgroup's region, 0 x 0 for VL3D_BWD_ATOMICS;
+ * a feasible plan is the device's to decide -- family says what runs when it is. */
+enum { VL3D_BWD_ENTRY_RENDER = 0, VL3D_BWD_ENTRY_MASK = 1, VL3D_BWD_ENTRY_ADAM = 2 };
+enum { VL3D_BWD_ATOMICS = 0, VL3D_BWD_TILE = 1, VL3D_BWD_PAIR = 2, VL3D_BWD_PAIR12 = 3 };
+typedef struct vl3d_bwd_choice {
+    int32_t family;                        /* VL3D_BWD_*: atomics only | one frame per thread | frame pairs | frame pairs, 64 x 12 kernel */
+    int32_t width, rows;
+    int32_t reg, mask, adam, cull, f16;    /* the instantiation: regularisers' build, fifth channel, fused step, quad map, fp16 texels */
+    int32_t owner4;                        /* the owner table is built four texels per thread */
+    int32_t gather9;                       /* the 3x3 gather everywhere (variant 4) */
+} vl3d_bwd_choice;
+int vl3d_render_bwd_choice(const vl3d_render_desc *desc, int32_t entry, int32_t has_quad_keep, int32_t has_reg_grads, int64_t scratch_bytes,
+                           int32_t fused_step, vl3d_bwd_choice *out);
 
 /* Tile culling (MPI.py:288-442 "Tile Culling Algorithm": stage 2 renders only the quads that survived).  quad_keep is a device
  * byte map [D][QH][QW] over the cells of each plane's vertex grid ((Ws-1)/QW x (Hs-1)/QH texels per quad), 1 = the quad exists.

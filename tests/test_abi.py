@@ -45,6 +45,19 @@ def test_struct_layout_matches_header(built):
     assert ctypes.sizeof(built.Stage1ObjectiveDesc) == 64      # 4 x int32 + 12 x float
     assert ctypes.sizeof(built.BakedFrames) == 24              # 2 x int32 + 2 pointers
     assert ctypes.sizeof(built.BakedOut) == 40                 # 3 pointers + int32 + pad + pointer
+    assert ctypes.sizeof(built.BwdChoice) == 40                # 10 x int32
+
+
+def test_bwd_choice_fields_match_header(built):
+    """vl3d_bwd_choice is written by the library into the caller's buffer: the binding has the header's fields, all int32, in the header's order"""
+    src = open(os.path.join(ROOT, "include", "vl3d.h")).read()
+    body = re.search(r"typedef struct vl3d_bwd_choice \{(.*?)\} vl3d_bwd_choice;", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decls = [d.strip() for d in body.split(";") if d.strip()]
+    assert all(d.startswith("int32_t ") for d in decls)
+    names = [n.strip() for d in decls for n in d[len("int32_t "):].split(",")]
+    assert names == [n for n, _ in built.BwdChoice._fields_] and len(names) == 10
+    assert all(t is ctypes.c_int32 for _, t in built.BwdChoice._fields_)
 
 
 def test_cpu_tensor_is_rejected_loudly(built):

@@ -41,10 +41,15 @@ def _plan_feasible():
     return int(render.LAST_BWD_SCRATCH.view(torch.int32)[0].item())
 
 
+# what vl3d_render_bwd_choice reports for a dense call of T >= 2 frames without regularisers inside the pair dispatch (`fits`): (family, width,
+# rows) -- variant 0 takes variant 7's kernel there, the other two are kernels of their own
+CHOICE = {PAIRS_32x16: ("pair", 32, 16), PAIRS_64x12: ("pair12", 64, 12), 0: ("pair12", 64, 12), ONE_FRAME_64x16: ("tile", 64, 16)}
+
+
 def _grads(dev, spec_name, H, W, stack_scale, T, dtype, with_alpha, variants, D=5, runs=1):
     """gradient of every variant for one scene: a 2-degree in-plane rotation with a little zoom and perspective (taps off the axes,
     plan feasible), the frame centred on a stack of stack_scale times its size"""
-    from videoloop3d_amd.render import RenderSpec, render_planes
+    from videoloop3d_amd.render import RenderSpec, last_bwd_choice, render_planes
     Hs, Ws = int(H * stack_scale), int(W * stack_scale)
     assert Hs * 100 <= H * 107 and Ws * 100 <= W * 107, "outside the pair dispatch (`fits`): the case would not reach the kernels under test"
     kw = SPECS[spec_name]
@@ -68,6 +73,8 @@ def _grads(dev, spec_name, H, W, stack_scale, T, dtype, with_alpha, variants, D=
             else:
                 (gs,) = torch.autograd.grad(rgb, stack, g_rgb)
             assert _plan_feasible() == 1
+            # the kernel the variant names ran (equal bits from ONE kernel reached twice would prove nothing): no REG / MASK / ADAM / CULL
+            assert last_bwd_choice() == CHOICE[v] + (False, False, False, False, dtype == torch.float16)
             out[(v, run)] = gs.clone()
     return out
 
@@ -118,6 +125,8 @@ def test_pair12_against_the_oracle(dev):
     rgb, alpha = render_planes(s_gpu, homos.to(dev), H, W, RenderSpec(variant=PAIRS_64x12, **kw))
     (gs,) = torch.autograd.grad([rgb, alpha], s_gpu, [g_rgb.to(dev), g_a.to(dev)])
     assert _plan_feasible() == 1
+    from videoloop3d_amd.render import last_bwd_choice
+    assert last_bwd_choice()[:3] == CHOICE[PAIRS_64x12]
     assert float((gs.cpu() - gs_o).abs().max()) <= 1e-4 * max(1.0, float(gs_o.abs().max()))
 
 

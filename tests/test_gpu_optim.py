@@ -311,11 +311,18 @@ def test_unwritten_culled_gradient_without_regularisers(dev, variant):
         tiles.cull_stack_(stack, keep)
     homos = (torch.tensor([[1.0, 0, 14.0], [0, 1.0, 9.0], [0, 0, 1.0]]) @ bench_homos(D, H, W)).to(dev)
     g = synth.hash_uniform((T, H, W, 3), seed=5, device=dev) - 0.5
-    grads = []
+    from videoloop3d_amd.render import last_bwd_choice
+    grads, chosen = [], []
     for lean, v in ((False, 0), (True, variant)):
         leaf = stack.clone().requires_grad_(True)
         rgb, _ = render_planes(leaf, homos, H, W, RenderSpec.mpv(variant=v), quad_keep=keep, grad_culled_unwritten=lean)
         grads.append(torch.autograd.grad(rgb, leaf, g)[0])
+        chosen.append(last_bwd_choice())
+    # the zero-filling 64 x 16 kernel against the one the docstring names: (family, width, rows, REG, MASK, ADAM, CULL, F16) -- REG is the
+    # instantiation that skips; the default takes the plain kernel's register budget in 32-wide regions
+    assert chosen[0] == ("tile", 64, 16, False, False, False, True, False)
+    assert chosen[1] == {0: ("tile", 32, 16, False, False, False, True, False), 3: ("tile", 64, 16, True, False, False, True, False),
+                         5: ("tile", 32, 16, True, False, False, True, False)}[variant]
     kt = tiles.quad_to_texel_mask(keep.cpu(), Hs, Ws).to(dev)[:, None, :, :, None].expand_as(grads[0])
     assert float(grads[0][kt].abs().max()) > 1e-4 and float(grads[0][~kt].abs().max()) == 0.0
     assert torch.equal(grads[1][kt], grads[0][kt])
@@ -541,7 +548,7 @@ def test_tile_culled_step_fused_into_the_backward(dev, smooth, T, scale, rot, pa
             Kc = K.copy()
             Kc[0, 2] -= ox
             Kc[1, 2] -= oy
-            losses, feasible = [], []
+            losses, feasible, chosen = [], [], []
             for model, opt in models:
                 for grp in opt.param_groups:
                     grp["lr"] = 5e-3 * 0.9 ** it
@@ -552,9 +559,14 @@ def test_tile_culled_step_fused_into_the_backward(dev, smooth, T, scale, rot, pa
                     loss = loss + 0.2 * extra["rgb_smooth"].sum() + 0.2 * extra["a_smooth"].sum() + 0.01 * extra["sparsity"].sum()
                 loss.backward()
                 feasible.append(int(R.LAST_BWD_SCRATCH[:1].view(torch.int32)))
+                chosen.append(R.last_bwd_choice())
                 opt.step()
                 losses.append(float(loss.detach()))
             assert feasible[0] == feasible[1] == (0 if rot else 1)
+            # two different kernels: the culled backward's one-frame kernel without the step | the fused step's instantiation in the regions
+            # the variant names -- (family, width, rows, REG, MASK, ADAM, CULL, F16)
+            assert chosen[0][0] == "tile" and chosen[0][5:7] == (False, True)
+            assert chosen[1] == ("tile", 64 if variant == 3 else 32, 16, True, False, True, True, False)
             sa, sb = oa.state[oa.p], ob.state[ob.p]
             assert torch.equal(sa["last_step"], sb["last_step"]) and oa.t == ob.t == it + 1
             if rot:

@@ -312,9 +312,9 @@ def test_bwd_tile_720p_matches_atomics(dev):
     stack = synth.make_plane_stack(D, T, Hs, Ws, seed=2, device=dev).requires_grad_(True)
     homos = bench_homos(D, H, W).to(dev)
     g = (synth.hash_uniform((T, H, W, 3), seed=5, device=dev) - 0.5)
-    out = {}
+    out, chosen = {}, {}
     from videoloop3d_amd import _lib as L
-    from videoloop3d_amd.render import _desc
+    from videoloop3d_amd.render import _desc, bwd_choice
     rgb, alpha = render_planes(stack.detach(), homos, H, W, RenderSpec.mpv())
     for variant in (1, 0, 3, 2):
         # raw ABI with the gradient buffer pre-filled with NaN: a texel no kernel writes stays NaN (deterministic, unlike hoping
@@ -328,6 +328,11 @@ def test_bwd_tile_720p_matches_atomics(dev):
         assert int(scratch.view(torch.int32)[0].item()) == (0 if variant == 1 else 1)
         assert torch.isfinite(gs).all()
         out[variant] = gs
+        c = bwd_choice(d, "render", False, False, nscratch)
+        chosen[variant] = (c.family, c.width, c.rows)
+    # ... from four different kernels: atomics | frame pairs in 64 x 12 regions | one frame per thread in 64 x 16 | in flat 64 x 8 regions
+    F = L.BWD_FAMILY
+    assert chosen == {1: (F["atomics"], 0, 0), 0: (F["pair12"], 64, 12), 3: (F["tile"], 64, 16), 2: (F["tile"], 64, 8)}
     scale = float(out[1].abs().max())
     # frame pairs (default dispatch) and the one-frame tile kernel: the same bits
     assert torch.equal(out[0], out[3])

@@ -66,6 +66,14 @@ class BakedOut(C.Structure):         # vl3d_baked_out: the float sink (rgb, alph
     _fields_ = [("rgb", _P), ("alpha", _P), ("frames", _P), ("channels", C.c_int32), ("bg", _P)]
 
 
+class BwdChoice(C.Structure):       # vl3d_bwd_choice: which kernel a backward call runs (vl3d_render_bwd_choice)
+    _fields_ = [(n, C.c_int32) for n in ("family", "width", "rows", "reg", "mask", "adam", "cull", "f16", "owner4", "gather9")]
+
+
+BWD_ENTRY = {"render": 0, "mask": 1, "adam": 2}
+BWD_FAMILY = {"atomics": 0, "tile": 1, "pair": 2, "pair12": 3}
+
+
 class Stage1ObjectiveDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("scale_invariant", C.c_int32),
                 ("w_img", C.c_float), ("w_loop", C.c_float), ("w_sparsity", C.c_float), ("w_density", C.c_float),
@@ -88,6 +96,7 @@ SIGNATURES = {
     "vl3d_render_path_cull_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
+    "vl3d_render_bwd_choice": ([C.POINTER(RenderDesc), _I32, _I32, _I32, _I64, _I32, C.POINTER(BwdChoice)], C.c_int),
     "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_bwd_adam": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(AdamWindow), _P], C.c_int),
     "vl3d_render_reg_state_bytes": ([C.POINTER(RenderDesc)], C.c_int64),

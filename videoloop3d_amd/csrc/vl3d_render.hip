@@ -15,19 +15,22 @@ namespace {
 //   (AFFINE,    HARDCUT, POST)  the reference's MPV.py planar convention              all nine activation pairs
 //   (AFFINE_PLANES, HARDCUT, POST)  MPV.py atlas-cell sampling: per-plane texel transform + quad extent   sigmoid/sigmoid
 //   (UTILS_MPI, ZEROS,   POST), (UTILS_MPI, HARDCUT, PRE)  cross-check conventions     sigmoid/sigmoid
-int dispatch(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s) {
+typedef int (*ConvFn)(bool, const vl3d_render_desc *, const RenderArgs &, hipStream_t);
+ConvFn conv_of(const vl3d_render_desc *d) {
     const int c = d->coord_mode, b = d->border_mode, o = d->act_order;
-    if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_ZEROS && o == VL3D_ACT_PRE) return conv_utils_zeros_pre(bwd, d, a, s);
-    if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_ZEROS && o == VL3D_ACT_POST) return conv_utils_zeros_post(bwd, d, a, s);
-    if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_PRE) return conv_utils_hardcut_pre(bwd, d, a, s);
-    if (c == VL3D_COORD_AFFINE_PLANES && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_POST) return conv_affine_planes_hardcut_post(bwd, d, a, s);
-    if (c == VL3D_COORD_AFFINE && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_POST) {
-        if (d->rgb_act == VL3D_ACT_SIGMOID && d->alpha_act == VL3D_ACT_SIGMOID) return conv_affine_hardcut_post_sig(bwd, d, a, s);
-        return conv_affine_hardcut_post_other(bwd, d, a, s);
-    }
+    if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_ZEROS && o == VL3D_ACT_PRE) return conv_utils_zeros_pre;
+    if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_ZEROS && o == VL3D_ACT_POST) return conv_utils_zeros_post;
+    if (c == VL3D_COORD_UTILS_MPI && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_PRE) return conv_utils_hardcut_pre;
+    if (c == VL3D_COORD_AFFINE_PLANES && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_POST) return conv_affine_planes_hardcut_post;
+    if (c == VL3D_COORD_AFFINE && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_POST)
+        return (d->rgb_act == VL3D_ACT_SIGMOID && d->alpha_act == VL3D_ACT_SIGMOID) ? conv_affine_hardcut_post_sig : conv_affine_hardcut_post_other;
     vl3d_set_error("unsupported (coord_mode, border_mode, act_order): built are (utils_mpi, zeros, pre|post), (utils_mpi, hardcut, pre), "
                    "(affine, hardcut, post)");
-    return VL3D_EUNSUPPORTED;
+    return nullptr;
+}
+int dispatch(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s) {
+    const ConvFn conv = conv_of(d);
+    return conv ? conv(bwd, d, a, s) : VL3D_EUNSUPPORTED;
 }
 
 int check_desc(const vl3d_render_desc *d) {
@@ -120,15 +123,10 @@ extern "C" int vl3d_render_fwd_culled(const vl3d_render_desc *desc, const void *
     return render_fwd_impl(desc, stack, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha, alpha_sums, stream);
 }
 
-// scratch layout: per-plane records | one int4 window per (tile, plane), sized for the smallest tile interior any variant
-// uses (60 x 6) | (256-byte aligned) owner table, one uint16 per (plane, texel)
+// scratch layout: per-plane records | one int4 window per (tile, plane), as many as the region shape with the most tiles needs
+// (bwd_max_tiles, vl3d_render_bwd_choice.h) | (256-byte aligned) owner table, one uint16 per (plane, texel)
 static int64_t owner_table_off(const vl3d_render_desc *desc) {
-    // window records: the largest tile count of any backward kernel (owned pixels per tile: 62 x 14 / 60 x 12 for the one-frame tile
-    // kernel without / with regularisers, 30 x 14 / 28 x 12 for the frame pairs, 62 x 6 for the flat one-frame regions of a single frame)
-    auto ntiles = [&](int iw, int ih) { return (int64_t)((desc->W + iw - 1) / iw) * ((desc->H + ih - 1) / ih); };
-    int64_t tiles = ntiles(62, 14);
-    for (const auto &t : {ntiles(60, 12), ntiles(30, 14), ntiles(28, 12), ntiles(62, 6)}) tiles = t > tiles ? t : tiles;
-    const int64_t b = (int64_t)plan_win_off(desc->D) * sizeof(float) + tiles * desc->D * 16;
+    const int64_t b = (int64_t)plan_win_off(desc->D) * sizeof(float) + bwd_max_tiles(desc->H, desc->W) * desc->D * 16;
     return (b + 255) & ~(int64_t)255;
 }
 
@@ -140,6 +138,75 @@ extern "C" int64_t vl3d_render_bwd_scratch_bytes(const vl3d_render_desc *desc) {
 
 static int render_reg_fwd_impl(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
                                int32_t QW, double *sums, void *reg_state, vl3d_stream_t stream);
+static void set_reg_state(RenderArgs &a, const vl3d_render_desc *d, const void *reg_state);
+static int check_mask_desc(const vl3d_render_desc *d, const char *who);
+static int check_adam_desc(const vl3d_render_desc *desc, bool has_quad_map);
+
+// ---- what the three backward entries share ----------------------------------------------------------------------------------------------
+// the forward's inputs and saved outputs, the incoming gradients and the gradient to write
+static void set_bwd_io(RenderArgs &a, const vl3d_render_desc *desc, const void *stack, const float *homos, const float *rgb, const float *alpha,
+                       const float *grad_rgb, const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
+                       float *grad_stack) {
+    if (grad_reg) set_reg_state(a, desc, reg_state);
+    a.stack = (const float *)stack; a.homos = homos;
+    a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
+    a.g_rgb = grad_rgb; a.g_alpha = grad_alpha; a.g_reg = grad_reg; a.g_asum = grad_alpha_sums; a.g_stack = grad_stack;
+}
+// the call's policy; with an owner-computes path: the plan and the owner table inside the caller's scratch
+static void set_bwd_setting(RenderArgs &a, const vl3d_render_desc *desc, const BwdSetting &set, void *scratch) {
+    a.bwd_policy = set.policy; a.gather9 = set.gather9; a.owner4 = set.owner4;
+    if (set.policy == BWD_NONE) return;
+    a.plan = (const float *)scratch;
+    a.owner = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(scratch) + owner_table_off(desc));
+}
+// the owner-computes kernels may take the call: enough scratch (0 bytes: none), and no add_uv_noise -- a jittered tap can leave the 1-pixel
+// halo they stage
+static bool bwd_tile_ok(const vl3d_render_desc *desc, int64_t scratch_bytes) {
+    return scratch_bytes >= vl3d_render_bwd_scratch_bytes(desc) && desc->uv_noise_seed == 0;
+}
+
+extern "C" int vl3d_render_bwd_choice(const vl3d_render_desc *desc, int32_t entry, int32_t has_quad_keep, int32_t has_reg_grads,
+                                      int64_t scratch_bytes, int32_t fused_step, vl3d_bwd_choice *out) {
+    int rc = check_desc(desc);
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(out != nullptr, "vl3d_render_bwd_choice: null out");
+    VL3D_REQUIRE(entry >= VL3D_BWD_ENTRY_RENDER && entry <= VL3D_BWD_ENTRY_ADAM && (fused_step != 0) == (entry == VL3D_BWD_ENTRY_ADAM),
+                 "vl3d_render_bwd_choice: entry is VL3D_BWD_ENTRY_RENDER, _MASK or _ADAM, and fused_step names the last");
+    if (entry == VL3D_BWD_ENTRY_MASK) {
+        rc = check_mask_desc(desc, "vl3d_render_bwd_mask");
+        if (rc != VL3D_OK) return rc;
+        VL3D_REQUIRE(!has_quad_keep && desc->uv_noise_seed == 0, "vl3d_render_bwd_mask: dense models without add_uv_noise");
+    }
+    if (entry == VL3D_BWD_ENTRY_ADAM) {
+        rc = check_adam_desc(desc, has_quad_keep != 0);
+        if (rc != VL3D_OK) return rc;
+        VL3D_REQUIRE(desc->uv_noise_seed == 0 && scratch_bytes >= vl3d_render_bwd_scratch_bytes(desc),
+                     "vl3d_render_bwd_adam: no add_uv_noise, scratch of vl3d_render_bwd_scratch_bytes()");
+    }
+    if (!conv_of(desc)) return VL3D_EUNSUPPORTED;
+    VL3D_REQUIRE(!has_quad_keep || desc->coord_mode != VL3D_COORD_AFFINE_PLANES, "tile culling is not available with per-plane texel transforms");
+    // the RenderArgs the entry would build, as far as the choice reads them (a flag the entries carry as a pointer: any non-null address, never
+    // dereferenced), then the launch's own bwd_facts_of() with the convention the descriptor dispatches to
+    static const float present = 0.0f;
+    const bool adam = entry == VL3D_BWD_ENTRY_ADAM, qk = has_quad_keep != 0;
+    RenderArgs a = render_args_of(desc);
+    a.g_reg = has_reg_grads ? &present : nullptr;
+    a.mask = entry == VL3D_BWD_ENTRY_MASK ? &present : nullptr;
+    a.ad.p = adam ? reinterpret_cast<float4 *>(const_cast<float *>(&present)) : nullptr;
+    a.quad_keep = qk ? reinterpret_cast<const unsigned char *>(&present) : nullptr;
+    a.g_f16 = desc->stack_dtype == VL3D_F16;
+    a.grad_culled_unwritten = (qk && (adam || (desc->grad_flags & VL3D_GRAD_CULLED_UNWRITTEN))) ? 1 : 0;
+    const BwdSetting set = bwd_setting_of(entry, desc->variant & 0xf, bwd_tile_ok(desc, scratch_bytes), qk);
+    a.bwd_policy = set.policy; a.gather9 = set.gather9; a.owner4 = set.owner4;
+    const bool planes = desc->coord_mode == VL3D_COORD_AFFINE_PLANES;      // compiled as VL3D_COORD_AFFINE with 16-float plane records
+    const BwdFacts f = bwd_facts_of(a, planes ? VL3D_COORD_AFFINE : desc->coord_mode, desc->border_mode, desc->act_order, desc->rgb_act, desc->alpha_act,
+                                    a.g_f16 != 0, planes ? 16 : 9);
+    const BwdChoice c = choose_bwd(f);
+    const bool none = c.family == VL3D_BWD_ATOMICS;
+    *out = vl3d_bwd_choice{c.family, none ? 0 : BWD_REGIONS[c.shape].width, none ? 0 : BWD_REGIONS[c.shape].rows,
+                           c.reg, c.mask, c.adam, c.cull, c.f16, c.owner4, f.set.gather9};
+    return VL3D_OK;
+}
 
 // reg_state: flags [H][W] u8 | coverage masks [H][W][2] u64 | sign words [ceil(D/4)][T][H][W][4] u16 | patch words (same shape) (256-byte aligned parts)
 struct RegLayout { int64_t masks, signs, patch, total; };
@@ -234,22 +301,12 @@ extern "C" int vl3d_render_bwd_mask(const vl3d_render_desc *desc, const void *st
     VL3D_REQUIRE(!grad_reg || reg_state, "vl3d_render_bwd_mask: grad_reg needs the reg_state the forward with regularisers filled");
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
     RenderArgs a = render_args_of(desc);
-    if (grad_reg) set_reg_state(a, desc, reg_state);
-    a.stack = (const float *)stack; a.homos = homos;
-    a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
-    a.g_rgb = grad_rgb; a.g_alpha = grad_alpha; a.g_reg = grad_reg; a.g_asum = grad_alpha_sums; a.g_stack = grad_stack;
+    set_bwd_io(a, desc, stack, homos, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums, grad_stack);
     a.mask = mask; a.g_label = grad_label; a.g_mask = grad_mask;
     VL3D_REQUIRE(desc->uv_noise_seed == 0, "vl3d_render_bwd_mask: add_uv_noise jitters the colour samples only (MPI.py:519-522, 568-572): render the label in a pass of its own");
-    const bool want_tile = (desc->variant & 0xf) != 1 && scratch != nullptr && scratch_bytes >= vl3d_render_bwd_scratch_bytes(desc);
-    a.gather9 = (desc->variant & 0xf) == 4;
-    a.owner4 = (desc->variant & 0xf) != 3 && (desc->variant & 0xf) != 4;
-    if (want_tile) {
-        a.plan = (const float *)scratch;
-        a.owner = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(scratch) + owner_table_off(desc));
-        // flat 64 x 8 regions (two 512-thread workgroups per CU at this instantiation's 128 registers) unless variant 3 / 4 ask for the 16 rows:
-        // stage-1 iterations +3.3 % at the reference's crop, +2 % for a 720p frame (profiles/r05d_s1_mask_rows.txt), same bits
-        a.tile_rows = ((desc->variant & 0xf) == 3 || (desc->variant & 0xf) == 4) ? 16 : 8;
-    } else {
+    const BwdSetting set = bwd_setting_of(VL3D_BWD_ENTRY_MASK, desc->variant & 0xf, bwd_tile_ok(desc, scratch ? scratch_bytes : 0), false);
+    set_bwd_setting(a, desc, set, scratch);
+    if (set.policy == BWD_NONE) {
         const size_t texels = (size_t)desc->D * desc->T * desc->Hs * desc->Ws;
         VL3D_HIP(hipMemsetAsync(grad_stack, 0, texels * 16, (hipStream_t)stream));
         VL3D_HIP(hipMemsetAsync(grad_mask, 0, texels * 4, (hipStream_t)stream));
@@ -349,35 +406,15 @@ static int render_bwd_impl(const vl3d_render_desc *desc, const void *stack, cons
     VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack, "null pointer passed to vl3d_render_bwd");
     VL3D_REQUIRE(!grad_reg || reg_state, "vl3d_render_bwd: grad_reg needs the reg_state the forward with regularisers filled");
     RenderArgs a = render_args_of(desc);
-    if (grad_reg) set_reg_state(a, desc, reg_state);
-    a.stack = (const float *)stack; a.homos = homos;
-    a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
-    a.g_rgb = grad_rgb; a.g_alpha = grad_alpha; a.g_reg = grad_reg; a.g_asum = grad_alpha_sums; a.g_stack = grad_stack;
+    set_bwd_io(a, desc, stack, homos, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums, grad_stack);
     a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
     set_cull_geometry(a, desc, QH, QW);
     a.g_f16 = desc->stack_dtype == VL3D_F16;
     a.grad_culled_unwritten = (quad_keep && (desc->grad_flags & VL3D_GRAD_CULLED_UNWRITTEN)) ? 1 : 0;
-    // variant: 0 auto (tile kernel when its on-device plan says feasible, else atomics), 1 force atomics,
-    //          3 tile kernel (16-row regions, one frame per thread), 4 = 3 without the 2x2 gather, 2 = the tile kernel in flat 64 x 8
-    //          regions (round 1 measured them 18.9 vs 16.8 ms at cfg3 and dropped them; round 5 brought them back for ONE frame, T = 1,
-    //          where 2520 half-size workgroups on 1024 slots beat 1092 on 512: 0.380 vs 0.394 ms, same bits -- the default there)
-    //          6 = the frame pairs in their 32 x 16 regions, 7 = in 64 x 12 regions (768 threads), wherever variant 0 takes frame pairs
-    // (add_uv_noise: a jittered tap can leave the 1-pixel halo the owner-computes kernels stage -- the atomics kernel takes the call)
-    const bool want_tile = (desc->variant & 0xf) != 1 && scratch != nullptr && scratch_bytes >= vl3d_render_bwd_scratch_bytes(desc) &&
-                           desc->uv_noise_seed == 0;
     a.ablate = (desc->variant >> 4) & 0xf;
-    a.gather9 = (desc->variant & 0xf) == 4;
-    a.owner4 = (desc->variant & 0xf) != 3 && (desc->variant & 0xf) != 4;
-    if (want_tile) {
-        a.plan = (const float *)scratch;
-        a.owner = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(scratch) + owner_table_off(desc));
-        const int bv = desc->variant & 0xf;
-        // 17: 16 rows, frame-pair kernels / flat one-frame regions allowed; 18: 32-wide one-frame regions; 8: flat 64 x 8 one-frame regions;
-        // 19 / 20: the frame pairs in 32 x 16 / 64 x 12 regions where variant 0 would take pairs (elsewhere the 16-row tile kernel)
-        a.tile_rows = bv == 0 ? 17 : (bv == 5 ? 18 : (bv == 2 ? 8 : (bv == 6 ? 19 : (bv == 7 ? 20 : 16))));
-    } else {
-        a.plan = nullptr;
-        a.tile_rows = 0;
+    const BwdSetting set = bwd_setting_of(VL3D_BWD_ENTRY_RENDER, desc->variant & 0xf, bwd_tile_ok(desc, scratch ? scratch_bytes : 0), quad_keep != nullptr);
+    set_bwd_setting(a, desc, set, scratch);
+    if (set.policy == BWD_NONE) {
         const size_t bytes = (size_t)desc->D * desc->T * desc->Hs * desc->Ws * (desc->stack_dtype == VL3D_F16 ? 8 : 16);
         VL3D_HIP(hipMemsetAsync(grad_stack, 0, bytes, (hipStream_t)stream));
     }
@@ -394,6 +431,18 @@ extern "C" int64_t vl3d_render_bwd_adam_class_bytes(const vl3d_render_desc *desc
     return ((int64_t)desc->D * desc->Hs * desc->Ws + 16 * (int64_t)desc->Ws + 64) * 8;
 }
 
+static int check_adam_desc(const vl3d_render_desc *desc, bool has_quad_map) {
+    const int bv = desc->variant & 0xf;
+    if (!(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT && desc->act_order == VL3D_ACT_POST &&
+          desc->rgb_act == VL3D_ACT_SIGMOID && desc->alpha_act == VL3D_ACT_SIGMOID && desc->stack_dtype == VL3D_F32 &&
+          (has_quad_map ? (bv == 0 || bv == 3 || bv == 5) : (desc->T >= 2 && bv == 0)))) {
+        vl3d_set_error("vl3d_render_bwd_adam: built for the stage-2 iteration -- (affine, hardcut, post), sigmoid / sigmoid, fp32 stack, "
+                       "T >= 2 and variant 0 for a dense model; use vl3d_render_bwd(_culled) + vl3d_adam_window_step otherwise");
+        return VL3D_EUNSUPPORTED;
+    }
+    return VL3D_OK;
+}
+
 extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *stack, const float *homos, const float *rgb, const float *alpha,
                                     const float *grad_rgb, const float *grad_alpha, const float *grad_reg, const void *reg_state,
                                     const float *grad_alpha_sums, float *grad_stack, void *scratch, int64_t scratch_bytes,
@@ -408,14 +457,8 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
     VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack && scratch, "null pointer passed to vl3d_render_bwd_adam");
     VL3D_REQUIRE(!grad_reg || reg_state, "vl3d_render_bwd_adam: grad_reg needs the reg_state the forward with regularisers filled");
     const uint8_t *qk = adam->quad_keep;
-    const int bv = desc->variant & 0xf;
-    if (!(desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT && desc->act_order == VL3D_ACT_POST &&
-          desc->rgb_act == VL3D_ACT_SIGMOID && desc->alpha_act == VL3D_ACT_SIGMOID && desc->stack_dtype == VL3D_F32 &&
-          (qk ? (bv == 0 || bv == 3 || bv == 5) : (desc->T >= 2 && bv == 0)))) {
-        vl3d_set_error("vl3d_render_bwd_adam: built for the stage-2 iteration -- (affine, hardcut, post), sigmoid / sigmoid, fp32 stack, "
-                       "T >= 2 and variant 0 for a dense model; use vl3d_render_bwd(_culled) + vl3d_adam_window_step otherwise");
-        return VL3D_EUNSUPPORTED;
-    }
+    rc = check_adam_desc(desc, qk != nullptr);
+    if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(scratch_bytes >= vl3d_render_bwd_scratch_bytes(desc), "vl3d_render_bwd_adam: scratch smaller than vl3d_render_bwd_scratch_bytes()");
     VL3D_REQUIRE(adam->param && adam->exp_avg && adam->exp_avg_sq && adam->last_step && adam->hist && adam->step >= 1 &&
                      adam->step < (1ll << 31), "vl3d_render_bwd_adam: null pointer / bad step in the adam window");
@@ -440,16 +483,11 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
                                     adam->step, qk, adam->quad_dyn, adam->QH, adam->QW, adam->plane_boxes, adam->blocks, nullptr, adam->boxes_scratch, s);
     if (rc != VL3D_OK) return rc;
     RenderArgs a = render_args_of(desc);
-    if (grad_reg) set_reg_state(a, desc, reg_state);
-    a.stack = (const float *)stack; a.homos = homos;
-    a.rgb = const_cast<float *>(rgb); a.alpha = const_cast<float *>(alpha);
-    a.g_rgb = grad_rgb; a.g_alpha = grad_alpha; a.g_reg = grad_reg; a.g_asum = grad_alpha_sums; a.g_stack = grad_stack;
+    set_bwd_io(a, desc, stack, homos, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums, grad_stack);
     a.quad_keep = qk; a.QH = adam->QH; a.QW = adam->QW;
     set_cull_geometry(a, desc, adam->QH, adam->QW);
     a.grad_culled_unwritten = qk ? 1 : 0;
-    a.plan = (const float *)scratch;
-    a.owner = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(scratch) + owner_table_off(desc));
-    a.tile_rows = qk ? (bv == 3 ? 16 : 18) : 17;      // 16 / 18: the one-frame tile kernel (64- / 32-wide regions, tile-culled models), 17: the frame pairs
+    set_bwd_setting(a, desc, bwd_setting_of(VL3D_BWD_ENTRY_ADAM, desc->variant & 0xf, true, qk != nullptr), scratch);
     const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step), bc2 = 1.0 - pow((double)adam->beta2, (double)adam->step);
     const int ts = vl3d_adam::TS;
     a.ad.p = reinterpret_cast<float4 *>(adam->param); a.ad.m = reinterpret_cast<float4 *>(adam->exp_avg);

@@ -13,9 +13,8 @@ namespace vl3d_render_detail {
 int VL3D_CONV_FN(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s) {
 #define VL3D_CASE(R, A)                                                                                     \
     if (d->rgb_act == R && d->alpha_act == A) {                                                             \
-        if (bwd) launch<true, VL3D_CONV_COORD, VL3D_CONV_BORDER, VL3D_CONV_ORDER, R, A>(a, s);              \
-        else launch<false, VL3D_CONV_COORD, VL3D_CONV_BORDER, VL3D_CONV_ORDER, R, A>(a, s);                 \
-        return VL3D_OK;                                                                                     \
+        if (bwd) return launch<true, VL3D_CONV_COORD, VL3D_CONV_BORDER, VL3D_CONV_ORDER, R, A>(a, s);       \
+        return launch<false, VL3D_CONV_COORD, VL3D_CONV_BORDER, VL3D_CONV_ORDER, R, A>(a, s);               \
     }
 #if VL3D_CONV_ACTS != 2
     VL3D_CASE(VL3D_ACT_SIGMOID, VL3D_ACT_SIGMOID)

@@ -19,6 +19,7 @@
 // This header holds every render kernel and its launch template; it is compiled once per sampling / compositing convention
 // (vl3d_render_conv.inc, included by the vl3d_render_c*.hip stubs) so that the conventions build in parallel.
 #pragma once
+#include <stddef.h>
 #include "vl3d_common.h"
 
 // per-plane records of the homography table: 9 floats (the 3x3 matrix) by default; the VL3D_COORD_AFFINE_PLANES convention
@@ -26,6 +27,7 @@
 // coordinates, 3 pad -- so that every plane can have its own affine texel transform (folded into its matrix by the host) and its own
 // quad extent: the reference's atlas-cell layout (MPV.py:75-81: plane p samples at xm*pitch - (p % grid_w)/grid_w, include/vl3d.h).
 #include "vl3d_adam.h"
+#include "vl3d_render_bwd_choice.h"
 
 #ifndef VL3D_HS
 #define VL3D_HS 9
@@ -87,8 +89,8 @@ struct RenderArgs {
     int QH, QW;
     const unsigned long long *cull_masks;
     // dispatch options (plain arguments: the ABI is re-entrant from any number of host threads / streams)
-    int tile_rows;           // backward: 0 = no owner-computes path for this call (atomics kernel only); 16 = tile kernel; 17 = 16 rows,
-                             // frame-pair kernels allowed
+    int bwd_policy;          // backward: the BwdPolicy of the call (vl3d_render_bwd_choice.h: what desc->variant asks for at its entry point;
+                             // BWD_NONE = the atomics kernel only).  Read by the host alone (choose_bwd): it stays in the slot so that no later field moves
     int reg_fwd;             // forward dispatch: 1 = the regulariser-sums kernel instead of the render, 2 = render AND sums in one pass
     // hit-slot layer order of the smoothness regularisers (see "Layer regularisers in hit-slot order" below): the caller's reg_state
     // buffer, written by the forward with regularisers and read by the backward
@@ -115,6 +117,8 @@ struct RenderArgs {
     // their border texels.  (At the END of the struct: no earlier kernel argument moves -- see Tstride above.)
     int q_th, q_tw;
 };
+// the byte layout is part of the kernels' schedules (Tstride above; tests/test_kernel_schedule_canary.py): a field that moves fails here first
+static_assert(sizeof(RenderArgs) == 440 && offsetof(RenderArgs, bwd_policy) == 240 && offsetof(RenderArgs, ad) == 320, "RenderArgs: the byte layout moved");
 
 // one entry point per compiled convention (coord_mode, border_mode, act_order): vl3d_render_c*.hip
 int conv_utils_zeros_pre(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s);
@@ -128,6 +132,7 @@ int conv_affine_planes_hardcut_post(bool bwd, const vl3d_render_desc *d, const R
 
 namespace {
 using vl3d_render_detail::RenderArgs;
+using namespace vl3d_render_detail;      // (the backward choice: vl3d_render_bwd_choice.h)
 
 // does the texel-space box [tnx,txx] x [tny,txy] (grown by 2 texels) touch a kept quad of plane d?  Quads are the QH x QW cells of
 // the plane's vertex grid, (Ws-1)/QW x (Hs-1)/QH texels each.  Conservative by construction: a workgroup skips a plane only
@@ -2024,16 +2029,17 @@ __global__ __launch_bounds__(PW * PROWS, VL3D_PAIR_MIN_WAVES) void render_bwd_pa
     }
 }
 
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool REG = false, bool ADAM = false, int PW = 32>
-void launch_pair(const RenderArgs &a, hipStream_t s) {
-    constexpr int RH = 1, IW = PW - 2 * RH, IH = PROWS - 2 * RH;
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool REG = false, bool ADAM = false>
+void launch_pair(const RenderArgs &a, hipStream_t s, const BwdChoice &) {
+    constexpr int SHAPE = BWD_32X16, PW = BWD_REGIONS[SHAPE].width, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
+    static_assert(PROWS == BWD_REGIONS[SHAPE].rows, "render_bwd_pair_k's rows are not the shape table's");
     RenderArgs b = a;
     b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
     const int nwin = b.tiles_x * b.tiles_y * a.D;
     hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
                        reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
     hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
-                       const_cast<unsigned short *>(a.owner), PW, PW == 64 ? 10 : 9);
+                       const_cast<unsigned short *>(a.owner), PW, bwd_slot_bits(SHAPE));
     hipLaunchKernelGGL((render_bwd_pair_k<COORD, BORDER, ORDER, RACT, AACT, F16, REG, ADAM, PW>),
                        dim3((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), dim3(PW * PROWS), 0, s, b);
 }
@@ -2125,15 +2131,16 @@ __global__ __launch_bounds__(P12W * P12ROWS, 6) void render_bwd_pair12_k(RenderA
 #undef VL3D_PAIR_GRAD
 
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
-void launch_pair12(const RenderArgs &a, hipStream_t s) {
-    constexpr int RH = 1, IW = P12W - 2 * RH, IH = P12ROWS - 2 * RH;
+void launch_pair12(const RenderArgs &a, hipStream_t s, const BwdChoice &) {
+    constexpr int SHAPE = BWD_64X12, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
+    static_assert(P12W == BWD_REGIONS[SHAPE].width && P12ROWS == BWD_REGIONS[SHAPE].rows, "render_bwd_pair12_k's region is not the shape table's");
     RenderArgs b = a;
     b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
     const int nwin = b.tiles_x * b.tiles_y * a.D;
     hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
                        reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
     hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
-                       const_cast<unsigned short *>(a.owner), P12W, 10);
+                       const_cast<unsigned short *>(a.owner), P12W, bwd_slot_bits(SHAPE));
     hipLaunchKernelGGL((render_bwd_pair12_k<COORD, BORDER, ORDER, RACT, AACT, F16>),
                        dim3((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), dim3(P12W * P12ROWS), 0, s, b);
 }
@@ -2268,144 +2275,110 @@ __global__ __launch_bounds__(512) void render_fwd_reg_k(RenderArgs a, int tiles_
 }
 
 // ---- launch templates ---------------------------------------------------------------------------------------------
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, int ROWS, bool REG, bool F16 = false, bool MASK = false, bool ADAM = false, int RWT = 64>
-void launch_tile(const RenderArgs &a, hipStream_t s) {
-    constexpr int RH = 1, IW = RWT - 2 * RH, IH = ROWS - 2 * RH;
-    constexpr int SLOT_BITS = RWT * ROWS > 512 ? 10 : 9;
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, int SHAPE, bool REG, bool F16 = false, bool MASK = false, bool ADAM = false>
+void launch_tile(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
+    constexpr int RWT = BWD_REGIONS[SHAPE].width, ROWS = BWD_REGIONS[SHAPE].rows, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
+    constexpr int SLOT_BITS = bwd_slot_bits(SHAPE);
     RenderArgs b = a;
     b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
     const int nwin = b.tiles_x * b.tiles_y * a.D;
     hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
                        reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
-    if (a.T == 1 && !a.ad.p && a.owner4)      // (a single frame: four texels per thread; the fused optimiser step keeps its per-texel records)
+    if (c.owner4)
         hipLaunchKernelGGL(bwd_owner_table4_k, dim3(((a.Ws + 3) / 4 + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH,
                            const_cast<unsigned short *>(a.owner), RWT, SLOT_BITS);
     else
         hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
                            const_cast<unsigned short *>(a.owner), RWT, SLOT_BITS);
     const dim3 grid((unsigned)(b.tiles_x * b.tiles_y * a.T)), block(RWT * ROWS);
-    if constexpr (ADAM) {      // (tile-culled models only: the dense fused step rides the frame pairs -- the one-frame form measured 202 against 213-218 it/s)
+    if constexpr (ADAM) {      // (tile-culled models only, with the regularisers' instantiation)
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, true, false, true, false, true, RWT>), grid, block, 0, s, b);
     } else if constexpr (MASK) {       // (dense models only: the entry point refuses a quad map)
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, REG, F16, false, true, false, RWT>), grid, block, 0, s, b);
-    } else if (a.quad_keep)
+    } else if (c.cull)
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, REG, F16, true, false, false, RWT>), grid, block, 0, s, b);
     else
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, REG, F16, false, false, false, RWT>), grid, block, 0, s, b);
 }
 
+// one signature for the three launch templates (the frame pairs read nothing of the choice: their instantiation is all of it)
+using BwdLauncher = void (*)(const RenderArgs &, hipStream_t, const BwdChoice &);
+
+// what choose_bwd() reads: a call's arguments and a compiled convention -- launch_t passes its template constants, vl3d_render_bwd_choice()
+// (vl3d_render.hip) the ones its descriptor dispatches to.  THE builder: both go through here
+inline BwdFacts bwd_facts_of(const RenderArgs &a, int coord, int border, int order, int ract, int aact, bool f16, int plane_record) {
+    BwdFacts f{};
+    f.coord = coord; f.border = border; f.order = order; f.ract = ract; f.aact = aact; f.f16 = f16; f.plane_record = plane_record;
+    f.T = a.T; f.H = a.H; f.W = a.W; f.Hs = a.Hs; f.Ws = a.Ws;
+    f.set = BwdSetting{(BwdPolicy)a.bwd_policy, a.gather9 != 0, a.owner4 != 0};
+    f.reg = a.g_reg || a.g_asum; f.mask = a.mask != nullptr; f.adam = a.ad.p != nullptr; f.qk = a.quad_keep != nullptr;
+    f.gcu = a.grad_culled_unwritten != 0;
+    return f;
+}
+
+inline int bwd_not_built(const BwdChoice &c) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "render backward: no kernel built for the choice (family %d, %d x %d regions, reg %d mask %d adam %d cull %d f16 %d)",
+             c.family, BWD_REGIONS[c.shape].width, BWD_REGIONS[c.shape].rows, (int)c.reg, (int)c.mask, (int)c.adam, (int)c.cull, (int)c.f16);
+    vl3d_set_error(msg);
+    return VL3D_EUNSUPPORTED;
+}
+
 template <bool BWD, int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
-void launch_t(const RenderArgs &a, hipStream_t s) {
+int launch_t(const RenderArgs &a, hipStream_t s) {
     dim3 grid((a.W + TILE_X - 1) / TILE_X, (a.H + TILE_Y - 1) / TILE_Y, a.T), block(TILE_X * TILE_Y);
     // the loop-mask channel (a.mask != NULL) is built for the convention stage 1 ships (MPI.py planar path, sigmoid / sigmoid, fp32); the
     // entry points refuse every other descriptor
     constexpr bool MASKABLE = COORD == VL3D_COORD_AFFINE && BORDER == VL3D_BORDER_HARDCUT && ORDER == VL3D_ACT_POST &&
                               RACT == VL3D_ACT_SIGMOID && AACT == VL3D_ACT_SIGMOID && !F16;
     if constexpr (BWD) {
-        if (a.tile_rows) {
+        constexpr bool SHIPPED9 = MASKABLE && VL3D_HS == 9, SIG = RACT == VL3D_ACT_SIGMOID && AACT == VL3D_ACT_SIGMOID;
+        const BwdChoice c = choose_bwd(bwd_facts_of(a, COORD, BORDER, ORDER, RACT, AACT, F16, VL3D_HS));
+        if (c.family != VL3D_BWD_ATOMICS) {
+            // (family, shape, REG, MASK, ADAM) -> the instantiation's launcher, before anything is enqueued.  The guards are choose_bwd()'s
+            // `shipped`, `shipped9` and `sig` at compile time: what this translation unit builds
+            BwdLauncher go = nullptr;
+#define VL3D_CONV COORD, BORDER, ORDER, RACT, AACT
+#define VL3D_BWD_CASE(BUILT, KEY, ...)      \
+    case bwd_key KEY:                       \
+        if constexpr (BUILT) go = &__VA_ARGS__; \
+        break;
+            switch (bwd_key(c)) {
+                VL3D_BWD_CASE(MASKABLE, (VL3D_BWD_TILE, BWD_64X8, true, true), launch_tile<VL3D_CONV, BWD_64X8, true, false, true>)
+                VL3D_BWD_CASE(MASKABLE, (VL3D_BWD_TILE, BWD_64X8, false, true), launch_tile<VL3D_CONV, BWD_64X8, false, false, true>)
+                VL3D_BWD_CASE(MASKABLE, (VL3D_BWD_TILE, BWD_64X16, true, true), launch_tile<VL3D_CONV, BWD_64X16, true, false, true>)
+                VL3D_BWD_CASE(MASKABLE, (VL3D_BWD_TILE, BWD_64X16, false, true), launch_tile<VL3D_CONV, BWD_64X16, false, false, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_32X16, true, false, true), launch_tile<VL3D_CONV, BWD_32X16, true, false, false, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_64X16, true, false, true), launch_tile<VL3D_CONV, BWD_64X16, true, false, false, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_PAIR, BWD_32X16, true, false, true), launch_pair<VL3D_CONV, false, true, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_PAIR, BWD_32X16, false, false, true), launch_pair<VL3D_CONV, false, false, true>)
+                VL3D_BWD_CASE(SIG, (VL3D_BWD_PAIR, BWD_32X16, false), launch_pair<VL3D_CONV, F16>)
+                VL3D_BWD_CASE(SIG, (VL3D_BWD_PAIR12, BWD_64X12, false), launch_pair12<VL3D_CONV, F16>)
+                VL3D_BWD_CASE(SIG && COORD != VL3D_COORD_UTILS_MPI, (VL3D_BWD_PAIR, BWD_32X16, true), launch_pair<VL3D_CONV, F16, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_32X16, true), launch_tile<VL3D_CONV, BWD_32X16, true, false>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_32X16, false), launch_tile<VL3D_CONV, BWD_32X16, false, false>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_64X8, false), launch_tile<VL3D_CONV, BWD_64X8, false, false>)
+                VL3D_BWD_CASE(true, (VL3D_BWD_TILE, BWD_64X16, true), launch_tile<VL3D_CONV, BWD_64X16, true, F16>)
+                VL3D_BWD_CASE(true, (VL3D_BWD_TILE, BWD_64X16, false), launch_tile<VL3D_CONV, BWD_64X16, false, F16>)
+            }
+#undef VL3D_BWD_CASE
+#undef VL3D_CONV
+            if (!go || c.f16 != F16) return bwd_not_built(c);
             hipLaunchKernelGGL((bwd_plan_k<COORD>), dim3(1), dim3(64), 0, s, a, 16, const_cast<float *>(a.plan));
             const size_t n8 = (size_t)a.D * a.T * a.Hs * a.Ws * (a.g_f16 ? 1 : 2);          // fp16 texels are 8 bytes, fp32 ones 16
             hipLaunchKernelGGL(bwd_fill_zero_if_infeasible_k, dim3(4096), dim3(256), 0, s, reinterpret_cast<float2 *>(a.g_stack), n8, a.plan);
-            bool done = false;
-            if constexpr (MASKABLE) {
-                if (a.mask) {      // one frame per thread, fifth channel in the sweep and the gather
-                    hipLaunchKernelGGL(bwd_fill_zero_f32_if_infeasible_k, dim3(1024), dim3(256), 0, s, a.g_mask, (size_t)a.D * a.T * a.Hs * a.Ws, a.plan);
-                    // (flat 64 x 8 regions, tile_rows 8: 512 threads at this instantiation's 128-register budget are TWO workgroups per CU -- the
-                    // 1024-thread regions run alone on theirs; variant 3 keeps the 16 rows)
-                    if (a.tile_rows == 8) {
-                        if (a.g_reg || a.g_asum) launch_tile<COORD, BORDER, ORDER, RACT, AACT, 8, true, false, true>(a, s);
-                        else launch_tile<COORD, BORDER, ORDER, RACT, AACT, 8, false, false, true>(a, s);
-                    } else if (a.g_reg || a.g_asum) launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, true, false, true>(a, s);
-                    else launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, false, false, true>(a, s);
-                    hipLaunchKernelGGL((render_bwd_k<COORD, BORDER, ORDER, RACT, AACT, false, true>), grid, block, 0, s, a);
-                    return;
-                }
-            }
-            // the optimiser step in the owner store (vl3d_render_bwd_adam; the entry point admits this convention only): always the frame pairs
-            if constexpr (COORD == VL3D_COORD_AFFINE && BORDER == VL3D_BORDER_HARDCUT && ORDER == VL3D_ACT_POST && RACT == VL3D_ACT_SIGMOID &&
-                          AACT == VL3D_ACT_SIGMOID && !F16 && VL3D_HS == 9) {
-                if (a.ad.p) {
-                    // tile-culled models: one frame per thread, 64-wide regions (the frame pairs are built for dense stacks)
-                    // (32-wide regions unless variant 3 asks for the 64-wide ones: two workgroups per CU, 0.60 against 0.71 ms per iteration of the
-                    // tile-culled schedule, docs/kernels/K2_render_backward.md round 5)
-                    if (a.quad_keep) {
-                        if (a.tile_rows != 16) launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, true, false, false, true, 32>(a, s);
-                        else launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, true, false, false, true>(a, s);
-                    }
-                    else if (a.g_reg || a.g_asum) launch_pair<COORD, BORDER, ORDER, RACT, AACT, false, true, true>(a, s);
-                    else launch_pair<COORD, BORDER, ORDER, RACT, AACT, false, false, true>(a, s);
-                    hipLaunchKernelGGL((render_bwd_k<COORD, BORDER, ORDER, RACT, AACT, F16>), grid, block, 0, s, a);
-                    return;
-                }
-            }
-            if constexpr (RACT == VL3D_ACT_SIGMOID && AACT == VL3D_ACT_SIGMOID) {
-                // two frames per thread: dense stacks without layer regularisers (tile_rows 17 = "16 rows, pairs allowed"), when a
-                // 30 x 14-pixel tile's texel window fits the 32 x 16 threads of its workgroup -- judged by the sizes alone (the
-                // homographies live on the device): along one axis at least the stack is no larger than the frame (+7 %) -- full frames
-                // and row bands (dist.render_band: full width, rows = band + halo) of a stack at the frame's resolution.  Beyond that
-                // the extra gather passes of the small tiles cost more than the pairs save (1.1x: 13.3 ms tile kernel, 13.9 ms
-                // pairs): crops of a larger stack and the reference's 1.1x stacks keep the 64 x 16 tile kernel.
-                const bool fits = (int64_t)a.Hs * 100 <= (int64_t)a.H * 107 || (int64_t)a.Ws * 100 <= (int64_t)a.W * 107;
-                // The pairs come in two region shapes: 64 x 12 (62 x 10 owned, 768 threads; render_bwd_pair12_k) is the default, 32 x 16 the
-                // kernel it replaced there (tile_rows 19 = variant 6 keeps it: the A/B partner and the reference of the bitwise tests;
-                // 20 = variant 7 forces the 64 x 12 regions).
-                const bool pairs_ok = (a.tile_rows == 17 || a.tile_rows == 19 || a.tile_rows == 20) && a.T >= 2 && !a.g_reg && !a.g_asum && !a.quad_keep && fits;
-                if (pairs_ok) {
-                    if (a.tile_rows == 19) launch_pair<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
-                    else launch_pair12<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
-                    done = true;
-                }
-                // with the layer regularisers the pair kernel wins at every stack size (round 3, in process: 15.7 ms against 20.0 ms for
-                // the one-frame tile kernel on a 1.1x stack, 15.4 against 19.6 ms at the frame's resolution: decoding the forward's sign
-                // words is frame-pair work the tile kernel does once per frame).  The utils_mpi cross-check convention keeps the tile
-                // kernel: its texel coordinates cost a reciprocal more and the pair instantiation spilled 8-28 bytes at 128 VGPRs.
-                if constexpr (COORD != VL3D_COORD_UTILS_MPI) {
-                    if (!done && a.tile_rows == 17 && a.T >= 2 && (a.g_reg || a.g_asum) && !a.quad_keep) {
-                        launch_pair<COORD, BORDER, ORDER, RACT, AACT, F16, true>(a, s);
-                        done = true;
-                    }
-                }
-            }
-            // 32-wide one-frame regions (variant 5; the shipped planar convention only): half the workgroup, twice as many of them
-            if constexpr (MASKABLE && VL3D_HS == 9) {
-                // (... and the default of a tile-culled call under VL3D_GRAD_CULLED_UNWRITTEN, which SKIPS the planes a tile cannot see: cfg3 at
-                // 16.5 % kept quads 3.7 ms at the plain kernel's register budget (70 VGPRs, three workgroups per CU), 4.5-4.8 ms in the
-                // instantiation with the regularisers' 128 (variant 5), 5.1 ms in its 64-wide form, profiles/r05b_cull_lean.txt.  A per-tile work list of the swept planes -- bit masks written by
-                // bwd_windows_k, scalar bit scans instead of one record load per skipped plane -- measured the same 4.49 ms / 0.60 ms per
-                // schedule iteration: the skipped planes' scalar loads are hidden, not built)
-                if (!done && (a.tile_rows == 18 || (a.tile_rows == 17 && a.quad_keep && a.grad_culled_unwritten))) {
-                    if (a.g_reg || a.g_asum || (a.tile_rows == 18 && a.quad_keep && a.grad_culled_unwritten)) launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, true, false, false, false, 32>(a, s);
-                    else launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, false, false, false, false, 32>(a, s);
-                    done = true;
-                }
-            }
-            // flat 64 x 8 one-frame regions (512 threads, four workgroups per CU at the plain kernel's 64 registers) for a SINGLE frame (cfg2, the
-            // stage-1 shape): 2520 workgroups on 1024 slots instead of 1092 on 512 -- the x1.33 halo costs less than the 2.13-round tail of the
-            // 16-row regions: backward 0.380 against 0.394 ms at 720p, D = 32, same bits (profiles/r05d_cfg2_rows.txt; 10 rows 0.442, 12 rows
-            // 0.393: measured, not instantiated).  Variant 2 forces them at any T, variant 3 keeps the 16 rows.
-            if constexpr (MASKABLE && VL3D_HS == 9) {
-                if (!done && !a.g_reg && !a.g_asum && !a.quad_keep && (a.tile_rows == 8 || (a.tile_rows == 17 && a.T == 1))) {
-                    launch_tile<COORD, BORDER, ORDER, RACT, AACT, 8, false, false>(a, s);
-                    done = true;
-                }
-            }
-            if (!done) {
-                // layer regularisers and / or sparsity sums: the REG instantiation (128-VGPR budget); a tile-culled call whose consumer never
-                // reads culled texels takes it too -- it is the one that SKIPS the planes a tile cannot see instead of zero-filling them
-                if (a.g_reg || a.g_asum || (a.quad_keep && a.grad_culled_unwritten)) {
-                    launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, true, F16>(a, s);
-                } else {
-                    launch_tile<COORD, BORDER, ORDER, RACT, AACT, 16, false, F16>(a, s);
-                }
-            }
+            if (c.mask) hipLaunchKernelGGL(bwd_fill_zero_f32_if_infeasible_k, dim3(1024), dim3(256), 0, s, a.g_mask, (size_t)a.D * a.T * a.Hs * a.Ws, a.plan);
+            go(a, s, c);
         }
+        // the atomics kernel: the whole gradient where the plan says infeasible (or no owner-computes path was asked for), a no-op behind a feasible plan
         if constexpr (MASKABLE) {
             if (a.mask) {
                 hipLaunchKernelGGL((render_bwd_k<COORD, BORDER, ORDER, RACT, AACT, false, true>), grid, block, 0, s, a);
-                return;
+                return VL3D_OK;
             }
         }
         hipLaunchKernelGGL((render_bwd_k<COORD, BORDER, ORDER, RACT, AACT, F16>), grid, block, 0, s, a);
+        return VL3D_OK;
     } else {
         // with the regularisers: coverage masks + pair flags (frame independent), the plane-by-plane kernel over the regular pairs,
         // then the slot-by-slot kernel over the irregular ones
@@ -2422,17 +2395,17 @@ void launch_t(const RenderArgs &a, hipStream_t s) {
             if (!with_mask)
                 hipLaunchKernelGGL((render_fwd_reg_k<COORD, BORDER, ORDER, RACT, AACT, F16>), dim3((unsigned)(tx * ty * a.T)), dim3(512), 0, s, a, tx, ty);
             launch_reg_slots<COORD, BORDER, ORDER, RACT, AACT, F16, true>(a, s);
-            return;
+            return VL3D_OK;
         }
         if (a.reg_fwd == 3) {       // render + regulariser sums of a tile-culled model in one pass: the slot kernel composites as it goes
             launch_reg_prepass<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
             launch_reg_slots<COORD, BORDER, ORDER, RACT, AACT, F16, false, true>(a, s);
-            return;
+            return VL3D_OK;
         }
         if (a.reg_fwd) {        // the sums alone (tile-culled models; the two-pass forward of dense ones): every pair slot by slot
             launch_reg_prepass<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
             launch_reg_slots<COORD, BORDER, ORDER, RACT, AACT, F16, false>(a, s);
-            return;
+            return VL3D_OK;
         }
         // frame pairs (shipped activations, dense stacks, T >= 2); forward variant 6 (desc->variant bits 8..11) keeps the one-frame
         // kernel (A/B, bitwise tests).  The workgroup-shape variants of round 1 (64x4, 64x16, no XCD remap) measured within the
@@ -2442,24 +2415,25 @@ void launch_t(const RenderArgs &a, hipStream_t s) {
                 const int tiles_x = (a.W + 63) / 64, tiles_y = (a.H + 7) / 8;
                 hipLaunchKernelGGL((render_fwd2_k<COORD, BORDER, ORDER, RACT, AACT, 8, true, false, false, true>), dim3((unsigned)(tiles_x * tiles_y * a.T)),
                                    dim3(64 * 8), 0, s, a, tiles_x, tiles_y);
-                return;
+                return VL3D_OK;
             }
         }
         if constexpr (RACT == VL3D_ACT_SIGMOID && AACT == VL3D_ACT_SIGMOID) {
             // (tile-culled models too; add_uv_noise: the jitter lives in the one-frame kernel)
-            if (a.T >= 2 && a.fwd_variant != 6 && !a.uv_seed) return launch_fwd2x<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s);
+            if (a.T >= 2 && a.fwd_variant != 6 && !a.uv_seed) { launch_fwd2x<COORD, BORDER, ORDER, RACT, AACT, F16>(a, s); return VL3D_OK; }
         }
         launch_fwd2<COORD, BORDER, ORDER, RACT, AACT, 8, true, F16>(a, s);
+        return VL3D_OK;
     }
 }
 
 // fp16 plane stacks (cfg5) are instantiated for the shipped (sigmoid, sigmoid) activations only
 template <bool BWD, int COORD, int BORDER, int ORDER, int RACT, int AACT>
-void launch(const RenderArgs &a, hipStream_t s) {
+int launch(const RenderArgs &a, hipStream_t s) {
     if constexpr (RACT == VL3D_ACT_SIGMOID && AACT == VL3D_ACT_SIGMOID) {
         if (a.g_f16) return launch_t<BWD, COORD, BORDER, ORDER, RACT, AACT, true>(a, s);
     }
-    launch_t<BWD, COORD, BORDER, ORDER, RACT, AACT, false>(a, s);
+    return launch_t<BWD, COORD, BORDER, ORDER, RACT, AACT, false>(a, s);
 }
 
 }  // namespace

@@ -120,6 +120,29 @@ def _cull_scratch(desc, device):
 # scratch (plan) buffer of the most recent backward: element 0 viewed as int32 is 1 when the LDS-staged
 # owner-computes kernel ran, 0 when the call fell back to the atomics kernel (read by tests / diagnostics only).
 LAST_BWD_SCRATCH = None
+# ... and that backward's call as bwd_choice() takes it: (desc, entry, quad_keep, reg_grads, scratch_bytes); None after a backward
+# vl3d_render_bwd_choice does not describe (the plane-rows band)
+LAST_BWD_CALL = None
+
+
+def bwd_choice(desc, entry="render", quad_keep=False, reg_grads=False, scratch_bytes=None):
+    """which kernel a backward call with these arguments runs (vl3d_render_bwd_choice: the entry points' own decision, no device touched) ->
+    L.BwdChoice.  scratch_bytes: None = what the wrappers pass (vl3d_render_bwd_scratch_bytes), 0 = no scratch."""
+    out = L.BwdChoice()
+    if scratch_bytes is None:
+        scratch_bytes = int(L.lib().vl3d_render_bwd_scratch_bytes(desc))
+    L.check(L.lib().vl3d_render_bwd_choice(desc, L.BWD_ENTRY[entry], int(bool(quad_keep)), int(bool(reg_grads)), int(scratch_bytes),
+                                           int(entry == "adam"), L.C.byref(out)), "vl3d_render_bwd_choice")
+    return out
+
+
+def last_bwd_choice():
+    """the choice of the most recent backward, as (family, width, rows, reg, mask, adam, cull, f16) with the family by name (L.BWD_FAMILY)."""
+    if LAST_BWD_CALL is None:
+        raise RuntimeError("last_bwd_choice(): no render backward has run yet, or the last one was a plane-rows band (its own frame-pair launch)")
+    c = bwd_choice(*LAST_BWD_CALL)
+    family = {v: k for k, v in L.BWD_FAMILY.items()}[c.family]
+    return (family, c.width, c.rows) + tuple(bool(getattr(c, n)) for n in ("reg", "mask", "adam", "cull", "f16"))
 
 
 class _RenderPlanes(torch.autograd.Function):
@@ -214,7 +237,10 @@ class _RenderPlanes(torch.autograd.Function):
         g_asum = g_asum.to(torch.float32).contiguous() if (ctx.with_reg and g_asum is not None) else None
         g_rgb = g_rgb.contiguous() if g_rgb is not None else torch.zeros_like(rgb)
         g_alpha = g_alpha.contiguous() if g_alpha is not None else None
-        global LAST_BWD_SCRATCH
+        global LAST_BWD_SCRATCH, LAST_BWD_CALL
+        LAST_BWD_CALL = (ctx.desc, "render" if ctx.fused_adam is None else "adam",
+                         (ctx.quad_keep if ctx.fused_adam is None else ctx.fused_adam.quad_keep) is not None, g_reg is not None or g_asum is not None,
+                         None)      # (the fused step's scratch is the optimiser's: at least vl3d_render_bwd_scratch_bytes, or the entry refuses)
         if ctx.fused_adam is not None:
             # backward + optimiser step in one pass over the window (vl3d_render_bwd_adam): no gradient tensor exists afterwards
             LAST_BWD_SCRATCH = ctx.fused_adam.backward_step(ctx.desc, ctx.leaf, homos, rgb, alpha, g_rgb, g_alpha, g_reg, ctx.reg_state, g_asum)
@@ -224,6 +250,7 @@ class _RenderPlanes(torch.autograd.Function):
             nscratch = int(L.lib().vl3d_render_bwd_scratch_bytes(ctx.desc))
             # every word the kernels read is written by the plan kernels of the same call, the header included (bwd_plan_k): nothing to clear
             scratch = torch.empty((nscratch + 3) // 4, dtype=torch.float32, device=stack.device)
+            LAST_BWD_CALL = LAST_BWD_CALL[:4] + (nscratch,)
             if (ctx.desc.variant & 0xf) == 1 or ctx.desc.uv_noise_seed:      # (no plan kernel will write the header: the diagnostic word reads 0)
                 scratch[:16].zero_()
             qk = ctx.quad_keep
@@ -298,8 +325,9 @@ class _RenderPlanesMask(torch.autograd.Function):
             L.check(L.lib().vl3d_render_bwd_mask(ctx.desc, L.ptr(stack), L.ptr(mask), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.ptr(g_rgb), L.ptr(g_alpha),
                                                  L.ptr(g_label), L.ptr(g_reg), L.ptr(ctx.reg_state), L.ptr(g_asum), L.ptr(g_stack), L.ptr(g_mask),
                                                  L.ptr(scratch), nscratch, L.stream_ptr(dev)), "vl3d_render_bwd_mask")
-        global LAST_BWD_SCRATCH
+        global LAST_BWD_SCRATCH, LAST_BWD_CALL
         LAST_BWD_SCRATCH = scratch
+        LAST_BWD_CALL = (ctx.desc, "mask", False, g_reg is not None or g_asum is not None, nscratch)
         return g_stack, g_mask, None, None, None, None, None
 
 
@@ -637,8 +665,8 @@ class _RenderPlaneRows(torch.autograd.Function):
             L.check(L.lib().vl3d_render_bwd_plane_rows(ctx.desc, L.ptr(local), L.ptr(plane_row0), ctx.R, L.ptr(homos), L.ptr(rgb), L.ptr(alpha),
                                                        L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_local), L.ptr(scratch), nscratch, L.stream_ptr(dev)),
                     "vl3d_render_bwd_plane_rows")
-        global LAST_BWD_SCRATCH
-        LAST_BWD_SCRATCH = scratch
+        global LAST_BWD_SCRATCH, LAST_BWD_CALL
+        LAST_BWD_SCRATCH, LAST_BWD_CALL = scratch, None      # (its own frame-pair launch: vl3d_render_bwd_choice does not describe it)
         return g_local, None, None, None, None, None, None, None, None
 
 
