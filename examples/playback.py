@@ -8,7 +8,10 @@ bytes of the three textures, PSNR between the float and the baked frames, and wh
 frames equal the dense baked frames --, then write the viewer package (geometry.obj, static.png,
 dynamic/%04d.png, meta.json), OPEN it again from the files alone (`baked.open_viewer_package`: no model, no arguments) and play the spiral
 from it: load time (PNG decode apart), frames / s, and the byte difference of its frames against the in-process pool's (this model's tiles
-share their borders, so the export resamples them: close, not equal).  `--full`: 720p, D = 32, T = 50."""
+share their borders, so the export resamples them: close, not equal).  `--full`: 720p, D = 32, T = 50.
+`--fps-out R` (default off): also play the spiral RETIMED from the loop's 25 fps to a display of R frames per second, from the clip and from
+the pool -- loop times `render_video.retime(N, R)`, texels interpolated between adjacent frames and across the loop seam
+(`render_frames(..., fractional=True)`): frames / s of both, and whether the two frame sets are equal."""
 import argparse
 import json
 import os
@@ -22,7 +25,7 @@ import numpy as np
 import torch
 
 
-def run(full=False, outdir=None, dev="cuda:0"):
+def run(full=False, outdir=None, dev="cuda:0", fps_out=None):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth, tiles
     from videoloop3d_amd.baked import bake, bake_pool, culled_texel_rgba8, open_viewer_package
@@ -77,6 +80,20 @@ def run(full=False, outdir=None, dev="cuda:0"):
     mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
     out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
     out["pool_frames_equal_baked_frames"] = bool(torch.equal(frames["baked_pool"], frames["baked"]))
+    if fps_out:      # the same spiral shown at another rate: pose i at loop time i * 25 / fps_out
+        ts = RV.retime(N, fps_out, 25.0)
+        retimed = {}
+        for name, b in (("baked", baked), ("baked_pool", pool)):
+            RV.render_frames(model, H, W, ext[:4], intr[:4], ts[:4], baked=b, fractional=True)      # untimed
+            sync(); t0 = time.perf_counter()
+            retimed[name] = RV.render_frames(model, H, W, ext, intr, ts, baked=b, fractional=True)
+            sync(); dt = time.perf_counter() - t0
+            out["retimed_" + name] = {"frames": N, "fps_out": fps_out, "fps_loop": 25.0, "loops_played": float(ts[-1]) / T, "frames_per_s": N / dt,
+                                      "ms_per_frame": dt / N * 1e3, "route": "render_display(fractional=True): one loop-time path call per chunk"}
+        out["retimed_pool_frames_equal_baked_frames"] = bool(torch.equal(retimed["baked_pool"], retimed["baked"]))
+        out["retimed_frames_at_integer_times_equal_the_spiral"] = bool(all(
+            torch.equal(retimed["baked"][i], RV.render_frames(model, H, W, ext[i:i + 1], intr[i:i + 1], np.array([int(ts[i]) % T]), baked=baked)[0])
+            for i in range(N) if float(ts[i]) == int(ts[i])))
     poses = np.linalg.inv(ext[:8])[:, :3, :4]              # eight of the cameras as the capture's views (camera-to-world)
     with tempfile.TemporaryDirectory() as tmp:
         where = outdir or tmp
@@ -110,7 +127,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--out", default=None, help="directory for the viewer package (default: a temporary one)")
+    ap.add_argument("--fps-out", type=float, default=None, help="also play the spiral retimed from 25 fps to this display rate (default: off)")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run(a.full, a.out)))
+    print(json.dumps(run(a.full, a.out, fps_out=a.fps_out)))

@@ -152,7 +152,25 @@ int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stac
  *     bg: a HOST pointer to 3 finite floats, read by the call (it travels in the kernel arguments).  RGB8 rows are stored lane-packed (a
  *     wave's 192 bytes as 48 dwords) where the 64-pixel row segment is full and 4-byte aligned, as bytes elsewhere; the environment variable
  *     VL3D_DISPLAY_STORE3=bytes selects byte stores everywhere -- a measurement hook (profiles/baked_fwd.py --legs display), same bytes.
- *     VL3D_EINVAL: both sinks or neither, a bg with the float sink, channels outside {3, 4}, misaligned RGBA8 frames, a non-finite bg. */
+ *     VL3D_EINVAL: both sinks or neither, a bg with the float sink, channels outside {3, 4}, misaligned RGBA8 frames, a non-finite bg.
+ *   Fractional loop time (vl3d_baked_times; vl3d_render_fwd_baked_times / vl3d_render_fwd_baked_pool_times).  The product is a LOOP of T
+ *     frames (T = T_alloc of a clip, T_model of a pool); the baked model at loop time tau in [0, T) is the linear interpolation of its TEXELS
+ *     between two adjacent frames, the last and the first included:
+ *         t0 = floor(tau),   t1 = t0 + 1 < T ? t0 + 1 : 0 (wraps at the seam),   f = tau - t0
+ *     Sample position, coverage, hard cut, kept-quad test, tile-exact offset and tent weights are those of the frame renders above.  Per
+ *     covered (pixel, plane), nothing contracted (blend, w255: csrc/vl3d_baked_core.h):
+ *         b0_K = blend<K>(taps of frame t0, w255),   b1_K = blend<K>(taps of frame t1, w255),   c_K = fmaf(f, b1_K - b0_K, b0_K),   K = 0..3
+ *     (alpha included), and c enters the one-frame composite step unchanged.  Exact consequences: f == 0 gives an output frame the bits of
+ *     the path frame (cam, t0); equal taps in both frames (a static block of the pool -- fetched once --, a static quad of a clip, T = 1) give
+ *     c_K = b0_K bit for bit at any f.  A path like the one above: output frame i is camera frame_cam[i] of homos (n_cams, D, 3, 3) at time
+ *     frame_time[i], one plan launch plus one render launch, one output frame and two source frames per thread; cull_scratch:
+ *     vl3d_render_path_cull_scratch_bytes(desc, n_cams); the sink is vl3d_baked_out, float or display.  In the kernel tau is an fp32 value read
+ *     from device memory: t0 = (int)tau, f = tau - (float)t0 (exact in fp32); a workgroup whose camera is outside [0, n_cams) or whose tau is
+ *     not in [0, T) -- a NaN fails the comparison -- returns before any other load or store and leaves its pixels unwritten.  The wrappers
+ *     (render.render_times_baked / _pool) check the times before they upload them; baked.loop_times reduces any real time into [0, T).
+ *     A clip: frame t1 at its own offset.  A pool: a static or unstored entry serves both frames from one fetch (or the register), a dynamic
+ *     entry is fetched at slot + t0 and slot + t1.  VL3D_EINVAL, nothing launched: what the path form refuses, with its messages, and a NULL
+ *     sel, frame_cam or frame_time, reserved != 0, n_cams outside [1, 65535]. */
 typedef struct vl3d_baked_frames {
     int32_t frame0;                        /* a run: its first frame */
     int32_t n_cams;                        /* a path: the cameras of homos; 0 for a run */
@@ -164,6 +182,12 @@ typedef struct vl3d_baked_out {
     int32_t channels;
     const float *bg;                       /* ... its background: host float[3] or NULL */
 } vl3d_baked_out;
+typedef struct vl3d_baked_times {
+    int32_t n_cams;                        /* cameras of homos (n_cams, D, 3, 3), 1 .. 65535 */
+    int32_t reserved;                      /* 0 */
+    const int32_t *frame_cam;              /* device int32[desc->T] */
+    const float *frame_time;               /* device float[desc->T], each in [0, T_alloc) / [0, T_model) */
+} vl3d_baked_times;                        /* 24 bytes */
 int vl3d_bake_rgba8(int64_t n_texels, const void *stack, int32_t stack_dtype, int32_t rgb_act, int32_t alpha_act, uint8_t *out,
                     vl3d_stream_t stream);
 int64_t vl3d_render_path_cull_scratch_bytes(const vl3d_render_desc *desc, int32_t n_cams);
@@ -173,6 +197,12 @@ int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, in
 int vl3d_render_fwd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos,
                                const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, uint32_t culled_rgba8,
                                void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_times(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                                const vl3d_baked_times *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
+                                const vl3d_baked_out *out, vl3d_stream_t stream);
+int vl3d_render_fwd_baked_pool_times(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model,
+                                     const float *homos, const vl3d_baked_times *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                     uint32_t culled_rgba8, void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream);
 
 /* A viewer package's atlases -> the baked pool (csrc/vl3d_pool_from_atlas.hip; baked.open_viewer_package).  A package IS a baked pool in another
  * order: RGBA8 tiles of th x tw texels of the kept quads, static tiles once (static_atlas, As_h x As_w texels, row-major grid of

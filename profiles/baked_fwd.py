@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|open] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -26,6 +26,15 @@ store, RGB8 with byte stores (VL3D_DISPLAY_STORE3=bytes), RGBA8.  Every (b) outp
 colour bytes, and its alpha byte with display_frames'); then the four legs alternate round by round under HIP events that span the whole
 path.  Prints ms per frame (median, min .. max) and the ratio to (a); the condition is RGB8 (the store the library ships: packed) median <=
 (a) median for every storage and background.
+
+The TIMES leg (--legs times; not part of `all`): the same spiral and storages retimed from the loop's 25 fps to a 60 Hz display, loop time
+tau_i = (i * 25 / 60) mod T, RGB8 frames as the product.  (a) the yardstick, the only retiming there was before the loop-time path: two path
+calls (frames t0 and t1) into fp32 buffers, torch.lerp of rgb and alpha, baked.display_frames into the uint8 result -- an output cross-fade,
+another picture but the same job; (b) ONE render_times_baked / _pool call into the display sink; (c), for the cost of the second frame, the
+whole-frame path call of --legs display at t0.  First (b)'s float sink is compared on three frames with the float kernels on interpolated
+texels (the comparison of tests/test_gpu_baked_times.py, bound 1e-5); then the three legs alternate round by round under HIP events that span
+the whole path.  Prints ms per frame (median, min .. max), (b) / (a) -- the condition is (b) median <= (a) median on every storage -- and
+(b) / (c).
 
 The OPEN leg (--legs open; not part of `all`; allocates neither stack): the scatter of a viewer package's atlases into the baked pool
 (vl3d_pool_from_atlas_rgba8, baked.open_viewer_package).  The culled pair's quad map in the tile-exact layout (35 x 63 tiles of 21 x 21 texels:
@@ -51,7 +60,7 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "open"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open"])
 ap.add_argument("--poses", type=int, default=120)
 ap.add_argument("--keep", type=float, default=0.165)
 ap.add_argument("--dyn", type=float, default=0.3)
@@ -62,10 +71,10 @@ assert a.warm >= 1 and a.iters >= a.rounds >= 1
 import __graft_entry__ as ge  # noqa: E402
 ge.build()
 from videoloop3d_amd import synth  # noqa: E402
-from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, display_frames  # noqa: E402
+from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, display_frames, loop_times  # noqa: E402
 from videoloop3d_amd.packed import PackedLayout  # noqa: E402
 from videoloop3d_amd.render import (RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool, render_path_baked,  # noqa: E402
-                                    render_path_baked_pool)
+                                    render_path_baked_pool, render_times_baked, render_times_baked_pool)
 from videoloop3d_amd.utils_mpi import compute_homography, make_depths  # noqa: E402
 
 assert torch.cuda.is_available(), "profiles/baked_fwd.py measures on the MI355X"
@@ -181,7 +190,7 @@ if a.legs in ("all", "culled"):
     res["pool_over_dense_culled"] = res["baked_pool"]["ms_median"] / res["baked_culled"]["ms_median"]
     print(f"pool render is {res['pool_over_dense_culled']:.3f}x the dense culled baked render's time (bar: <= 1.05)")
 
-if a.legs in ("path", "display"):
+if a.legs in ("path", "display", "times"):
     import math
     del stack, out
     N = a.poses
@@ -271,6 +280,65 @@ if a.legs == "display":
                 print(f"display [{name:6s} {'bg   ' if bg else 'no bg'}] {k:20s} {med[k] / N:.4f} ms/frame ({min(ms[k]) / N:.4f} .. {max(ms[k]) / N:.4f}) "
                       f"{med[k] / med['a_float_then_torch']:.3f} of (a); equal to (a): {same.get(k, '-')}{verdict}", flush=True)
     os.environ.pop("VL3D_DISPLAY_STORE3", None)
+if a.legs == "times":
+    import numpy as np
+    from videoloop3d_amd.render_video import retime
+    tau = loop_times(retime(N, 60, 25), T)                # float32 [N] in [0, T)
+    t0s = np.floor(tau).astype(np.int64)
+    t1s = np.where(t0s + 1 < T, t0s + 1, 0)
+    frac = torch.from_numpy(tau - t0s.astype(np.float32)).to(dev)
+    o_0 = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    o_1 = (torch.empty_like(o_0[0]), torch.empty_like(o_0[1]))
+    f_a, f_b, f_c = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(3))
+    ident = RenderSpec.mpv(rgb_act="none", alpha_act="none")      # the oracle renders decoded texels: nothing to activate
+    storages = {"dense": (lambda ts_, **o: render_path_baked(baked, cam, ts_, path_homos, H, W, spec, **o),
+                          lambda **o: render_times_baked(baked, cam, tau, path_homos, H, W, spec, **o), baked, None),
+                "culled": (lambda ts_, **o: render_path_baked(dense, cam, ts_, path_homos, H, W, spec, quad_keep=qk, **o),
+                           lambda **o: render_times_baked(dense, cam, tau, path_homos, H, W, spec, quad_keep=qk, **o), dense, qk),
+                "pool": (lambda ts_, **o: render_path_baked_pool(lay, pool, cam, ts_, path_homos, H, W, spec, **kwp, **o),
+                         lambda **o: render_times_baked_pool(lay, pool, cam, tau, path_homos, H, W, spec, **kwp, **o), dense, qk)}
+    res["times"] = {"poses": N, "fps_out": 60, "fps_loop": 25, "fractional_frames": int((frac > 0).sum())}
+    for name, (path, times, clip, keep_map) in storages.items():
+        bg = (0.2, 0.4, 0.6)
+        bg_dev = torch.tensor(bg, dtype=torch.float32, device=dev)
+        # (b) against the float kernels on interpolated texels, three frames: the first fractional one, the middle, the last
+        times(out=o_0)
+        worst = [0.0, 0.0]
+        for i in (1, N // 2 + 1, N - 1):
+            d0, d1 = clip[:, int(t0s[i])].float() / 255, clip[:, int(t1s[i])].float() / 255
+            s1 = (d0 + float(frac[i]) * (d1 - d0))[:, None].contiguous()
+            r, al = render_frame_run(s1, 0, 1, path_homos[i], H, W, ident, quad_keep=keep_map)
+            worst = [max(worst[0], float((o_0[0][i] - r[0]).abs().max())), max(worst[1], float((o_0[1][i] - al[0]).abs().max()))]
+            del d0, d1, s1, r, al
+        parity_ok = worst[0] <= 1e-5 and worst[1] <= 1e-5
+
+        def leg_a():      # two whole-frame path calls, the cross-fade and the display rule in torch
+            path(t0s, out=o_0)
+            path(t1s, out=o_1)
+            f_a[:] = display_frames(torch.lerp(o_0[0], o_1[0], frac[:, None, None, None]), torch.lerp(o_0[1], o_1[1], frac[:, None, None]), bg_dev, 3)
+
+        def leg_b():
+            times(frames8=f_b, bg=bg)
+
+        def leg_c():
+            path(t0s, frames8=f_c, bg=bg)
+        legs = {"a_two_paths_lerp_torch": leg_a, "b_times_rgb8": leg_b, "c_whole_frame_rgb8": leg_c}
+        for f in legs.values():
+            f()
+        level = int((f_a.int() - f_b.int()).abs().max())      # a cross-fade of outputs is another picture: reported, not required to be 0
+        ms, per = ab(legs)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        ok = med["b_times_rgb8"] <= med["a_two_paths_lerp_torch"]
+        res["times"][name] = {"parity_max_abs": {"rgb": worst[0], "alpha": worst[1], "ok": parity_ok}, "max_level_diff_b_vs_a": level,
+                              "condition_times_le_yardstick": bool(ok), "times_over_yardstick": med["b_times_rgb8"] / med["a_two_paths_lerp_torch"],
+                              "times_over_whole_frame": med["b_times_rgb8"] / med["c_whole_frame_rgb8"],
+                              "legs": {k: {"ms_per_frame_median": med[k] / N, "min": min(ms[k]) / N, "max": max(ms[k]) / N} for k in legs}}
+        print(f"times [{name:6s}] parity with the float kernels on 3 frames: max |d rgb| {worst[0]:.3e}, |d alpha| {worst[1]:.3e} -> "
+              f"{'ok' if parity_ok else 'MISSED'}; (b) against (a): max level diff {level}")
+        for k in legs:
+            print(f"times [{name:6s}] {k:24s} {med[k] / N:.4f} ms/frame ({min(ms[k]) / N:.4f} .. {max(ms[k]) / N:.4f})", flush=True)
+        print(f"times [{name:6s}] (b) / (a) {med['b_times_rgb8'] / med['a_two_paths_lerp_torch']:.3f} -> {'ok' if ok else 'MISSED'}; "
+              f"(b) / (c), the cost of the second frame: {med['b_times_rgb8'] / med['c_whole_frame_rgb8']:.3f}", flush=True)
 if a.legs == "open":
     import tempfile
     import time

@@ -62,6 +62,10 @@ class BakedFrames(C.Structure):      # vl3d_baked_frames: a run (frame0) or a ca
     _fields_ = [("frame0", C.c_int32), ("n_cams", C.c_int32), ("frame_cam", _P), ("frame_t", _P)]
 
 
+class BakedTimes(C.Structure):       # vl3d_baked_times: a camera path in loop time (n_cams, frame_cam, frame_time) of a baked render
+    _fields_ = [("n_cams", C.c_int32), ("reserved", C.c_int32), ("frame_cam", _P), ("frame_time", _P)]
+
+
 class BakedOut(C.Structure):         # vl3d_baked_out: the float sink (rgb, alpha) or the display sink (frames, channels, bg)
     _fields_ = [("rgb", _P), ("alpha", _P), ("frames", _P), ("channels", C.c_int32), ("bg", _P)]
 
@@ -92,6 +96,9 @@ SIGNATURES = {
     "vl3d_render_fwd_baked": ([C.POINTER(RenderDesc), _P, _I32, _P, C.POINTER(BakedFrames), _P, _I32, _I32, _P, C.POINTER(BakedOut), _P], C.c_int),
     "vl3d_render_fwd_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, C.POINTER(BakedFrames), _P, _I32, _I32, C.c_uint32, _P,
                                     C.POINTER(BakedOut), _P], C.c_int),
+    "vl3d_render_fwd_baked_times": ([C.POINTER(RenderDesc), _P, _I32, _P, C.POINTER(BakedTimes), _P, _I32, _I32, _P, C.POINTER(BakedOut), _P], C.c_int),
+    "vl3d_render_fwd_baked_pool_times": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, C.POINTER(BakedTimes), _P, _I32, _I32, C.c_uint32, _P,
+                                          C.POINTER(BakedOut), _P], C.c_int),
     "vl3d_pool_from_atlas_rgba8": ([_I32] * 8 + [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, C.c_uint32, _P, _P], C.c_int),
     "vl3d_render_path_cull_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),

@@ -14,6 +14,8 @@ atlases ACTIVATED, multiplied by 255, clipped and truncated to 8 bits; a player 
                                        the bits of the dense baked render.  256 bytes per slot: a quarter of the float pool.
   display_frames(rgb, alpha, bg, C)    the ONE display rule: a float render -> the uint8 frames a viewer shows (over the background, to8b).
   BakedMPV / BakedPool.render_display  poses in, uint8 frames out: the render kernels store that rule's bytes themselves (`frames8=`).
+  loop_times(times, T)                 any real playback times -> float32 loop times in [0, T): what `fractional=True` of render_path /
+                                       render_display renders, texels interpolated between adjacent frames and across the loop seam.
 """
 import copy
 
@@ -61,6 +63,23 @@ def display_frames(rgb, alpha, bg=None, channels=3):
     return out
 
 
+def loop_times(times, T):
+    """Real playback times, of any sign and size -> float32 numpy array of loop times in [0, T), the `frame_time` of render.render_times_baked /
+    _pool.  The loop has T frames and frame T is frame 0 again: the reduction is t - T floor(t / T) in float64 (negative times wrap:
+    -0.25 -> T - 0.25), then the cast to float32; a value the cast (or the float64 subtraction) rounds up to T -- -1e-9 -- is 0.0, the same
+    instant of the loop.  A non-finite time is a ValueError."""
+    import numpy as np
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"loop_times: a loop of T >= 1 frames, got {T}")
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    if not np.isfinite(t).all():
+        raise ValueError("loop_times: a time is not finite")
+    r = (t - T * np.floor(t / T)).astype(np.float32)
+    r[~((r >= 0) & (r < T))] = 0.0      # T itself (rounded up), or -0.0 / a last-bit negative of the subtraction
+    return r
+
+
 class _Camera:
     """the camera side of a plane model without its texture: reference camera, plane depths and the module's own `plane_homographies`
     (the same code object: the same bits as the module's forward)."""
@@ -91,7 +110,8 @@ def path_cameras(camera, view_extrins, view_intrins):
 class _Baked:
     """what BakedMPV and BakedPool share: camera, background and the module's eval forward over runs of consecutive frames.  A subclass has
     `device`, `frm_num`, `bg_color`, `camera`, `_run(frame0, n, homos, H, W, out)`: its render of a run of frames, read in place, and
-    `_path(frame_cam, frame_t, homos [C,D,3,3], H, W, out)`: its render of a camera path; both take `frames8=`, `bg=` for the display frames."""
+    `_path(frame_cam, frame_t, homos [C,D,3,3], H, W, out)`: its render of a camera path; both take `frames8=`, `bg=` for the display frames.
+    `_times(frame_cam, frame_time, homos, H, W, out)`: the path in loop time (`fractional=True`), float32 times in [0, frm_num)."""
 
     def extrins_to_ref(self, tar_extrins):
         """world-to-camera poses -> reference-camera-to-target transforms, as MPMeshVid.forward forms them (MPV.py:481)."""
@@ -131,17 +151,22 @@ class _Baked:
 
 
     @torch.no_grad()
-    def render_path(self, H, W, extrins, intrins, ts):
+    def render_path(self, H, W, extrins, intrins, ts, fractional=False):
         """a camera path in one plan launch plus one render launch (render.render_path_baked / _pool): N poses (extrins [N,4,4] world-to-camera,
         intrins [N,3,3]), output frame i showing frame ts[i] of the clip -> (rgb [N,3,H,W] over the background, alpha [N,H,W]); frame i has
-        the bits of render(H, W, extrins[i:i+1], intrins[i:i+1], ts[i:i+1])."""
+        the bits of render(H, W, extrins[i:i+1], intrins[i:i+1], ts[i:i+1]).  `fractional`: ts are real LOOP TIMES of any sign and size
+        (loop_times reduces them into the loop): the texels are interpolated between the two adjacent frames, the last and the first
+        included (render.render_times_baked / _pool); without it every entry of ts is truncated to a frame index."""
         extrins = torch.as_tensor(extrins, dtype=torch.float32).cpu()
         intrins = torch.as_tensor(intrins, dtype=torch.float32).cpu()
-        tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        if fractional:
+            tl = loop_times(torch.as_tensor(ts).reshape(-1).tolist(), self.frm_num)
+        else:
+            tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
         if not (len(extrins) == len(intrins) == len(tl)):
             raise RuntimeError(f"render_path: one pose and one frame per output frame ({len(extrins)} extrins, {len(intrins)} intrins, {len(tl)} frames)")
         cam_of, homos = path_cameras(self.camera, extrins, intrins)
-        rgb, alpha = self._path(cam_of, tl, homos.pin_memory().to(self.device, non_blocking=True), H, W, None)
+        rgb, alpha = (self._times if fractional else self._path)(cam_of, tl, homos.pin_memory().to(self.device, non_blocking=True), H, W, None)
         bg = self.background()
         if bg is not None:
             rgb = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
@@ -154,16 +179,20 @@ class _Baked:
         return [float(v) for v in self.bg_color.split('#')] if len(self.bg_color) > 0 else None
 
     @torch.no_grad()
-    def render_display(self, H, W, extrins, intrins, ts, channels=3, out=None, max_batch=64):
+    def render_display(self, H, W, extrins, intrins, ts, channels=3, out=None, max_batch=64, fractional=False):
         """Poses in, the frames a viewer shows out: N poses (extrins [N,4,4] world-to-camera, intrins [N,3,3]), output frame i showing frame
         ts[i] of the clip -> uint8 [N,H,W,channels] on the device (`out`: written in place), display_frames of render / render_path byte
         for byte, stored by the render launches themselves (`frames8=`): no float frame exists.  Equal poses share a camera (path_cameras);
         chunks of at most `max_batch` frames are launched as render_video.path_segments says -- one run call for a chunk that is one run,
-        else one path call."""
+        else one path call.  `fractional`: ts are real LOOP TIMES of any sign and size, as render_path takes them; every chunk is one call
+        of the path in loop time."""
         from .render_video import path_segments
         extrins = torch.as_tensor(extrins, dtype=torch.float32).cpu()
         intrins = torch.as_tensor(intrins, dtype=torch.float32).cpu()
-        tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        if fractional:
+            tl = loop_times(torch.as_tensor(ts).reshape(-1).tolist(), self.frm_num)
+        else:
+            tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
         n, dev = len(tl), self.device
         if not (len(extrins) == len(intrins) == n):
             raise RuntimeError(f"render_display: one pose and one frame per output frame ({len(extrins)} extrins, {len(intrins)} intrins, {n} frames)")
@@ -179,6 +208,13 @@ class _Baked:
         cam_of, homos = path_cameras(self.camera, extrins, intrins)
         if dev.type == "cuda":
             homos = homos.pin_memory().to(dev, non_blocking=True)      # [cameras, D, 3, 3], one copy
+        if fractional:
+            chunk = max(1, min(int(max_batch), n))
+            for c0 in range(0, n, chunk):
+                c1 = min(n, c0 + chunk)
+                lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras, as below
+                self._times([c - lo for c in cam_of[c0:c1]], tl[c0:c1], homos[lo:hi], H, W, None, frames8=out[c0:c1], bg=bg)
+            return out
         for kind, c0, c1 in path_segments(cam_of, tl, max_batch):
             if kind == "run":
                 if not (0 <= tl[c0] and tl[c1 - 1] < self.frm_num):
@@ -219,6 +255,11 @@ class BakedMPV(_Baked):
         return render_path_baked(self.texels, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep, cull_scratch=cull_scratch,
                                  **display)
 
+    def _times(self, frame_cam, frame_time, homos, H, W, out, cull_scratch=None, **display):
+        from .render import render_times_baked
+        return render_times_baked(self.texels, frame_cam, frame_time, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
+                                  cull_scratch=cull_scratch, **display)
+
 
 class BakedPool(_Baked):
     """bake_pool(module)'s product: the playback model of a tile-culled model without a dense clip.  pool [n_slots * 64, 4] uint8 on the device
@@ -256,6 +297,11 @@ class BakedPool(_Baked):
         from .render import render_path_baked_pool
         return render_path_baked_pool(self.layout, self.pool, frame_cam, frame_t, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
                                       culled_rgba8=self.culled_rgba8, cull_scratch=cull_scratch, **display)
+
+    def _times(self, frame_cam, frame_time, homos, H, W, out, cull_scratch=None, **display):
+        from .render import render_times_baked_pool
+        return render_times_baked_pool(self.layout, self.pool, frame_cam, frame_time, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
+                                       culled_rgba8=self.culled_rgba8, cull_scratch=cull_scratch, **display)
 
     @torch.no_grad()
     def unpack_frames(self, frames):

@@ -42,6 +42,31 @@ __device__ __forceinline__ bool path_frame(const PathIdx &p, int i, int &cam, in
     return (unsigned)cam < (unsigned)p.n_cams && (unsigned)t < (unsigned)p.n_t;
 }
 
+// A camera path in LOOP TIME (vl3d_baked_times: vl3d_render_fwd_baked_times / _pool_times): output frame i shows the model at the real-valued time
+// frame_time[i] in [0, n_t), device float[N] -- the linear interpolation of its texels between frame t0 = floor(time) and frame t1 = t0 + 1,
+// which wraps to 0 at the loop seam, with f = time - t0 (exact in fp32).  One output frame per thread, TWO source frames.
+struct PathTime {
+    const int *frame_cam;
+    const float *frame_time;
+    int n_cams, n_t;
+};
+// (cam, t0, t1, f) of output frame i as two workgroup-uniform scalar loads; false -- the workgroup returns before any other load or store --
+// unless cam is in [0, n_cams) and the time in [0, n_t).  A NaN fails both comparisons.  The conversion comes after the check, and t0 < n_t
+// is checked once more as an integer (n_t >= 2^24 is not a float): t0 and t1 are frames of the model whatever device memory holds.
+__device__ __forceinline__ bool path_frame(const PathTime &p, int i, int &cam, int &t0, int &t1, float &f) {
+    cam = ((cint_p)p.frame_cam)[i];
+    const float time = ((cfloat_p)p.frame_time)[i];
+    if (!((unsigned)cam < (unsigned)p.n_cams && time >= 0.0f && time < (float)p.n_t)) return false;
+    t0 = (int)time;
+    if (!((unsigned)t0 < (unsigned)p.n_t)) return false;
+    t1 = t0 + 1 < p.n_t ? t0 + 1 : 0;
+    f = time - (float)t0;
+    return true;
+}
+// frames a thread composites (NF) and source frames whose taps it fetches: NF, but two for the one output frame of a loop-time path
+template <int NF, typename PATH>
+constexpr int baked_sources() { return std::is_same<PATH, PathTime>::value ? 2 : NF; }
+
 // Where a composited pixel goes.  FloatOut: a.rgb / a.alpha, fp32 -- an empty argument, so that the two sinks are one kernel text (as NoPath
 // beside PathIdx).  DisplayOut (the display sink, vl3d_baked_out.frames): the frame a viewer shows, frames (N,H,W,channels) uint8, over the background
 // bg when has_bg; pack3: the lane-packed RGB8 store instead of three byte stores per lane.  bg travels in the kernel arguments.
@@ -140,6 +165,29 @@ struct BakedComposite {
             Tr[f] *= (1.0f - al);
         }
     }
+    // one plane at a fractional loop time (PathTime): v[0], v[1] = the taps of frames t0 and t1, fr = time - t0.  Every channel, alpha
+    // included, is c = fmaf(fr, b1 - b0, b0) of the two frames' blends, and c takes the place of the blend in the one-frame step above --
+    // the same five statements, repeated here and not factored out: a helper both operators call moves the one-frame kernels' registers
+    // (the register table, docs/kernels/K9_baked_playback.md).  Exact consequences: fr == 0 gives the bits of b0 (the product is a zero, b0
+    // is never -0), equal taps give b1 - b0 = 0 and the bits of b0 at any fr.
+    template <typename TAPS>
+    __device__ __forceinline__ void operator()(const TAPS &t, const BakedTaps *v, float fr) const {
+#pragma clang fp contract(off)
+        static_assert(NF == 1, "a loop-time path renders one output frame per thread");
+        const f4 w255 = t.w * (1.0f / 255.0f);
+        const auto c = [&](auto k) {
+#pragma clang fp contract(off)
+            const float b0 = blend<decltype(k)::value>(v[0], w255), b1 = blend<decltype(k)::value>(v[1], w255);
+            return fmaf(fr, b1 - b0, b0);
+        };
+        const float al = c(std::integral_constant<int, 3>{}) * t.cov;
+        const float w = al * Tr[0];
+        cr[0] = fmaf(w, c(std::integral_constant<int, 0>{}), cr[0]);
+        cg[0] = fmaf(w, c(std::integral_constant<int, 1>{}), cg[0]);
+        cb[0] = fmaf(w, c(std::integral_constant<int, 2>{}), cb[0]);
+        A[0] += w;
+        Tr[0] *= (1.0f - al);
+    }
     // pixel (x, y) of frame t0, then of frame t0 + 1 under has1 (odd T: the last pair composites frame t0 twice and stores it once)
     __device__ __forceinline__ void store(const RenderArgs &a, const DisplayOut &o, int t0, int x, int y, bool has1) const {
         const size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
@@ -161,6 +209,16 @@ struct BakedComposite {
             }
         }
     }
+};
+
+// The composite of a loop-time kernel: the one-frame composite with the fraction bound, so that the dense kernel's call composite(t, v)
+// is one text for every PATH (a wrapper lambda around the two operators moves the one-frame kernels' registers).
+template <typename OWNER>
+struct BakedCompositeAt : BakedComposite<1, OWNER> {
+    float fr = 0.0f;      // time - t0, set by the kernel once path_frame has given it
+    using BakedComposite<1, OWNER>::BakedComposite;
+    template <typename TAPS>
+    __device__ __forceinline__ void operator()(const TAPS &t, const BakedTaps *v) const { BakedComposite<1, OWNER>::operator()(t, v, fr); }
 };
 
 }  // namespace

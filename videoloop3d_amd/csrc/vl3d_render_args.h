@@ -98,6 +98,18 @@ inline int check_baked_frames(const vl3d_render_desc *desc, const vl3d_baked_fra
     return VL3D_OK;
 }
 
+// the selection of a path in loop time: both pointers, reserved = 0, n_cams in [1, 65535], tiles x frames inside the grid
+inline int check_baked_times(const vl3d_render_desc *desc, const vl3d_baked_times *sel, const char *who) {
+    const char *bad = nullptr;
+    if (!sel) bad = "null pointer (sel)";
+    else if (!sel->frame_cam) bad = "null pointer (sel->frame_cam: device int32[desc->T])";
+    else if (!sel->frame_time) bad = "null pointer (sel->frame_time: device float[desc->T])";
+    else if (sel->reserved != 0) bad = "sel->reserved must be 0";
+    else if (!(sel->n_cams >= 1 && sel->n_cams <= 65535)) bad = "n_cams must be in [1, 65535]";
+    else if ((int64_t)((desc->W + 63) / 64) * ((desc->H + 7) / 8) * desc->T > 0x7fffffffll) bad = "tiles x frames exceed the grid";
+    return bad ? refuse(who, bad) : VL3D_OK;
+}
+
 // the sink: exactly one of (rgb and alpha) or frames -- the display sink's own rules are display_out_of's (vl3d_baked_core.h)
 inline int check_baked_out(const vl3d_baked_out *out, const char *who) {
     const char *bad = nullptr;

@@ -68,21 +68,31 @@ __device__ __forceinline__ BakedTaps load_baked(const char *__restrict__ plane, 
 // PATH = PathIdx (a camera path, sel->frame_cam / frame_t): the block index's outermost factor is the OUTPUT frame i; the workgroup reads its camera and
 // its frame of the clip (path_frame: scalar loads, range-checked) and from them forms its homography, mask and texel bases.  One frame per
 // thread: from there on the one-frame kernel.
+// PATH = PathTime (a path in loop time, vl3d_baked_times): as PathIdx, but the workgroup reads a real-valued time and fetches the taps of
+// TWO frames, t0 and t1 (t1 wraps to 0 at the seam), which the composite interpolates by f before its one-frame step.
 // OUT = FloatOut: rgb / alpha fp32 at a.rgb / a.alpha.  OUT = DisplayOut (out->frames): the 8-bit display frame over
 // the background, written by the same launch (vl3d_baked_core.h); everything in front of the store is the one text.
 template <int NF, bool CULL, typename PATH = NoPath, typename OUT = FloatOut>
 __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tiles_x, int tiles_y, PATH path, OUT out) {
     constexpr bool IS_PATH = !std::is_same<PATH, NoPath>::value;
+    constexpr bool IS_TIME = std::is_same<PATH, PathTime>::value;
+    constexpr int NS = baked_sources<NF, PATH>();      // source frames fetched per thread
     static_assert(!IS_PATH || NF == 1, "a camera path renders one frame per thread");
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_x = b % tiles_x, rest = b / tiles_x;
     const int tile_y = rest % tiles_y, t0 = (rest / tiles_y) * NF;      // (a path: the output frame)
     const bool has1 = NF == 2 && t0 + 1 < a.T;      // odd T: the last pair composites frame t0 twice and stores it once
     int tile = tile_y * tiles_x + tile_x, src_t = t0;
+    [[maybe_unused]] int src_t1 = 0;          // a loop time: the second source frame and the fraction
+    [[maybe_unused]] float frac = 0.0f;
     const float *homos = a.homos;
     if constexpr (IS_PATH) {
         int cam;
-        if (!path_frame(path, t0, cam, src_t)) return;      // uniform: nothing loaded, nothing stored
+        if constexpr (IS_TIME) {
+            if (!path_frame(path, t0, cam, src_t, src_t1, frac)) return;
+        } else {
+            if (!path_frame(path, t0, cam, src_t)) return;      // uniform: nothing loaded, nothing stored
+        }
         homos += (size_t)cam * a.D * VL3D_HS;
         tile += cam * tiles_x * tiles_y;
     }
@@ -93,22 +103,24 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     const unsigned row_b = (unsigned)a.Ws * 4u;
     const size_t frame_b = (size_t)a.Hs * a.Ws * 4;
     const size_t plane_stride_b = (size_t)a.Tstride * frame_b;
-    const char *base[NF];
+    const char *base[NS];
     base[0] = reinterpret_cast<const char *>(a.stack) + (size_t)src_t * frame_b;
-    if constexpr (NF == 2) base[1] = base[0] + (has1 ? frame_b : 0);
+    if constexpr (IS_TIME) base[1] = reinterpret_cast<const char *>(a.stack) + (size_t)src_t1 * frame_b;
+    else if constexpr (NF == 2) base[1] = base[0] + (has1 ? frame_b : 0);
     float Tr[NF], cr[NF], cg[NF], cb[NF], A[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) { Tr[f] = 1.0f; cr[f] = cg[f] = cb[f] = A[f] = 0.0f; }
-    BakedTaps vA[NF], vB[NF];
+    BakedTaps vA[NS], vB[NS];
     struct Owner;      // a type of this kernel instantiation alone: its own copy of the composite (vl3d_baked_core.h)
-    const BakedComposite<NF, Owner> composite(Tr, cr, cg, cb, A);
+    std::conditional_t<IS_TIME, BakedCompositeAt<Owner>, const BakedComposite<NF, Owner>> composite(Tr, cr, cg, cb, A);
+    if constexpr (IS_TIME) composite.fr = frac;
     auto fetch = [&](int d, Taps2 &t, BakedTaps *v) {
         float h[VL3D_HN];
         load_uniform(homos + VL3D_HS * d, h);
         if constexpr (CULL) t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
         else t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
 #pragma unroll
-        for (int f = 0; f < NF; ++f) v[f] = load_baked(base[f] + (size_t)d * plane_stride_b, t, row_b);
+        for (int f = 0; f < NS; ++f) v[f] = load_baked(base[f] + (size_t)d * plane_stride_b, t, row_b);
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
     Taps2 tA, tB;
@@ -172,30 +184,37 @@ extern "C" int64_t vl3d_render_path_cull_scratch_bytes(const vl3d_render_desc *d
     return (int64_t)n_cams * ((desc->W + 63) / 64) * ((desc->H + 7) / 8) * 16;
 }
 
-// The one entry: the refusals, RenderArgs, then the plan launch of a tile-culled model (the float forward's plan over its 64 x 8 tiles: one
-// camera's, or all cameras' of a path in one launch) and the render launch on <NF, CULL, PATH, OUT> as `sel` and `out` name them.
-extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
-                                     const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
-                                     const vl3d_baked_out *out, vl3d_stream_t stream) {
-    const char *who = "vl3d_render_fwd_baked";
+namespace {
+
+// The one body of the two entries: the refusals, RenderArgs, then the plan launch of a tile-culled model (the float forward's plan over its
+// 64 x 8 tiles: one camera's, or all cameras' of a path in one launch) and the render launch on <NF, CULL, PATH, OUT> as the selection --
+// `sel` (a run or a path of frames) or `times` (a path in loop time), exactly one of them -- and `out` name them.
+int render_fwd_baked(const char *who, const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                     const vl3d_baked_frames *sel, const vl3d_baked_times *times, bool by_time, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                     void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream) {
     // a row's two taps are one 8-byte load, the two rows a constant step apart
     int rc = check_baked_desc(desc, 1ll << 28, "plane too large for 32-bit tap offsets", who);
     if (rc != VL3D_OK) return rc;
-    bool is_path = false;
-    if ((rc = check_baked_frames(desc, sel, is_path, who)) != VL3D_OK || (rc = check_baked_out(out, who)) != VL3D_OK) return rc;
-    VL3D_REQUIRE(baked && homos, "vl3d_render_fwd_baked: null pointer");
-    VL3D_REQUIRE(((uintptr_t)baked & 3) == 0, "vl3d_render_fwd_baked: the texels must be 4-byte aligned");
+    bool is_path = by_time;
+    if ((rc = by_time ? check_baked_times(desc, times, who) : check_baked_frames(desc, sel, is_path, who)) != VL3D_OK ||
+        (rc = check_baked_out(out, who)) != VL3D_OK)
+        return rc;
+    if (!(baked && homos)) return refuse(who, "null pointer");
+    if (((uintptr_t)baked & 3) != 0) return refuse(who, "the texels must be 4-byte aligned");
     DisplayOut disp;
     if (out->frames && (rc = display_out_of(out->frames, out->channels, out->bg, who, disp)) != VL3D_OK) return rc;
-    if (is_path) VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_baked: a clip of T_alloc >= 1 frames");
-    else VL3D_REQUIRE(T_alloc > 0 && sel->frame0 >= 0 && sel->frame0 + desc->T <= T_alloc, "vl3d_render_fwd_baked: the run of frames leaves the clip");
+    if (is_path) {
+        if (!(T_alloc > 0)) return refuse(who, "a clip of T_alloc >= 1 frames");
+    } else if (!(T_alloc > 0 && sel->frame0 >= 0 && sel->frame0 + desc->T <= T_alloc)) {
+        return refuse(who, "the run of frames leaves the clip");
+    }
     RenderArgs a = render_args_of(desc);      // (a.uv_seed is 0, checked above; a path: a.T is the count of its output frames)
     a.Tstride = T_alloc;
     a.stack = reinterpret_cast<const float *>(baked + (is_path ? 0 : (size_t)sel->frame0 * desc->Hs * desc->Ws * 4));
     a.homos = homos; a.rgb = out->rgb; a.alpha = out->alpha;
     if (quad_keep) {
         if ((rc = check_cull_grid(desc, QH, QW, who)) != VL3D_OK) return rc;
-        VL3D_REQUIRE(cull_scratch, "vl3d_render_fwd_baked: tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
+        if (!cull_scratch) return refuse(who, "tile culling needs vl3d_render_cull_scratch_bytes() of scratch");
         a.quad_keep = quad_keep;
         a.cull_masks = (const unsigned long long *)cull_scratch;
         set_cull_geometry(a, desc, QH, QW);
@@ -208,8 +227,8 @@ extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t
         using OUT = std::decay_t<decltype(o)>;
         const dim3 grid((unsigned)(tiles_x * tiles_y * ((a.T + NF - 1) / NF))), block(512);
         if (a.quad_keep) {
-            if constexpr (std::is_same<PATH, PathIdx>::value) launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
-            else launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
+            if constexpr (std::is_same<PATH, NoPath>::value) launch_cull_fwd_plan<VL3D_COORD_AFFINE>(a, 8, tiles_x, tiles_y, s);
+            else launch_cull_fwd_plan_cams<VL3D_COORD_AFFINE>(a, path.n_cams, 8, tiles_x, tiles_y, s);
             hipLaunchKernelGGL((render_fwd_baked_k<NF, true, PATH, OUT>), grid, block, 0, s, a, tiles_x, tiles_y, path, o);
             return;
         }
@@ -217,11 +236,32 @@ extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t
     };
     const std::integral_constant<int, 1> one;      // frames per thread: pairs for a run of two or more, one along a path
     const std::integral_constant<int, 2> two;
-    const PathIdx path{sel->frame_cam, sel->frame_t, sel->n_cams, T_alloc};
-    if (!is_path && !out->frames) desc->T >= 2 ? launch(two, NoPath{}, FloatOut{}) : launch(one, NoPath{}, FloatOut{});
-    else if (!is_path) desc->T >= 2 ? launch(two, NoPath{}, disp) : launch(one, NoPath{}, disp);
-    else if (!out->frames) launch(one, path, FloatOut{});
-    else launch(one, path, disp);
+    if (by_time) {
+        const PathTime path{times->frame_cam, times->frame_time, times->n_cams, T_alloc};
+        if (!out->frames) launch(one, path, FloatOut{});
+        else launch(one, path, disp);
+    } else {
+        const PathIdx path{sel->frame_cam, sel->frame_t, sel->n_cams, T_alloc};
+        if (!is_path && !out->frames) desc->T >= 2 ? launch(two, NoPath{}, FloatOut{}) : launch(one, NoPath{}, FloatOut{});
+        else if (!is_path) desc->T >= 2 ? launch(two, NoPath{}, disp) : launch(one, NoPath{}, disp);
+        else if (!out->frames) launch(one, path, FloatOut{});
+        else launch(one, path, disp);
+    }
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
+}
+
+}  // namespace
+
+extern "C" int vl3d_render_fwd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                                     const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
+                                     const vl3d_baked_out *out, vl3d_stream_t stream) {
+    return render_fwd_baked("vl3d_render_fwd_baked", desc, baked, T_alloc, homos, sel, nullptr, false, quad_keep, QH, QW, cull_scratch, out, stream);
+}
+
+extern "C" int vl3d_render_fwd_baked_times(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos,
+                                           const vl3d_baked_times *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch,
+                                           const vl3d_baked_out *out, vl3d_stream_t stream) {
+    return render_fwd_baked("vl3d_render_fwd_baked_times", desc, baked, T_alloc, homos, nullptr, sel, true, quad_keep, QH, QW, cull_scratch, out,
+                            stream);
 }

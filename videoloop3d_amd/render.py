@@ -424,6 +424,29 @@ def _path_indices(frame_cam, frame_t, n_cams, T, device, who):
     return len(cam), idx
 
 
+def _time_indices(frame_cam, frame_time, n_cams, T, device, who):
+    """the (camera, loop time) pairs of a path in loop time, checked on the host (the kernels cannot report a bad value: they skip its frame)
+    and uploaded in ONE pinned copy -> (N, int32 [2,N] on `device`: row 0 the cameras, row 1 the BITS of the float32 times).  The times are
+    cast to float32 first and must then be finite and in [0, T) (baked.loop_times reduces any real time): ValueError."""
+    import numpy as np
+    cam, t = np.asarray(frame_cam).reshape(-1), np.asarray(frame_time).reshape(-1)
+    if len(cam) != len(t):
+        raise RuntimeError(f"{who}: frame_cam and frame_time name the same output frames ({len(cam)} cameras, {len(t)} times)")
+    if len(cam) == 0:
+        raise RuntimeError(f"{who}: an empty path (N = 0 output frames)")
+    if cam.dtype.kind not in "iu" or t.dtype.kind not in "iuf":
+        raise RuntimeError(f"{who}: frame_cam are integer indices, frame_time real loop times")
+    if int(cam.min()) < 0 or int(cam.max()) >= n_cams:
+        raise IndexError(f"{who}: camera index {int(cam.min())} .. {int(cam.max())} outside the {n_cams} cameras of homos")
+    t = t.astype(np.float32)
+    if not np.isfinite(t).all():
+        raise ValueError(f"{who}: a loop time is not finite")
+    if float(t.min()) < 0 or float(t.max()) >= T:
+        raise ValueError(f"{who}: loop time {float(t.min())} .. {float(t.max())} outside [0, {T}) (baked.loop_times reduces any time into the loop)")
+    idx = torch.from_numpy(np.stack([cam.astype(np.int32), t.view(np.int32)])).pin_memory().to(device, non_blocking=True)
+    return len(cam), idx
+
+
 def _path_cull_scratch(desc, n_cams, device, cull_scratch, who):
     """the plane masks of a path render, [n_cams][tiles][2] uint64 (vl3d_render_path_cull_scratch_bytes): the caller's buffer checked for
     device, dtype and size, or a fresh one; call under torch.cuda.device(device)."""
@@ -480,15 +503,18 @@ def _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8):
                                            head=(L.ptr(bl), L.ptr(pool), int(layout.T)), culled=(int(culled_rgba8) & 0xFFFFFFFF,))
 
 
-def _baked_render(who, src, n, frame0, path, homos, H, W, spec, out, frames8, bg, cull_scratch=None):
-    """the one call of the four baked renders: `n` output frames of source `src` (_baked_dense / _baked_pool) -- the run from `frame0` under
+def _baked_render(who, src, n, frame0, path, homos, H, W, spec, out, frames8, bg, cull_scratch=None, by_time=False):
+    """the one call of the six baked renders: `n` output frames of source `src` (_baked_dense / _baked_pool) -- the run from `frame0` under
     homos [D,3,3], or the `path` (C, idx [2,n] on the device) under homos [C,D,3,3] -- into the float sink (`out`, or fresh buffers) or the
-    display sink (`frames8`, `bg`).  Fills vl3d_baked_frames and vl3d_baked_out and calls src.entry."""
+    display sink (`frames8`, `bg`).  Fills vl3d_baked_frames and vl3d_baked_out and calls src.entry; `by_time`: the path's second row holds
+    float32 loop times (_time_indices): vl3d_baked_times and the entry's `_times` form."""
     dev = src.device
     homos = homos.detach().to(torch.float32).contiguous()
     desc = _desc_dims(src.dims[0], n, src.dims[1], src.dims[2], H, W, spec, L.STACK_DTYPE["u8"])
-    sel, sink = L.BakedFrames(frame0=int(frame0)), L.BakedOut()
-    if path is not None:
+    sel, sink, entry = L.BakedFrames(frame0=int(frame0)), L.BakedOut(), src.entry
+    if by_time:
+        sel, entry = L.BakedTimes(n_cams=path[0], frame_cam=path[1][0].data_ptr(), frame_time=path[1][1].data_ptr()), src.entry + "_times"
+    elif path is not None:
         sel.n_cams, sel.frame_cam, sel.frame_t = path[0], path[1][0].data_ptr(), path[1][1].data_ptr()
     if frames8 is not None:
         sink.channels, bgc = _display_out(out, frames8, bg, n, H, W, dev, who)
@@ -501,8 +527,8 @@ def _baked_render(who, src, n, frame0, path, homos, H, W, spec, out, frames8, bg
         if src.qk is not None:
             cull = _cull_scratch(desc, dev) if path is None else _path_cull_scratch(desc, path[0], dev, cull_scratch, who)
         grid = (0, 0) if src.qk is None else _qgrid(src.qk, spec)
-        L.check(getattr(L.lib(), src.entry)(desc, *src.head, L.ptr(homos), sel, L.ptr(src.qk), *grid, *src.culled, L.ptr(cull), sink,
-                                            L.stream_ptr(dev)), src.entry)
+        L.check(getattr(L.lib(), entry)(desc, *src.head, L.ptr(homos), sel, L.ptr(src.qk), *grid, *src.culled, L.ptr(cull), sink,
+                                        L.stream_ptr(dev)), entry)
     return ret
 
 
@@ -520,6 +546,15 @@ def _check_path(who, frame_cam, frame_t, T, homos, D, device):
         raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
     C = int(homos.shape[0])
     n, idx = _path_indices(frame_cam, frame_t, C, T, device, who)
+    return n, (C, idx)
+
+
+def _check_times(who, frame_cam, frame_time, T, homos, D, device):
+    """a camera path in loop time: homos [C,D,3,3], cameras and times checked and uploaded -> (n output frames, (C, idx [2,n] on `device`))"""
+    if homos.dim() != 4 or tuple(homos.shape[1:]) != (D, 3, 3) or homos.shape[0] < 1:
+        raise RuntimeError(f"homos must be [C,D,3,3] = [C,{D},3,3] with C >= 1 cameras, got {tuple(homos.shape)}")
+    C = int(homos.shape[0])
+    n, idx = _time_indices(frame_cam, frame_time, C, T, device, who)
     return n, (C, idx)
 
 
@@ -585,6 +620,34 @@ def render_path_baked_pool(layout, pool, frame_cam, frame_t, homos, H, W, spec: 
     T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
     n, path = _check_path(who, frame_cam, frame_t, T, homos, src.dims[0], src.device)
     return _baked_render(who, src, n, 0, path, homos, H, W, spec, out, frames8, bg, cull_scratch)
+
+
+def render_times_baked(baked, frame_cam, frame_time, homos, H, W, spec: RenderSpec, out=None, quad_keep=None, cull_scratch=None, frames8=None, bg=None):
+    """A camera path in LOOP TIME on the baked clip (vl3d_render_fwd_baked_times): render_path_baked with a real-valued time per output frame.
+    The clip is a loop of T frames; output frame i shows it at time frame_time[i] in [0, T) -- the linear interpolation of its TEXELS between
+    frame t0 = floor(time) and frame t1 = t0 + 1, which wraps to frame 0 behind the last frame, by f = time - t0 -- seen by camera frame_cam[i]
+    of `homos` [C,D,3,3], in ONE plan launch plus ONE render launch.  A frame at an integer time has the bits of render_path_baked's frame
+    (cam, t0).  frame_time: a host sequence or numpy array, finite and already in [0, T) as float32 (ValueError; baked.loop_times reduces any
+    time); frame_cam as render_path_baked checks it (IndexError); both go up in one pinned copy.  Everything else -- `out`, `quad_keep`,
+    `cull_scratch`, `frames8` / `bg` -- as render_path_baked."""
+    who = "render_times_baked"
+    _check_bg(who, frames8, bg)
+    T, src = _baked_dense(who, baked, homos, spec, quad_keep)
+    n, path = _check_times(who, frame_cam, frame_time, T, homos, src.dims[0], src.device)
+    return _baked_render(who, src, n, 0, path, homos, H, W, spec, out, frames8, bg, cull_scratch, by_time=True)
+
+
+def render_times_baked_pool(layout, pool, frame_cam, frame_time, homos, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8, cull_scratch=None,
+                            frames8=None, bg=None):
+    """render_times_baked from the baked POOL (vl3d_render_fwd_baked_pool_times): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
+    render_frame_run_baked_pool takes them, cameras and times as render_times_baked takes them (the loop is the model's layout.T frames).  A
+    static block serves both frames of a time from one fetch, a dynamic block is read at slot + t0 and slot + t1.  -> the bits of
+    render_times_baked on the unpacked texels."""
+    who = "render_times_baked_pool"
+    _check_bg(who, frames8, bg)
+    T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
+    n, path = _check_times(who, frame_cam, frame_time, T, homos, src.dims[0], src.device)
+    return _baked_render(who, src, n, 0, path, homos, H, W, spec, out, frames8, bg, cull_scratch, by_time=True)
 
 
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,

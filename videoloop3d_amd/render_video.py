@@ -161,6 +161,16 @@ def to8b(x):
     return (255 * x.clamp(0, 1)).to(torch.uint8)
 
 
+def retime(n_out, fps_out, fps_loop=25.0, speed=1.0):
+    """The loop times of `n_out` output frames shown at `fps_out` frames per second, for a loop recorded at `fps_loop` (the reference writes its
+    videos at 25 fps, script_render_video.py:149) and played at `speed`: float64 i * fps_loop * speed / fps_out, UNREDUCED -- they grow past
+    the loop's length (and run backwards for a negative speed); `fractional=True` of render_frames / BakedMPV.render_display reduces them
+    (baked.loop_times)."""
+    if not (fps_out > 0 and fps_loop > 0):
+        raise ValueError(f"retime: frame rates are positive (fps_out {fps_out}, fps_loop {fps_loop})")
+    return np.arange(int(n_out), dtype=np.float64) * float(fps_loop) * float(speed) / float(fps_out)
+
+
 def path_segments(cam_of, render_t, chunk):
     """How render_frames(baked=) launches a selection of n output frames (cam_of[i]: the index of frame i's camera, render_t[i]: its frame of
     the clip) in chunks of at most `chunk` frames -> [(kind, i, j)], one segment per chunk, frames i .. j - 1:
@@ -246,7 +256,7 @@ def _in_place_runs(camera, stack, packed, qk, spec, bg_color, H, W, view_extrins
 
 
 @torch.no_grad()
-def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64, in_place=True, baked=None):
+def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64, in_place=True, baked=None, fractional=False):
     """script_render_video.py:129-139: `nerf(H, W, extrin, intrin, t)` in eval mode for every output frame -> uint8 [N,H,W,3] on the
     model's device.  A dense model on the device renders every frame where it lies in the clip, with the path's homographies uploaded once
     (`_render_frames_in_place`: 720p, D = 32, T = 50 along a spiral 1430 -> several thousand frames / s; `in_place=False` keeps the loop below).
@@ -255,7 +265,18 @@ def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64
     `baked` (baked.BakedMPV or baked.BakedPool, the product of baked.bake(model) / baked.bake_pool(model)): the frames of the PLAYBACK model -- its 8-bit texels filtered after the
     activation, what the exported viewer package shows -- through the same run logic; the float stack is not read.  A chunk of `max_batch`
     frames that is not one run (a spiral: every frame its own camera) is ONE path call (render.render_path_baked / _pool: one plan launch and one
-    render launch for the chunk; `path_segments`), with the bits of the per-frame calls."""
+    render launch for the chunk; `path_segments`), with the bits of the per-frame calls.
+    `fractional` (with `baked=` only): render_t are real LOOP TIMES of any sign and size -- `retime(...)` for a display rate other than the
+    loop's -- and every frame is the playback model interpolated between its two adjacent frames, across the loop seam too
+    (baked.render_display(fractional=True)).  The float model is not retimed here: without `baked=` a ValueError."""
+    if fractional:
+        if baked is None:
+            raise ValueError("render_frames: fractional=True renders loop times of the playback model (pass baked=); the float model is not retimed here")
+        n = min(len(np.asarray(render_t).reshape(-1)), len(view_extrins))
+        view_extrins = torch.as_tensor(np.asarray(view_extrins), dtype=torch.float32)
+        view_intrins = torch.as_tensor(np.asarray(view_intrins), dtype=torch.float32)
+        return baked.render_display(H, W, view_extrins[:n], view_intrins[:n], np.asarray(render_t, dtype=np.float64).reshape(-1)[:n], channels=3,
+                                    max_batch=max_batch, fractional=True)
     module = getattr(nerf, "module", nerf)
     was_training = module.training
     nerf.eval()
