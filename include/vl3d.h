@@ -73,11 +73,11 @@ typedef struct vl3d_render_desc {
                             * T >= 2: two frames per thread, same bits); bits 12-15: 1 = the two-pass forward with regularisers.  Bits 4-7
                             * (timing-only ablations, wrong results) exist only in a -DVL3D_VARIANTS measurement build: the product
                             * library returns VL3D_EINVAL for them. */
-    /* tile culling on a WINDOW of the stack (vl3d_render_*_culled only; all 0 = the stack is the whole plane): the stack passed in is
+    /* tile culling on a WINDOW of the stack (a call with a quad map only; all 0 = the stack is the whole plane): the stack passed in is
      * the texel window [cull_row0, cull_row0+Hs) x [cull_col0, cull_col0+Ws) of a cull_Hs x cull_Ws plane, and the quad grid of
      * quad_keep lies over that whole plane. */
     int32_t cull_row0, cull_col0, cull_Hs, cull_Ws;
-    /* vl3d_render_bwd_culled only.  Bit 0 (VL3D_GRAD_CULLED_UNWRITTEN): the caller never reads the gradient of texels no kept quad can
+    /* vl3d_render_bwd with a quad map only.  Bit 0 (VL3D_GRAD_CULLED_UNWRITTEN): the caller never reads the gradient of texels no kept quad can
      * read (vl3d_adam_window_step / vl3d_adam_step_tiles skip them: they are no parameters), so the texels a workgroup owns on a plane it
      * skips are not written at all instead of being zero-filled -- on a 16 %-kept model that fill was a quarter of the backward's time.
      * Those slots of grad_stack are then UNDEFINED.  0 = every texel of grad_stack is written (a gradient any consumer may read).
@@ -95,18 +95,19 @@ typedef struct vl3d_render_desc {
 enum { VL3D_GRAD_CULLED_UNWRITTEN = 1 };
 
 /* alpha_sums (optional, may be NULL): (T,H,W,2) per pixel (sum_k a_k, sum_k a_k^2) over the planes -- the two sums the
- * sparsity regulariser (MPV.py:511-515 / MPI.py:599-603: |a|_1 / |a|_2 per pixel) is made of. */
-int vl3d_render_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos,
-                    float *rgb, float *alpha, float *alpha_sums, vl3d_stream_t stream);
+ * sparsity regulariser (MPV.py:511-515 / MPI.py:599-603: |a|_1 / |a|_2 per pixel) is made of.
+ * quad_keep NULL = a dense model (QH, QW and cull_scratch are not read), else the quad map [D][|QH|][|QW|] of a tile-culled (sparsified)
+ * model, its quad grid (negative: tile-exact layout) and vl3d_render_cull_scratch_bytes(desc) bytes of scratch: "Tile culling" below. */
+int vl3d_render_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                    void *cull_scratch, float *rgb, float *alpha, float *alpha_sums, vl3d_stream_t stream);
 /* ... of frames frame0 .. frame0 + desc->T - 1 of a LONGER clip, read in place: `stack` is the base of a (D, T_alloc, Hs, Ws, 4) allocation,
  * desc->T the number of consecutive frames to render (an evaluation render of single frames or runs of frames -- scripts/script_render_video.py:
- * 129-139 renders one frame per camera of its path -- without gathering `stack[:, ts]` first: 571 MB per 720p frame at D = 32 on 1.1x planes). */
-int vl3d_render_fwd_frames(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos, float *rgb,
-                           float *alpha, vl3d_stream_t stream);
-/* ... of a tile-culled (sparsified) dense model: vl3d_render_fwd_culled's quad map and scratch, the same run of frames. */
-int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
-                                  const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
-                                  vl3d_stream_t stream);
+ * 129-139 renders one frame per camera of its path -- without gathering `stack[:, ts]` first: 571 MB per 720p frame at D = 32 on 1.1x planes).
+ * quad_keep NULL = a dense model, else a tile-culled (sparsified) dense model: vl3d_render_fwd's quad map, grid and scratch, the same run of
+ * frames. */
+int vl3d_render_fwd_frames(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
+                           const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
+                           vl3d_stream_t stream);
 
 /* Baked playback (csrc/vl3d_render_baked.hip, csrc/vl3d_render_baked_pool.hip).  The viewer package the reference exports
  * (scripts/script_export_mesh.py:117-191) holds ACTIVATED 8-bit atlases, and a player filters those texels bilinearly after the activation --
@@ -122,7 +123,7 @@ int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stac
  *     the texels are activated already).  Anything else, a NULL pointer, a misaligned source: VL3D_EINVAL, nothing launched.  Forward only;
  *     no host synchronisation.  The two entries differ in the SOURCE; both take the SELECTION and the SINK as the two structs below.
  *   Source.  vl3d_render_fwd_baked: a baked clip (D, T_alloc, Hs, Ws, 4) uint8, 4-byte aligned, read in place.  quad_keep NULL = a dense
- *     model, else vl3d_render_fwd_frames_culled's map, quad grid (negative: tile-exact layout), desc->cull_* window and cull_scratch.
+ *     model, else vl3d_render_fwd_frames's map, quad grid (negative: tile-exact layout), desc->cull_* window and cull_scratch.
  *     vl3d_render_fwd_baked_pool: the baked POOL of a packed tile-culled model -- the "Packed storage" block table below with RGBA8 texels
  *     behind it.  blocks [D][ceil(Hs/8)][ceil(Ws/8)] int32: -1 (not stored) | slot << 1 | dynamic; pool: n_slots * 256 bytes, a slot = one
  *     8 x 8 block of 4-byte texels, row-major; a static block owns one slot, a dynamic block T_model consecutive ones (frame t at slot + t);
@@ -245,12 +246,14 @@ int vl3d_pool_from_atlas_rgba8(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int
  *   6 / 7  two frames per thread in 32 x 16 / 64 x 12 regions wherever 0 takes frame pairs WITHOUT regularisers; = 3 elsewhere
  *   every other value = 3.  All of them produce the same gradient bits.
  * vl3d_render_bwd_mask: 3 / 4 the 64 x 16 regions, 1 atomics, every other value flat 64 x 8 regions (its default).  vl3d_render_bwd_adam: a
- * dense model (variant 0 only) rides the 32 x 16 frame pairs; a tile-culled one 32 x 16 one-frame regions, 64 x 16 with variant 3. */
+ * dense model (variant 0 only) rides the 32 x 16 frame pairs; a tile-culled one 32 x 16 one-frame regions, 64 x 16 with variant 3.
+ * quad_keep NULL = a dense model (QH, QW are not read), else the forward's quad map and grid ("Tile culling" below): a sample in a culled
+ * quad passes no gradient; the plan of the culled backward lives in the same scratch. */
 int64_t vl3d_render_bwd_scratch_bytes(const vl3d_render_desc *desc);
-int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float *homos,
-                    const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha,
-                    const float *grad_reg, const void *reg_state, const float *grad_alpha_sums, float *grad_stack, void *scratch,
-                    int64_t scratch_bytes, vl3d_stream_t stream);
+int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                    const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha, const float *grad_reg,
+                    const void *reg_state, const float *grad_alpha_sums, float *grad_stack, void *scratch, int64_t scratch_bytes,
+                    vl3d_stream_t stream);
 
 /* Which kernel a backward call runs, without running it: the value the entry points themselves compute (the same two functions, no device
  * touched, nothing enqueued).  entry: which entry point; has_quad_keep / has_reg_grads (grad_reg or grad_alpha_sums non-NULL) / scratch_bytes:
@@ -283,7 +286,7 @@ int vl3d_render_bwd_choice(const vl3d_render_desc *desc, int32_t entry, int32_t 
  * neighbouring tiles hold two copies of their common border samples), every face's UVs span exactly its tile (gen_quad_uvs, MPI.py:403-418;
  * sampled by MPV.py:394-427 / MPI.py:497-536), and stage 2 trains the two copies APART -- a static tile's copy is one texture, its dynamic
  * neighbour's copy moves per frame.  A stack on which neighbouring quads SHARE their border texels (the layout above) cannot hold such a
- * checkpoint.  Passing a NEGATIVE quad grid (-QH, -QW) to any entry point that takes one selects the tile-exact layout instead:
+ * checkpoint.  Passing a NEGATIVE quad grid (-QH, -QW) to an entry that takes a quad map selects the tile-exact layout instead:
  *   - a plane is QH x QW tiles of th x tw texels, th = Hs / QH, tw = Ws / QW (whole tiles of at least 2 x 2 texels; with desc->cull_*: of the
  *     cull_Hs x cull_Ws plane the stack is a window of -- the window itself need not be tile aligned); texel (y, x) belongs to quad
  *     (y / th, x / tw) and to no other: its class (culled / static / dynamic) is that quad's;
@@ -296,13 +299,6 @@ int vl3d_render_bwd_choice(const vl3d_render_desc *desc, int32_t entry, int32_t 
  *     texel coordinate.  VL3D_COORD_AFFINE + VL3D_BORDER_HARDCUT only (the reference has tiles on the planar MPV / MPI path only).
  * Pinned by golden G19 (tests/golden/make_golden_r06.py: the reference's own forward on a checkpoint whose border copies differ). */
 int64_t vl3d_render_cull_scratch_bytes(const vl3d_render_desc *desc);
-int vl3d_render_fwd_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep,
-                           int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha, float *alpha_sums,
-                           vl3d_stream_t stream);
-int vl3d_render_bwd_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep,
-                           int32_t QH, int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb,
-                           const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
-                           float *grad_stack, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
 
 /* Row bands with PER-PLANE source windows (videoloop3d_amd/dist.py plan_plane_bands; csrc/vl3d_render_plane_rows.hip).  The stack is a
  * rank's local (D, T, R, Ws, 4) rows: local row r of plane d is plane row plane_row0[d] + r (plane_row0: device int32[D]).  desc is the
@@ -327,7 +323,7 @@ int vl3d_render_bwd_plane_rows(const vl3d_render_desc *desc, const void *stack, 
  * gradient (D,T,Hs,Ws,4): texels that only static quads can read get the sum over the T frames in every frame (the T copies
  * then stay one texture under any optimiser), texels no kept quad can read get 0, texels a dynamic quad can read are left
  * alone.  quad_keep / quad_dyn: device byte maps [D][QH][QW].  mode bit 0: the gradient comes from the culled render
- * (vl3d_render_bwd_culled), which leaves exactly 0 in culled texels -- they are not rewritten.  mode bit 1: the consumer is
+ * (vl3d_render_bwd with a quad map), which leaves exactly 0 in culled texels -- they are not rewritten.  mode bit 1: the consumer is
  * vl3d_adam_step_tiles with the same quad_dyn, which reads a static texel's gradient from frame 0 only -- the sum is written
  * to frame 0 alone (the other frames keep their per-frame values and must not be used). */
 int vl3d_tie_static_grad(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const uint8_t *quad_keep, const uint8_t *quad_dyn,
@@ -393,7 +389,7 @@ int vl3d_adam_window_step(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t 
  * host synchronisation either way); it is left unwritten otherwise.
  * Tile-culled models (adam->quad_keep != NULL; the render culls with the same map, desc->cull_* = the window (y0, x0) of the (Hs, Ws) plane):
  * a DYNAMIC texel is stepped in the owner's store, a STATIC texel (one parameter for all frames) has its gradient stored to grad_stack as
- * vl3d_render_bwd_culled does and the step kernel behind the backward sums it over the frames -- static texels only, unless the plan was
+ * vl3d_render_bwd with a quad map does and the step kernel behind the backward sums it over the frames -- static texels only, unless the plan was
  * infeasible --, culled texels are nobody's (grad_stack holds defined values in static texels only).  adam->blocks: packed storage.
  * fp32 stacks, the planar convention with the shipped activations ((affine, hardcut, post), sigmoid / sigmoid); dense models: T >= 2,
  * desc->variant 0 (the frame pairs; tile-culled models always take the one-frame tile kernel: 32-wide regions, variant 3 = 64-wide); anything else: VL3D_EUNSUPPORTED,
@@ -456,7 +452,7 @@ int vl3d_packed_unpack_frames(int32_t D, int32_t T, int32_t Hs, int32_t Ws, cons
  * tile lists (MPV.py:389-449), never from a dense texture.  desc: D, T (frames of the model), Hs x Ws (texels of a plane), the H x W view,
  * pixel_center / sx / sy / ox / oy, activations; convention (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, VL3D_ACT_POST), fp32.  blocks / pool:
  * as above; frames = device int32 [n]; quad_keep [D][QH][QW] = the map the block table was built from (a sample in a culled quad is not
- * covered).  rgb (n,H,W,3), alpha (n,H,W): the bits of vl3d_render_fwd_culled on the unpacked frames.  Forward only (evaluation renders):
+ * covered).  rgb (n,H,W,3), alpha (n,H,W): the bits of vl3d_render_fwd with the same map on the unpacked frames.  Forward only (evaluation renders):
  * training renders from the compact window copy of the crop-aware optimiser (vl3d_adam_window_catchup). */
 int vl3d_render_fwd_packed(const vl3d_render_desc *desc, const int32_t *blocks, const float *pool, const int32_t *frames, int32_t n,
                            const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, float culled_alpha, float *rgb,
@@ -474,21 +470,19 @@ void vl3d_adam_step_scalars(float lr, float beta1, float beta2, int64_t step, fl
  * reg_state: caller-owned device buffer of vl3d_render_reg_state_bytes(desc) bytes, written by these forwards (per-pixel coverage
  * masks and pair flags; per (plane, frame, pixel) the signs of the four differences its layer value takes part in) and read by
  * vl3d_render_bwd, which takes the gradient w.r.t. the four sums as grad_reg = device float[4] (NULL: no regulariser term;
- * non-NULL requires the reg_state of the matching forward).  At most 128 planes. */
+ * non-NULL requires the reg_state of the matching forward).  At most 128 planes.
+ * quad_keep NULL = a dense model (QH, QW are not read), else the quad map and grid of vl3d_render_fwd: a culled quad's layer value is 0
+ * like any uncovered pixel's.  No cull_scratch: the regulariser kernels walk the map themselves. */
 int64_t vl3d_render_reg_state_bytes(const vl3d_render_desc *desc);
-int vl3d_render_reg_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos, double *sums, void *reg_state,
-                        vl3d_stream_t stream);
-/* vl3d_render_fwd and vl3d_render_reg_fwd in ONE pass over the stack (dense stacks): what MPMeshVid.forward needs per training step
- * when rgb_smooth / a_smooth are on (configs/mpv_base.txt:33-34).  rgb / alpha / alpha_sums bit-identical to vl3d_render_fwd. */
-int vl3d_render_fwd_reg(const vl3d_render_desc *desc, const void *stack, const float *homos, float *rgb, float *alpha,
-                        float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream);
-int vl3d_render_reg_fwd_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep,
-                               int32_t QH, int32_t QW, double *sums, void *reg_state, vl3d_stream_t stream);
-/* ... and the whole forward of a tile-culled model WITH the regularisers in one pass: rgb / alpha / alpha_sums as vl3d_render_fwd_culled
- * writes them (the same bits) and sums / reg_state as vl3d_render_reg_fwd_culled -- the slot kernel visits every covered plane of every
- * pixel nearest first, which is the order of the over-composite, so the render falls out of the samples it takes anyway. */
-int vl3d_render_fwd_reg_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                               int32_t QW, float *rgb, float *alpha, float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream);
+int vl3d_render_reg_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                        double *sums, void *reg_state, vl3d_stream_t stream);
+/* vl3d_render_fwd and vl3d_render_reg_fwd in ONE pass over the stack: what MPMeshVid.forward needs per training step when rgb_smooth /
+ * a_smooth are on (configs/mpv_base.txt:33-34).  rgb / alpha / alpha_sums bit-identical to vl3d_render_fwd, sums / reg_state as
+ * vl3d_render_reg_fwd writes them.  quad_keep NULL = a dense model (QH, QW are not read), else the whole forward of a tile-culled model
+ * from its quad map and grid: the slot kernel visits every covered plane of every pixel nearest first, which is the order of the
+ * over-composite, so the render falls out of the samples it takes anyway. */
+int vl3d_render_fwd_reg(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                        float *rgb, float *alpha, float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream);
 
 /* Stage 1's learned loop mask (MPI.py:115-117 `atlas_mask`, 568-583) as a FIFTH composited channel of the same pass:
  *     label(pixel) = sum_k w_k sigmoid(sample(mask_k)),   w_k = a_k T_k  the colour composite's blend weights,

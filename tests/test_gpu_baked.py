@@ -201,10 +201,10 @@ def test_determinism_and_guards(dev, scene):
     # the float entry points refuse baked texels (error returns, before any launch)
     d = desc(specs["dense"], "u8")
     d.T = T_ALLOC
-    assert lib.vl3d_render_fwd(d, L.ptr(scene.baked), L.ptr(scene.homos), L.ptr(rgb), L.ptr(alpha), None, stream) == EINVAL
+    assert lib.vl3d_render_fwd(d, L.ptr(scene.baked), L.ptr(scene.homos), None, 0, 0, None, L.ptr(rgb), L.ptr(alpha), None, stream) == EINVAL
     assert b"stack_dtype" in lib.vl3d_last_error()
     d.T = NF
-    assert lib.vl3d_render_fwd_frames(d, L.ptr(scene.baked), F0, T_ALLOC, L.ptr(scene.homos), L.ptr(rgb), L.ptr(alpha), stream) == EINVAL
+    assert lib.vl3d_render_fwd_frames(d, L.ptr(scene.baked), F0, T_ALLOC, L.ptr(scene.homos), None, 0, 0, None, L.ptr(rgb), L.ptr(alpha), stream) == EINVAL
     # the baked entry refuses everything but the planar convention on VL3D_U8 texels
     assert baked_rc(desc(RenderSpec(), "u8")) == EINVAL                                              # utils_mpi coordinates
     assert b"planar" in lib.vl3d_last_error()

@@ -299,7 +299,7 @@ def test_determinism_and_guards(dev, scenes):
 
 # ---- 7. the four culled forward entries share one quad-grid rule ---------------------------------------------------------------------------
 def test_culled_forward_entries_share_the_grid_rule(dev, scenes):
-    """vl3d_render_fwd_frames_culled, _fwd_packed, _fwd_baked and _fwd_baked_pool at the C ABI, on the `exact` (30 x 70 texels, 5 x 7 tiles) and
+    """vl3d_render_fwd_frames (with a quad map), _fwd_packed, _fwd_baked and _fwd_baked_pool at the C ABI, on the `exact` (30 x 70 texels, 5 x 7 tiles) and
     `shared` (40 x 72 texels, 5 x 9 quads) scenes: every entry refuses the same bad quad grids with VL3D_EINVAL -- mixed signs, a zero, a
     tile-exact grid that does not divide the plane, a tile-exact grid of 1-texel tiles -- before anything is launched (the sentinel-filled
     outputs stay untouched), and accepts the scene's own grid."""
@@ -323,8 +323,7 @@ def test_culled_forward_entries_share_the_grid_rule(dev, scenes):
         hom, qk, out = L.ptr(scenes.homos), L.ptr(s.qk), (L.ptr(rgb), L.ptr(alpha))
         sel, sink = BM.run_sel(1), BM.float_out(rgb, alpha)
         entries = {
-            "vl3d_render_fwd_frames_culled": lambda qh, qw: lib.vl3d_render_fwd_frames_culled(d_f32, L.ptr(stack), 1, T_MODEL, hom, qk, qh, qw,
-                                                                                              L.ptr(cull), *out, stream),
+            "vl3d_render_fwd_frames": lambda qh, qw: lib.vl3d_render_fwd_frames(d_f32, L.ptr(stack), 1, T_MODEL, hom, qk, qh, qw, L.ptr(cull), *out, stream),
             "vl3d_render_fwd_packed": lambda qh, qw: lib.vl3d_render_fwd_packed(d_pk, L.ptr(lay.blocks), L.ptr(fpool), L.ptr(frames), n, hom, qk, qh, qw,
                                                                                 0.0, *out, stream),
             "vl3d_render_fwd_baked": lambda qh, qw: lib.vl3d_render_fwd_baked(d_u8, L.ptr(s.dense), T_MODEL, hom, sel, qk, qh, qw, L.ptr(cull), sink, stream),

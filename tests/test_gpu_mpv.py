@@ -885,7 +885,7 @@ def test_packed_model_trains_and_renders_like_the_dense_one(dev):
 
 
 def test_offline_renderer_reads_sparsified_and_packed_models_in_place(dev):
-    """render_video.render_frames on a sparsified dense model (frames read where they lie, vl3d_render_fwd_frames_culled) and on its packed
+    """render_video.render_frames on a sparsified dense model (frames read where they lie, vl3d_render_fwd_frames with its quad map) and on its packed
     twin (the pool through the block table, frame indices uploaded once): the frames of the loop over the module's eval forward, and the two
     models agree -- a camera per frame, a fixed camera's run with a wrap-around, any chunk size."""
     from videoloop3d_amd import render_video as RV

@@ -225,7 +225,7 @@ def test_window_adam_with_quad_maps_stores_static_texels_once(dev):
 
 
 def test_culled_render_from_a_window_of_the_stack(dev):
-    """vl3d_render_*_culled with desc->cull_* : the stack is a texel window of the plane the quad grid lies over -- same image and
+    """the render entries with a quad map and desc->cull_* : the stack is a texel window of the plane the quad grid lies over -- same image and
     gradient (on the window) as the culled render of the whole stack."""
     from videoloop3d_amd.render import RenderSpec, render_planes_with_regularisers
     import dataclasses
@@ -494,7 +494,7 @@ def test_step_fused_into_the_backward_equals_backward_then_step(dev, smooth, T, 
 def test_tile_culled_step_fused_into_the_backward(dev, smooth, T, scale, rot, packed, variant):
     """the same for a TILE-CULLED model (vl3d_render_bwd_adam with quad maps): dynamic texels are stepped in the owner's store, a static
     texel's gradient is stored and summed over the frames by the step kernel behind the backward (static texels only), culled texels are
-    no parameters -- against vl3d_render_bwd_culled + vl3d_adam_window_step_boxes over all classes: the same bits in p, m, v and the step
+    no parameters -- against vl3d_render_bwd (with the quad map) + vl3d_adam_window_step_boxes over all classes: the same bits in p, m, v and the step
     table after every iteration (kept texels; culled slots hold whatever they held).  rot: the infeasible view (atomics + full step kernel).
     packed: parameters and moments in the pools of 8 x 8-texel blocks (block table addressing in the owner's store)."""
     import warnings

@@ -323,7 +323,7 @@ def test_bwd_tile_720p_matches_atomics(dev):
         gs = torch.full_like(stack, float("nan")).detach()
         nscratch = int(L.lib().vl3d_render_bwd_scratch_bytes(d))
         scratch = torch.zeros((nscratch + 3) // 4, dtype=torch.float32, device=dev)
-        L.check(L.lib().vl3d_render_bwd(d, L.ptr(stack), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.ptr(g), None, None, None, None, L.ptr(gs),
+        L.check(L.lib().vl3d_render_bwd(d, L.ptr(stack), L.ptr(homos), None, 0, 0, L.ptr(rgb), L.ptr(alpha), L.ptr(g), None, None, None, None, L.ptr(gs),
                                         L.ptr(scratch), nscratch, L.stream_ptr(dev)), "vl3d_render_bwd")
         assert int(scratch.view(torch.int32)[0].item()) == (0 if variant == 1 else 1)
         assert torch.isfinite(gs).all()
@@ -509,7 +509,7 @@ def test_bwd_tile_path_is_deterministic(dev, spec_name):
 @pytest.mark.parametrize("spec_name", ["mpv", "utils_mpi", "hardcut_pre"])
 @pytest.mark.parametrize("keep_frac", [0.0, 0.3, 1.0])
 def test_tile_culling_matches_oracle(dev, spec_name, keep_frac):
-    """vl3d_render_fwd/bwd_culled (include/vl3d.h; MPI.py:288-442): samples in culled quads are uncovered -- outputs and the stack
+    """vl3d_render_fwd / _bwd with a quad map (include/vl3d.h; MPI.py:288-442): samples in culled quads are uncovered -- outputs and the stack
     gradient match the oracle's quad coverage, culled texels get exactly zero gradient, and a map that keeps everything is bitwise
     the plain render."""
     from videoloop3d_amd import tiles
@@ -599,14 +599,14 @@ def test_abi_refuses_bad_dims_with_a_status_not_a_crash(dev):
     for field in ("D", "T", "Hs", "Ws", "H", "W"):
         keep = getattr(d, field)
         setattr(d, field, 0)
-        rc = L.lib().vl3d_render_fwd(d, L.ptr(stack), L.ptr(homos), L.ptr(out), L.ptr(al), None, L.stream_ptr(dev))
+        rc = L.lib().vl3d_render_fwd(d, L.ptr(stack), L.ptr(homos), None, 0, 0, None, L.ptr(out), L.ptr(al), None, L.stream_ptr(dev))
         assert rc == 1                                                       # VL3D_EINVAL
         with pytest.raises(RuntimeError, match="non-positive render dims"):
             L.check(rc, "vl3d_render_fwd")
         setattr(d, field, keep)
-    assert L.lib().vl3d_render_fwd(d, None, L.ptr(homos), L.ptr(out), L.ptr(al), None, L.stream_ptr(dev)) == 1
+    assert L.lib().vl3d_render_fwd(d, None, L.ptr(homos), None, 0, 0, None, L.ptr(out), L.ptr(al), None, L.stream_ptr(dev)) == 1
     d.stack_dtype = 7
-    assert L.lib().vl3d_render_fwd(d, L.ptr(stack), L.ptr(homos), L.ptr(out), L.ptr(al), None, L.stream_ptr(dev)) == 1
+    assert L.lib().vl3d_render_fwd(d, L.ptr(stack), L.ptr(homos), None, 0, 0, None, L.ptr(out), L.ptr(al), None, L.stream_ptr(dev)) == 1
 
 
 def test_cfg3_full_size_frame_independence_and_linearity(dev):
@@ -841,8 +841,8 @@ def test_fused_forward_with_regularisers_equals_the_two_pass_forward(dev, spec_n
 
 @pytest.mark.parametrize("T,window", [(1, False), (3, False), (4, True)])
 def test_one_pass_culled_forward_with_regularisers_equals_the_two_passes(dev, T, window):
-    """vl3d_render_fwd_reg_culled (a tile-culled model's render AND its regulariser sums from one walk over every pixel's covered planes:
-    the slot kernel composites as it goes) against vl3d_render_fwd_culled followed by vl3d_render_reg_fwd_culled (variant 0x1000): image,
+    """vl3d_render_fwd_reg with a quad map (a tile-culled model's render AND its regulariser sums from one walk over every pixel's covered planes:
+    the slot kernel composites as it goes) against vl3d_render_fwd followed by vl3d_render_reg_fwd with the same map (variant 0x1000): image,
     alpha and alpha sums bit for bit, the four sums and -- through the sign words both forwards leave for the backward -- the stack
     gradient too.  window: the stack is a texel window of a larger plane the quad grid lies over (crop-aware training)."""
     from videoloop3d_amd.render import RenderSpec, render_planes_with_regularisers
@@ -923,3 +923,67 @@ def test_smoothness_regularisers_are_hit_slot_indexed(dev, mode, T):
     else:
         # the sign of a near-zero layer difference may flip with a 1-ulp sampling difference: robust criterion
         assert float((diff > TOL * scale).float().mean()) <= 1e-4 and float(diff.max()) <= 5e-3 * scale
+
+
+@pytest.mark.parametrize("spec_name", ["mpv", "utils_mpi"])
+def test_null_quad_map_is_the_dense_call(dev, spec_name):
+    """The five render entries at the C ABI with quad_keep = NULL: a dense model, QH / QW (and cull_scratch) are not read -- the call with
+    (NULL, 3, 5) leaves the bits of the call with (NULL, 0, 0) in every output (rgb, alpha, alpha sums, the four sums, reg_state, the stack
+    gradient), and both are what render_planes / render_frame_run / render_planes_with_regularisers return.  D 3, T 2 (frames 1 .. 2 of a
+    clip of 3), planes 24 x 24, frame 16 x 70: two workgroup columns, the right one ragged."""
+    from videoloop3d_amd import _lib as L
+    from videoloop3d_amd import render as R
+    D, T, Hs, Ws, H, W, T_alloc, frame0 = 3, 2, 24, 24, 16, 70, 3, 1
+    spec = R.RenderSpec(**SPECS[spec_name][0])
+    clip = synth.make_plane_stack(D, T_alloc, Hs, Ws, seed=13, device=dev)
+    stack = clip[:, frame0:frame0 + T].contiguous()
+    # frame pixel -> plane pixel, every plane a little sheared and shifted: the planes lie under pixel columns 44 .. 67, across the seam of the two
+    # workgroup columns, one texel per pixel along x (at more than 1.4 pixels per texel the backward falls back to the atomics kernel, whose
+    # bits depend on the order of the adds: nothing to compare bit for bit)
+    homos = torch.stack([torch.tensor([[1.0, 0.01 * d, 0.3 * d - 44.0], [0.005 * d, (Hs - 1) / H, 0.2 * d], [0, 0, 1.0]]) for d in range(D)]).to(dev)
+    g_rgb = (synth.hash_uniform((T, H, W, 3), seed=5) - 0.5).to(dev)
+    g_reg = torch.tensor([1.1e-3, 0.7e-3, 1.6e-3, 0.9e-3], device=dev)
+    g_asum = torch.full((T, H, W, 2), 1e-3, device=dev)
+    lib, stream = L.lib(), L.stream_ptr(dev)
+    d, d_run = R._desc(stack, H, W, spec, 0, 0), R._desc(clip, H, W, spec, 0, 0)
+    d_run.T = T
+    n_state, n_scratch = int(lib.vl3d_render_reg_state_bytes(d)), int(lib.vl3d_render_bwd_scratch_bytes(d))
+
+    def run(QH, QW):
+        """every output of the five entries, in buffers that start from the same fill"""
+        new = lambda *shape, dtype=torch.float32: torch.full(shape, 3, dtype=dtype, device=dev)
+        o = dict(rgb=new(T, H, W, 3), alpha=new(T, H, W), asum=new(T, H, W, 2), run_rgb=new(T, H, W, 3), run_alpha=new(T, H, W),
+                 reg_rgb=new(T, H, W, 3), reg_alpha=new(T, H, W), reg_asum=new(T, H, W, 2), reg_sums=new(4, dtype=torch.float64),
+                 reg_state=new(n_state, dtype=torch.uint8), sums=new(4, dtype=torch.float64), state=new(n_state, dtype=torch.uint8),
+                 grad=new(*stack.shape))
+        scratch = torch.zeros((n_scratch + 3) // 4, dtype=torch.float32, device=dev)
+        p = {k: L.ptr(v) for k, v in o.items()}
+        L.check(lib.vl3d_render_fwd(d, L.ptr(stack), L.ptr(homos), None, QH, QW, None, p["rgb"], p["alpha"], p["asum"], stream), "vl3d_render_fwd")
+        L.check(lib.vl3d_render_fwd_frames(d_run, L.ptr(clip), frame0, T_alloc, L.ptr(homos), None, QH, QW, None, p["run_rgb"], p["run_alpha"],
+                                           stream), "vl3d_render_fwd_frames")
+        L.check(lib.vl3d_render_fwd_reg(d, L.ptr(stack), L.ptr(homos), None, QH, QW, p["reg_rgb"], p["reg_alpha"], p["reg_asum"], p["reg_sums"],
+                                        p["reg_state"], stream), "vl3d_render_fwd_reg")
+        L.check(lib.vl3d_render_reg_fwd(d, L.ptr(stack), L.ptr(homos), None, QH, QW, p["sums"], p["state"], stream), "vl3d_render_reg_fwd")
+        L.check(lib.vl3d_render_bwd(d, L.ptr(stack), L.ptr(homos), None, QH, QW, p["reg_rgb"], p["reg_alpha"], L.ptr(g_rgb), None, L.ptr(g_reg),
+                                    p["reg_state"], L.ptr(g_asum), p["grad"], L.ptr(scratch), n_scratch, stream), "vl3d_render_bwd")
+        torch.cuda.synchronize()
+        assert int(scratch.view(torch.int32)[0]) == 1                            # the owner-computes backward ran: reproducible bits
+        return o
+    a, b = run(0, 0), run(3, 5)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    assert not R.bwd_choice(d, "render", False, True, n_scratch).cull
+    # ... and the wrappers' outputs
+    rgb, alpha = R.render_planes(stack, homos, H, W, spec)
+    assert torch.equal(rgb, a["rgb"]) and torch.equal(alpha, a["alpha"]) and float(alpha.max()) > 0.1
+    rgb, alpha = R.render_frame_run(clip, frame0, T, homos, H, W, spec)
+    assert torch.equal(rgb, a["run_rgb"]) and torch.equal(alpha, a["run_alpha"]) and torch.equal(rgb, a["rgb"])
+    leaf = stack.clone().requires_grad_(True)
+    rgb, alpha, sums, asum = R.render_planes_with_regularisers(leaf, homos, H, W, spec)
+    assert torch.equal(rgb, a["reg_rgb"]) and torch.equal(alpha, a["reg_alpha"]) and torch.equal(asum, a["reg_asum"])
+    assert torch.equal(sums, a["reg_sums"].to(torch.float32)) and float(sums.detach().abs().min()) > 0
+    ((rgb * g_rgb).sum() + (sums * g_reg).sum() + (asum * 1e-3).sum()).backward()
+    assert torch.equal(leaf.grad, a["grad"]) and float(leaf.grad.abs().max()) > 0
+    assert R.last_bwd_choice()[6] is False                                   # (family, width, rows, reg, mask, adam, cull, f16)
+    two_pass = R.render_planes_with_regularisers(stack, homos, H, W, R.RenderSpec(**dict(SPECS[spec_name][0], variant=0x1000)))
+    assert torch.equal(two_pass[0], a["rgb"]) and torch.equal(two_pass[3], a["asum"]) and torch.equal(two_pass[2], a["sums"].to(torch.float32))

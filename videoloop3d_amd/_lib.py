@@ -89,9 +89,8 @@ class Stage1ObjectiveDesc(C.Structure):
 SIGNATURES = {
     "vl3d_last_error": ([], C.c_char_p),
     "vl3d_version": ([], C.c_int),
-    "vl3d_render_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_fwd_frames": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_fwd_frames_culled": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_fwd_frames": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_bake_rgba8": ([_I64, _P, _I32, _I32, _I32, _P, _P], C.c_int),
     "vl3d_render_fwd_baked": ([C.POINTER(RenderDesc), _P, _I32, _P, C.POINTER(BakedFrames), _P, _I32, _I32, _P, C.POINTER(BakedOut), _P], C.c_int),
     "vl3d_render_fwd_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, C.POINTER(BakedFrames), _P, _I32, _I32, C.c_uint32, _P,
@@ -104,11 +103,9 @@ SIGNATURES = {
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_choice": ([C.POINTER(RenderDesc), _I32, _I32, _I32, _I64, _I32, C.POINTER(BwdChoice)], C.c_int),
-    "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
+    "vl3d_render_bwd": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_bwd_adam": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(AdamWindow), _P], C.c_int),
     "vl3d_render_reg_state_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
-    "vl3d_render_fwd_reg_culled": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_reg_fwd_culled": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P], C.c_int),
     "vl3d_tie_static_grad": ([_I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, _P], C.c_int),
     "vl3d_adam_step_tiles": ([_I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P],
                              C.c_int),
@@ -122,13 +119,11 @@ SIGNATURES = {
     "vl3d_adam_flush_older": ([_I32] * 4 + [_P, _P, _P, _P, _P, _I32, _I32, _F, _F, _F, _P, _P, _I32, _I32, _P, _P], C.c_int),
     "vl3d_adam_step_scalars": ([_F, _F, _F, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float)], None),
     "vl3d_render_cull_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
-    "vl3d_render_fwd_culled": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_bwd_culled": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_fwd_plane_rows": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_plane_rows_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
     "vl3d_render_bwd_plane_rows": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
-    "vl3d_render_reg_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P], C.c_int),
-    "vl3d_render_fwd_reg": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_reg_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P], C.c_int),
+    "vl3d_render_fwd_reg": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P], C.c_int),
     "vl3d_render_fwd_mask": ([C.POINTER(RenderDesc)] + [_P] * 10, C.c_int),
     "vl3d_render_bwd_mask": ([C.POINTER(RenderDesc)] + [_P] * 14 + [_I64, _P], C.c_int),
     "vl3d_label_noise_fwd": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P], C.c_int),

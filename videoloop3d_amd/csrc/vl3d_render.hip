@@ -51,14 +51,15 @@ int check_desc(const vl3d_render_desc *d) {
     return VL3D_OK;
 }
 
-// tile culling of the float render: the shared grid rules (vl3d_render_args.h) plus what only this unit's conventions need
-int check_cull(const vl3d_render_desc *desc, const uint8_t *quad_keep, int32_t QH, int32_t QW) {
+// tile culling of the float render (quad_keep NULL: a dense model, the grid is not read): the shared grid rules (vl3d_render_args.h) plus
+// what only this unit's conventions need, `who` in front of the message
+int check_cull(const vl3d_render_desc *desc, const uint8_t *quad_keep, int32_t QH, int32_t QW, const char *who) {
     if (!quad_keep) return VL3D_OK;
-    VL3D_REQUIRE(desc->coord_mode != VL3D_COORD_AFFINE_PLANES, "tile culling is not available with per-plane texel transforms");
-    const int rc = check_cull_grid(desc, QH, QW, "tile culling");
+    if (desc->coord_mode == VL3D_COORD_AFFINE_PLANES) return refuse(who, "tile culling is not available with per-plane texel transforms");
+    const int rc = check_cull_grid(desc, QH, QW, who);
     if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(QH > 0 || (desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT),
-                 "tile-exact layout: the planar MPV / MPI convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
+    if (!(QH > 0 || (desc->coord_mode == VL3D_COORD_AFFINE && desc->border_mode == VL3D_BORDER_HARDCUT)))
+        return refuse(who, "tile-exact layout: the planar MPV / MPI convention only (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT)");
     return VL3D_OK;
 }
 
@@ -68,59 +69,6 @@ extern "C" int64_t vl3d_render_cull_scratch_bytes(const vl3d_render_desc *desc) 
     if (!desc || desc->H <= 0 || desc->W <= 0) return 0;
     // two 64-bit plane masks per forward workgroup, sized for the smallest workgroup any forward variant uses (64 x 4 pixels)
     return (int64_t)((desc->W + 63) / 64) * ((desc->H + 3) / 4) * 16;
-}
-
-static int render_fwd_impl(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                           int32_t QW, void *cull_scratch, float *rgb, float *alpha, float *alpha_sums, vl3d_stream_t stream, int32_t frame0 = 0,
-                           int32_t T_alloc = 0) {
-    int rc = check_desc(desc);
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(stack && homos && rgb && alpha, "null pointer passed to vl3d_render_fwd");
-    rc = check_cull(desc, quad_keep, QH, QW);
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(!quad_keep || cull_scratch, "tile culling: the forward needs vl3d_render_cull_scratch_bytes() of scratch");
-    RenderArgs a = render_args_of(desc);
-    a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums;
-    a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
-    set_cull_geometry(a, desc, QH, QW); a.cull_masks = (const unsigned long long *)cull_scratch;
-    a.fwd_variant = (desc->variant >> 8) & 0xf;
-    a.ablate = (desc->variant >> 4) & 0xf;
-    VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    a.g_f16 = desc->stack_dtype == VL3D_F16;
-    if (T_alloc > 0) {      // vl3d_render_fwd_frames: frames frame0 .. frame0 + T - 1 of a (D, T_alloc, Hs, Ws, 4) allocation, read in place
-        VL3D_REQUIRE(frame0 >= 0 && frame0 + desc->T <= T_alloc, "vl3d_render_fwd_frames: the run of frames leaves the clip");
-        a.stack = reinterpret_cast<const float *>(reinterpret_cast<const char *>(stack) + (size_t)frame0 * desc->Hs * desc->Ws * (a.g_f16 ? 8 : 16));
-        a.Tstride = T_alloc;
-    }
-    rc = dispatch(false, desc, a, (hipStream_t)stream);
-    if (rc != VL3D_OK) return rc;
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
-extern "C" int vl3d_render_fwd_frames(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
-                                      float *rgb, float *alpha, vl3d_stream_t stream) {
-    VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_frames: T_alloc must be the clip length of the stack allocation");
-    return render_fwd_impl(desc, stack, homos, nullptr, 0, 0, nullptr, rgb, alpha, nullptr, stream, frame0, T_alloc);
-}
-
-extern "C" int vl3d_render_fwd_frames_culled(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
-                                             const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
-                                             vl3d_stream_t stream) {
-    VL3D_REQUIRE(T_alloc > 0, "vl3d_render_fwd_frames_culled: T_alloc must be the clip length of the stack allocation");
-    VL3D_REQUIRE(quad_keep != nullptr, "vl3d_render_fwd_frames_culled: null quad map (vl3d_render_fwd_frames renders a dense model)");
-    return render_fwd_impl(desc, stack, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha, nullptr, stream, frame0, T_alloc);
-}
-
-extern "C" int vl3d_render_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos,
-                               float *rgb, float *alpha, float *alpha_sums, vl3d_stream_t stream) {
-    return render_fwd_impl(desc, stack, homos, nullptr, 0, 0, nullptr, rgb, alpha, alpha_sums, stream);
-}
-
-extern "C" int vl3d_render_fwd_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep,
-                                      int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha, float *alpha_sums,
-                                      vl3d_stream_t stream) {
-    return render_fwd_impl(desc, stack, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha, alpha_sums, stream);
 }
 
 // scratch layout: per-plane records | one int4 window per (tile, plane), as many as the region shape with the most tiles needs
@@ -136,8 +84,6 @@ extern "C" int64_t vl3d_render_bwd_scratch_bytes(const vl3d_render_desc *desc) {
     return owner_table_off(desc) + ((int64_t)desc->D * desc->Hs * desc->Ws + 16 * (int64_t)desc->Ws + 64) * 2;
 }
 
-static int render_reg_fwd_impl(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                               int32_t QW, double *sums, void *reg_state, vl3d_stream_t stream);
 static void set_reg_state(RenderArgs &a, const vl3d_render_desc *d, const void *reg_state);
 static int check_mask_desc(const vl3d_render_desc *d, const char *who);
 static int check_adam_desc(const vl3d_render_desc *desc, bool has_quad_map);
@@ -233,25 +179,6 @@ extern "C" int64_t vl3d_render_reg_state_bytes(const vl3d_render_desc *desc) {
     return reg_layout(desc).total;
 }
 
-extern "C" int vl3d_render_fwd_reg(const vl3d_render_desc *desc, const void *stack, const float *homos, float *rgb, float *alpha,
-                                   float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream) {
-    int rc = check_desc(desc);
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(stack && homos && rgb && alpha && sums && reg_state, "null pointer passed to vl3d_render_fwd_reg");
-    VL3D_REQUIRE(desc->D <= 128, "the layer regularisers support at most 128 planes (coverage masks)");
-    VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = render_args_of(desc);
-    a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums; a.reg_sums = sums;
-    set_reg_state(a, desc, reg_state);
-    a.g_f16 = desc->stack_dtype == VL3D_F16;
-    a.reg_fwd = 2;
-    // (the sums are cleared by reg_masks_k, the first kernel of the regulariser forward)
-    rc = dispatch(false, desc, a, (hipStream_t)stream);
-    if (rc != VL3D_OK) return rc;
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
 // ---- stage 1's loop mask as a fifth composited channel (MPI.py:115-117, 568-583) ---------------------------------------------------
 static int check_mask_desc(const vl3d_render_desc *d, const char *who) {
     if (d->coord_mode == VL3D_COORD_AFFINE && d->border_mode == VL3D_BORDER_HARDCUT && d->act_order == VL3D_ACT_POST &&
@@ -262,31 +189,91 @@ static int check_mask_desc(const vl3d_render_desc *d, const char *who) {
     return VL3D_EUNSUPPORTED;
 }
 
-extern "C" int vl3d_render_fwd_mask(const vl3d_render_desc *desc, const void *stack, const float *mask, const float *homos, float *rgb,
-                                    float *alpha, float *label, float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream) {
+// ---- the five forwards: one body ------------------------------------------------------------------------------------------------------
+// An entry passes NULL / 0 for what it does not take.  quad_keep NULL: a dense model -- QH, QW and cull_scratch are not read.
+enum FwdEntry { FWD, FWD_FRAMES, FWD_REG, REG_FWD, FWD_MASK };
+
+static int render_fwd(FwdEntry e, const char *who, const vl3d_render_desc *desc, const void *stack, const float *mask, int32_t frame0,
+                      int32_t T_alloc, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb,
+                      float *alpha, float *label, float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream) {
     int rc = check_desc(desc);
     if (rc != VL3D_OK) return rc;
-    rc = check_mask_desc(desc, "vl3d_render_fwd_mask");
+    const bool plain = e == FWD || e == FWD_FRAMES;      // the render alone
+    const bool image = e != REG_FWD;                     // rgb / alpha are written
+    if (e == FWD_MASK) {
+        rc = check_mask_desc(desc, who);
+        if (rc != VL3D_OK) return rc;
+        if (!(mask && label)) return refuse(who, "null pointer");
+        if (desc->uv_noise_seed != 0)
+            return refuse(who, "add_uv_noise jitters the colour samples only (MPI.py:519-522, 568-572): render the label in a pass of its own");
+        if ((sums == nullptr) != (reg_state == nullptr)) return refuse(who, "sums and reg_state come together (both NULL: no layer regularisers)");
+    }
+    const bool reg = e == FWD_REG || e == REG_FWD || (e == FWD_MASK && sums);      // the layer regularisers' sums are formed
+    if (!(stack && homos && (!image || (rgb && alpha)) && (!reg || (sums && reg_state)))) return refuse(who, "null pointer");
+    if (reg && desc->D > 128) return refuse(who, "the layer regularisers support at most 128 planes (coverage masks)");
+    if (!quad_keep) { QH = QW = 0; cull_scratch = nullptr; }
+    rc = check_cull(desc, quad_keep, QH, QW, who);
     if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(stack && mask && homos && rgb && alpha && label, "null pointer passed to vl3d_render_fwd_mask");
-    VL3D_REQUIRE(desc->uv_noise_seed == 0, "vl3d_render_fwd_mask: add_uv_noise jitters the colour samples only (MPI.py:519-522, 568-572): render the label in a pass of its own");
-    VL3D_REQUIRE((sums == nullptr) == (reg_state == nullptr), "vl3d_render_fwd_mask: sums and reg_state come together (both NULL: no layer regularisers)");
-    VL3D_REQUIRE(!sums || desc->D <= 128, "the layer regularisers support at most 128 planes (coverage masks)");
-    VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
+    // (the regulariser kernels walk the quad map themselves: only the render alone plans with plane masks)
+    if (plain && quad_keep && !cull_scratch) return refuse(who, "tile culling: the forward needs vl3d_render_cull_scratch_bytes() of scratch");
+    if (!((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32))) return refuse(who, "frame too large for 32-bit byte offsets");
     RenderArgs a = render_args_of(desc);
     a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums;
     a.mask = mask; a.label = label;
-    a.fwd_variant = (desc->variant >> 8) & 0xf;
-    if (sums) {
-        a.reg_sums = sums;
+    a.quad_keep = quad_keep;
+    set_cull_geometry(a, desc, QH, QW);
+    if (plain) a.cull_masks = (const unsigned long long *)cull_scratch;
+    if (plain || e == FWD_MASK) a.fwd_variant = (desc->variant >> 8) & 0xf;
+    if (plain) a.ablate = (desc->variant >> 4) & 0xf;
+    a.g_f16 = desc->stack_dtype == VL3D_F16;      // (the mask forward is fp32 by refusal)
+    if (reg) {
+        a.reg_sums = sums;      // (cleared by reg_masks_k, the first kernel of the regulariser forward)
         set_reg_state(a, desc, reg_state);
-        a.reg_fwd = 2;
-        // (the sums are cleared by reg_masks_k, the first kernel of the regulariser forward)
+        // 1: the sums alone | 2: render + sums in one sweep | 3: a tile-culled model's slot kernel composites the render as it goes
+        a.reg_fwd = e == REG_FWD ? 1 : (quad_keep ? 3 : 2);
+    }
+    if (e == FWD_FRAMES) {      // frames frame0 .. frame0 + T - 1 of a (D, T_alloc, Hs, Ws, 4) allocation, read in place
+        if (T_alloc <= 0) return refuse(who, "T_alloc must be the clip length of the stack allocation");
+        if (!(frame0 >= 0 && frame0 + desc->T <= T_alloc)) return refuse(who, "the run of frames leaves the clip");
+        a.stack = reinterpret_cast<const float *>(reinterpret_cast<const char *>(stack) + (size_t)frame0 * desc->Hs * desc->Ws * (a.g_f16 ? 8 : 16));
+        a.Tstride = T_alloc;
     }
     rc = dispatch(false, desc, a, (hipStream_t)stream);
     if (rc != VL3D_OK) return rc;
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
+}
+
+extern "C" int vl3d_render_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
+                               int32_t QW, void *cull_scratch, float *rgb, float *alpha, float *alpha_sums, vl3d_stream_t stream) {
+    return render_fwd(FWD, "vl3d_render_fwd", desc, stack, nullptr, 0, 0, homos, quad_keep, QH, QW, cull_scratch, rgb, alpha, nullptr, alpha_sums,
+                      nullptr, nullptr, stream);
+}
+
+extern "C" int vl3d_render_fwd_frames(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
+                                      const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *rgb, float *alpha,
+                                      vl3d_stream_t stream) {
+    return render_fwd(FWD_FRAMES, "vl3d_render_fwd_frames", desc, stack, nullptr, frame0, T_alloc, homos, quad_keep, QH, QW, cull_scratch, rgb,
+                      alpha, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int vl3d_render_fwd_reg(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
+                                   int32_t QW, float *rgb, float *alpha, float *alpha_sums, double *sums, void *reg_state,
+                                   vl3d_stream_t stream) {
+    return render_fwd(FWD_REG, "vl3d_render_fwd_reg", desc, stack, nullptr, 0, 0, homos, quad_keep, QH, QW, nullptr, rgb, alpha, nullptr,
+                      alpha_sums, sums, reg_state, stream);
+}
+
+extern "C" int vl3d_render_reg_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
+                                   int32_t QW, double *sums, void *reg_state, vl3d_stream_t stream) {
+    return render_fwd(REG_FWD, "vl3d_render_reg_fwd", desc, stack, nullptr, 0, 0, homos, quad_keep, QH, QW, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, sums, reg_state, stream);
+}
+
+extern "C" int vl3d_render_fwd_mask(const vl3d_render_desc *desc, const void *stack, const float *mask, const float *homos, float *rgb,
+                                    float *alpha, float *label, float *alpha_sums, double *sums, void *reg_state, vl3d_stream_t stream) {
+    return render_fwd(FWD_MASK, "vl3d_render_fwd_mask", desc, stack, mask, 0, 0, homos, nullptr, 0, 0, nullptr, rgb, alpha, label, alpha_sums,
+                      sums, reg_state, stream);
 }
 
 extern "C" int vl3d_render_bwd_mask(const vl3d_render_desc *desc, const void *stack, const float *mask, const float *homos, const float *rgb,
@@ -317,97 +304,21 @@ extern "C" int vl3d_render_bwd_mask(const vl3d_render_desc *desc, const void *st
     return VL3D_OK;
 }
 
-extern "C" int vl3d_render_reg_fwd(const vl3d_render_desc *desc, const void *stack, const float *homos, double *sums, void *reg_state,
-                                   vl3d_stream_t stream) {
-    return render_reg_fwd_impl(desc, stack, homos, nullptr, 0, 0, sums, reg_state, stream);
-}
-
-extern "C" int vl3d_render_reg_fwd_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep,
-                                          int32_t QH, int32_t QW, double *sums, void *reg_state, vl3d_stream_t stream) {
-    return render_reg_fwd_impl(desc, stack, homos, quad_keep, QH, QW, sums, reg_state, stream);
-}
-
-extern "C" int vl3d_render_fwd_reg_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                                          int32_t QW, float *rgb, float *alpha, float *alpha_sums, double *sums, void *reg_state,
-                                          vl3d_stream_t stream) {
+// quad_keep NULL: a dense model -- QH and QW are not read
+extern "C" int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
+                               int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha,
+                               const float *grad_reg, const void *reg_state, const float *grad_alpha_sums, float *grad_stack, void *scratch,
+                               int64_t scratch_bytes, vl3d_stream_t stream) {
     int rc = check_desc(desc);
     if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(stack && homos && quad_keep && rgb && alpha && sums && reg_state, "null pointer passed to vl3d_render_fwd_reg_culled");
-    VL3D_REQUIRE(desc->D <= 128, "the layer regularisers support at most 128 planes (coverage masks)");
-    rc = check_cull(desc, quad_keep, QH, QW);
+    if (!quad_keep) QH = QW = 0;
+    rc = check_cull(desc, quad_keep, QH, QW, "vl3d_render_bwd");
     if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = render_args_of(desc);
-    a.stack = (const float *)stack; a.homos = homos; a.rgb = rgb; a.alpha = alpha; a.asum = alpha_sums; a.reg_sums = sums;
-    a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
-    set_cull_geometry(a, desc, QH, QW);
-    set_reg_state(a, desc, reg_state);
-    // (the sums are cleared by reg_masks_k, the first kernel of the regulariser forward)
-    a.reg_fwd = 3;
-    a.g_f16 = desc->stack_dtype == VL3D_F16;
-    rc = dispatch(false, desc, a, (hipStream_t)stream);
-    if (rc != VL3D_OK) return rc;
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
-static int render_reg_fwd_impl(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                               int32_t QW, double *sums, void *reg_state, vl3d_stream_t stream) {
-    int rc = check_desc(desc);
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(stack && homos && sums && reg_state, "null pointer passed to vl3d_render_reg_fwd");
-    VL3D_REQUIRE(desc->D <= 128, "the layer regularisers support at most 128 planes (coverage masks)");
-    rc = check_cull(desc, quad_keep, QH, QW);
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32), "frame too large for 32-bit byte offsets");
-    RenderArgs a = render_args_of(desc);
-    a.stack = (const float *)stack; a.homos = homos; a.reg_sums = sums;
-    a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
-    set_cull_geometry(a, desc, QH, QW);
-    set_reg_state(a, desc, reg_state);
-    // (the sums are cleared by reg_masks_k, the first kernel of the regulariser forward)
-    a.reg_fwd = 1;
-    a.g_f16 = desc->stack_dtype == VL3D_F16;
-    rc = dispatch(false, desc, a, (hipStream_t)stream);
-    if (rc != VL3D_OK) return rc;
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
-static int render_bwd_impl(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                           int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb,
-                           const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
-                           float *grad_stack, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
-
-extern "C" int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float *homos,
-                               const float *rgb, const float *alpha, const float *grad_rgb,
-                               const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
-                               float *grad_stack, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream) {
-    return render_bwd_impl(desc, stack, homos, nullptr, 0, 0, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums, grad_stack,
-                           scratch, scratch_bytes, stream);
-}
-
-extern "C" int vl3d_render_bwd_culled(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep,
-                                      int32_t QH, int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb,
-                                      const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
-                                      float *grad_stack, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream) {
-    return render_bwd_impl(desc, stack, homos, quad_keep, QH, QW, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums,
-                           grad_stack, scratch, scratch_bytes, stream);
-}
-
-static int render_bwd_impl(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH,
-                           int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb,
-                           const float *grad_alpha, const float *grad_reg, const void *reg_state, const float *grad_alpha_sums,
-                           float *grad_stack, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream) {
-    int rc = check_desc(desc);
-    if (rc != VL3D_OK) return rc;
-    rc = check_cull(desc, quad_keep, QH, QW);
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack, "null pointer passed to vl3d_render_bwd");
+    VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack, "vl3d_render_bwd: null pointer");
     VL3D_REQUIRE(!grad_reg || reg_state, "vl3d_render_bwd: grad_reg needs the reg_state the forward with regularisers filled");
     RenderArgs a = render_args_of(desc);
     set_bwd_io(a, desc, stack, homos, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums, grad_stack);
-    a.quad_keep = quad_keep; a.QH = QH; a.QW = QW;
+    a.quad_keep = quad_keep;
     set_cull_geometry(a, desc, QH, QW);
     a.g_f16 = desc->stack_dtype == VL3D_F16;
     a.grad_culled_unwritten = (quad_keep && (desc->grad_flags & VL3D_GRAD_CULLED_UNWRITTEN)) ? 1 : 0;
@@ -437,7 +348,7 @@ static int check_adam_desc(const vl3d_render_desc *desc, bool has_quad_map) {
           desc->rgb_act == VL3D_ACT_SIGMOID && desc->alpha_act == VL3D_ACT_SIGMOID && desc->stack_dtype == VL3D_F32 &&
           (has_quad_map ? (bv == 0 || bv == 3 || bv == 5) : (desc->T >= 2 && bv == 0)))) {
         vl3d_set_error("vl3d_render_bwd_adam: built for the stage-2 iteration -- (affine, hardcut, post), sigmoid / sigmoid, fp32 stack, "
-                       "T >= 2 and variant 0 for a dense model; use vl3d_render_bwd(_culled) + vl3d_adam_window_step otherwise");
+                       "T >= 2 and variant 0 for a dense model; use vl3d_render_bwd + vl3d_adam_window_step otherwise");
         return VL3D_EUNSUPPORTED;
     }
     return VL3D_OK;
@@ -451,7 +362,7 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
     if (rc != VL3D_OK) return rc;
     VL3D_REQUIRE(adam != nullptr, "vl3d_render_bwd_adam: null adam window");
     if (desc->uv_noise_seed) {
-        vl3d_set_error("vl3d_render_bwd_adam: add_uv_noise takes the atomics backward (vl3d_render_bwd(_culled) + vl3d_adam_window_step)");
+        vl3d_set_error("vl3d_render_bwd_adam: add_uv_noise takes the atomics backward (vl3d_render_bwd + vl3d_adam_window_step)");
         return VL3D_EUNSUPPORTED;
     }
     VL3D_REQUIRE(stack && homos && rgb && alpha && grad_rgb && grad_stack && scratch, "null pointer passed to vl3d_render_bwd_adam");
@@ -465,7 +376,7 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
     VL3D_REQUIRE((int64_t)desc->Hs * desc->Ws * 16 < (1ll << 32) && (int64_t)adam->Hs * adam->Ws * 16 < (1ll << 32),
                  "frame too large for 32-bit byte offsets");
     if (qk) {
-        rc = check_cull(desc, qk, adam->QH, adam->QW);
+        rc = check_cull(desc, qk, adam->QH, adam->QW, "vl3d_render_bwd_adam");
         if (rc != VL3D_OK) return rc;
         VL3D_REQUIRE(adam->class_scratch, "vl3d_render_bwd_adam: a tile-culled model needs class_scratch (vl3d_render_bwd_adam_class_bytes())");
         VL3D_REQUIRE(adam->step < (1ll << 29), "vl3d_render_bwd_adam: tile-culled models keep the step in 29 bits of the texel records");

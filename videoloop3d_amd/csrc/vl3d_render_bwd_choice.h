@@ -26,7 +26,7 @@ struct BwdSetting {
 
 // (entry point, desc->variant & 0xf) -> policy.  `tile_ok`: the caller passed vl3d_render_bwd_scratch_bytes() of scratch and no uv noise
 // (add_uv_noise: a jittered tap can leave the 1-pixel halo the owner-computes kernels stage -- the atomics kernel takes the call).
-//   vl3d_render_bwd(_culled): 0 auto, 1 atomics, 2 flat 64 x 8, 5 narrow 32 x 16, 6 / 7 pairs 32 x 16 / 64 x 12, every other value 64 x 16
+//   vl3d_render_bwd (dense or with a quad map): 0 auto, 1 atomics, 2 flat 64 x 8, 5 narrow 32 x 16, 6 / 7 pairs 32 x 16 / 64 x 12, every other value 64 x 16
 //   vl3d_render_bwd_mask:     1 atomics, 3 / 4 the 16 rows, every other value the flat 64 x 8 regions: 512 threads at that instantiation's
 //                             128-register budget are TWO workgroups per CU -- stage-1 iterations +3.3 % at the reference's crop, +2 % for a
 //                             720p frame (profiles/r05d_s1_mask_rows.txt), same bits

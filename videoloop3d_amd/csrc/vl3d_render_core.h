@@ -587,7 +587,7 @@ __device__ __forceinline__ f4 reg_sample(const RenderArgs &a, const float *hs, f
 // RENDER (with PATCH = false): the composite as well -- a thread visits its covered planes nearest first, which is the order of the
 //   over-composite, so rgb / alpha / the alpha sums of its pixel fall out of the same samples (the planes it skips have alpha exactly 0
 //   for it: the bits of render_fwd2_k's culled composite).  The whole forward of a tile-culled model with regularisers in one pass
-//   (vl3d_render_fwd_reg_culled) instead of the culled render + this kernel over the same taps.
+//   (vl3d_render_fwd_reg with a quad map) instead of the culled render + this kernel over the same taps.
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool PATCH, bool RENDER = false>
 __global__ __launch_bounds__(512) void reg_slot_fwd_k(RenderArgs a, int tiles_x, int tiles_y) {
     static_assert(!(PATCH && RENDER), "the composite rides the kernel that visits every covered plane of every pixel");

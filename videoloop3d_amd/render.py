@@ -45,6 +45,11 @@ def _qgrid(quad_keep, spec):
     return (-QH, -QW) if getattr(spec, "tile", (0, 0))[0] else (QH, QW)
 
 
+def _qmap(quad_keep, spec):
+    """(map, QH, QW) as every entry with a quad map takes them: (None, 0, 0) for a dense model."""
+    return (None, 0, 0) if quad_keep is None else (L.ptr(quad_keep),) + _qgrid(quad_keep, spec)
+
+
 def _desc_dims(D, T, Hs, Ws, H, W, spec, stack_dtype=0, row0=0, col0=0):
     """the render descriptor of `spec` for a model given by its dimensions (a stack, or the block table of a packed model)."""
     d = L.RenderDesc()
@@ -194,21 +199,17 @@ class _RenderPlanes(torch.autograd.Function):
                 reg_state = torch.empty(int(L.lib().vl3d_render_reg_state_bytes(desc)), dtype=torch.uint8, device=stack.device)
         # variant bits 12-15: 1 = keep the two-pass forward with regularisers (render, then the sums kernel) for A/B and cross-checks
         fused_reg = with_reg and ((int(spec.variant) >> 12) & 0xf) != 1
+        qmap = _qmap(quad_keep, spec)
         with torch.cuda.device(stack.device):
-            if fused_reg and quad_keep is None:         # render + smoothness sums in ONE sweep over the stack
-                L.check(L.lib().vl3d_render_fwd_reg(desc, L.ptr(stack), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.ptr(asum), L.ptr(sums),
+            if fused_reg:
+                # render + smoothness sums in ONE sweep over the stack (tile-culled model: the slot-by-slot regulariser kernel composites the
+                # render from the samples it takes)
+                L.check(L.lib().vl3d_render_fwd_reg(desc, L.ptr(stack), L.ptr(homos), *qmap, L.ptr(rgb), L.ptr(alpha), L.ptr(asum), L.ptr(sums),
                                                     L.ptr(reg_state), L.stream_ptr(stack.device)), "vl3d_render_fwd_reg")
-            elif fused_reg:       # tile-culled model: the slot-by-slot regulariser kernel composites the render from the samples it takes
-                L.check(L.lib().vl3d_render_fwd_reg_culled(desc, L.ptr(stack), L.ptr(homos), L.ptr(quad_keep), *_qgrid(quad_keep, spec),
-                                                           L.ptr(rgb), L.ptr(alpha), L.ptr(asum), L.ptr(sums), L.ptr(reg_state),
-                                                           L.stream_ptr(stack.device)), "vl3d_render_fwd_reg_culled")
-            elif quad_keep is None:
-                L.check(L.lib().vl3d_render_fwd(desc, L.ptr(stack), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.ptr(asum),
-                                                L.stream_ptr(stack.device)), "vl3d_render_fwd")
             else:
-                cull = _cull_scratch(desc, stack.device)
-                L.check(L.lib().vl3d_render_fwd_culled(desc, L.ptr(stack), L.ptr(homos), L.ptr(quad_keep), *_qgrid(quad_keep, spec), L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.ptr(asum),
-                                                       L.stream_ptr(stack.device)), "vl3d_render_fwd_culled")
+                cull = None if quad_keep is None else _cull_scratch(desc, stack.device)
+                L.check(L.lib().vl3d_render_fwd(desc, L.ptr(stack), L.ptr(homos), *qmap, L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.ptr(asum),
+                                                L.stream_ptr(stack.device)), "vl3d_render_fwd")
         ctx.save_for_backward(stack, homos, rgb, alpha)
         ctx.quad_keep = quad_keep
         ctx.spec = spec
@@ -217,13 +218,8 @@ class _RenderPlanes(torch.autograd.Function):
         ctx.with_reg = with_reg
         if with_reg and not fused_reg:
             with torch.cuda.device(stack.device):
-                if quad_keep is None:
-                    L.check(L.lib().vl3d_render_reg_fwd(desc, L.ptr(stack), L.ptr(homos), L.ptr(sums), L.ptr(reg_state), L.stream_ptr(stack.device)),
-                            "vl3d_render_reg_fwd")
-                else:
-                    L.check(L.lib().vl3d_render_reg_fwd_culled(desc, L.ptr(stack), L.ptr(homos), L.ptr(quad_keep), *_qgrid(quad_keep, spec),
-                                                               L.ptr(sums), L.ptr(reg_state), L.stream_ptr(stack.device)),
-                            "vl3d_render_reg_fwd_culled")
+                L.check(L.lib().vl3d_render_reg_fwd(desc, L.ptr(stack), L.ptr(homos), *qmap, L.ptr(sums), L.ptr(reg_state),
+                                                    L.stream_ptr(stack.device)), "vl3d_render_reg_fwd")
         if asum is None:
             asum = torch.zeros((0,), dtype=torch.float32, device=stack.device)
         return rgb, alpha, sums.to(torch.float32), asum
@@ -253,16 +249,9 @@ class _RenderPlanes(torch.autograd.Function):
             LAST_BWD_CALL = LAST_BWD_CALL[:4] + (nscratch,)
             if (ctx.desc.variant & 0xf) == 1 or ctx.desc.uv_noise_seed:      # (no plan kernel will write the header: the diagnostic word reads 0)
                 scratch[:16].zero_()
-            qk = ctx.quad_keep
-            if qk is None:
-                L.check(L.lib().vl3d_render_bwd(ctx.desc, L.ptr(stack), L.ptr(homos), L.ptr(rgb), L.ptr(alpha),
-                                                L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_reg), L.ptr(ctx.reg_state), L.ptr(g_asum), L.ptr(g_stack), L.ptr(scratch), nscratch,
-                                                L.stream_ptr(stack.device)), "vl3d_render_bwd")
-            else:
-                L.check(L.lib().vl3d_render_bwd_culled(ctx.desc, L.ptr(stack), L.ptr(homos), L.ptr(qk), *_qgrid(qk, ctx.spec),
-                                                       L.ptr(rgb), L.ptr(alpha), L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_reg), L.ptr(ctx.reg_state), L.ptr(g_asum),
-                                                       L.ptr(g_stack), L.ptr(scratch), nscratch, L.stream_ptr(stack.device)),
-                        "vl3d_render_bwd_culled")
+            L.check(L.lib().vl3d_render_bwd(ctx.desc, L.ptr(stack), L.ptr(homos), *_qmap(ctx.quad_keep, ctx.spec), L.ptr(rgb), L.ptr(alpha),
+                                            L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_reg), L.ptr(ctx.reg_state), L.ptr(g_asum), L.ptr(g_stack),
+                                            L.ptr(scratch), nscratch, L.stream_ptr(stack.device)), "vl3d_render_bwd")
         LAST_BWD_SCRATCH = scratch
         return (g_stack,) + (None,) * 11
 
@@ -394,14 +383,10 @@ def render_frame_run(stack, frame0, nframes, homos, H, W, spec: RenderSpec = Ren
     desc.T = int(nframes)
     rgb, alpha = _out_buffers(out, nframes, H, W, stack.device, "render_frame_run")
     with torch.cuda.device(stack.device):
-        if quad_keep is None:
-            L.check(L.lib().vl3d_render_fwd_frames(desc, L.ptr(stack), int(frame0), int(T), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(stack.device)),
-                    "vl3d_render_fwd_frames")
-        else:
-            qk = _quad_map(quad_keep, D)
-            cull = _cull_scratch(desc, stack.device)
-            L.check(L.lib().vl3d_render_fwd_frames_culled(desc, L.ptr(stack), int(frame0), int(T), L.ptr(homos), L.ptr(qk), *_qgrid(qk, spec),
-                                                          L.ptr(cull), L.ptr(rgb), L.ptr(alpha), L.stream_ptr(stack.device)), "vl3d_render_fwd_frames_culled")
+        qk = None if quad_keep is None else _quad_map(quad_keep, D)
+        cull = None if qk is None else _cull_scratch(desc, stack.device)
+        L.check(L.lib().vl3d_render_fwd_frames(desc, L.ptr(stack), int(frame0), int(T), L.ptr(homos), *_qmap(qk, spec), L.ptr(cull), L.ptr(rgb),
+                                               L.ptr(alpha), L.stream_ptr(stack.device)), "vl3d_render_fwd_frames")
     return rgb, alpha
 
 
