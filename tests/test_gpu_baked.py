@@ -100,6 +100,32 @@ def test_bake_random_texels_within_one_level(dev, dtype, acts):
     assert int((bake_texels(t.cpu(), *acts).int() - want.cpu().int()).abs().max()) <= 1
 
 
+_ACT64 = {"sigmoid": lambda v: 1 / (1 + torch.exp(-v)), "none": lambda v: v, "clamp": lambda v: v.clamp(0, 1), "relu": torch.relu, "abs": torch.abs}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+@pytest.mark.parametrize("acts", ACT_PAIRS, ids=["-".join(a) for a in ACT_PAIRS])
+def test_bake_rule_fp64_interval(dev, dtype, acts):
+    """the bake rule against fp64, where the test above accepts any byte within one level (a kernel that rounds instead of truncating passes
+    it).  a64 = act(s widened) in float64; every byte b satisfies floor(255 a64 (1 - r)) <= b <= floor(255 a64 (1 + r)) after the clip to
+    [0, 255].  r = 8 * 2^-24 for sigmoid: __expf(-v) is an exp2 of a rounded product -- |v| <= 3 ulp in the result --, one ulp each for the
+    exp2, the reciprocal, `1 +` and `* 255` (vl3d_common.h: "4 instrs, ~1 ulp").  r = 2^-24 for clamp / relu / abs / none, exact in fp32: the only
+    rounding is `* 255`.  The same inputs as above (|s| <= 3, the odd texel count); the host path of bake_texels meets the same interval."""
+    from videoloop3d_amd.baked import bake_texels
+    t = (synth.hash_uniform((3, 37, 23, 4), seed=13, device=dev) * 6 - 3).to(dtype)
+    s = t.cpu().double()
+    a64 = torch.cat([_ACT64[acts[0]](s[..., :3]), _ACT64[acts[1]](s[..., 3:])], -1)
+    r = torch.tensor([8 * 2.0 ** -24 if a == "sigmoid" else 2.0 ** -24 for a in (acts[0],) * 3 + (acts[1],)], dtype=torch.float64)
+    lo = (255 * a64 * (1 - r)).clamp(0, 255).floor().long()
+    hi = (255 * a64 * (1 + r)).clamp(0, 255).floor().long()
+    two = int((hi > lo).sum())
+    for where, out in (("device", bake_texels(t, *acts)), ("host", bake_texels(t.cpu(), *acts))):
+        b = out.cpu().long()
+        outside = int(((b < lo) | (b > hi)).sum())
+        print(f"bake {acts} {dtype} [{where}]: {outside} bytes outside the fp64 interval, {two} two-valued intervals of {b.numel()}")
+        assert out.dtype == torch.uint8 and outside == 0, (where, outside)
+
+
 # ---- 2. parity with the pinned float kernels ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", ["dense", "shared", "exact"])
 def test_baked_render_matches_the_float_kernels(dev, scene, layout):
