@@ -40,8 +40,18 @@ enum { VL3D_COORD_UTILS_MPI = 0, VL3D_COORD_AFFINE = 1, VL3D_COORD_AFFINE_PLANES
 /* ZEROS: grid_sample padding_mode='zeros' (utils_mpi.py:174).  HARDCUT: quad extent, uncovered -> 0 after
  * activation (MPV.py:389,441-447). */
 enum { VL3D_BORDER_ZEROS = 0, VL3D_BORDER_HARDCUT = 1 };
-/* PRE: activate texels, then sample (sigmoid -> warp_homography chain).  POST: sample, then activate (MPV.py:425-435). */
-enum { VL3D_ACT_PRE = 0, VL3D_ACT_POST = 1 };
+/* PRE: activate texels, then sample (sigmoid -> warp_homography chain).  POST: sample, then activate (MPV.py:425-435).
+ * BAKED: the render of the model the viewer package shows ("Baked playback" below), differentiable -- training under the bake rule.
+ * Per tap and channel, with s the stored logit:
+ *     a = act(s);  u = uint8(trunc(clip(a * 255, 0, 255)))  (THE bake rule: the byte vl3d_bake_rgba8 writes for that texel, bit for bit --
+ *     one device function serves both);  v = (float)u / 255  (the decoded texel; the 1 / 255 is folded into the four tent weights);
+ *     the four v are blended with the tent weights, then coverage and composite exactly as PRE.
+ *     backward: dL/ds = dL/dv * act'(s) with act'(s) from the UNROUNDED a -- PRE's gradient, the rounding is straight-through.
+ * Built for the planar MPV convention (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT), sigmoid / sigmoid, fp32 and fp16 stacks: vl3d_render_fwd,
+ * _fwd_frames, _fwd_reg, _reg_fwd and vl3d_render_bwd, dense and tile-culled (shared-border and tile-exact).  Every other geometry or
+ * activation pair with it is VL3D_EUNSUPPORTED; the loop-mask channel, vl3d_render_fwd_packed, the plane-rows band and
+ * vl3d_render_bwd_adam keep refusing everything but POST. */
+enum { VL3D_ACT_PRE = 0, VL3D_ACT_POST = 1, VL3D_ACT_BAKED = 2 };
 enum { VL3D_F32 = 0, VL3D_F16 = 1, VL3D_U8 = 2 };
 /* VL3D_U8: the baked RGBA8 texels of the playback model (vl3d_bake_rgba8 / vl3d_render_fwd_baked below) -- accepted by
  * vl3d_render_fwd_baked and vl3d_render_fwd_baked_pool alone; every other entry point returns VL3D_EINVAL for it. */

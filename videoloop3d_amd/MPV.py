@@ -250,6 +250,9 @@ class MPMeshVid(PlaneModel):
         self.packed = None               # packed.PackedLayout once pack_() has replaced the dense stack by the pool `stack_pool`
         self.tile_full = None            # (th, tw): texels per quad of a model loaded from a sparsified REFERENCE checkpoint (tile lattice)
 
+        if getattr(args, "train_baked", False):      # train under the bake rule from the start (playback_rule_)
+            self.playback_rule_(True)
+
         self.swd_patch_size, self.swd_patcht_size = args.swd_patch_size, args.swd_patcht_size
         self.swd_stride, self.swd_stridet = args.swd_stride, args.swd_stridet
         self.losses = {                                   # MPV.py:131-138 ('swd' is None there too; 'gpnn_down' is off-path)
@@ -259,6 +262,31 @@ class MPMeshVid(PlaneModel):
             'mse': Patch3DMSE,
             'avg': Patch3DAvg,
         }
+
+    # ---- the picture the viewer package shows (include/vl3d.h VL3D_ACT_BAKED) ----------------------------------------------
+    @property
+    def playback_rule(self):
+        """True while the module renders -- and trains -- under the bake rule (playback_rule_)."""
+        return self.spec.act_order == "baked"
+
+    def playback_rule_(self, on=True):
+        """Switch the render between the float picture (`act_order="post"`: interpolate the logits, then activate -- the reference's rule) and
+        the SHIPPED picture (`"baked"`: every texel activated, truncated to the byte bake() writes, decoded, then interpolated -- what a player
+        shows of the viewer package).  With it on, forward / objective / render give the shipped picture in training and in eval, and the
+        gradient is the activate-first one with the rounding straight-through: a final fine-tune sees the picture that ships.  The rule is
+        not a parameter: state_dict() does not carry it.  Refused where bake() refuses -- a packed model, an atlas_exact model -- and for
+        activations other than sigmoid / sigmoid (the kernels of the rule are built for the shipped pair).  -> self."""
+        if on:
+            if self.packed is not None:
+                raise RuntimeError("playback_rule_: a packed model has no dense stack to bake (switch the rule on before pack_(), or load the "
+                                   "checkpoint with packed=False)")
+            if self.atlas_exact:
+                raise RuntimeError("playback_rule_: atlas_exact models sample the reference's atlas cells; the bake rule is built for the planar convention")
+            if (self.spec.rgb_act, self.spec.alpha_act) != ("sigmoid", "sigmoid"):
+                raise RuntimeError(f"playback_rule_: the bake rule is built for sigmoid / sigmoid activations, this model has "
+                                   f"{self.spec.rgb_act} / {self.spec.alpha_act}")
+        self.spec = dataclasses.replace(self.spec, act_order="baked" if on else "post")
+        return self
 
     # ---- packed storage of a tile-culled model (videoloop3d_amd/packed.py) -------------------------------------------------
     def _apply(self, fn, *a, **k):
@@ -319,6 +347,8 @@ class MPMeshVid(PlaneModel):
             raise RuntimeError("pack_() needs the quad maps of a sparsified model (init_from_mpi of a sparsified MPI)")
         if self.atlas_exact:
             raise RuntimeError("atlas_exact renders the dense stack")
+        if self.playback_rule:
+            raise RuntimeError("pack_(): the bake rule (playback_rule_) renders the dense stack; switch it off first (playback_rule_(False))")
         self._flush_deferred_updates()
         self._window_opt = None
         dev = self._param().device
@@ -710,6 +740,9 @@ class MPMeshVid(PlaneModel):
                                            grad_culled_unwritten=lean_grad, fused_adam=fused_adam)
         variables = {"pix_to_face": None, "blend_weight": None, "mpi": None, "disp_norm": None, "alpha": alpha,
                      "smooth_sums": smooth_sums, "alpha_sums": alpha_sums}
+        if need_layers and self.playback_rule:
+            raise RuntimeError("the materialised-layer path (d_smooth_loss_weight > 0) samples the float layers: not available under the bake rule "
+                               "(playback_rule_)")
         if need_layers and self.tile_own is not None:
             raise RuntimeError("the materialised-layer path (d_smooth_loss_weight > 0: off in every shipped configuration) is built for shared-border "
                                "stacks: load the checkpoint with init_from_mpi(..., tile_layout='lattice')")

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("VL3D_LIB_PATH") or os.path.join(_HERE, "lib", "libvl3
 ACT = {"none": 0, "sigmoid": 1, "relu": 2, "clamp": 3, "abs": 4}
 COORD = {"utils_mpi": 0, "affine": 1, "affine_planes": 2}
 BORDER = {"zeros": 0, "hardcut": 1}
-ACT_ORDER = {"pre": 0, "post": 1}
+ACT_ORDER = {"pre": 0, "post": 1, "baked": 2}      # baked: train under the bake rule (include/vl3d.h VL3D_ACT_BAKED)
 STACK_DTYPE = {"f32": 0, "f16": 1, "u8": 2}
 RHO = {"mse": 0, "abs": 1, "barron": 2}
 

@@ -15,6 +15,7 @@ namespace {
 //   (AFFINE,    HARDCUT, POST)  the reference's MPV.py planar convention              all nine activation pairs
 //   (AFFINE_PLANES, HARDCUT, POST)  MPV.py atlas-cell sampling: per-plane texel transform + quad extent   sigmoid/sigmoid
 //   (UTILS_MPI, ZEROS,   POST), (UTILS_MPI, HARDCUT, PRE)  cross-check conventions     sigmoid/sigmoid
+//   (AFFINE,    HARDCUT, BAKED) the planar convention under the bake rule: the picture the viewer package shows   sigmoid/sigmoid
 typedef int (*ConvFn)(bool, const vl3d_render_desc *, const RenderArgs &, hipStream_t);
 ConvFn conv_of(const vl3d_render_desc *d) {
     const int c = d->coord_mode, b = d->border_mode, o = d->act_order;
@@ -24,8 +25,14 @@ ConvFn conv_of(const vl3d_render_desc *d) {
     if (c == VL3D_COORD_AFFINE_PLANES && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_POST) return conv_affine_planes_hardcut_post;
     if (c == VL3D_COORD_AFFINE && b == VL3D_BORDER_HARDCUT && o == VL3D_ACT_POST)
         return (d->rgb_act == VL3D_ACT_SIGMOID && d->alpha_act == VL3D_ACT_SIGMOID) ? conv_affine_hardcut_post_sig : conv_affine_hardcut_post_other;
+    if (o == VL3D_ACT_BAKED) {      // the bake rule: the planar MPV geometry with the shipped activations alone (no clip gradient for unbounded ones)
+        if (c == VL3D_COORD_AFFINE && b == VL3D_BORDER_HARDCUT && d->rgb_act == VL3D_ACT_SIGMOID && d->alpha_act == VL3D_ACT_SIGMOID)
+            return conv_affine_hardcut_baked;
+        vl3d_set_error("unsupported with act_order VL3D_ACT_BAKED: built is (affine, hardcut, baked) with sigmoid / sigmoid activations, fp32 and fp16 stacks");
+        return nullptr;
+    }
     vl3d_set_error("unsupported (coord_mode, border_mode, act_order): built are (utils_mpi, zeros, pre|post), (utils_mpi, hardcut, pre), "
-                   "(affine, hardcut, post)");
+                   "(affine, hardcut, post), (affine, hardcut, baked)");
     return nullptr;
 }
 int dispatch(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s) {

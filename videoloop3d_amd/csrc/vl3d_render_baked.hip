@@ -12,6 +12,7 @@
 //     the 1 / 255 of the decode is folded into the four blend weights once per plane, and nothing is activated.  The launch shape is the float
 //     forward's: 64 x 8 pixels per workgroup, XCD remap, two frames per thread for T >= 2 (an odd tail frame composited twice, stored once).
 // Forward only: a baked model is not trained.
+#include "vl3d_bake_rule.h"
 #include "vl3d_baked_core.h"      // taps, decode, blend, composite step and pixel store: shared with csrc/vl3d_render_baked_pool.hip
 #include "vl3d_render_args.h"
 
@@ -20,18 +21,7 @@ using namespace vl3d_render_detail;
 namespace {
 
 // ---- bake ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float act_rt(int act, float v) {      // (the activation is uniform: a scalar branch)
-    switch (act) {
-    case VL3D_ACT_SIGMOID: return act_fwd<VL3D_ACT_SIGMOID>(v);
-    case VL3D_ACT_RELU: return act_fwd<VL3D_ACT_RELU>(v);
-    case VL3D_ACT_CLAMP: return act_fwd<VL3D_ACT_CLAMP>(v);
-    case VL3D_ACT_ABS: return act_fwd<VL3D_ACT_ABS>(v);
-    default: return v;
-    }
-}
-__device__ __forceinline__ unsigned bake_channel(float a) {      // trunc(clip(a * 255, 0, 255)); a NaN bakes to 0 (fmaxf returns the number)
-    return (unsigned)fminf(fmaxf(a * 255.0f, 0.0f), 255.0f);
-}
+// (act_rt and bake_channel -- THE bake rule -- live in vl3d_bake_rule.h: the render core's VL3D_ACT_BAKED order calls the same text)
 __device__ __forceinline__ unsigned bake_texel(f4 s, int ract, int aact) {
     return bake_channel(act_rt(ract, s.x)) | bake_channel(act_rt(ract, s.y)) << 8 | bake_channel(act_rt(ract, s.z)) << 16 |
            bake_channel(act_rt(aact, s.w)) << 24;

@@ -21,6 +21,7 @@
 #pragma once
 #include <stddef.h>
 #include "vl3d_common.h"
+#include "vl3d_bake_rule.h"
 
 // per-plane records of the homography table: 9 floats (the 3x3 matrix) by default; the VL3D_COORD_AFFINE_PLANES convention
 // (vl3d_render_c5_mpv_planes.hip) carries 16 per plane -- matrix, then the hard-cut coverage box (x0, x1, y0, y1) in texel
@@ -127,6 +128,7 @@ int conv_utils_hardcut_pre(bool bwd, const vl3d_render_desc *d, const RenderArgs
 int conv_affine_hardcut_post_sig(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s);
 int conv_affine_hardcut_post_other(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s);
 int conv_affine_planes_hardcut_post(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s);
+int conv_affine_hardcut_baked(bool bwd, const vl3d_render_desc *d, const RenderArgs &a, hipStream_t s);
 
 }  // namespace vl3d_render_detail
 
@@ -396,6 +398,13 @@ __device__ __forceinline__ f4 act4(f4 s) {
     return f4{act_fwd<RACT>(s.x), act_fwd<RACT>(s.y), act_fwd<RACT>(s.z), act_fwd<AACT>(s.w)};
 }
 
+// VL3D_ACT_BAKED: the four channels of a tap as the bytes of the baked texel (bake_channel, vl3d_bake_rule.h), still scaled by 255
+template <int RACT, int AACT>
+__device__ __forceinline__ f4 baked4(f4 s) {
+    return f4{(float)bake_channel(act_fwd<RACT>(s.x)), (float)bake_channel(act_fwd<RACT>(s.y)), (float)bake_channel(act_fwd<RACT>(s.z)),
+              (float)bake_channel(act_fwd<AACT>(s.w))};
+}
+
 // bilinear blend + activation (vector types so the blend compiles to packed FMAs)
 template <int ORDER, int RACT, int AACT>
 __device__ __forceinline__ f4 shade2(const Taps2 &t, const f4 v[4], f4 *pre_out = nullptr) {
@@ -404,6 +413,18 @@ __device__ __forceinline__ f4 shade2(const Taps2 &t, const f4 v[4], f4 *pre_out 
         s = v[0] * t.w[0] + (v[1] * t.w[1] + (v[2] * t.w[2] + v[3] * t.w[3]));
         if (pre_out) *pre_out = s;
         s = act4<RACT, AACT>(s);
+    } else if constexpr (ORDER == VL3D_ACT_BAKED) {
+        // the picture the viewer package shows: every tap is the BYTE vl3d_bake_rgba8 writes for its texel, decoded (the 1 / 255 folded into
+        // the four tent weights, as BakedComposite's w255) and blended after the activation.  The rounding is straight-through: the backward
+        // kernels treat this order as VL3D_ACT_PRE.  The chain is spelt as vector FMAs, tap 3 first: every kernel that inlines it gets the
+        // same sequence (the kernel families are compared bit for bit), and it is the form in which all instantiations stay without scratch
+        // -- left to the contraction pass the fp16 frame pairs with regularisers spilled 8 bytes, as four scalar chains the 64 x 12 pairs did
+        const f4 w255 = t.w * (1.0f / 255.0f);
+        s = baked4<RACT, AACT>(v[3]) * w255[3];
+        s = __builtin_elementwise_fma(baked4<RACT, AACT>(v[2]), f4{w255[2], w255[2], w255[2], w255[2]}, s);
+        s = __builtin_elementwise_fma(baked4<RACT, AACT>(v[1]), f4{w255[1], w255[1], w255[1], w255[1]}, s);
+        s = __builtin_elementwise_fma(baked4<RACT, AACT>(v[0]), f4{w255[0], w255[0], w255[0], w255[0]}, s);
+        if (pre_out) *pre_out = s;
     } else {
         s = act4<RACT, AACT>(v[0]) * t.w[0] + (act4<RACT, AACT>(v[1]) * t.w[1] + (act4<RACT, AACT>(v[2]) * t.w[2] + act4<RACT, AACT>(v[3]) * t.w[3]));
         if (pre_out) *pre_out = s;
@@ -778,7 +799,7 @@ __global__ __launch_bounds__(TILE_X *TILE_Y) void render_bwd_k(RenderArgs a) {
         for (int i = 0; i < 4; ++i) {
             if (tp.w[i] != 0.0f) {
                 f4 c = go * tp.w[i];
-                if constexpr (ORDER == VL3D_ACT_PRE) {
+                if constexpr (ORDER == VL3D_ACT_PRE || ORDER == VL3D_ACT_BAKED) {
                     const f4 sv = tv[i];
                     c = f4{c.x * act_bwd<RACT>(sv.x, act_fwd<RACT>(sv.x)), c.y * act_bwd<RACT>(sv.y, act_fwd<RACT>(sv.y)),
                            c.z * act_bwd<RACT>(sv.z, act_fwd<RACT>(sv.z)), c.w * act_bwd<AACT>(sv.w, act_fwd<AACT>(sv.w))};
@@ -1720,7 +1741,7 @@ __global__ __launch_bounds__(RWT *ROWS, ((REG || MASK || (CULL && COORD == VL3D_
                     if constexpr (MASK) accm = fmaf(s_gm[buf][li], wgt, accm);
                 }
             }
-            if constexpr (ORDER == VL3D_ACT_PRE) {   // d act(s_tau)/d s_tau factors out of the tap sum
+            if constexpr (ORDER == VL3D_ACT_PRE || ORDER == VL3D_ACT_BAKED) {   // d act(s_tau)/d s_tau factors out of the tap sum
                 const f4 sv = load_texel<F16>(plane, tix << 4);
                 acc = f4{acc.x * act_bwd<RACT>(sv.x, act_fwd<RACT>(sv.x)), acc.y * act_bwd<RACT>(sv.y, act_fwd<RACT>(sv.y)),
                          acc.z * act_bwd<RACT>(sv.z, act_fwd<RACT>(sv.z)), acc.w * act_bwd<AACT>(sv.w, act_fwd<AACT>(sv.w))};
@@ -1840,7 +1861,7 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
                     acc1 += *reinterpret_cast<const f4 *>(&sg1[li]) * wgt;
                 }
         }
-        if constexpr (ORDER == VL3D_ACT_PRE) {
+        if constexpr (ORDER == VL3D_ACT_PRE || ORDER == VL3D_ACT_BAKED) {
             const f4 sv0 = load_texel<F16>(plane0, tix << 4), sv1 = load_texel<F16>(plane0 + f1, tix << 4);
             acc0 = f4{acc0.x * act_bwd<RACT>(sv0.x, act_fwd<RACT>(sv0.x)), acc0.y * act_bwd<RACT>(sv0.y, act_fwd<RACT>(sv0.y)),
                       acc0.z * act_bwd<RACT>(sv0.z, act_fwd<RACT>(sv0.z)), acc0.w * act_bwd<AACT>(sv0.w, act_fwd<AACT>(sv0.w))};

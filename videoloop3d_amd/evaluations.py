@@ -214,13 +214,16 @@ def loop_static_mask(gt_u8):
     return 1 - compute_loopable_mask(vid).float()
 
 
-def evaluate_views(nerf, gt_videos, extrins, intrins, crop=40, loopmasks=None, lpips=False, timings=None):
+def evaluate_views(nerf, gt_videos, extrins, intrins, crop=40, loopmasks=None, lpips=False, timings=None, baked=None):
     """script_evaluate_ours.py:108-246 for the test views: render every frame of the loop at each view's fixed camera, build the static
     mask, crop `crop` pixels off every border, score.  nerf: an MPMeshVid, bare or in nn.DataParallel (:82); gt_videos: uint8 [F,H,W,3] per
     view (arrays or tensors); extrins [V,4,4] world-to-camera, intrins [V,3,3]; loopmasks: the script's own masks (:68-69, uncropped,
     1 = static) instead of loop_static_mask.  Returns one dict per view: nnf / nnb / loop (means over the configurations), the nine
     per-configuration values, dyn, psnr, ssim, and lpips = lpips_sw = 0.0 -- not computed (the script's own value with COMPUTE_LPIPS off,
-    :197-199).  timings: an optional dict that receives the seconds spent per stage (synchronised)."""
+    :197-199).  timings: an optional dict that receives the seconds spent per stage (synchronised).
+    baked (baked.BakedMPV / baked.BakedPool -- bake(model), bake_pool(model) or an opened viewer package): score the frames of the PLAYBACK
+    model, render_frames(..., baked=baked) -- the picture that ships -- with the same metrics; `nerf` then only names the device and the clip
+    length."""
     if lpips:
         raise NotImplementedError("LPIPS needs the torchvision / LPIPS backbone weights, which this package does not carry")
     import time
@@ -240,7 +243,7 @@ def evaluate_views(nerf, gt_videos, extrins, intrins, crop=40, loopmasks=None, l
         gt = torch.as_tensor(np.asarray(gt) if not torch.is_tensor(gt) else gt).to(dev)
         H, W = gt.shape[1:3]
         t0 = time.perf_counter()
-        pred = render_frames(nerf, H, W, np.repeat(extrins[v:v + 1], frm, 0), np.repeat(intrins[v:v + 1], frm, 0), np.arange(frm))
+        pred = render_frames(nerf, H, W, np.repeat(extrins[v:v + 1], frm, 0), np.repeat(intrins[v:v + 1], frm, 0), np.arange(frm), baked=baked)
         tick("render", t0)
         t0 = time.perf_counter()
         m = loop_static_mask(gt) if loopmasks is None else torch.as_tensor(np.asarray(loopmasks[v]), dtype=torch.float32)
@@ -298,11 +301,11 @@ def write_metrics_txt(path, dataname, results):
         f.write(", " + fmt(forwards[:-1].tolist()) + ", " + fmt(backwards[:-1].tolist()) + ", " + fmt(loops[:-1].tolist()) + "\n")
 
 
-def evaluate(nerf, args, poses_bounds, videos, ckpt=None, test_view_idx=None, dataname="", out_dir=None, loopmasks=None, timings=None):
+def evaluate(nerf, args, poses_bounds, videos, ckpt=None, test_view_idx=None, dataname="", out_dir=None, loopmasks=None, timings=None, baked=None):
     """The whole of script_evaluate_ours.evaluate() but the disk I/O of the videos (mirrors render_video.render_video): LLFF poses ->
     test-view selection -> (optional) checkpoint -> evaluate_views -> `out_dir`/eval_metrics.txt.  videos: uint8 [F,H,W,3] per view, in
     view order (decoding mp4 is the caller's); nerf: the MPMeshVid built with render_video.reference_camera(...) of the same poses, bare or
-    in nn.DataParallel.  Returns evaluate_views' list of dicts."""
+    in nn.DataParallel.  baked: the playback model to score instead (evaluate_views).  Returns evaluate_views' list of dicts."""
     import os
     from .render_video import load_llff_poses, pose2extrin_np
     poses, intrins, _, _, _ = load_llff_poses(poses_bounds, factor=getattr(args, "factor", 1), recenter=True,
@@ -316,7 +319,7 @@ def evaluate(nerf, args, poses_bounds, videos, ckpt=None, test_view_idx=None, da
     if ckpt is not None:
         sd = torch.load(ckpt, weights_only=False) if isinstance(ckpt, (str, os.PathLike)) else ckpt
         getattr(nerf, "module", nerf).init_from_mpi(sd['network_state_dict'])
-    results = evaluate_views(nerf, videos, pose2extrin_np(poses[views]), intrins[views], loopmasks=loopmasks, timings=timings)
+    results = evaluate_views(nerf, videos, pose2extrin_np(poses[views]), intrins[views], loopmasks=loopmasks, timings=timings, baked=baked)
     if out_dir is not None:
         write_metrics_txt(os.path.join(out_dir, "eval_metrics.txt"), dataname, results)
     return results

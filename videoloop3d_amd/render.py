@@ -17,7 +17,9 @@ class RenderSpec:
 
     Defaults = the utils_mpi convention (sigmoid -> warp_homography -> over-composite).
     `RenderSpec.mpv()` = the planar MPV.py convention (pixel centres at +0.5, hard-cut quad borders,
-    sample-then-activate)."""
+    sample-then-activate).  `act_order="baked"` (with the planar convention, sigmoid / sigmoid): the picture the viewer package shows --
+    every tap activated, truncated to the byte baked.bake_texels writes, decoded, then blended (include/vl3d.h VL3D_ACT_BAKED); the gradient
+    is the activate-first one, the rounding straight-through."""
     pixel_center: float = 0.0
     coord_mode: str = "utils_mpi"
     scale: tuple = (1.0, 1.0)
@@ -324,6 +326,8 @@ def render_planes_with_mask(stack, mask, homos, H, W, spec: RenderSpec = RenderS
     """-> (rgb [T,H,W,3], alpha [T,H,W], label [T,H,W], smooth_sums[4], alpha_sums [T,H,W,2]) -- render_planes (with_regularisers: plus
     render_planes_with_regularisers' sums) and the composited loop-mask label `sum_k w_k sigmoid(sample(mask_k))` of MPI.py:568-583 from the
     same pass; `mask` [D,T,Hs,Ws] logits.  Needs mask_channel_supported(stack, spec)."""
+    if spec.act_order == "baked":
+        raise RuntimeError("the loop-mask channel is not built for the bake rule (act_order='baked'): stage 1 trains under 'post'")
     return _RenderPlanesMask.apply(stack, mask, homos, int(H), int(W), spec, bool(with_regularisers))
 
 
@@ -723,6 +727,8 @@ def render_plane_rows(local, homos, plane_row0, H, W, Hs, spec: RenderSpec, wind
     being its plane row plane_row0[d] + r (plane_row0: int32 [D] on the device), Hs the true plane height.  The same bits as
     render_planes(full_stack, ..., window=window) wherever the windows hold every row the band's taps reach (dist.plan_plane_bands).
     The planar MPV convention (RenderSpec.mpv(), sigmoid / sigmoid), fp32 or fp16 stacks.  -> (rgb [T,H,W,3], alpha [T,H,W])."""
+    if spec.act_order == "baked":
+        raise RuntimeError("per-plane row windows are not built for the bake rule (act_order='baked'): render the band from the whole stack (render_planes)")
     if spec.coord_mode != "affine" or spec.border != "hardcut" or spec.act_order != "post":
         raise RuntimeError("per-plane row windows render in the planar MPV convention (RenderSpec.mpv())")
     return _RenderPlaneRows.apply(local, homos, plane_row0, int(H), int(W), int(Hs), spec, int(window[0]), int(window[1]))
@@ -736,6 +742,8 @@ def render_planes_packed(layout, pool, frames, homos, H, W, spec: RenderSpec, qu
     `out`: (rgb, alpha) buffers to write into; `frames_dev`: the same frame indices as an int32 device tensor (a caller rendering a long path
     uploads them once instead of per call)."""
     L.check_cuda(pool, homos, quad_keep, layout.blocks)
+    if spec.act_order == "baked":
+        raise RuntimeError("a packed model is not rendered under the bake rule (act_order='baked'): baked.bake_pool(model) gives its playback model")
     if spec.coord_mode != "affine" or spec.border != "hardcut" or spec.act_order != "post":
         raise RuntimeError("a packed model renders in the planar MPV convention (RenderSpec.mpv())")
     frames = [int(t) for t in frames]
