@@ -57,6 +57,8 @@ enum { VL3D_F32 = 0, VL3D_F16 = 1, VL3D_U8 = 2 };
  * vl3d_render_fwd_baked and vl3d_render_fwd_baked_pool alone; every other entry point returns VL3D_EINVAL for it. */
 
 const char *vl3d_last_error(void);
+/* Raised by one whenever an exported signature or the layout of a struct of this header changes (101: the vl3d_adam_window family takes the
+ * struct); a caller built against another header compares it before its first call. */
 int vl3d_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -351,13 +353,13 @@ int vl3d_adam_step_tiles(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const uin
                          float eps, int64_t step, vl3d_stream_t stream);
 
 /* Crop-aware Adam for the DENSE stack (csrc/vl3d_optim.hip; the optimiser of train_3dvid.py:263-290 / MPV.py:199-214).  A training
- * iteration renders one crop, so only the texels of the crop's parallax window (y0, x0, wh, ww; aligned to
+ * iteration renders one crop, so only the texels of the crop's parallax window (vl3d_adam_window's y0, x0, wh, ww; aligned to
  * vl3d_adam_window_tile()-texel tiles, or ending at the plane border) receive a gradient; the zero-gradient Adam steps of all
  * other texels (m <- b1 m, v <- b2 v, p <- p - lr_t m^/(sqrt(v^) + eps)) are deferred and replayed exactly, per tile, when a tile is
  * next needed.  last_step: device int32 [D][ceil(Hs/16)][ceil(Ws/16)], the step each tile is current for (0 initially).
  * hist: device float2 [steps+1], entry t = (lr_t / (1 - beta1^t), sqrt(1 - beta2^t)) as vl3d_adam_step_scalars computes them.
- * Round 6: the step functions (vl3d_adam_window_step / _boxes, vl3d_render_bwd_adam) WRITE row `step` themselves from their own lr / betas /
- * step arguments, behind the update, in the launch that marks the tiles (the table is `const` for every reader; a caller that also fills the row
+ * Round 6: the step functions (vl3d_adam_window_step, vl3d_render_bwd_adam) WRITE row `step` themselves from the struct's lr / betas /
+ * step, behind the update, in the launch that marks the tiles (the table is `const` for every reader; a caller that also fills the row
  * writes the same two floats).  The caller sizes the table (step < its length) and keeps rows 0 .. step intact.
  *   vl3d_adam_window_catchup: the window's parameters as of step `upto` (steps last_step+1 .. upto replayed with g = 0).  With
  *     compact != NULL they are written to the compact (D,T,wh,ww,4) buffer the render then reads and the stack is left untouched;
@@ -374,25 +376,58 @@ int vl3d_adam_step_tiles(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const uin
  * buffer that was zero-filled once and has only ever been written by this call), so the slots the render cannot read with a non-zero
  * weight -- culled texels, texels outside their plane's box -- are not written: for a tile-culled model they were most of the copy. */
 int32_t vl3d_adam_window_tile(void);
-int vl3d_adam_window_catchup(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                             float *param, float *exp_avg, float *exp_avg_sq, int32_t *last_step, const float *hist, int32_t upto,
-                             float beta1, float beta2, float eps, float *compact, const uint8_t *quad_keep, const uint8_t *quad_dyn,
-                             int32_t QH, int32_t QW, float culled_alpha, int32_t mirror_static, vl3d_stream_t stream);
-int vl3d_adam_window_step(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                          float *param, const float *grad_compact, float *exp_avg, float *exp_avg_sq, int32_t *last_step,
-                          const float *hist, float lr, float beta1, float beta2, float eps, int64_t step, const uint8_t *quad_keep,
-                          const uint8_t *quad_dyn,
-                          int32_t QH, int32_t QW, int32_t static_tied, vl3d_stream_t stream);
+/* One argument for the whole family: the model, the window, the optimiser's state and hyper-parameters.  Which entry reads what:
+ *   vl3d_adam_window_catchup  everything but lr / step and the two scratch pointers;
+ *   vl3d_adam_window_step     everything but the two scratch pointers;
+ *   vl3d_adam_flush_older     the model, the state, betas / eps, the quad maps and `blocks` -- not the window, not the boxes, not lr / step;
+ *   vl3d_render_bwd_adam      everything (boxes_scratch / class_scratch are this entry's only).
+ * Every entry refuses, before it launches anything, a struct whose dims are not positive (D <= 65535), whose window (where it is read) leaves the
+ * plane or the bookkeeping tiles, `blocks` without quad maps, a quad grid of mixed signs or a tile-exact grid that does not divide the plane into
+ * tiles of at least 2 x 2 texels, and a NULL state pointer.  The layout is ABI (152 bytes, `blocks` at 144: asserted in csrc/vl3d_optim.hip and
+ * tests/test_adam_window_cpu.py). */
+typedef struct vl3d_adam_window {
+    int32_t D, T;                /* the model: param / exp_avg / exp_avg_sq are (D,T,Hs,Ws,4), or the pools of `blocks` */
+    int32_t Hs, Ws;              /* the full planes */
+    int32_t y0, x0, wh, ww;      /* the window [y0, y0 + wh) x [x0, x0 + ww), aligned to vl3d_adam_window_tile() or ending at the plane border */
+    float *param, *exp_avg, *exp_avg_sq;
+    int32_t *last_step;
+    const float *hist;
+    float lr, beta1, beta2, eps;
+    int64_t step;
+    /* Per-plane boxes, HOST [D][4] = (y0, y1, x0, x1) in plane texels, tile aligned, inside the window, or NULL: 16 bytes per plane that travel
+     * in the kernel arguments, no copy, no synchronisation (NULL, or more than 128 planes: the whole window for every plane).  The window of a
+     * crop is the union of the planes' footprints; texels of the window outside their own plane's box cannot be sampled in this iteration, their
+     * gradient is exactly zero and their update stays deferred like that of every texel outside the window: the catch-up leaves their slots of the
+     * compact copy unwritten (never read), the step skips them. */
+    const int32_t *plane_boxes;
+    void *boxes_scratch;         /* vl3d_render_bwd_adam: device, 16 * D bytes; required with plane_boxes */
+    /* tile-culled model (NULL quad_keep: dense): the quad maps (device byte maps [D][|QH|][|QW|], a negative grid: tile-exact layout) and, for
+     * vl3d_render_bwd_adam, a device scratch of vl3d_render_bwd_adam_class_bytes(desc) bytes for the texel records of the window (8 bytes per
+     * plane texel: class, the step its bookkeeping tile is current for, its slot in the parameter tensors / pools -- written by the pre-pass,
+     * read by the owner's store) */
+    const uint8_t *quad_keep, *quad_dyn;
+    int32_t QH, QW;
+    void *class_scratch;
+    const int32_t *blocks;       /* PACKED storage ("PACKED storage" below; needs the quad maps): param / exp_avg / exp_avg_sq are the pools */
+} vl3d_adam_window;
+int vl3d_adam_window_catchup(const vl3d_adam_window *w, int32_t upto, float *compact, float culled_alpha, int32_t mirror_static,
+                             vl3d_stream_t stream);
+int vl3d_adam_window_step(const vl3d_adam_window *w, const float *grad_compact, int32_t static_tied, vl3d_stream_t stream);
+/* Bound on the deferral: every bookkeeping tile that has missed at least min_depth steps is replayed up to `upto`, written back and marked
+ * (the others are left alone).  Run after each step it keeps what a returning crop window has to replay below min_depth steps per texel
+ * -- the reference shuffles 32-72 crops x views per epoch (train_3dvid.py:263-290), so a window comes back after that many steps. */
+int vl3d_adam_flush_older(const vl3d_adam_window *w, int32_t upto, int32_t min_depth, vl3d_stream_t stream);
+void vl3d_adam_step_scalars(float lr, float beta1, float beta2, int64_t step, float *lr_bc1, float *bc2s);
 
 /* The optimiser step INSIDE the render backward (train_3dvid.py:242-244: loss.backward(); optimizer.step() -- for the dense stage-2 model
  * they are one pass over the window's texels).  vl3d_render_bwd of the crop-aware iteration writes the window's compact gradient
  * (one stream) only for vl3d_adam_window_step to read it back beside (p, m, v) and write (p, m, v): 2 + 7 streams of the window.  Here the
  * owner-computes backward applies the step of `adam->step` where it would have stored a texel's complete gradient sum: 1 (taps) + 2 (m, v)
  * + 3 (p, m, v) streams, no gradient round trip.  `stack` is the compact copy of the texel window at (adam->y0, adam->x0) of the
- * (D,T,adam->Hs,adam->Ws,4) parameter -- desc->Hs x desc->Ws texels, written by vl3d_adam_window_catchup(_boxes) with upto = step - 1, so it
- * holds the parameters current for step - 1 and only the two moments are replayed (multiplications).  Window / plane_boxes / last_step /
- * hist: as vl3d_adam_window_step_boxes (hist[step] is written by this call); on return the window's tiles are marked `step` and (p, m, v) are
- * bit for bit what vl3d_render_bwd followed by vl3d_adam_window_step_boxes would have left (tests/test_gpu_optim.py).  Every texel of
+ * (D,T,adam->Hs,adam->Ws,4) parameter -- desc->Hs x desc->Ws texels, written by vl3d_adam_window_catchup with upto = step - 1, so it
+ * holds the parameters current for step - 1 and only the two moments are replayed (multiplications); adam->D, T, wh, ww must be
+ * desc->D, T, Hs, Ws (VL3D_EINVAL otherwise).  Window / plane_boxes / last_step / hist: as vl3d_adam_window_step (hist[step] is written
+ * by this call); on return the window's tiles are marked `step` and (p, m, v) are bit for bit what vl3d_render_bwd followed by vl3d_adam_window_step would have left (tests/test_gpu_optim.py).  Every texel of
  * window and box is stepped exactly once: by the tile that owns it, or -- texels no tile's gather reaches: zero gradient -- by the
  * backward's pre-pass.  grad_stack (the compact gradient, desc's dims) is still required: when the device-side plan finds the view
  * infeasible for the owner-computes kernels the atomics kernel fills it and the step kernel runs behind it, decided on the device (no
@@ -404,56 +439,19 @@ int vl3d_adam_window_step(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t 
  * fp32 stacks, the planar convention with the shipped activations ((affine, hardcut, post), sigmoid / sigmoid); dense models: T >= 2,
  * desc->variant 0 (the frame pairs; tile-culled models always take the one-frame tile kernel: 32-wide regions, variant 3 = 64-wide); anything else: VL3D_EUNSUPPORTED,
  * nothing launched. */
-typedef struct vl3d_adam_window {
-    int32_t Hs, Ws;              /* the full planes: param / exp_avg / exp_avg_sq are (D,T,Hs,Ws,4) */
-    int32_t y0, x0;              /* the window [y0, y0 + desc->Hs) x [x0, x0 + desc->Ws), aligned to vl3d_adam_window_tile() */
-    float *param, *exp_avg, *exp_avg_sq;
-    int32_t *last_step;
-    const float *hist;
-    float lr, beta1, beta2, eps;
-    int64_t step;
-    const int32_t *plane_boxes;  /* HOST [D][4] or NULL */
-    void *boxes_scratch;         /* device, 16 * D bytes; required with plane_boxes */
-    /* tile-culled model (NULL quad_keep: dense): the quad maps of vl3d_adam_window_step (device byte maps [D][QH][QW]) and a device scratch
-     * of vl3d_render_bwd_adam_class_bytes(desc) bytes for the texel records of the window (8 bytes per plane texel: class, the step its
-     * bookkeeping tile is current for, its slot in the parameter tensors / pools -- written by the pre-pass, read by the owner's store) */
-    const uint8_t *quad_keep, *quad_dyn;
-    int32_t QH, QW;
-    void *class_scratch;
-    const int32_t *blocks;       /* PACKED storage (as vl3d_adam_window_step_boxes; needs the quad maps): param / exp_avg / exp_avg_sq are the pools */
-} vl3d_adam_window;
 int64_t vl3d_render_bwd_adam_class_bytes(const vl3d_render_desc *desc);
 int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *stack, const float *homos, const float *rgb, const float *alpha,
                          const float *grad_rgb, const float *grad_alpha, const float *grad_reg, const void *reg_state,
                          const float *grad_alpha_sums, float *grad_stack, void *scratch, int64_t scratch_bytes,
                          const vl3d_adam_window *adam, vl3d_stream_t stream);
 
-/* PACKED storage of a tile-culled model (`blocks` != NULL on the three entry points below; quad maps required): the reference keeps a
+/* PACKED storage of a tile-culled model (vl3d_adam_window's `blocks` != NULL; quad maps required): the reference keeps a
  * static atlas (one frame), a dynamic atlas (T frames) and no storage for culled quads (MPI.py:364-436, MPV.py:235-288).  Here
  * param / exp_avg / exp_avg_sq are pools of 8 x 8-texel blocks (vl3d_adam_window_tile()): blocks [D][ceil(Hs/8)][ceil(Ws/8)] int32 = -1 for
  * a block no kept quad can read (not stored), else slot << 1 | dynamic, a slot being 64 texels (1 KiB); a static block owns one slot, a
  * dynamic block T consecutive ones (frame-major).  The compact window copy / gradient the render kernels work on stay dense, so the
  * kernels of the hot path are unchanged and the parameters after every step have the bits of the dense (D,T,Hs,Ws,4) model; the pool of
- * a model with 16 % of its quads kept is about a seventh of the dense stack (videoloop3d_amd/packed.py).
- *
- * The same two with per-plane boxes: plane_boxes [D][4] = (y0, y1, x0, x1) in plane texels, tile aligned, inside the window, in HOST
- * memory -- 16 bytes per plane that travel in the kernel arguments, no copy, no synchronisation (NULL, or more than 128 planes: the whole
- * window for every plane).  The window of a crop is the union of the planes' footprints; texels of the window outside
- * their own plane's box cannot be sampled in this iteration, their gradient is exactly zero and their update stays deferred like that of
- * every texel outside the window: the catch-up leaves their slots of the compact copy unwritten (never read), the step skips them. */
-int vl3d_adam_window_catchup_boxes(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                                   float *param, float *exp_avg, float *exp_avg_sq, int32_t *last_step, const float *hist, int32_t upto,
-                                   float beta1, float beta2, float eps, float *compact, const uint8_t *quad_keep, const uint8_t *quad_dyn,
-                                   int32_t QH, int32_t QW, float culled_alpha, int32_t mirror_static, const int32_t *plane_boxes,
-                                   const int32_t *blocks, vl3d_stream_t stream);
-int vl3d_adam_window_step_boxes(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                                float *param, const float *grad_compact, float *exp_avg, float *exp_avg_sq, int32_t *last_step,
-                                const float *hist, float lr, float beta1, float beta2, float eps, int64_t step, const uint8_t *quad_keep,
-                                const uint8_t *quad_dyn, int32_t QH, int32_t QW, int32_t static_tied, const int32_t *plane_boxes,
-                                const int32_t *blocks, vl3d_stream_t stream);
-/* Bound on the deferral: every bookkeeping tile that has missed at least min_depth steps is replayed up to `upto`, written back and marked
- * (the others are left alone).  Run after each step it keeps what a returning crop window has to replay below min_depth steps per texel
- * -- the reference shuffles 32-72 crops x views per epoch (train_3dvid.py:263-290), so a window comes back after that many steps. */
+ * a model with 16 % of its quads kept is about a seventh of the dense stack (videoloop3d_amd/packed.py). */
 /* Chosen frames of a PACKED model as a dense stack for an evaluation render (MPV.py:439 `atlas_dyn[ts]`): out (D,n,Hs,Ws,4); frames =
  * device int32 [n], each in [0,T); blocks without storage read (0, 0, 0, culled_alpha), static blocks their one copy in every frame. */
 int vl3d_packed_unpack_frames(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const int32_t *blocks, const float *pool, int32_t n,
@@ -467,10 +465,6 @@ int vl3d_packed_unpack_frames(int32_t D, int32_t T, int32_t Hs, int32_t Ws, cons
 int vl3d_render_fwd_packed(const vl3d_render_desc *desc, const int32_t *blocks, const float *pool, const int32_t *frames, int32_t n,
                            const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW, float culled_alpha, float *rgb,
                            float *alpha, vl3d_stream_t stream);
-int vl3d_adam_flush_older(int32_t D, int32_t T, int32_t Hs, int32_t Ws, float *param, float *exp_avg, float *exp_avg_sq, int32_t *last_step,
-                          const float *hist, int32_t upto, int32_t min_depth, float beta1, float beta2, float eps, const uint8_t *quad_keep,
-                          const uint8_t *quad_dyn, int32_t QH, int32_t QW, const int32_t *blocks, vl3d_stream_t stream);
-void vl3d_adam_step_scalars(float lr, float beta1, float beta2, int64_t step, float *lr_bc1, float *bc2s);
 
 /* Layer-space smoothness regularisers (MPV.py:517-531 rgb_smooth / a_smooth; MPI.py:608-622) WITHOUT the materialised [T,h,w,K,4]
  * layer tensor: sums[0..3] (device doubles, overwritten) = sum over frames, layer SLOTS and neighbouring pixel pairs of |L[p]-L[q]|

@@ -596,7 +596,7 @@ def test_tile_culled_step_fused_into_the_backward(dev, smooth, T, scale, rot, pa
 def test_render_bwd_adam_refuses_what_it_is_not_built_for(dev):
     """vl3d_render_bwd_adam launches nothing for descriptors outside its scope (include/vl3d.h): other conventions / activations / fp16 stacks,
     a dense model with one frame, a window that is not aligned to the bookkeeping tiles, quad maps without the class scratch, a packed
-    layout without quad maps -- VL3D_EUNSUPPORTED / VL3D_EINVAL with a message, parameters untouched."""
+    layout without quad maps, a window extent that is not the descriptor's stack -- VL3D_EUNSUPPORTED / VL3D_EINVAL with a message, parameters untouched."""
     import ctypes as C
     from videoloop3d_amd import _lib as L
     from videoloop3d_amd.render import RenderSpec, _desc
@@ -610,7 +610,7 @@ def test_render_bwd_adam_refuses_what_it_is_not_built_for(dev):
     def call(spec=RenderSpec.mpv(), stack=stack, y0=8, **over):
         desc = _desc(stack, H, W, spec, 0, 0)
         aw = L.AdamWindow()
-        aw.Hs, aw.Ws, aw.y0, aw.x0 = Hs, Ws, y0, 8
+        aw.D, aw.T, aw.Hs, aw.Ws, aw.y0, aw.x0, aw.wh, aw.ww = D, stack.shape[1], Hs, Ws, y0, 8, wh, ww
         aw.param, aw.exp_avg, aw.exp_avg_sq, aw.last_step, aw.hist = (t.data_ptr() for t in (p, m, v, last, hist))
         aw.lr, aw.beta1, aw.beta2, aw.eps, aw.step = 1e-3, 0.9, 0.999, 1e-8, 1
         for k, val in over.items():
@@ -623,7 +623,8 @@ def test_render_bwd_adam_refuses_what_it_is_not_built_for(dev):
     qk = torch.ones((D, 3, 4), dtype=torch.uint8, device=dev)
     blocks = z(D, 4, 5, dt=torch.int32)
     cases = [dict(spec=RenderSpec()), dict(spec=RenderSpec.mpv(rgb_act="none")), dict(stack=stack.half()), dict(stack=stack[:, :1].contiguous()),
-             dict(spec=RenderSpec.mpv(variant=1)), dict(y0=4), dict(quad_keep=qk.data_ptr(), QH=3, QW=4), dict(blocks=blocks.data_ptr())]
+             dict(spec=RenderSpec.mpv(variant=1)), dict(y0=4), dict(quad_keep=qk.data_ptr(), QH=3, QW=4), dict(blocks=blocks.data_ptr()),
+             dict(wh=wh - 8)]      # (a window that is not the descriptor's stack: adam->wh != desc->Hs)
     for kw in cases:
         rc, msg = call(**kw)
         assert rc != 0 and msg, (kw, rc, msg)

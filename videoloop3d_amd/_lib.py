@@ -49,8 +49,9 @@ class EvalDesc(C.Structure):
                 ("gt_sf", C.c_int64), ("gt_sr", C.c_int64), ("pred_sf", C.c_int64), ("pred_sr", C.c_int64)]
 
 
-class AdamWindow(C.Structure):
-    _fields_ = [("Hs", C.c_int32), ("Ws", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32),
+class AdamWindow(C.Structure):       # vl3d_adam_window: 152 bytes, `blocks` at 144 (asserted in csrc/vl3d_optim.hip and tests/test_adam_window_cpu.py)
+    _fields_ = [("D", C.c_int32), ("T", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
+                ("y0", C.c_int32), ("x0", C.c_int32), ("wh", C.c_int32), ("ww", C.c_int32),
                 ("param", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("last_step", _P), ("hist", _P),
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("step", C.c_int64), ("plane_boxes", _P), ("boxes_scratch", _P),
@@ -110,13 +111,11 @@ SIGNATURES = {
     "vl3d_adam_step_tiles": ([_I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P],
                              C.c_int),
     "vl3d_adam_window_tile": ([], C.c_int32),
-    "vl3d_adam_window_catchup": ([_I32] * 8 + [_P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _I32, _I32, _F, _I32, _P], C.c_int),
-    "vl3d_adam_window_catchup_boxes": ([_I32] * 8 + [_P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _I32, _I32, _F, _I32, _P, _P, _P], C.c_int),
-    "vl3d_adam_window_step": ([_I32] * 8 + [_P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I64, _P, _P, _I32, _I32, _I32, _P], C.c_int),
-    "vl3d_adam_window_step_boxes": ([_I32] * 8 + [_P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P], C.c_int),
+    "vl3d_adam_window_catchup": ([C.POINTER(AdamWindow), _I32, _P, _F, _I32, _P], C.c_int),
+    "vl3d_adam_window_step": ([C.POINTER(AdamWindow), _P, _I32, _P], C.c_int),
     "vl3d_packed_unpack_frames": ([_I32] * 4 + [_P, _P, _I32, _P, _F, _P, _P], C.c_int),
     "vl3d_render_fwd_packed": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _P, _P, _I32, _I32, _F, _P, _P, _P], C.c_int),
-    "vl3d_adam_flush_older": ([_I32] * 4 + [_P, _P, _P, _P, _P, _I32, _I32, _F, _F, _F, _P, _P, _I32, _I32, _P, _P], C.c_int),
+    "vl3d_adam_flush_older": ([C.POINTER(AdamWindow), _I32, _I32, _P], C.c_int),
     "vl3d_adam_step_scalars": ([_F, _F, _F, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float)], None),
     "vl3d_render_cull_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_fwd_plane_rows": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, _P, _P], C.c_int),

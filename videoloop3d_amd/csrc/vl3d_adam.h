@@ -56,6 +56,13 @@ __device__ __forceinline__ void replay_moments(float4 &mm, float4 &vv, int from,
     }
 }
 
+// the scalars of step `step`, (lr / (1 - beta1^step), sqrt(1 - beta2^step)): what the step kernels take, the fused owner store takes and row `step` of
+// the history table holds -- one double expression, so a replayed step has the bits of the step that was taken
+__host__ inline float2 adam_step_scalars(float lr, float beta1, float beta2, int64_t step) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    return make_float2((float)((double)lr / bc1), (float)sqrt(bc2));
+}
+
 // tile-culled models (quad maps keep / dyn [D][QH][QW], MPI.py:288-442): 0 = culled texel (no kept quad can read it: no parameter),
 // 1 = dynamic (a parameter per frame), 2 = static (only static quads can read it: ONE parameter, living in frame 0 -- the reference's
 // static atlas, MPV.py:235-288).  Same classification as tiles.quad_to_texel_mask / adam_tiles_k.  keep == NULL: everything dynamic.
@@ -108,18 +115,16 @@ struct vl3d_adam_epilogue {
     // .y = the texel's 16-byte slot inside a frame of p / m / v (dense tensors or packed pools; dynamic texels only)
     const unsigned char *quad_dyn;
     uint2 *cls;                    // NULL: dense model (every texel dynamic)
-    // PACKED storage (vl3d_adam_window_step_boxes' `blocks`): p / m / v are pools of 8 x 8-texel blocks, blocks [D][tiles_y][tiles_x] = -1 or
+    // PACKED storage (vl3d_adam_window's `blocks`): p / m / v are pools of 8 x 8-texel blocks, blocks [D][tiles_y][tiles_x] = -1 or
     // slot << 1 | dynamic; a dynamic block owns T consecutive slots (frame-major).  NULL: the dense (D,T,Hs,Ws,4) tensors.
     const int *blocks;
 };
 
-// (internal, vl3d_optim.hip) the tail of vl3d_render_bwd_adam: the window step from the compact gradient for what the backward did not step
-// itself -- static texels of a tile-culled model always; everything when the device-side plan of the backward said "infeasible"
-// (*plan_ok == 0: the atomics kernel produced the gradient) -- then the tile marks.  Called BEFORE the render kernels with
-// grad_compact == NULL: window / box checks and the box table onto the device (boxes_dev).
-__attribute__((visibility("hidden"))) int vl3d_adam_window_step_tail(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
-                                                                     int32_t ww, float *param, const float *grad_compact, float *exp_avg,
-                                                                     float *exp_avg_sq, int32_t *last_step, const float *hist, float lr, float beta1,
-                                                                     float beta2, float eps, int64_t step, const uint8_t *quad_keep,
-                                                                     const uint8_t *quad_dyn, int32_t QH, int32_t QW, const int32_t *plane_boxes,
-                                                                     const int32_t *blocks, const int *plan_ok, void *boxes_dev, hipStream_t stream);
+// (internal, vl3d_optim.hip) the optimiser's two halves of vl3d_render_bwd_adam, around its render kernels.
+// before: the window checks every entry shares, the per-plane boxes validated and their table onto the device (w.boxes_scratch).
+// behind: the window step from the compact gradient for what the backward did not step itself -- static texels of a tile-culled model always;
+// everything when the device-side plan of the backward said "infeasible" (*plan_ok == 0: the atomics kernel produced the gradient) -- then the
+// tile marks.
+__attribute__((visibility("hidden"))) int vl3d_adam_window_before_render(const vl3d_adam_window &w, hipStream_t stream);
+__attribute__((visibility("hidden"))) int vl3d_adam_window_behind_render(const vl3d_adam_window &w, const float *grad_compact, const int *plan_ok,
+                                                                         hipStream_t stream);

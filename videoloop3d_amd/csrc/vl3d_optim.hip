@@ -14,6 +14,8 @@
 //   * a catch-up over the full stack brings everything current (checkpoints, lod(), evaluation renders).
 // Per-step scalars (lr / (1 - b1^t), sqrt(1 - b2^t)) come from a device table written by the host when the step is taken, so a
 // changing learning rate (train_3dvid.py:263-277) is replayed as it was.
+#include <stddef.h>
+
 #include "vl3d_adam.h"
 
 namespace {
@@ -263,11 +265,52 @@ __global__ __launch_bounds__(256) void mark_tiles_k(int *last_step, int tiles_y,
     last_step[((size_t)d * tiles_y + ty0 + ty) * tiles_x + tx0 + tx] = step;
 }
 
-int check_window(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww) {
-    VL3D_REQUIRE(D > 0 && D <= 65535 && T > 0 && Hs > 0 && Ws > 0, "adam window: bad dims");
-    VL3D_REQUIRE(y0 >= 0 && x0 >= 0 && wh > 0 && ww > 0 && y0 + wh <= Hs && x0 + ww <= Ws, "adam window: window outside the plane");
-    VL3D_REQUIRE(y0 % TS == 0 && x0 % TS == 0 && ((y0 + wh) % TS == 0 || y0 + wh == Hs) && ((x0 + ww) % TS == 0 || x0 + ww == Ws),
-                 "adam window: the window must be aligned to the bookkeeping tiles (or end at the plane border)");
+// Every refusal the window entries share, in one place and before any launch: the model, the window inside the plane and on the bookkeeping
+// tiles, the packed layout only with quad maps, the quad grid, the state pointers.  (The per-plane boxes are validated by the fused entry
+// alone: vl3d_adam_window_before_render.)
+int check_adam_window(const vl3d_adam_window &w, const char *who) {
+    const char *why =
+        !(w.D > 0 && w.D <= 65535 && w.T > 0 && w.Hs > 0 && w.Ws > 0) ? "bad dims"
+        : !(w.y0 >= 0 && w.x0 >= 0 && w.wh > 0 && w.ww > 0 && w.y0 + w.wh <= w.Hs && w.x0 + w.ww <= w.Ws) ? "window outside the plane"
+        : !(w.y0 % TS == 0 && w.x0 % TS == 0 && ((w.y0 + w.wh) % TS == 0 || w.y0 + w.wh == w.Hs) && ((w.x0 + w.ww) % TS == 0 || w.x0 + w.ww == w.Ws))
+            ? "the window must be aligned to the bookkeeping tiles (or end at the plane border)"
+        : (w.blocks && !w.quad_keep) ? "the packed layout belongs to a tile-culled model (quad maps)"
+        : (w.quad_keep && !quad_grid_ok(w.QH, w.QW, w.Hs, w.Ws)) ? "bad quad grid"
+        : !(w.param && w.exp_avg && w.exp_avg_sq && w.last_step && w.hist) ? "null state pointer"
+                                                                            : nullptr;
+    if (!why) return VL3D_OK;
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    vl3d_set_error(msg);
+    return VL3D_EINVAL;
+}
+
+// (the ctypes mirror _lib.AdamWindow and tests/test_adam_window_cpu.py carry the same two literals)
+static_assert(sizeof(vl3d_adam_window) == 152, "vl3d_adam_window: the layout is ABI");
+static_assert(offsetof(vl3d_adam_window, blocks) == 144, "vl3d_adam_window: the layout is ABI");
+
+inline int tiles_of(int n) { return (n + TS - 1) / TS; }
+inline Quads quads_of(const vl3d_adam_window &w) { return make_quads(w.quad_keep, w.quad_dyn, w.QH, w.QW, w.Hs, w.Ws); }
+inline float4 *f4(float *p) { return reinterpret_cast<float4 *>(p); }
+
+// the window's tiles (inside their plane's box) are current for `step`; hist_row / hist_val: mark_tiles_k
+void launch_mark_tiles(const vl3d_adam_window &w, const BoxTable &boxes, int step, float2 *hist_row, float2 hist_val, hipStream_t s) {
+    const int ty0 = w.y0 / TS, tx0 = w.x0 / TS, nty = tiles_of(w.y0 + w.wh) - ty0, ntx = tiles_of(w.x0 + w.ww) - tx0;
+    hipLaunchKernelGGL(mark_tiles_k, dim3((w.D * nty * ntx + 255) / 256), dim3(256), 0, s, w.last_step, tiles_of(w.Hs), tiles_of(w.Ws), ty0, tx0, nty, ntx,
+                       w.D, step, boxes, hist_row, hist_val);
+}
+
+// the step of a checked window from its compact gradient, then the tile marks (which also put the step's scalars into hist[step]).
+// dyn_stepped: the device-side flag of vl3d_render_bwd_adam's plan (adam_window_step_k), NULL for the plain step
+int launch_window_step(const vl3d_adam_window &w, const float *grad_compact, int static_tied, const int *dyn_stepped, hipStream_t s) {
+    const float2 sc = adam_step_scalars(w.lr, w.beta1, w.beta2, w.step);
+    const BoxTable boxes = make_boxes(w.plane_boxes, w.D);
+    hipLaunchKernelGGL(adam_window_step_k, dim3((w.ww + 63) / 64, (w.wh + 3) / 4, w.D), dim3(256), 0, s, w.T, w.Hs, w.Ws, Win{w.y0, w.x0, w.wh, w.ww},
+                       f4(w.param), reinterpret_cast<const float4 *>(grad_compact), f4(w.exp_avg), f4(w.exp_avg_sq), sc.x, w.beta1, w.beta2, w.eps, sc.y,
+                       quads_of(w), static_tied, w.last_step, tiles_of(w.Hs), tiles_of(w.Ws), reinterpret_cast<const float2 *>(w.hist), (int)w.step,
+                       boxes, Layout{w.blocks}, dyn_stepped);
+    launch_mark_tiles(w, boxes, (int)w.step, reinterpret_cast<float2 *>(const_cast<float *>(w.hist)) + w.step, sc, s);
+    VL3D_CHECK_LAUNCH();
     return VL3D_OK;
 }
 
@@ -347,134 +390,74 @@ extern "C" int vl3d_packed_unpack_frames(int32_t D, int32_t T, int32_t Hs, int32
 
 extern "C" int32_t vl3d_adam_window_tile(void) { return TS; }
 
-extern "C" int vl3d_adam_flush_older(int32_t D, int32_t T, int32_t Hs, int32_t Ws, float *param, float *exp_avg, float *exp_avg_sq,
-                                     int32_t *last_step, const float *hist, int32_t upto, int32_t min_depth, float beta1, float beta2, float eps,
-                                     const uint8_t *quad_keep, const uint8_t *quad_dyn, int32_t QH, int32_t QW, const int32_t *blocks,
-                                     vl3d_stream_t stream) {
-    VL3D_REQUIRE(D > 0 && D <= 65535 && T > 0 && Hs > 0 && Ws > 0, "vl3d_adam_flush_older: bad dims");
-    VL3D_REQUIRE(!blocks || quad_keep, "vl3d_adam_flush_older: the packed layout belongs to a tile-culled model (quad maps)");
-    VL3D_REQUIRE(param && exp_avg && exp_avg_sq && last_step && hist && upto >= 0 && min_depth >= 1, "vl3d_adam_flush_older: null pointer / bad step");
-    VL3D_REQUIRE(!quad_keep || quad_grid_ok(QH, QW, Hs, Ws), "vl3d_adam_flush_older: bad quad grid");
+extern "C" int vl3d_adam_flush_older(const vl3d_adam_window *w, int32_t upto, int32_t min_depth, vl3d_stream_t stream) {
+    VL3D_REQUIRE(w, "vl3d_adam_flush_older: null adam window");
+    vl3d_adam_window planes = *w;      // the sweep is over the whole planes: the struct's window is not read
+    planes.y0 = planes.x0 = 0; planes.wh = w->Hs; planes.ww = w->Ws;
+    int rc = check_adam_window(planes, "vl3d_adam_flush_older");
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(upto >= 0 && min_depth >= 1, "vl3d_adam_flush_older: bad step / depth");
     static_assert(TS * TS == 64, "one wave per bookkeeping tile");
-    const int tiles_y = (Hs + TS - 1) / TS, tiles_x = (Ws + TS - 1) / TS;
-    hipLaunchKernelGGL(adam_flush_older_k, dim3(tiles_y * tiles_x, D), dim3(64), 0, (hipStream_t)stream, T, Hs, Ws, reinterpret_cast<float4 *>(param),
-                       reinterpret_cast<float4 *>(exp_avg), reinterpret_cast<float4 *>(exp_avg_sq), last_step, tiles_y, tiles_x,
-                       reinterpret_cast<const float2 *>(hist), upto, min_depth, beta1, beta2, eps, make_quads(quad_keep, quad_dyn, QH, QW, Hs, Ws), Layout{blocks});
+    const int tiles_y = tiles_of(w->Hs), tiles_x = tiles_of(w->Ws);
+    hipLaunchKernelGGL(adam_flush_older_k, dim3(tiles_y * tiles_x, w->D), dim3(64), 0, (hipStream_t)stream, w->T, w->Hs, w->Ws, f4(w->param), f4(w->exp_avg),
+                       f4(w->exp_avg_sq), w->last_step, tiles_y, tiles_x, reinterpret_cast<const float2 *>(w->hist), upto, min_depth, w->beta1, w->beta2,
+                       w->eps, quads_of(*w), Layout{w->blocks});
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
 }
 
-extern "C" int vl3d_adam_window_catchup_boxes(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                                              float *param, float *exp_avg, float *exp_avg_sq, int32_t *last_step, const float *hist,
-                                              int32_t upto, float beta1, float beta2, float eps, float *compact, const uint8_t *quad_keep,
-                                              const uint8_t *quad_dyn, int32_t QH, int32_t QW, float culled_alpha, int32_t mirror_static,
-                                              const int32_t *plane_boxes, const int32_t *blocks, vl3d_stream_t stream) {
-    int rc = check_window(D, T, Hs, Ws, y0, x0, wh, ww);
-    VL3D_REQUIRE(!blocks || quad_keep, "vl3d_adam_window_catchup: the packed layout belongs to a tile-culled model (quad maps)");
-    if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(param && exp_avg && exp_avg_sq && last_step && hist && upto >= 0, "vl3d_adam_window_catchup: null pointer / negative step");
-    VL3D_REQUIRE(!quad_keep || quad_grid_ok(QH, QW, Hs, Ws), "vl3d_adam_window_catchup: bad quad grid");
-    const BoxTable boxes = make_boxes(plane_boxes, D);
-    const int tiles_y = (Hs + TS - 1) / TS, tiles_x = (Ws + TS - 1) / TS;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(compact ? adam_window_catchup_k<false> : adam_window_catchup_k<true>, dim3((ww + 63) / 64, (wh + 3) / 4, D), dim3(256), 0, s, T, Hs, Ws, Win{y0, x0, wh, ww},
-                       reinterpret_cast<float4 *>(param), reinterpret_cast<float4 *>(exp_avg), reinterpret_cast<float4 *>(exp_avg_sq), last_step,
-                       tiles_y, tiles_x, reinterpret_cast<const float2 *>(hist), upto, beta1, beta2, eps, reinterpret_cast<float4 *>(compact),
-                       make_quads(quad_keep, quad_dyn, QH, QW, Hs, Ws), culled_alpha, mirror_static, compact ? 0 : 1,
-                       boxes, Layout{blocks});
-    if (!compact) {      // a flush writes the replayed state back and marks the tiles; a catch-up for a render only fills the compact copy
-        const int nty = (y0 + wh + TS - 1) / TS - y0 / TS, ntx = (x0 + ww + TS - 1) / TS - x0 / TS;
-        hipLaunchKernelGGL(mark_tiles_k, dim3((D * nty * ntx + 255) / 256), dim3(256), 0, s, last_step, tiles_y, tiles_x, y0 / TS, x0 / TS, nty, ntx, D, upto, boxes);
-    }
-    VL3D_CHECK_LAUNCH();
-    return VL3D_OK;
-}
-
-extern "C" int vl3d_adam_window_catchup(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                                        float *param, float *exp_avg, float *exp_avg_sq, int32_t *last_step, const float *hist,
-                                        int32_t upto, float beta1, float beta2, float eps, float *compact, const uint8_t *quad_keep,
-                                        const uint8_t *quad_dyn, int32_t QH, int32_t QW, float culled_alpha, int32_t mirror_static,
+extern "C" int vl3d_adam_window_catchup(const vl3d_adam_window *w, int32_t upto, float *compact, float culled_alpha, int32_t mirror_static,
                                         vl3d_stream_t stream) {
-    return vl3d_adam_window_catchup_boxes(D, T, Hs, Ws, y0, x0, wh, ww, param, exp_avg, exp_avg_sq, last_step, hist, upto, beta1, beta2, eps,
-                                          compact, quad_keep, quad_dyn, QH, QW, culled_alpha, mirror_static, nullptr, nullptr, stream);
-}
-
-static int window_step_impl(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                            float *param, const float *grad_compact, float *exp_avg, float *exp_avg_sq, int32_t *last_step,
-                            const float *hist, float lr, float beta1, float beta2, float eps, int64_t step,
-                            const uint8_t *quad_keep, const uint8_t *quad_dyn, int32_t QH, int32_t QW, int32_t static_tied,
-                            const int32_t *plane_boxes, const int32_t *blocks, const int *dyn_stepped, void *boxes_dev, hipStream_t s) {
-    int rc = check_window(D, T, Hs, Ws, y0, x0, wh, ww);
-    VL3D_REQUIRE(!blocks || quad_keep, "vl3d_adam_window_step: the packed layout belongs to a tile-culled model (quad maps)");
+    VL3D_REQUIRE(w, "vl3d_adam_window_catchup: null adam window");
+    int rc = check_adam_window(*w, "vl3d_adam_window_catchup");
     if (rc != VL3D_OK) return rc;
-    VL3D_REQUIRE(param && grad_compact && exp_avg && exp_avg_sq && last_step && hist && step >= 1, "vl3d_adam_window_step: null pointer / bad step");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const int tiles_y = (Hs + TS - 1) / TS, tiles_x = (Ws + TS - 1) / TS;
-    const BoxTable boxes = make_boxes(plane_boxes, D);
-    if (boxes_dev && boxes.n) hipLaunchKernelGGL(write_boxes_k, dim3(1), dim3(MAX_BOX_PLANES), 0, s, boxes, reinterpret_cast<int4 *>(boxes_dev));
-    hipLaunchKernelGGL(adam_window_step_k, dim3((ww + 63) / 64, (wh + 3) / 4, D), dim3(256), 0, s, T, Hs, Ws, Win{y0, x0, wh, ww},
-                       reinterpret_cast<float4 *>(param), reinterpret_cast<const float4 *>(grad_compact), reinterpret_cast<float4 *>(exp_avg),
-                       reinterpret_cast<float4 *>(exp_avg_sq), (float)((double)lr / bc1), beta1, beta2, eps, (float)sqrt(bc2),
-                       make_quads(quad_keep, quad_dyn, QH, QW, Hs, Ws), static_tied, last_step, tiles_y, tiles_x,
-                       reinterpret_cast<const float2 *>(hist), (int)step, boxes, Layout{blocks}, dyn_stepped);
-    const int nty = (y0 + wh + TS - 1) / TS - y0 / TS, ntx = (x0 + ww + TS - 1) / TS - x0 / TS;
-    hipLaunchKernelGGL(mark_tiles_k, dim3((D * nty * ntx + 255) / 256), dim3(256), 0, s, last_step, tiles_y, tiles_x, y0 / TS, x0 / TS, nty, ntx, D, (int)step, boxes,
-                       reinterpret_cast<float2 *>(const_cast<float *>(hist)) + step, make_float2((float)((double)lr / bc1), (float)sqrt(bc2)));
+    VL3D_REQUIRE(upto >= 0, "vl3d_adam_window_catchup: negative step");
+    const BoxTable boxes = make_boxes(w->plane_boxes, w->D);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(compact ? adam_window_catchup_k<false> : adam_window_catchup_k<true>, dim3((w->ww + 63) / 64, (w->wh + 3) / 4, w->D), dim3(256), 0, s,
+                       w->T, w->Hs, w->Ws, Win{w->y0, w->x0, w->wh, w->ww}, f4(w->param), f4(w->exp_avg), f4(w->exp_avg_sq), w->last_step, tiles_of(w->Hs),
+                       tiles_of(w->Ws), reinterpret_cast<const float2 *>(w->hist), upto, w->beta1, w->beta2, w->eps, f4(compact), quads_of(*w), culled_alpha,
+                       mirror_static, compact ? 0 : 1, boxes, Layout{w->blocks});
+    // a flush writes the replayed state back and marks the tiles; a catch-up for a render only fills the compact copy
+    if (!compact) launch_mark_tiles(*w, boxes, upto, nullptr, make_float2(0.f, 0.f), s);
     VL3D_CHECK_LAUNCH();
     return VL3D_OK;
 }
 
-extern "C" int vl3d_adam_window_step_boxes(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                                           float *param, const float *grad_compact, float *exp_avg, float *exp_avg_sq, int32_t *last_step,
-                                           const float *hist, float lr, float beta1, float beta2, float eps, int64_t step,
-                                           const uint8_t *quad_keep, const uint8_t *quad_dyn, int32_t QH, int32_t QW, int32_t static_tied,
-                                           const int32_t *plane_boxes, const int32_t *blocks, vl3d_stream_t stream) {
-    return window_step_impl(D, T, Hs, Ws, y0, x0, wh, ww, param, grad_compact, exp_avg, exp_avg_sq, last_step, hist, lr, beta1, beta2, eps, step,
-                            quad_keep, quad_dyn, QH, QW, static_tied, plane_boxes, blocks, nullptr, nullptr, (hipStream_t)stream);
+extern "C" int vl3d_adam_window_step(const vl3d_adam_window *w, const float *grad_compact, int32_t static_tied, vl3d_stream_t stream) {
+    VL3D_REQUIRE(w, "vl3d_adam_window_step: null adam window");
+    int rc = check_adam_window(*w, "vl3d_adam_window_step");
+    if (rc != VL3D_OK) return rc;
+    VL3D_REQUIRE(grad_compact && w->step >= 1, "vl3d_adam_window_step: null gradient / bad step");
+    return launch_window_step(*w, grad_compact, static_tied, nullptr, (hipStream_t)stream);
 }
 
-// (vl3d_adam.h) the tail of vl3d_render_bwd_adam.  Called BEFORE the render kernels with grad_compact == NULL: only the checks and the box
-// table onto the device (boxes_dev); called after them: the step of what the backward left + the tile marks.
-int vl3d_adam_window_step_tail(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww, float *param,
-                               const float *grad_compact, float *exp_avg, float *exp_avg_sq, int32_t *last_step, const float *hist, float lr,
-                               float beta1, float beta2, float eps, int64_t step, const uint8_t *quad_keep, const uint8_t *quad_dyn, int32_t QH,
-                               int32_t QW, const int32_t *plane_boxes, const int32_t *blocks, const int *plan_ok, void *boxes_dev,
-                               hipStream_t stream) {
-    if (!grad_compact) {
-        int rc = check_window(D, T, Hs, Ws, y0, x0, wh, ww);
-        if (rc != VL3D_OK) return rc;
-        VL3D_REQUIRE(!plane_boxes || (boxes_dev && D <= MAX_BOX_PLANES), "vl3d_render_bwd_adam: per-plane boxes need boxes_scratch and at most 128 planes");
-        VL3D_REQUIRE(!quad_keep || quad_grid_ok(QH, QW, Hs, Ws), "vl3d_render_bwd_adam: bad quad grid");
-        if (plane_boxes) {
-            const BoxTable boxes = make_boxes(plane_boxes, D);
-            for (int d = 0; d < D; ++d) {
-                const int4 b = boxes.b[d];
-                if (b.y <= b.x || b.w <= b.z) continue;      // an empty box: nothing of this plane is stepped
-                VL3D_REQUIRE(b.x % TS == 0 && b.z % TS == 0 && b.x >= y0 && b.z >= x0 && b.y <= y0 + wh && b.w <= x0 + ww &&
-                                 (b.y % TS == 0 || b.y == Hs) && (b.w % TS == 0 || b.w == Ws),
-                             "vl3d_render_bwd_adam: plane boxes must be aligned to the bookkeeping tiles and lie inside the window");
-            }
-            hipLaunchKernelGGL(write_boxes_k, dim3(1), dim3(MAX_BOX_PLANES), 0, stream, boxes, reinterpret_cast<int4 *>(boxes_dev));
-            VL3D_CHECK_LAUNCH();
-        }
-        return VL3D_OK;
+// (vl3d_adam.h) vl3d_render_bwd_adam, before its render kernels: the window checks, the per-plane boxes validated and onto the device
+int vl3d_adam_window_before_render(const vl3d_adam_window &w, hipStream_t stream) {
+    int rc = check_adam_window(w, "vl3d_render_bwd_adam");
+    if (rc != VL3D_OK || !w.plane_boxes) return rc;
+    VL3D_REQUIRE(w.boxes_scratch && w.D <= MAX_BOX_PLANES, "vl3d_render_bwd_adam: per-plane boxes need boxes_scratch and at most 128 planes");
+    const BoxTable boxes = make_boxes(w.plane_boxes, w.D);
+    for (int d = 0; d < w.D; ++d) {
+        const int4 b = boxes.b[d];
+        if (b.y <= b.x || b.w <= b.z) continue;      // an empty box: nothing of this plane is stepped
+        VL3D_REQUIRE(b.x % TS == 0 && b.z % TS == 0 && b.x >= w.y0 && b.z >= w.x0 && b.y <= w.y0 + w.wh && b.w <= w.x0 + w.ww &&
+                         (b.y % TS == 0 || b.y == w.Hs) && (b.w % TS == 0 || b.w == w.Ws),
+                     "vl3d_render_bwd_adam: plane boxes must be aligned to the bookkeeping tiles and lie inside the window");
     }
-    return window_step_impl(D, T, Hs, Ws, y0, x0, wh, ww, param, grad_compact, exp_avg, exp_avg_sq, last_step, hist, lr, beta1, beta2, eps, step,
-                            quad_keep, quad_dyn, QH, QW, 0, plane_boxes, blocks, plan_ok, nullptr, stream);
+    hipLaunchKernelGGL(write_boxes_k, dim3(1), dim3(MAX_BOX_PLANES), 0, stream, boxes, reinterpret_cast<int4 *>(w.boxes_scratch));
+    VL3D_CHECK_LAUNCH();
+    return VL3D_OK;
 }
 
-extern "C" int vl3d_adam_window_step(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
-                                     float *param, const float *grad_compact, float *exp_avg, float *exp_avg_sq, int32_t *last_step,
-                                     const float *hist, float lr, float beta1, float beta2, float eps, int64_t step,
-                                     const uint8_t *quad_keep, const uint8_t *quad_dyn, int32_t QH, int32_t QW, int32_t static_tied,
-                                     vl3d_stream_t stream) {
-    return vl3d_adam_window_step_boxes(D, T, Hs, Ws, y0, x0, wh, ww, param, grad_compact, exp_avg, exp_avg_sq, last_step, hist, lr, beta1, beta2,
-                                       eps, step, quad_keep, quad_dyn, QH, QW, static_tied, nullptr, nullptr, stream);
+// (vl3d_adam.h) ... and behind them, under the plan's device-side flag: the step of what the backward left, then the tile marks
+int vl3d_adam_window_behind_render(const vl3d_adam_window &w, const float *grad_compact, const int *plan_ok, hipStream_t stream) {
+    return launch_window_step(w, grad_compact, 0, plan_ok, stream);
 }
 
-// the per-step scalars of the table, computed exactly like vl3d_adam_window_step / vl3d_adam_step_tiles compute theirs
+// the per-step scalars of the table, computed exactly like vl3d_adam_window_step / vl3d_render_bwd_adam compute theirs
 extern "C" void vl3d_adam_step_scalars(float lr, float beta1, float beta2, int64_t step, float *lr_bc1, float *bc2s) {
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    *lr_bc1 = (float)((double)lr / bc1);
-    *bc2s = (float)sqrt(bc2);
+    const float2 sc = adam_step_scalars(lr, beta1, beta2, step);
+    *lr_bc1 = sc.x;
+    *bc2s = sc.y;
 }

@@ -361,6 +361,24 @@ static int check_adam_desc(const vl3d_render_desc *desc, bool has_quad_map) {
     return VL3D_OK;
 }
 
+// what the owner's fused store needs of a (checked) adam window: its state, geometry and the scalars of its step
+static vl3d_adam_epilogue adam_epilogue_of(const vl3d_adam_window &w) {
+    const int ts = vl3d_adam::TS;
+    const float2 sc = vl3d_adam::adam_step_scalars(w.lr, w.beta1, w.beta2, w.step);
+    vl3d_adam_epilogue e{};
+    e.p = reinterpret_cast<float4 *>(w.param); e.m = reinterpret_cast<float4 *>(w.exp_avg); e.v = reinterpret_cast<float4 *>(w.exp_avg_sq);
+    e.last_step = w.last_step;
+    e.boxes = (w.plane_boxes && w.D <= 128) ? reinterpret_cast<const int4 *>(w.boxes_scratch) : nullptr;
+    e.y0 = w.y0; e.x0 = w.x0; e.Hs = w.Hs; e.Ws = w.Ws;
+    e.tiles_y = (w.Hs + ts - 1) / ts; e.tiles_x = (w.Ws + ts - 1) / ts;
+    e.step = (int)w.step;
+    e.lr_bc1 = sc.x; e.beta1 = w.beta1; e.beta2 = w.beta2; e.eps = w.eps; e.bc2s = sc.y;
+    e.quad_dyn = w.quad_keep ? w.quad_dyn : nullptr;
+    e.cls = w.quad_keep ? reinterpret_cast<uint2 *>(w.class_scratch) : nullptr;
+    e.blocks = w.blocks;
+    return e;
+}
+
 extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *stack, const float *homos, const float *rgb, const float *alpha,
                                     const float *grad_rgb, const float *grad_alpha, const float *grad_reg, const void *reg_state,
                                     const float *grad_alpha_sums, float *grad_stack, void *scratch, int64_t scratch_bytes,
@@ -394,11 +412,10 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
         VL3D_REQUIRE(desc->cull_Hs == adam->Hs && desc->cull_Ws == adam->Ws && desc->cull_row0 == adam->y0 && desc->cull_col0 == adam->x0,
                      "vl3d_render_bwd_adam: desc->cull_* must name the optimiser's window (y0, x0) of its (Hs, Ws) planes");
     }
+    VL3D_REQUIRE(adam->D == desc->D && adam->T == desc->T && adam->wh == desc->Hs && adam->ww == desc->Ws,
+                 "vl3d_render_bwd_adam: the adam window's D, T, wh, ww must be desc->D, desc->T, desc->Hs, desc->Ws (the stack is the window's compact copy)");
     hipStream_t s = (hipStream_t)stream;
-    // window / box checks and the box table on the device (the tail with a NULL gradient does exactly that)
-    rc = vl3d_adam_window_step_tail(desc->D, desc->T, adam->Hs, adam->Ws, adam->y0, adam->x0, desc->Hs, desc->Ws, adam->param, nullptr,
-                                    adam->exp_avg, adam->exp_avg_sq, adam->last_step, adam->hist, adam->lr, adam->beta1, adam->beta2, adam->eps,
-                                    adam->step, qk, adam->quad_dyn, adam->QH, adam->QW, adam->plane_boxes, adam->blocks, nullptr, adam->boxes_scratch, s);
+    rc = vl3d_adam_window_before_render(*adam, s);
     if (rc != VL3D_OK) return rc;
     RenderArgs a = render_args_of(desc);
     set_bwd_io(a, desc, stack, homos, rgb, alpha, grad_rgb, grad_alpha, grad_reg, reg_state, grad_alpha_sums, grad_stack);
@@ -406,26 +423,10 @@ extern "C" int vl3d_render_bwd_adam(const vl3d_render_desc *desc, const void *st
     set_cull_geometry(a, desc, adam->QH, adam->QW);
     a.grad_culled_unwritten = qk ? 1 : 0;
     set_bwd_setting(a, desc, bwd_setting_of(VL3D_BWD_ENTRY_ADAM, desc->variant & 0xf, true, qk != nullptr), scratch);
-    const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step), bc2 = 1.0 - pow((double)adam->beta2, (double)adam->step);
-    const int ts = vl3d_adam::TS;
-    a.ad.p = reinterpret_cast<float4 *>(adam->param); a.ad.m = reinterpret_cast<float4 *>(adam->exp_avg);
-    a.ad.v = reinterpret_cast<float4 *>(adam->exp_avg_sq);
-    a.ad.last_step = adam->last_step;
-    a.ad.boxes = (adam->plane_boxes && desc->D <= 128) ? reinterpret_cast<const int4 *>(adam->boxes_scratch) : nullptr;
-    a.ad.y0 = adam->y0; a.ad.x0 = adam->x0; a.ad.Hs = adam->Hs; a.ad.Ws = adam->Ws;
-    a.ad.tiles_y = (adam->Hs + ts - 1) / ts; a.ad.tiles_x = (adam->Ws + ts - 1) / ts;
-    a.ad.step = (int)adam->step;
-    a.ad.lr_bc1 = (float)((double)adam->lr / bc1); a.ad.beta1 = adam->beta1; a.ad.beta2 = adam->beta2; a.ad.eps = adam->eps;
-    a.ad.bc2s = (float)sqrt(bc2);
-    a.ad.quad_dyn = qk ? adam->quad_dyn : nullptr;
-    a.ad.cls = qk ? reinterpret_cast<uint2 *>(adam->class_scratch) : nullptr;
-    a.ad.blocks = adam->blocks;
+    a.ad = adam_epilogue_of(*adam);
     rc = dispatch(true, desc, a, s);
     if (rc != VL3D_OK) return rc;
     // behind the backward, under the plan's device-side flag: nothing more (dense, feasible) / the static texels (tile-culled, feasible) / the
     // whole window from the atomics kernel's gradient (infeasible view); the tiles are marked either way
-    return vl3d_adam_window_step_tail(desc->D, desc->T, adam->Hs, adam->Ws, adam->y0, adam->x0, desc->Hs, desc->Ws, adam->param, grad_stack,
-                                      adam->exp_avg, adam->exp_avg_sq, adam->last_step, adam->hist, adam->lr, adam->beta1, adam->beta2, adam->eps,
-                                      adam->step, qk, adam->quad_dyn, adam->QH, adam->QW, adam->plane_boxes, adam->blocks,
-                                      reinterpret_cast<const int *>(scratch), nullptr, s);
+    return vl3d_adam_window_behind_render(*adam, grad_stack, reinterpret_cast<const int *>(scratch), s);
 }

@@ -20,6 +20,7 @@ kernel behind the backward sums it over the frames (static texels only).  `loss.
 learning rate is the group's at the time of the backward (train_3dvid.py:263-277 sets it before the iteration).  The parameters are bit
 for bit those of the two-kernel path.  Contract: one backward per window_leaf(), nothing else reads the leaf's gradient (it stays None).
 """
+import collections
 import ctypes as C
 import warnings
 
@@ -85,6 +86,13 @@ def crop_window(spec, Hs, Ws, homos, H, W, margin=3, per_plane=False):
     return win, boxes
 
 
+# the windowed forward since the last step: its window (y0, x0, wh, ww), the compact leaf, the per-plane boxes (host int32 [D,4] or None)
+Pending = collections.namedtuple("Pending", "window leaf boxes")
+# ... and where it stands: OPEN (its step is still to be taken), STEPPED (the fused backward took it: step() is housekeeping), MULTIPLE (a second
+# windowed forward came before the step: step() refuses)
+OPEN, STEPPED, MULTIPLE = "open", "stepped", "multiple"
+
+
 class WindowAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, quad_keep=None, quad_dyn=None, culled_alpha=-1e4, max_defer=32, layout=None,
                  lean_window=True, fused_backward=False, tile=None):
@@ -103,7 +111,8 @@ class WindowAdam(torch.optim.Optimizer):
         if len(ps) != 1:
             raise RuntimeError("WindowAdam drives exactly one parameter: the plane stack (D,T,Hs,Ws,4)")
         self.p = ps[0]
-        self.pending = None          # (window, compact leaf) of the forward since the last step
+        self.pending = None          # Pending of the forward since the last step
+        self.pending_state = OPEN
         self.t = 0
         # packed.PackedLayout: the parameter is the pool of 8 x 8-texel blocks of a tile-culled model (static blocks once, dynamic blocks
         # per frame, culled blocks not at all) instead of the dense (D,T,Hs,Ws,4) stack; moments live in pools of the same shape
@@ -133,9 +142,6 @@ class WindowAdam(torch.optim.Optimizer):
             return self.layout.D, self.layout.T, self.layout.Hs, self.layout.Ws
         return tuple(self.p.shape[:4])
 
-    def _blocks(self):
-        return None if self.layout is None else L.ptr(self.layout.blocks)
-
     def _st(self):
         p = self.p
         L.check_cuda(p)
@@ -154,25 +160,48 @@ class WindowAdam(torch.optim.Optimizer):
             st["hist"] = torch.zeros((1024, 2), dtype=torch.float32, device=p.device)
         return st
 
-    def _quads(self):
+    def _window_struct(self, window, boxes=None, step=0):
+        """-> L.AdamWindow (include/vl3d.h vl3d_adam_window) of `window` = (y0, x0, wh, ww) with the per-plane boxes (host int32 [D,4] or None):
+        model, state, hyper-parameters, quad maps, packed layout.  `step`: the step about to be taken (the catch-up and the flush do not read it).
+        The struct carries references to everything its addresses point into: hold IT until the call has returned."""
+        st, p = self._st(), self.p
+        grp = self.param_groups[0]
+        aw = L.AdamWindow()
+        aw.D, aw.T, aw.Hs, aw.Ws = self.dims()
+        aw.y0, aw.x0, aw.wh, aw.ww = window
+        aw.param, aw.exp_avg, aw.exp_avg_sq = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        aw.last_step, aw.hist = st["last_step"].data_ptr(), st["hist"].data_ptr()
+        aw.beta1, aw.beta2 = grp["betas"]
+        aw.lr, aw.eps, aw.step = float(grp["lr"]), float(grp["eps"]), int(step)
+        if boxes is not None and aw.D <= 128:      # (more planes than the kernels' table holds: the whole window for every plane)
+            aw.plane_boxes = boxes.ctypes.data
         qk, qd = self.quad_keep, self.quad_dyn
-        sgn = -1 if self.tile is not None else 1
-        return L.ptr(qk), L.ptr(qd), (0 if qk is None else sgn * qk.shape[1]), (0 if qk is None else sgn * qk.shape[2])
+        if qk is not None:
+            sgn = -1 if self.tile is not None else 1      # the tile-exact layout travels as a NEGATIVE quad grid
+            aw.quad_keep, aw.QH, aw.QW = qk.data_ptr(), sgn * qk.shape[1], sgn * qk.shape[2]
+            aw.quad_dyn = None if qd is None else qd.data_ptr()
+        if self.layout is not None:
+            aw.blocks = self.layout.blocks.data_ptr()
+        aw.refs = (p, st["exp_avg"], st["exp_avg_sq"], st["last_step"], st["hist"], boxes, qk, qd, self.layout)
+        return aw
+
+    def _grown(self, name, need, dtype, alloc=None, zero=False):
+        """the persistent buffer self.<name> with at least `need` elements on the parameter's device, grown on demand to `alloc` elements (default:
+        an eighth of headroom -- the windows of a pyramid level's crops differ by a few bookkeeping tiles, and every growth is a multi-GB hipMalloc in
+        the middle of training: usually 2 ms, on some boxes 1.2 s, docs/measurement_log.md, round 6)"""
+        buf, dev = getattr(self, name), self.p.device
+        if buf is None or buf.numel() < need or buf.device != dev:
+            setattr(self, name, None)                                          # (release before growing)
+            buf = (torch.zeros if zero else torch.empty)(need + need // 8 if alloc is None else alloc, dtype=dtype, device=dev)
+            setattr(self, name, buf)
+        return buf
 
     def _catchup(self, window, upto, compact, mirror=False, boxes=None, lean=False):
-        st, p = self._st(), self.p
-        D, T, Hs, Ws = self.dims()
-        y0, x0, wh, ww = window
-        b1, b2 = self.param_groups[0]["betas"]
-        qk, qd, QH, QW = self._quads()
-        with torch.cuda.device(p.device):
-            L.check(L.lib().vl3d_adam_window_catchup_boxes(D, T, Hs, Ws, y0, x0, wh, ww, L.ptr(p), L.ptr(st["exp_avg"]),
-                                                           L.ptr(st["exp_avg_sq"]), L.ptr(st["last_step"]), L.ptr(st["hist"]), int(upto),
-                                                           float(b1), float(b2), float(self.param_groups[0]["eps"]), L.ptr(compact), qk, qd,
-                                                           QH, QW, self.culled_alpha, (1 if mirror else 0) | (2 if lean else 0),
-                                                           None if boxes is None else boxes.ctypes.data,
-                                                           self._blocks(), L.stream_ptr(p.device)),
-                    "vl3d_adam_window_catchup")
+        aw = self._window_struct(window, boxes)
+        dev = self.p.device
+        with torch.cuda.device(dev):
+            L.check(L.lib().vl3d_adam_window_catchup(C.byref(aw), int(upto), L.ptr(compact), self.culled_alpha, (1 if mirror else 0) | (2 if lean else 0),
+                                                     L.stream_ptr(dev)), "vl3d_adam_window_catchup")
 
     # ---- forward side ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -190,17 +219,12 @@ class WindowAdam(torch.optim.Optimizer):
             plane_boxes = np.ascontiguousarray(np.asarray(plane_boxes, dtype=np.int32).reshape(D, 4))
         if self.lean_window:
             n = D * T * wh * ww * 4
-            if self._compact_buf is None or self._compact_buf.numel() < n or self._compact_buf.device != p.device:
-                self._compact_buf = None                                       # (release before growing)
-                # (an eighth of headroom: the windows of a pyramid level's crops differ by a few bookkeeping tiles, and every growth is a multi-GB
-                # hipMalloc in the middle of training -- usually 2 ms, on some boxes 1.2 s: docs/measurement_log.md, round 6)
-                self._compact_buf = torch.zeros(n + n // 8, dtype=p.dtype, device=p.device)
-            compact = self._compact_buf[:n].view(D, T, wh, ww, 4)
+            compact = self._grown("_compact_buf", n, p.dtype, zero=True)[:n].view(D, T, wh, ww, 4)
         else:
             compact = torch.empty((D, T, wh, ww, 4), dtype=p.dtype, device=p.device)
         self._catchup(window, self.t, compact, boxes=plane_boxes, lean=self.lean_window)
         compact.requires_grad_(True)
-        if self._stepped(self.pending):
+        if self.pending_state == STEPPED:
             # the previous backward took its step and step() was not called since: legal (step() is housekeeping only then), but the caller
             # should know that nothing accumulates -- every backward of a fused window is one Adam step
             self._check_stepped_leaf(self.pending)
@@ -208,21 +232,17 @@ class WindowAdam(torch.optim.Optimizer):
                 self._warned_no_step = True
                 warnings.warn("WindowAdam(fused_backward=True): a second windowed forward before optimizer.step() -- each loss.backward() has "
                               "already applied its own Adam step (no gradient accumulation on this path)", RuntimeWarning, stacklevel=3)
-            self.pending = None
+            self.pending, self.pending_state = None, OPEN
         if self.pending is not None:
-            self.pending = "multiple"
+            self.pending_state = MULTIPLE
         else:
-            self.pending = (window, compact, plane_boxes)
+            self.pending, self.pending_state = Pending(window, compact, plane_boxes), OPEN
         return compact
-
-    @staticmethod
-    def _stepped(pend):
-        return isinstance(pend, tuple) and len(pend) == 2 and pend[0] == "stepped"
 
     @staticmethod
     def _check_stepped_leaf(pend):
         """after a fused backward the window leaf must not hold a gradient: one that arrived through another autograd path would be dropped"""
-        if pend[1].grad is not None:
+        if pend.leaf.grad is not None:
             raise RuntimeError("WindowAdam: the window leaf received a gradient outside the render's fused backward (another autograd path into "
                                "the leaf); that gradient is not part of the step the backward took -- use fused_backward=False for such graphs")
 
@@ -251,7 +271,7 @@ class WindowAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self.pending = None
+        self.pending, self.pending_state = None, OPEN
         st = self.state.get(self.p)
         if st:
             self.t = int(st.pop("step", torch.tensor(0.0)).item())
@@ -263,59 +283,37 @@ class WindowAdam(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none=True):
         super().zero_grad(set_to_none)
-        if isinstance(self.pending, tuple) and self.pending[1].grad is not None:
-            self.pending[1].grad = None
+        if self.pending is not None and self.pending_state != MULTIPLE and self.pending.leaf.grad is not None:
+            self.pending.leaf.grad = None
 
     # ---- the step inside the render's backward -------------------------------------------------------------------------
     def fuses(self, stack, spec):
         """does the backward of a render of `stack` (the pending window leaf?) under `spec` take this optimiser's step itself?"""
         pend = self.pending
-        return (self.fused_backward and isinstance(pend, tuple) and len(pend) == 3 and self._is_leaf(pend, stack) and stack.dtype == torch.float32
+        return (self.fused_backward and self._is_open_leaf(pend, stack) and stack.dtype == torch.float32
                 and (stack.shape[1] >= 2 or self.quad_keep is not None) and spec.coord_mode == "affine" and spec.border == "hardcut" and spec.act_order == "post"
                 and spec.rgb_act == "sigmoid" and spec.alpha_act == "sigmoid" and (int(spec.variant) & 0xf) in ((0, 3, 5) if self.quad_keep is not None else (0,))
                 and not getattr(spec, "uv_noise_seed", 0)       # (add_uv_noise: the atomics backward + the step kernel)
                 and (tuple(getattr(spec, "tile", (0, 0))) == (self.tile or (0, 0))))
 
-    @staticmethod
-    def _is_leaf(pend, stack):
-        return pend[1].data_ptr() == stack.data_ptr() and pend[1].shape == stack.shape
+    def _is_open_leaf(self, pend, stack):
+        return pend is not None and self.pending_state == OPEN and pend.leaf.data_ptr() == stack.data_ptr() and pend.leaf.shape == stack.shape
 
     @torch.no_grad()
     def backward_step(self, desc, stack, homos, rgb, alpha, g_rgb, g_alpha, g_reg, reg_state, g_asum):
         """called by the render's autograd backward (render._RenderPlanes) instead of vl3d_render_bwd: backward + step of the pending window in
         one pass (vl3d_render_bwd_adam).  -> the scratch buffer of the call (its first word: 1 = the owner-computes kernels ran)."""
         pend = self.pending
-        if not (isinstance(pend, tuple) and len(pend) == 3 and self._is_leaf(pend, stack)):
+        if not self._is_open_leaf(pend, stack):
             raise RuntimeError("WindowAdam: the fused backward belongs to the pending window leaf (one backward per window_leaf())")
-        st, p = self._st(), self.p
-        grp = self.param_groups[0]
-        b1, b2 = grp["betas"]
-        t = self._register_step(st, float(grp["lr"]), b1, b2)
-        window, _, boxes = pend
-        D, T, Hs, Ws = self.dims()
-        dev = p.device
-        aw = L.AdamWindow()
-        aw.Hs, aw.Ws, aw.y0, aw.x0 = Hs, Ws, window[0], window[1]
-        aw.param, aw.exp_avg, aw.exp_avg_sq = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-        aw.last_step, aw.hist = st["last_step"].data_ptr(), st["hist"].data_ptr()
-        aw.lr, aw.beta1, aw.beta2, aw.eps, aw.step = float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), t
-        if boxes is not None and D <= 128:
-            if self._boxes_dev is None or self._boxes_dev.device != dev:
-                self._boxes_dev = torch.empty(128 * 4, dtype=torch.int32, device=dev)
-            aw.plane_boxes, aw.boxes_scratch = boxes.ctypes.data, self._boxes_dev.data_ptr()
+        t = self._register_step(self._st())
+        aw = self._window_struct(pend.window, pend.boxes, step=t)
+        dev = self.p.device
+        if aw.plane_boxes:
+            aw.boxes_scratch = self._grown("_boxes_dev", 128 * 4, torch.int32, alloc=128 * 4).data_ptr()
         if self.quad_keep is not None:
             n = int(L.lib().vl3d_render_bwd_adam_class_bytes(desc))
-            if self._class_dev is None or self._class_dev.numel() < n or self._class_dev.device != dev:
-                self._class_dev = None
-                self._class_dev = torch.empty(n, dtype=torch.uint8, device=dev)
-            sgn = -1 if self.tile is not None else 1
-            aw.quad_keep, aw.QH, aw.QW = self.quad_keep.data_ptr(), sgn * self.quad_keep.shape[1], sgn * self.quad_keep.shape[2]
-            aw.quad_dyn = None if self.quad_dyn is None else self.quad_dyn.data_ptr()
-            aw.class_scratch = self._class_dev.data_ptr()
-            if self.layout is not None:
-                aw.blocks = self.layout.blocks.data_ptr()
-        # the compact gradient buffer: static texels of a tile-culled model (summed over the frames by the step kernel behind the backward) and
-        # everything when the device-side plan finds the view infeasible; untouched otherwise (an allocation, no traffic)
+            aw.class_scratch = self._grown("_class_dev", n, torch.uint8, alloc=n).data_ptr()
         if not self._fused_ack:
             self._fused_ack = True
             warnings.warn("WindowAdam(fused_backward=True): loss.backward() APPLIES the Adam update of the rendered window (the optimiser step "
@@ -323,22 +321,18 @@ class WindowAdam(torch.optim.Optimizer):
                           "it (NaN guards, GradScaler) does NOT skip the update.  Pass fused_adam_backward=False to get_optimizer's args for the "
                           "two-kernel path, or call optimizer.acknowledge_fused_backward() to silence this.", RuntimeWarning, stacklevel=2)
         # (buffers of the call kept on the optimiser, grown on demand like the compact window: no allocator traffic inside autograd)
-        if self._gfb is None or self._gfb.numel() < stack.numel() or self._gfb.device != dev:
-            self._gfb = None
-            self._gfb = torch.empty(stack.numel() + stack.numel() // 8, dtype=torch.float32, device=dev)
-        g_fallback = self._gfb[:stack.numel()].view(stack.shape)
+        # the compact gradient buffer: static texels of a tile-culled model (summed over the frames by the step kernel behind the backward) and
+        # everything when the device-side plan finds the view infeasible; untouched otherwise (an allocation, no traffic)
+        g_fallback = self._grown("_gfb", stack.numel(), torch.float32)[:stack.numel()].view(stack.shape)
         with torch.cuda.device(dev):
             nscratch = max(int(L.lib().vl3d_render_bwd_scratch_bytes(desc)), 64)
-            if self._bwd_scratch is None or self._bwd_scratch.numel() * 4 < nscratch or self._bwd_scratch.device != dev:
-                self._bwd_scratch = None
-                self._bwd_scratch = torch.empty((nscratch + nscratch // 8 + 3) // 4, dtype=torch.float32, device=dev)
-            scratch = self._bwd_scratch
+            scratch = self._grown("_bwd_scratch", (nscratch + 3) // 4, torch.float32, alloc=(nscratch + nscratch // 8 + 3) // 4)
             L.check(L.lib().vl3d_render_bwd_adam(desc, L.ptr(stack), L.ptr(homos), L.ptr(rgb), L.ptr(alpha), L.ptr(g_rgb), L.ptr(g_alpha),
                                                  L.ptr(g_reg), L.ptr(reg_state), L.ptr(g_asum), L.ptr(g_fallback), L.ptr(scratch), nscratch,
                                                  C.byref(aw), L.stream_ptr(dev)), "vl3d_render_bwd_adam")
         self.t = t
         self.fused_steps += 1
-        self.pending = ("stepped", pend[1])              # the leaf stays referenced: step() / the next window_leaf() check that nothing else reached it
+        self.pending_state = STEPPED                     # the leaf stays referenced: step() / the next window_leaf() check that nothing else reached it
         return scratch
 
     def reserve(self, window_texels):
@@ -349,36 +343,30 @@ class WindowAdam(torch.optim.Optimizer):
         D, T = self.dims()[:2]
         n = int(D) * int(T) * int(window_texels) * 4
         n += n // 8
-        if self.lean_window and (self._compact_buf is None or self._compact_buf.numel() < n or self._compact_buf.device != p.device):
-            self._compact_buf = None
-            self._compact_buf = torch.zeros(n, dtype=p.dtype, device=p.device)
-        if self.fused_backward and (self._gfb is None or self._gfb.numel() < n or self._gfb.device != p.device):
-            self._gfb = None
-            self._gfb = torch.empty(n, dtype=torch.float32, device=p.device)
+        if self.lean_window:
+            self._grown("_compact_buf", n, p.dtype, alloc=n, zero=True)
+        if self.fused_backward:
+            self._grown("_gfb", n, torch.float32, alloc=n)
 
-    def _register_step(self, st, lr, b1, b2):
-        """the scalars of the step about to be taken into the history table -> its number."""
+    def _register_step(self, st):
+        """room for the scalars of the step about to be taken in the history table -> its number."""
         t = self.t + 1
         if t >= st["hist"].shape[0]:
             st["hist"] = torch.cat([st["hist"], torch.zeros_like(st["hist"])])
-        # (row t itself is written by the step's own launch -- vl3d_adam_window_step* / vl3d_render_bwd_adam put (lr / bc1, sqrt(bc2)) of the step they
+        # (row t itself is written by the step's own launch -- vl3d_adam_window_step / vl3d_render_bwd_adam put (lr / bc1, sqrt(bc2)) of the step they
         # take into hist[step], include/vl3d.h: the 8-byte fill the host issued here was one launch per iteration)
         return t
 
-    def _bound_deferral(self, st, t):
+    def _bound_deferral(self, t):
         # every `every` steps, tiles that have missed max_defer - every steps or more are brought up to date: nothing is ever older than
         # max_defer when its window comes back, and the sweep over the step table (a wave per tile) is paid on one step in `every`
-        p = self.p
-        D, T, Hs, Ws = self.dims()
-        grp = self.param_groups[0]
-        b1, b2 = grp["betas"]
-        qk, qd, QH, QW = self._quads()
         every = max(1, min(8, self.max_defer // 4))
         if self.max_defer > 0 and t >= self.max_defer - every and t % every == 0:
-            with torch.cuda.device(p.device):
-                L.check(L.lib().vl3d_adam_flush_older(D, T, Hs, Ws, L.ptr(p), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), L.ptr(st["last_step"]),
-                                                      L.ptr(st["hist"]), t, max(1, self.max_defer - every), float(b1), float(b2), float(grp["eps"]),
-                                                      qk, qd, QH, QW, self._blocks(), L.stream_ptr(p.device)), "vl3d_adam_flush_older")
+            D, T, Hs, Ws = self.dims()
+            aw = self._window_struct((0, 0, Hs, Ws))
+            dev = self.p.device
+            with torch.cuda.device(dev):
+                L.check(L.lib().vl3d_adam_flush_older(C.byref(aw), t, max(1, self.max_defer - every), L.stream_ptr(dev)), "vl3d_adam_flush_older")
 
     # ---- the step -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -388,47 +376,41 @@ class WindowAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         st, p = self._st(), self.p
-        grp = self.param_groups[0]
-        b1, b2 = grp["betas"]
-        lr, eps = float(grp["lr"]), float(grp["eps"])
-        pending, self.pending = self.pending, None
-        if self._stepped(pending):                        # the backward took the step (fused_backward): housekeeping only
+        pending, state = self.pending, self.pending_state
+        self.pending, self.pending_state = None, OPEN
+        if state == STEPPED:                              # the backward took the step (fused_backward): housekeeping only
             self._check_stepped_leaf(pending)
-            self._bound_deferral(st, self.t)
+            self._bound_deferral(self.t)
             return loss
-        if pending == "multiple":
+        if state == MULTIPLE:
             raise RuntimeError("WindowAdam: two windowed forwards before one step(); accumulate through the dense path (model.stack.grad) instead")
         dense = pending is None
         if dense and p.grad is None:
             return loss                                   # nothing flowed: the step does not count (like torch.optim.Adam)
-        if not dense and pending[1].grad is None:
+        if not dense and pending.leaf.grad is None:
             if p.grad is None:
                 return loss
             dense = True                                   # the graph went around the window leaf
-        t = self._register_step(st, lr, b1, b2)
+        t = self._register_step(st)
         D, T, Hs, Ws = self.dims()
         if dense and self.layout is not None:
             raise RuntimeError("WindowAdam: a packed model trains through its window leaf only (no dense gradient of the pool exists)")
         if dense:        # (the step kernel replays what is outstanding itself: no flush needed first)
             window, g, boxes = (0, 0, Hs, Ws), (p.grad if p.grad.is_contiguous() else p.grad.contiguous()), None
         else:
-            window, g, boxes = pending[0], pending[1].grad, pending[2]
+            window, g, boxes = pending.window, pending.leaf.grad, pending.boxes
             if g.dtype != torch.float32 or tuple(g.shape) != (D, T, window[2], window[3], 4) or not g.is_contiguous():
                 raise RuntimeError(f"WindowAdam: the window leaf's gradient must be contiguous float32 {(D, T, window[2], window[3], 4)}, "
                                    f"got {g.dtype} {tuple(g.shape)}")
             if p.grad is not None:
                 raise RuntimeError("WindowAdam: both the window leaf and the dense parameter received a gradient in one step")
-        y0, x0, wh, ww = window
-        qk, qd, QH, QW = self._quads()
+        aw = self._window_struct(window, boxes, step=t)
         with torch.cuda.device(p.device):
-            L.check(L.lib().vl3d_adam_window_step_boxes(D, T, Hs, Ws, y0, x0, wh, ww, L.ptr(p), L.ptr(g), L.ptr(st["exp_avg"]),
-                                                        L.ptr(st["exp_avg_sq"]), L.ptr(st["last_step"]), L.ptr(st["hist"]), lr, float(b1),
-                                                        float(b2), eps, t, qk, qd, QH, QW,
-                                                        1 if (dense and qk is not None) else 0,  # a dense p.grad of a sparsified model went through the tie hook
-                                                        None if boxes is None else boxes.ctypes.data, self._blocks(), L.stream_ptr(p.device)),
+            # (static_tied: a dense p.grad of a sparsified model went through the tie hook)
+            L.check(L.lib().vl3d_adam_window_step(C.byref(aw), L.ptr(g), 1 if (dense and self.quad_keep is not None) else 0, L.stream_ptr(p.device)),
                     "vl3d_adam_window_step")
         self.t = t
-        self._bound_deferral(st, t)
+        self._bound_deferral(t)
         return loss
 
 

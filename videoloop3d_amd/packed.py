@@ -14,8 +14,8 @@ is dynamic when one of its texels is.  A static texel inside a dynamic block kee
 parameter lives in frame 0, flush() mirrors it), so every number a packed model computes has the dense model's bits.
 
 The HOT PATH does not change: a training iteration renders from the compact, dense copy of the crop's texel window that
-`vl3d_adam_window_catchup` builds (now reading the pool), the backward writes a compact gradient, and `vl3d_adam_window_step` updates the
-pool.  Everything else (evaluation renders of chosen frames, lod, export, checkpoints) goes through `PackedLayout.unpack_*`, plane by plane
+`vl3d_adam_window_catchup` builds (reading the pool through `blocks` of its `vl3d_adam_window` argument), the backward writes a compact gradient,
+and `vl3d_adam_window_step` updates the pool.  Everything else (evaluation renders of chosen frames, lod, export, checkpoints) goes through `PackedLayout.unpack_*`, plane by plane
 or frame by frame: the dense stack never exists."""
 import torch
 
