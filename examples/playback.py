@@ -11,7 +11,11 @@ from it: load time (PNG decode apart), frames / s, and the byte difference of it
 share their borders, so the export resamples them: close, not equal).  `--full`: 720p, D = 32, T = 50.
 `--fps-out R` (default off): also play the spiral RETIMED from the loop's 25 fps to a display of R frames per second, from the clip and from
 the pool -- loop times `render_video.retime(N, R)`, texels interpolated between adjacent frames and across the loop seam
-(`render_frames(..., fractional=True)`): frames / s of both, and whether the two frame sets are equal."""
+(`render_frames(..., fractional=True)`): frames / s of both, and whether the two frame sets are equal.
+`--trim`: every fourth kept quad is made invisible first (alpha logit -12 on the texels it can read) and every second dynamic quad frozen (frame 0
+in every frame) -- synthetic weights have nothing a player cannot show --, then `pool.trimmed()`: its report, whether the trimmed pool's spiral
+equals the pool's, and the viewer package written with and without `quad_maps=` (this model's tiles share their borders, so the package may
+only drop quads): MB, face count, and whether the two opened packages play equal frames."""
 import argparse
 import json
 import os
@@ -25,7 +29,7 @@ import numpy as np
 import torch
 
 
-def run(full=False, outdir=None, dev="cuda:0", fps_out=None):
+def run(full=False, outdir=None, dev="cuda:0", fps_out=None, trim=False):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth, tiles
     from videoloop3d_amd.baked import bake, bake_pool, culled_texel_rgba8, open_viewer_package
@@ -48,6 +52,12 @@ def run(full=False, outdir=None, dev="cuda:0", fps_out=None):
         # a static quad is ONE texture shared by all frames (what training keeps true): frame 0 over every texel no dynamic quad reads
         dyn_t = tiles.quad_to_texel_mask(dyn.to(dev), *model.stack.shape[2:4])
         model.stack.copy_(torch.where(dyn_t[:, None, :, :, None], model.stack.data, model.stack.data[:, :1]))
+        if trim:
+            pick = lambda m, n: (torch.zeros(m.numel(), dtype=torch.bool).index_fill_(0, m.flatten().nonzero()[:, 0][::n], True)).reshape(m.shape)      # noqa: E731
+            invisible, frozen = pick(keep, 4), pick(dyn, 2)
+            fr = tiles.quad_to_texel_mask(frozen.to(dev), *model.stack.shape[2:4])
+            model.stack.copy_(torch.where(fr[:, None, :, :, None], model.stack.data[:, :1], model.stack.data))
+            model.stack.data[..., 3].masked_fill_(tiles.quad_to_texel_mask(invisible.to(dev), *model.stack.shape[2:4])[:, None], -12.0)
     model._set_quad_maps(keep, dyn, dev)
     model.is_sparse = model.has_dyn = True
     sync = torch.cuda.synchronize
@@ -80,6 +90,17 @@ def run(full=False, outdir=None, dev="cuda:0", fps_out=None):
     mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
     out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
     out["pool_frames_equal_baked_frames"] = bool(torch.equal(frames["baked_pool"], frames["baked"]))
+    if trim:
+        sync(); t0 = time.perf_counter()
+        lean = pool.trimmed()
+        sync(); t1 = time.perf_counter()
+        RV.render_frames(model, H, W, ext[:4], intr[:4], rt[:4], baked=lean)      # untimed
+        sync(); t0f = time.perf_counter()
+        lean_frames = RV.render_frames(model, H, W, ext, intr, rt, baked=lean)
+        sync(); dt = time.perf_counter() - t0f
+        out["trim"] = {"seconds": t1 - t0, "report": lean.trim_report, "pool_MB": lean.nbytes / 1e6, "frames_per_s": N / dt,
+                       "frames_equal_the_pools": bool(torch.equal(lean_frames, frames["baked_pool"])),
+                       "made_invisible_quads": int(invisible.sum()), "frozen_dynamic_quads": int(frozen.sum())}
     if fps_out:      # the same spiral shown at another rate: pose i at loop time i * 25 / fps_out
         ts = RV.retime(N, fps_out, 25.0)
         retimed = {}
@@ -119,6 +140,16 @@ def run(full=False, outdir=None, dev="cuda:0", fps_out=None):
                          "tile": list(opened.layout.tile), "planes": opened.layout.D, "frames": N, "frames_per_s": N / dt, "ms_per_frame": dt / N * 1e3,
                          "bytes_differing_from_in_process_pool": int((diff > 0).sum()), "bytes": diff.numel(), "max_level_difference": int(diff.max()),
                          "mean_level_difference": float(diff.float().mean())}
+        if trim:      # the package with the trimmed maps: a lattice model drops quads, its dynamic quads stay dynamic
+            def facts(d, fs):
+                return {"MB": sum(os.path.getsize(f) for f in fs) / 1e6, "faces": sum(1 for line in open(os.path.join(d, "geometry.obj")) if line.startswith("f "))}
+            with tempfile.TemporaryDirectory() as tmp2:
+                lk = lean.quad_keep.bool().cpu()
+                lean_files = save_viewer_package(model, tmp2, poses, intr[:8], np.array([1.0, 100.0]), quad_maps=(lk, lk & dyn))
+                lean_opened = open_viewer_package(tmp2, dev, bg_color="", culled_rgba8=culled_texel_rgba8("sigmoid", "sigmoid"))
+                same_grid = lean_opened.layout.D == opened.layout.D and tuple(lean_opened.quad_keep.shape) == tuple(opened.quad_keep.shape)
+                out["trim"]["package"] = {"without": facts(where, files), "with_quad_maps": facts(tmp2, lean_files),
+                                          "opened_frames_equal": bool(same_grid and torch.equal(lean_opened.render_display(H, W, ext, intr, rt), shown))}
     out["shape"] = f"{H}x{W}, D={D}, T={T}, planes {tuple(model.stack.shape[2:4])}, {float(keep.float().mean()):.0%} of the quads kept, {N} spiral frames"
     return out
 
@@ -128,7 +159,8 @@ if __name__ == "__main__":
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--out", default=None, help="directory for the viewer package (default: a temporary one)")
     ap.add_argument("--fps-out", type=float, default=None, help="also play the spiral retimed from 25 fps to this display rate (default: off)")
+    ap.add_argument("--trim", action="store_true", help="also trim the pool (BakedPool.trimmed) and write the package with its quad maps")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run(a.full, a.out, fps_out=a.fps_out)))
+    print(json.dumps(run(a.full, a.out, fps_out=a.fps_out, trim=a.trim)))

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 
-def run(fit=1500, tune=600, lr_fit=0.1, lr_tune=0.02, dev="cuda:0"):
+def run(fit=1500, tune=600, lr_fit=0.1, lr_tune=0.02, dev="cuda:0", models=None):
+    """`models`: a dict that receives the three trained modules (student, control, treatment) -- profiles/trim_students.py trims their pools"""
     from videoloop3d_amd import evaluations as E
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth
@@ -114,6 +115,8 @@ def run(fit=1500, tune=600, lr_fit=0.1, lr_tune=0.02, dev="cuda:0"):
     out["control"], out["treatment"] = score(control), score(treatment)
     out["iterations_per_s"] = {"post": its_post, "baked": its_baked}
     out["shipped_psnr_gain_of_treatment_over_control_dB"] = out["treatment"]["shipped"]["psnr_dB"] - out["control"]["shipped"]["psnr_dB"]
+    if models is not None:
+        models.update(student=student, control=control, treatment=treatment)
     return out
 
 

@@ -236,6 +236,30 @@ int vl3d_pool_from_atlas_rgba8(int32_t D, int32_t T, int32_t Hs, int32_t Ws, int
                                const uint8_t *dyn_atlas, int32_t Ad_h, int32_t Ad_w, int32_t frame, uint32_t culled_rgba8, uint8_t *pool,
                                vl3d_stream_t stream);
 
+/* Trimming a baked pool (csrc/vl3d_baked_trim.hip; baked.BakedPool.trimmed; docs/kernels/K9_baked_playback.md "Trimming the pool").  The pool
+ * stands for the clip [D][T][Hs][Ws] RGBA8 its table gives (a block without storage reads culled_rgba8).  Over the in-plane texels of that clip:
+ * A = the largest alpha byte of the T frames; show = some texel of the 3 x 3 neighbourhood (clipped to the plane) has A > 0; moves = show and the
+ * texel's four bytes differ between some frame and frame 0.  A stored block none of whose texels shows needs no storage when the alpha byte of
+ * culled_rgba8 is 0; a dynamic block that is kept and none of whose texels moves is one static block holding frame 0.
+ * vl3d_baked_trim_classify: two launches, one wave per block of the table, one lane per texel.  The first writes the texel flags (bit 0 A > 0,
+ * bit 1 "differs from frame 0") as a [D][Hs][Ws] byte map into `scratch` (vl3d_baked_trim_scratch_bytes(D, Hs, Ws) bytes: the map, rounded up to
+ * 256), the second block_slots [D][ceil(Hs/8)][ceil(Ws/8)] int32 = the block's new slot count 0 | 1 | T and texel_class [D][Hs][Ws] bytes (bit 0
+ * show, bit 1 moves).  Texels of a ragged block past the plane's last row / column are not read into either map and write nothing.
+ * vl3d_baked_trim_move: new_blocks is the table of the exclusive scan of block_slots (-1 | start << 1 | (count > 1)), which the caller forms;
+ * one wave per (block, frame) copies the 256 bytes of every slot the new table keeps from pool to new_pool (frame 0 of a block that became static).
+ * Bounds.  The table is trusted as packed.PackedLayout builds it for T frames (as the render entries trust it).  What cannot be crossed whatever it
+ * holds: the block index is below D * ceil(Hs/8) * ceil(Ws/8); an entry -1 is never dereferenced, and an entry whose slots (1, or T for a dynamic
+ * block) would end past n_slots / new_n_slots is read as -1; neighbour reads of the flag map are clamped to the plane; a block of the new table
+ * that is dynamic where the old one is not is not copied.  No LDS, no atomics, one writer per byte: bit-for-bit deterministic; every launch on
+ * `stream`.  VL3D_EINVAL, nothing launched: a NULL pointer (a pool may be NULL with 0 slots), D, T, Hs, Ws < 1, D > 65535, blocks per plane * T
+ * > 2^31 - 5, a misaligned (4 bytes) table or pool, scratch_bytes below the size function's value, texel_class == scratch, new_pool == pool. */
+int64_t vl3d_baked_trim_scratch_bytes(int32_t D, int32_t Hs, int32_t Ws);
+int vl3d_baked_trim_classify(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const int32_t *blocks, const uint8_t *pool, int64_t n_slots,
+                             uint32_t culled_rgba8, void *scratch, int64_t scratch_bytes, int32_t *block_slots, uint8_t *texel_class,
+                             vl3d_stream_t stream);
+int vl3d_baked_trim_move(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const int32_t *blocks, const uint8_t *pool, int64_t n_slots,
+                         const int32_t *new_blocks, uint8_t *new_pool, int64_t new_n_slots, vl3d_stream_t stream);
+
 /* Backward of the above w.r.t. the stack (geometry is not differentiated: MPV.py:354).
  * rgb/alpha are the saved forward outputs; grad_alpha may be NULL (treated as 0).
  * grad_alpha_sums (optional): (T,H,W,2) gradient w.r.t. alpha_sums of the forward.

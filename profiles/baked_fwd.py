@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open|trim] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -36,6 +36,12 @@ texels (the comparison of tests/test_gpu_baked_times.py, bound 1e-5); then the t
 the whole path.  Prints ms per frame (median, min .. max), (b) / (a) -- the condition is (b) median <= (a) median on every storage -- and
 (b) / (c).
 
+The TRIM leg (--legs trim; not part of `all`): BakedPool.trimmed() on the culled pair's model, in whose FLOAT stack, before it is baked, the
+outermost --trim-invisible (0.25) of each plane's kept quads get the alpha logit -12 on the texels they can read and the outermost --trim-frozen
+(0.5) of its dynamic quads repeat frame 0 (the shares of quads and of texels are printed).  The report (blocks, slots, bytes, quads), the ms of
+trimmed() itself (5 calls), then the trimmed pool against the untrimmed one: the run of the whole clip and one path call of the spiral, outputs
+compared bit for bit first, legs alternating round by round; the difference of the medians beside the trimmed leg's own min..max spread.
+
 The OPEN leg (--legs open; not part of `all`; allocates neither stack): the scatter of a viewer package's atlases into the baked pool
 (vl3d_pool_from_atlas_rgba8, baked.open_viewer_package).  The culled pair's quad map in the tile-exact layout (35 x 63 tiles of 21 x 21 texels:
 planes of 735 x 1323), synthetic RGBA8 atlases packed like export._pack_tiles (atlas_grid, row major), resident on the device.  (a) the
@@ -48,6 +54,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
@@ -60,7 +67,9 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open", "trim"])
+ap.add_argument("--trim-invisible", type=float, default=0.25, help="--legs trim: the share of each plane's kept quads (the outermost of its blob) made invisible")
+ap.add_argument("--trim-frozen", type=float, default=0.5, help="--legs trim: the share of each plane's dynamic quads (the outermost) that repeat frame 0")
 ap.add_argument("--poses", type=int, default=120)
 ap.add_argument("--keep", type=float, default=0.165)
 ap.add_argument("--dyn", type=float, default=0.3)
@@ -168,6 +177,36 @@ def culled_model(baked):
     return lay, pool, qk, bp, dense
 
 
+def trim_edit_(stack):
+    """--legs trim: something to trim in the culled pair's model, in the FLOAT stack before it is baked -- per plane the outermost --trim-invisible of
+    the blob's kept quads get the alpha logit -12 (byte 0) on the texels they can read, the outermost --trim-frozen of its dynamic quads repeat
+    frame 0 on theirs.  -> the shares, for the record"""
+    from videoloop3d_amd import tiles
+    keep, dyn = culled_maps()
+    QH, QW = keep.shape[1:]
+    qy, qx = torch.meshgrid(torch.arange(QH, device=dev), torch.arange(QW, device=dev), indexing="ij")
+    invisible, frozen = torch.zeros_like(keep).view(D, -1), torch.zeros_like(keep).view(D, -1)
+    for d in range(D):
+        cy, cx = (7 * d + 3) % QH, (11 * d + 5) % QW      # culled_maps' blob centre and order
+        order = (((qy - cy) * (H / QH)) ** 2 + ((qx - cx) * (W / QW)) ** 2).flatten().argsort(stable=True)
+        n_keep, n_dyn = int(keep[d].sum()), int(dyn[d].sum())
+        invisible[d, order[n_keep - round(a.trim_invisible * n_keep):n_keep]] = True
+        frozen[d, order[n_dyn - round(a.trim_frozen * n_dyn):n_dyn]] = True
+    inv_t = tiles.quad_to_texel_mask(invisible.view(D, QH, QW), H, W)
+    fr_t = tiles.quad_to_texel_mask(frozen.view(D, QH, QW), H, W)
+    for d in range(D):
+        stack[d] = torch.where(fr_t[d, None, :, :, None], stack[d, :1], stack[d])
+        stack[d, ..., 3].masked_fill_(inv_t[d, None], -12.0)
+    return {"invisible_quads_of_kept": float(invisible.sum()) / float(keep.sum()), "frozen_quads_of_dynamic": float(frozen.sum()) / float(dyn.sum()),
+            "invisible_texels_of_kept_texels": float(inv_t.sum()) / float(tiles.quad_to_texel_mask(keep, H, W).sum()),
+            "frozen_texels_of_dynamic_texels": float(fr_t.sum()) / float(tiles.quad_to_texel_mask(dyn, H, W).sum())}
+
+
+if a.legs == "trim":
+    res["trim_model"] = trim_edit_(stack)
+    baked = bake_texels(stack, "sigmoid", "sigmoid")
+    print(f"trim model: the culled pair's map with {res['trim_model']}")
+
 if a.legs in ("all", "culled"):
     del stack
     lay, pool, qk, bp, dense = culled_model(baked)
@@ -190,7 +229,7 @@ if a.legs in ("all", "culled"):
     res["pool_over_dense_culled"] = res["baked_pool"]["ms_median"] / res["baked_culled"]["ms_median"]
     print(f"pool render is {res['pool_over_dense_culled']:.3f}x the dense culled baked render's time (bar: <= 1.05)")
 
-if a.legs in ("path", "display", "times"):
+if a.legs in ("path", "display", "times", "trim"):
     import math
     del stack, out
     N = a.poses
@@ -339,6 +378,48 @@ if a.legs == "times":
             print(f"times [{name:6s}] {k:24s} {med[k] / N:.4f} ms/frame ({min(ms[k]) / N:.4f} .. {max(ms[k]) / N:.4f})", flush=True)
         print(f"times [{name:6s}] (b) / (a) {med['b_times_rgb8'] / med['a_two_paths_lerp_torch']:.3f} -> {'ok' if ok else 'MISSED'}; "
               f"(b) / (c), the cost of the second frame: {med['b_times_rgb8'] / med['c_whole_frame_rgb8']:.3f}", flush=True)
+if a.legs == "trim":
+    # the trimmed pool against the untrimmed one of the same visit: the same kernels with fewer loads.  Outputs first, then the run of the whole clip
+    # and one path call of the spiral, legs alternating
+    del baked, dense
+    times = []
+    for _ in range(5):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        lean = bp.trimmed()
+        torch.cuda.synchronize(); times.append((time.perf_counter() - t0) * 1e3)
+    res["trim"] = {"report": lean.trim_report, "trimmed_ms": {"median": statistics.median(times), "min": min(times), "max": max(times), "calls": len(times)},
+                   "pool_MB": {"before": bp.nbytes / 1e6, "after": lean.nbytes / 1e6}}
+    print(f"trimmed(): {res['trim']['report']}\n  pool {bp.nbytes / 1e6:.1f} -> {lean.nbytes / 1e6:.1f} MB; conversion {statistics.median(times):.2f} ms (min {min(times):.2f}, max {max(times):.2f} of {len(times)})")
+    kwl = dict(quad_keep=lean.quad_keep, culled_rgba8=lean.culled_rgba8)
+    o_a = (torch.empty((T, H, W, 3), device=dev), torch.empty((T, H, W), device=dev))
+    o_b = (torch.empty_like(o_a[0]), torch.empty_like(o_a[1]))
+    render_frame_run_baked_pool(lay, pool, 0, T, homos, H, W, spec, out=o_a, **kwp)
+    render_frame_run_baked_pool(lean.layout, lean.pool, 0, T, homos, H, W, spec, out=o_b, **kwl)
+    same_run = torch.equal(o_a[0], o_b[0]) and torch.equal(o_a[1], o_b[1])
+    covered = float((o_a[1] > 0).float().mean())
+    del o_b
+    p_a = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    p_b = (torch.empty_like(p_a[0]), torch.empty_like(p_a[1]))
+    render_path_baked_pool(lay, pool, cam, ts, path_homos, H, W, spec, out=p_a, **kwp)
+    render_path_baked_pool(lean.layout, lean.pool, cam, ts, path_homos, H, W, spec, out=p_b, **kwl)
+    same_path = torch.equal(p_a[0], p_b[0]) and torch.equal(p_a[1], p_b[1])
+    del p_b
+    res["trim"].update({"run_outputs_bit_equal": same_run, "path_outputs_bit_equal": same_path, "covered_pixels": covered})
+    print(f"outputs bit-equal: run of {T} frames {same_run}, path of {N} poses {same_path}; covered pixels {covered:.3f}")
+    assert same_run and same_path
+    for what, legs in (("run", {"pool": lambda: render_frame_run_baked_pool(lay, pool, 0, T, homos, H, W, spec, out=o_a, **kwp),
+                                "trimmed": lambda: render_frame_run_baked_pool(lean.layout, lean.pool, 0, T, homos, H, W, spec, out=o_a, **kwl)}),
+                       ("path", {"pool": lambda: render_path_baked_pool(lay, pool, cam, ts, path_homos, H, W, spec, out=p_a, **kwp),
+                                 "trimmed": lambda: render_path_baked_pool(lean.layout, lean.pool, cam, ts, path_homos, H, W, spec, out=p_a, **kwl)})):
+        ms, per = ab(legs)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        spread = max(ms["trimmed"]) - min(ms["trimmed"])
+        res["trim"][what] = {k: {"ms_median": med[k], "ms_min": min(ms[k]), "ms_max": max(ms[k])} for k in legs}
+        res["trim"][what].update({"trimmed_minus_pool_ms": med["trimmed"] - med["pool"], "trimmed_leg_spread_ms": spread,
+                                  "within_spread": med["trimmed"] - med["pool"] <= spread})
+        print(f"{what}: pool {med['pool']:.3f} ms (min {min(ms['pool']):.3f}, max {max(ms['pool']):.3f}), trimmed {med['trimmed']:.3f} ms (min {min(ms['trimmed']):.3f}, "
+              f"max {max(ms['trimmed']):.3f}) over {a.rounds} rounds of {per}; trimmed - pool {med['trimmed'] - med['pool']:+.3f} ms, the trimmed leg's spread {spread:.3f} ms")
+
 if a.legs == "open":
     import tempfile
     import time

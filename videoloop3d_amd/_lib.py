@@ -100,6 +100,9 @@ SIGNATURES = {
     "vl3d_render_fwd_baked_pool_times": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, C.POINTER(BakedTimes), _P, _I32, _I32, C.c_uint32, _P,
                                           C.POINTER(BakedOut), _P], C.c_int),
     "vl3d_pool_from_atlas_rgba8": ([_I32] * 8 + [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, C.c_uint32, _P, _P], C.c_int),
+    "vl3d_baked_trim_scratch_bytes": ([_I32, _I32, _I32], C.c_int64),
+    "vl3d_baked_trim_classify": ([_I32] * 4 + [_P, _P, _I64, C.c_uint32, _P, _I64, _P, _P, _P], C.c_int),
+    "vl3d_baked_trim_move": ([_I32] * 4 + [_P, _P, _I64, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_path_cull_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
     "vl3d_render_bwd_scratch_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_render_bwd_adam_class_bytes": ([C.POINTER(RenderDesc)], C.c_int64),

@@ -14,6 +14,8 @@ atlases ACTIVATED, multiplied by 255, clipped and truncated to 8 bits; a player 
                                        the bits of the dense baked render.  256 bytes per slot: a quarter of the float pool.
   display_frames(rgb, alpha, bg, C)    the ONE display rule: a float render -> the uint8 frames a viewer shows (over the background, to8b).
   BakedMPV / BakedPool.render_display  poses in, uint8 frames out: the render kernels store that rule's bytes themselves (`frames8=`).
+  BakedPool.trimmed()                  the pool without what a player provably cannot show: blocks that never show dropped, frozen dynamic blocks
+                                       stored once, quads of alpha byte 0 off the map -- every frame keeps its bits (vl3d_baked_trim_*).
   loop_times(times, T)                 any real playback times -> float32 loop times in [0, T): what `fractional=True` of render_path /
                                        render_display renders, texels interpolated between adjacent frames and across the loop seam.
 """
@@ -271,9 +273,12 @@ class BakedPool(_Baked):
     (0, 0, 0, CULLED_ALPHA).  Other values in culled texels show at ~1e-7 in the float render -- a sample on a tile border can tap the
     neighbouring tile with such a weight -- and not in the uint8 frames (docs/kernels/K9_baked_playback.md, "Culled texels")."""
 
-    def __init__(self, pool, layout, quad_keep, spec, bg_color, camera, culled_rgba8):
+    def __init__(self, pool, layout, quad_keep, spec, bg_color, camera, culled_rgba8, quad_dyn=None):
         self.pool, self.layout, self.quad_keep, self.spec, self.bg_color, self.camera = pool, layout, quad_keep, spec, bg_color, camera
         self.culled_rgba8 = int(culled_rgba8)
+        # quad_dyn [D,QH,QW] uint8 or None: the dynamic quads, where the maker knows them (bake_pool, open_viewer_package, trimmed); the render
+        # does not read it.  trim_report: what trimmed() found (None on every other pool)
+        self.quad_dyn, self.trim_report = quad_dyn, None
 
     @property
     def nbytes(self):
@@ -313,6 +318,86 @@ class BakedPool(_Baked):
             raise IndexError(f"frame index out of range [0, {lay.T})")
         culled = [(self.culled_rgba8 >> (8 * k)) & 0xff for k in range(4)]
         return torch.stack([lay.unpack_plane(self.pool, d, frames, culled=culled) for d in range(lay.D)], 0)
+
+    @torch.no_grad()
+    def trimmed(self):
+        """-> a new BakedPool without what a player provably cannot show (docs/kernels/K9_baked_playback.md "Trimming the pool"): stored blocks
+        none of whose texels shows are dropped from the table, dynamic blocks none of whose texels moves keep frame 0 in one static slot, the
+        slots are renumbered densely in table order, and quads whose readable texels all have alpha byte 0 in every frame leave `quad_keep`.
+        Every frame the result renders has the bits of this pool's frame -- for every selection, sink and tile layout.  The result has a
+        table of its own (a PackedLayout copy), `quad_dyn` (uint8 [D,QH,QW]: kept quads some readable texel of which moves) and `trim_report`;
+        this pool and its tensors are not touched.  A pool on the host is refused: the classification and the move are HIP kernels."""
+        if not self.pool.is_cuda:
+            raise RuntimeError("BakedPool.trimmed: the pool is on the host; the trim runs on the device where the baked model lives and renders")
+        lay = self.layout
+        flags, slots, tclass = trim_classify(lay, self.pool, self.culled_rgba8)
+        size = slots.flatten().long()
+        start = torch.cumsum(size, 0) - size
+        table = torch.where(size > 0, start * 2 + (size > 1).long(), torch.full_like(start, -1)).to(torch.int32).reshape(lay.blocks.shape).contiguous()
+        new = copy.copy(lay)      # D, T, Hs, Ws, tile, quad_grid
+        new.blocks, new._index_cache = table, {}
+        new.n_slots, new.n_static, new.n_dynamic = int(size.sum()), int((size == 1).sum()), int((size > 1).sum())
+        if new.n_slots >= 2 ** 30:
+            raise RuntimeError("packed pool too large for 31-bit slot indices")
+        pool = torch.empty((new.n_slots * 64, 4), dtype=torch.uint8, device=self.pool.device)
+        with torch.cuda.device(self.pool.device):
+            L.check(L.lib().vl3d_baked_trim_move(lay.D, lay.T, lay.Hs, lay.Ws, L.ptr(lay.blocks), L.ptr(self.pool), lay.n_slots, L.ptr(table),
+                                                 L.ptr(pool) if new.n_slots else None, new.n_slots, L.stream_ptr(self.pool.device)), "vl3d_baked_trim_move")
+        QH, QW = (int(v) for v in self.quad_keep.shape[1:])
+        keep0 = self.quad_keep.to(self.pool.device).bool()
+        keep = keep0 & quad_any((flags & 1).bool(), QH, QW, lay.tile)
+        dyn = keep & quad_any((tclass & 2).bool(), QH, QW, lay.tile)
+        out = BakedPool(pool, new, keep.to(torch.uint8).contiguous(), self.spec, self.bg_color, self.camera, self.culled_rgba8,
+                        quad_dyn=dyn.to(torch.uint8).contiguous())
+        e = lay.blocks.flatten()
+        stored, was_dyn = e >= 0, (e >= 0) & ((e & 1) == 1)
+        dyn0 = None if self.quad_dyn is None else (self.quad_dyn.to(self.pool.device).bool() & keep0)
+        out.trim_report = {
+            "blocks_stored": int(stored.sum()), "blocks_dropped": int((stored & (size == 0)).sum()), "blocks_demoted": int((was_dyn & (size == 1)).sum()),
+            "slots_before": int(lay.n_slots), "slots_after": int(new.n_slots), "bytes_before": int(lay.n_slots) * 256, "bytes_after": int(new.n_slots) * 256,
+            "quads_before": int(keep0.sum()), "quads_kept": int(keep.sum()), "quads_dropped": int((keep0 & ~keep).sum()),
+            "quads_dynamic": int(dyn.sum()), "quads_demoted": None if dyn0 is None else int((dyn0 & keep & ~dyn).sum())}
+        return out
+
+
+def quad_any(texel_map, QH, QW, tile=None):
+    """[D,Hs,Ws] bool -> [D,QH,QW] bool: some texel the quad can read is true -- the texels of tiles.quad_to_texel_mask of that quad alone
+    (a quad's closed rectangle grown by one texel on the shared-border lattice; its own th x tw tile in the tile-exact layout).  That mask
+    is a product of a row set and a column set, so the reduction is two small matrix products of 0 / 1 values."""
+    D, Hs, Ws = texel_map.shape
+    dev = texel_map.device
+
+    def members(S, n, t):      # [n, S] float: texel index a of the axis is readable from quad index q
+        a, q = torch.arange(S, device=dev, dtype=torch.int64), torch.arange(n, device=dev, dtype=torch.int64)[:, None]
+        if t:
+            return ((a // t)[None] == q).float()
+        qi = lambda v: torch.div(v * n, max(S - 1, 1), rounding_mode="floor").clamp(0, n - 1)      # noqa: E731  (tiles.quad_to_texel_mask)
+        return ((qi(a - 1)[None] == q) | (qi(a + 1)[None] == q)).float()
+    th, tw = tile if (tile is not None and tile[0]) else (0, 0)
+    cols = (texel_map.float() @ members(Ws, QW, tw).t()) > 0                  # D,Hs,QW
+    return (members(Hs, QH, th) @ cols.float()) > 0                            # D,QH,QW
+
+
+def trim_classify(layout, pool, culled_rgba8):
+    """vl3d_baked_trim_classify on a baked pool -> (flags [D,Hs,Ws] uint8: bit 0 "alpha byte > 0 in some frame", bit 1 "bytes differ from frame
+    0 in some frame"; block_slots int32 like layout.blocks: the block's new slot count 0 | 1 | T; texel_class [D,Hs,Ws] uint8: bit 0 show,
+    bit 1 moves), all on the pool's device.  The flag map is the entry's scratch."""
+    L.check_cuda(pool, layout.blocks)
+    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != 4 or not pool.is_contiguous() or pool.shape[0] != layout.n_slots * 64:
+        raise RuntimeError("trim_classify: a contiguous uint8 pool [n_slots * 64, 4] of the layout")
+    bl = layout.blocks
+    if bl.dtype != torch.int32 or not bl.is_contiguous() or tuple(bl.shape) != (layout.D, -(-layout.Hs // 8), -(-layout.Ws // 8)) or bl.device != pool.device:
+        raise RuntimeError("trim_classify: the layout's block table must be contiguous int32 [D, ceil(Hs/8), ceil(Ws/8)] on the pool's device")
+    dev = pool.device
+    n = int(L.lib().vl3d_baked_trim_scratch_bytes(layout.D, layout.Hs, layout.Ws))
+    scratch = torch.empty((n,), dtype=torch.uint8, device=dev)
+    slots = torch.empty(bl.shape, dtype=torch.int32, device=dev)
+    tclass = torch.empty((layout.D, layout.Hs, layout.Ws), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().vl3d_baked_trim_classify(layout.D, layout.T, layout.Hs, layout.Ws, L.ptr(bl), L.ptr(pool) if layout.n_slots else None,
+                                                 layout.n_slots, int(culled_rgba8) & 0xFFFFFFFF, L.ptr(scratch), n, L.ptr(slots), L.ptr(tclass),
+                                                 L.stream_ptr(dev)), "vl3d_baked_trim_classify")
+    return scratch[:layout.D * layout.Hs * layout.Ws].view(layout.D, layout.Hs, layout.Ws), slots, tclass
 
 
 def culled_texel_rgba8(rgb_act, alpha_act):
@@ -358,7 +443,8 @@ def bake_pool(module):
         for d in range(lay.D):
             lay.pack_plane_(pool, d, bake_texels(stack[d], ra, aa))      # (T,Hs,Ws,4) uint8: one plane at a time, never the clip
     qk = module.quad_keep.to(torch.uint8).contiguous().clone()
-    return BakedPool(pool, lay, qk, module.spec, str(module.args.bg_color), _Camera(module), culled_texel_rgba8(ra, aa))
+    qd = (module.quad_keep.bool() & module.quad_dyn.bool()).to(torch.uint8).contiguous().clone()
+    return BakedPool(pool, lay, qk, module.spec, str(module.args.bg_color), _Camera(module), culled_texel_rgba8(ra, aa), quad_dyn=qd)
 
 
 @torch.no_grad()
@@ -508,4 +594,5 @@ def open_viewer_package(dir, device, bg_color="", culled_rgba8=0):
                     left[h].record()
         torch.cuda.current_stream(dev).synchronize()
     camera, spec = package_camera(pk)
-    return BakedPool(pool, lay, keep.to(dev).to(torch.uint8).contiguous(), spec, str(bg_color), camera, culled_rgba8)
+    return BakedPool(pool, lay, keep.to(dev).to(torch.uint8).contiguous(), spec, str(bg_color), camera, culled_rgba8,
+                     quad_dyn=(keep & dyn).to(dev).to(torch.uint8).contiguous())

@@ -100,9 +100,30 @@ def _pack_tiles(stack, mask, frames, tile_hw, own=False):
     return idx, atlas, uvs, uvfaces, (gh, gw)
 
 
-def reference_state_dict(model, tile_texels=None):
+def check_quad_maps(quad_maps, keep, dyn, own):
+    """quad_maps = (keep', dyn') [D,QH,QW] of an export against the model's maps (bool, host) -> (keep', dyn') bool on the host.  The quads written
+    are the given ones, so they must be subsets: keep' within quad_keep, dyn' within keep' & quad_dyn (a quad of dyn outside dyn' is written from
+    frame 0 into the static atlas) -- else ValueError.  A model of the shared-border lattice (own false) may only drop quads, dyn' == keep' &
+    quad_dyn: its export resamples logits, under which "alpha byte 0" survives (a convex combination of logits below the threshold stays below
+    it) and "equal bytes in every frame" does not."""
+    k, d = (torch.as_tensor(m).detach().cpu().bool() for m in quad_maps)
+    if k.shape != keep.shape or d.shape != keep.shape:
+        raise ValueError(f"quad_maps: two maps of the model's quad grid {tuple(keep.shape)}, got {tuple(k.shape)} and {tuple(d.shape)}")
+    if bool((k & ~keep).any()):
+        raise ValueError("quad_maps: keep holds a quad outside the model's quad_keep (an export writes the model's quads, or fewer)")
+    if bool((d & ~(k & dyn)).any()):
+        raise ValueError("quad_maps: dyn holds a quad outside keep & the model's quad_dyn")
+    if not own and not torch.equal(d, k & dyn):
+        raise ValueError("quad_maps: a model of the shared-border lattice exports resampled logits and may only drop quads (dyn == keep & quad_dyn); "
+                         "writing a dynamic quad from frame 0 needs the tile-exact layout, whose texels are copied")
+    return k, d
+
+
+def reference_state_dict(model, tile_texels=None, quad_maps=None, atlas_to_host=True):
     """model: videoloop3d_amd MPMeshVid / MPMesh (dense or sparsified).  tile_texels=(ih, iw) overrides the tile size (default:
-    one sample per texel of the quad, round(quad extent) + 1, the choice oracle/ckpt_oracle.py pins the reader with)."""
+    one sample per texel of the quad, round(quad extent) + 1, the choice oracle/ckpt_oracle.py pins the reader with).
+    quad_maps=(keep, dyn): write these quads in place of the model's (check_quad_maps: subsets of them; BakedPool.trimmed gives such maps).
+    atlas_to_host=False leaves `atlas` / `atlas_dyn` on the model's device (save_viewer_package bakes them there)."""
     class _Planes:
         """plane accessor: stack[d, :frames] of the dense model without ever holding more than one plane of a packed one."""
         def __init__(self, m):
@@ -138,6 +159,8 @@ def reference_state_dict(model, tile_texels=None):
         dyn = keep.clone()
         if not hasattr(model, "frm_num"):           # ... a dense stage-1 MPI is one static atlas (MPI.py:95-117)
             dyn = torch.zeros_like(keep)
+    if quad_maps is not None:
+        keep, dyn = check_quad_maps(quad_maps, keep, keep & dyn, own)
     faces = quad_faces(D, hv, wv)
     idx_s, atlas_s, uvs_s, uvf_s, (gh_s, gw_s) = _pack_tiles(stack, keep & ~dyn, 1, tile_texels, own)
     idx_d, atlas_d, uvs_d, uvf_d, (gh_d, gw_d) = _pack_tiles(stack, dyn, T, tile_texels, own)
@@ -159,8 +182,8 @@ def reference_state_dict(model, tile_texels=None):
     return {
         "_verts": verts, "planedepth": model.planedepth.detach().cpu().clone(), "ref_extrin": model.ref_extrin.detach().cpu().clone(),
         "ref_intrin": model.ref_intrin.detach().cpu().clone(),
-        "faces": faces[idx_s].reshape(-1, 3), "uvfaces": uvf_s, "uvs": uvs_s.cpu(), "atlas": atlas_s.cpu(),
-        "faces_dyn": faces[idx_d].reshape(-1, 3), "uvfaces_dyn": uvf_d, "uvs_dyn": uvs_d.cpu(), "atlas_dyn": atlas_d.cpu(),
+        "faces": faces[idx_s].reshape(-1, 3), "uvfaces": uvf_s, "uvs": uvs_s.cpu(), "atlas": atlas_s.cpu() if atlas_to_host else atlas_s,
+        "faces_dyn": faces[idx_d].reshape(-1, 3), "uvfaces_dyn": uvf_d, "uvs_dyn": uvs_d.cpu(), "atlas_dyn": atlas_d.cpu() if atlas_to_host else atlas_d,
         "self.is_sparse": sparse, "self.has_dyn": True,
         "self.atlas_grid_h": gh_s, "self.atlas_grid_w": gw_s, "self.atlas_full_h": gh_s * full_hw[0] if gh_s else int(atlas_s.shape[-2]), "self.atlas_full_w": gw_s * full_hw[1] if gw_s else int(atlas_s.shape[-1]),
         "self.atlas_grid_dyn_h": gh_d, "self.atlas_grid_dyn_w": gw_d, "self.atlas_full_dyn_h": gh_d * full_hw[0] if gh_d else int(atlas_d.shape[-2]),
@@ -302,23 +325,32 @@ def _write_viewer_obj(path, sd):
 
 
 @torch.no_grad()
-def save_viewer_package(model, outdir, poses, intrins, bds, fps=25):
+def save_viewer_package(model, outdir, poses, intrins, bds, fps=25, quad_maps=None):
     """scripts/script_export_mesh.py:76-191: the viewer package of `model` (MPMeshVid, dense or sparsified) in `outdir` -- geometry.obj,
     static.png, dynamic/%04d.png, meta.json; poses [V,3,4] camera-to-world, intrins [V,3,3], bds (near, far) as render_video.load_llff_poses
     returns them.  The PNGs are the atlases of reference_state_dict(model) through baked.bake_texels: activated, times 255, clipped, truncated,
-    straight RGBA -- the texels a player filters and baked.BakedMPV renders from.  Returns the paths written."""
+    straight RGBA -- the texels a player filters and baked.BakedMPV renders from.  Returns the paths written.
+    quad_maps=(keep, dyn): the quads written are these (reference_state_dict; the maps of BakedPool.trimmed drop what never shows and write
+    frozen dynamic quads once).  With them, a tile-exact model on the device has its atlases baked THERE (vl3d_bake_rgba8): its tiles are
+    copied texel for texel, so the package holds the bytes of bake_pool(model) -- the bytes the maps were decided on.  Without the keyword
+    nothing changes: the host bake, the model's own maps."""
     import json
     from concurrent.futures import ThreadPoolExecutor
     from .baked import bake_texels
     if hasattr(model, "_flush_deferred_updates"):
         model._flush_deferred_updates()
-    sd = reference_state_dict(model)
+    param = model._param() if hasattr(model, "_param") else getattr(model, "stack", None)
+    on_device = quad_maps is not None and getattr(model, "tile_own", None) is not None and param is not None and param.is_cuda
+    sd = reference_state_dict(model) if quad_maps is None else reference_state_dict(model, quad_maps=quad_maps, atlas_to_host=not on_device)
     if "atlas_dyn" not in sd:
         raise RuntimeError("save_viewer_package: a video model (MPMeshVid) with its dynamic atlas")
     os.makedirs(os.path.join(outdir, "dynamic"), exist_ok=True)
     acts = (model.args.rgb_activate, model.args.alpha_activate)
-    static = bake_texels(sd["atlas"][0].permute(1, 2, 0).float().cpu(), *acts).numpy()
-    frames = bake_texels(sd["atlas_dyn"].permute(0, 2, 3, 1).float().cpu(), *acts).numpy()
+    place = (lambda t: t.contiguous()) if on_device else (lambda t: t.cpu())      # the device rule where the texels lie, else the host rule
+    static = bake_texels(place(sd["atlas"][0].permute(1, 2, 0).float()), *acts).cpu().numpy()
+    frames = bake_texels(place(sd["atlas_dyn"].permute(0, 2, 3, 1).float()), *acts).cpu().numpy()
+    if on_device:
+        sd["atlas"], sd["atlas_dyn"] = sd["atlas"].cpu(), sd["atlas_dyn"].cpu()
     meta = _viewer_meta(poses, intrins, bds, len(frames), fps)
     out = [os.path.join(outdir, "meta.json"), os.path.join(outdir, "geometry.obj"), os.path.join(outdir, "static.png")]
     with open(out[0], "w") as f:
