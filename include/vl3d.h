@@ -586,22 +586,51 @@ typedef struct vl3d_loss_desc {
     float alpha;           /* utils_vid.py:133-134 normaliser offset */
     int64_t x_sc, x_st, x_sr;
     int64_t y_sc, y_st, y_sr;
-    int32_t variant;       /* kernel variant selector for A/B measurements and cross-checks; 0 = default.  Bits 0-3, vl3d_patchnn: 1 strided
-                            * staging (no scratch), 2 one location per workgroup, 4 the vector-ALU kernel, 6 the split-f16 matrix-core kernel
-                            * (0 picks 6 wherever the clip lengths allow it -- x <= 128, y <= 192 frames -- and 4 otherwise); vl3d_vote_fold: 1 = the
-                            * unstaged kernel.  Bits 4-7: refused (ablation switches of a -DVL3D_VARIANTS measurement build).  Bit 8: see vl3d_patchnn.
-                            * Bit 11 (0x800), kernel 6: the workgroup-wide epilogue also without alpha.  Bits 12-15, vl3d_vote_fold*: tile shape index + 1. */
+    int32_t variant;       /* kernel variant selector for A/B measurements and cross-checks; 0 = default.  Bits 0-3, vl3d_patchnn: 2 one location
+                            * per workgroup (1, the removed strided-staging kernel's number, and every value not named here run it too), 4 the
+                            * vector-ALU kernel, 6 the split-f16 matrix-core kernel, 0 the measured default among them -- the rules and their
+                            * limits: choose_patchnn(), csrc/vl3d_patchnn_choice.h; ask vl3d_patchnn_choice(); vl3d_vote_fold: 1 = the unstaged
+                            * kernel.  Bits 4-7: refused (ablation switches of a -DVL3D_VARIANTS measurement build).  Bit 8: see vl3d_patchnn.
+                            * Bit 9 (0x200), staged fold: dynamic covering loops.  Bit 11 (0x800), kernel 6: the workgroup-wide epilogue also
+                            * without alpha.  Bits 12-15, vl3d_vote_fold*: tile shape index + 1 (choose_fold(), same header). */
 } vl3d_loss_desc;
 
-/* bytes of device scratch vl3d_patchnn needs for this problem (0 if none). */
+/* bytes of device scratch vl3d_patchnn / vl3d_patchnn_prepared need for this problem: positive for every valid descriptor. */
 int64_t vl3d_patchnn_scratch_bytes(const vl3d_loss_desc *desc);
+
+/* Which kernel a search or a fold call runs, without running it: the value the entry points themselves compute (the same function, no
+ * device touched, nothing enqueued).  They return what the entry would return for the descriptor and these facts: its descriptor check,
+ * then the chooser's status (VL3D_EINVAL / VL3D_EUNSUPPORTED leave *out zeroed).  entry: which search entry; has_scratch: scratch != NULL;
+ * x_pitch, x_frames: vl3d_patchnn_grams' x clip; y_pitch: the prepared y clip's (both unread at VL3D_NN_ENTRY_PLAIN).  fused: vl3d_vote_fold_robust*. */
+enum { VL3D_NN_ENTRY_PLAIN = 0, VL3D_NN_ENTRY_PREPARED = 1, VL3D_NN_ENTRY_GRAMS = 2 };
+enum { VL3D_NN_LAYOUT_GRAM16 = 1, VL3D_NN_LAYOUT_PIXEL_MAJOR = 2 };
+typedef struct vl3d_nn_choice {
+    int32_t kernel;                        /* 2, 4 or 6: the variant numbers */
+    int32_t tyt, nl, nw, xs, ch;           /* kernel 6: patchnn6_k<tyt, nl, nw, xs>, columns per LDS-DMA stage */
+    int32_t runsum;                        /* kernel 4: patchnn4_k<runsum, threads> */
+    int32_t threads;                       /* workgroup size */
+    int32_t kc;                            /* kernel 2: k terms staged at a time */
+    int32_t lds_bytes;                     /* dynamic LDS of the launch */
+    int32_t scratch_layout;                /* VL3D_NN_LAYOUT_*: the form of x and y the kernel reads (what `scratch` holds) */
+} vl3d_nn_choice;
+int vl3d_patchnn_choice(const vl3d_loss_desc *desc, int32_t entry, int32_t has_scratch, int32_t x_pitch, int32_t x_frames, int32_t y_pitch,
+                        vl3d_nn_choice *out);
+typedef struct vl3d_fold_choice {
+    int32_t staged;                        /* the LDS-staged kernel (else one thread per voxel, vl3d_vote_fold only) */
+    int32_t shape;                         /* staged: row of the tile-shape table, -1 otherwise */
+    int32_t fw, fh, threads;               /* staged: vote_fold_lds_k<fw, fh, threads, nb> */
+    int32_t nb;                            /* staged: fixed-trip covering loops over nb x nb locations (2, 3), 0 = dynamic loops */
+    int32_t lds_bytes;
+} vl3d_fold_choice;
+int vl3d_vote_fold_choice(const vl3d_loss_desc *desc, int32_t fused, vl3d_fold_choice *out);
 
 /* Per spatial location b=(by,bx): dist[i,j] = |Px_i - Py_j|^2 / (3*pt*ps*ps) (utils_vid.py:72-86),
  * optional column-min normalisation (utils_vid.py:109-119,133-134), row argmin, first minimum wins
  * (utils_vid.py:139-141).  nn is int32 [h_o, w_o, n1].  Replaces extract_3Dpatches x2 +
  * get_NN_indices_low_memory (utils_vid.py:209-216).
- * The kernel works on pixel-major copies of x and y kept in `scratch` (their layout belongs to the kernel variant: a scratch filled
- * under one variant is not valid for another).  desc->variant bit 8 (0x100): the y copy in `scratch`
+ * The kernel works on pixel-major copies of x and y kept in `scratch`, vl3d_patchnn_scratch_bytes(desc) bytes (their layout belongs to the
+ * kernel variant: a scratch filled under one variant is not valid for another); scratch == NULL: VL3D_EINVAL -- the kernel that read the
+ * videos in place was removed, and desc->variant 1, its number, runs kernel 2 like every value not named.  desc->variant bit 8 (0x100): the y copy in `scratch`
  * is still valid from the previous call with the same y, configuration and scratch buffer -- skip re-building it (the
  * captured video y is constant over the iterations of a training loop; x, the render, is not). */
 int vl3d_patchnn(const vl3d_loss_desc *desc, const float *x, const float *y, int32_t *nn,
@@ -611,8 +640,9 @@ int vl3d_patchnn(const vl3d_loss_desc *desc, const float *x, const float *y, int
  * vl3d_video_to_gram_major rewrites a whole clip [3,T,H,W] (element strides per channel / frame / row, unit column stride) ONCE into
  * the NN kernel's own form (vl3d_gram_major_bytes(T, H, W) bytes), and vl3d_patchnn_prepared searches against the crop
  * (y_row0, y_col0) + (desc->H, desc->W) of that buffer (rows of y_pitch pixels, y_rows of them; desc->Ty = T) without touching y again
- * -- the y half of the per-iteration layout change (0.4 of the 2.7 ms of a 720p search) leaves the iteration.  Matrix-core kernel only
- * (x <= 128, y <= 192 frames): VL3D_EUNSUPPORTED otherwise, and the caller falls back to vl3d_patchnn.  `scratch` as for vl3d_patchnn. */
+ * -- the y half of the per-iteration layout change (0.4 of the 2.7 ms of a 720p search) leaves the iteration.  Matrix-core kernel only:
+ * VL3D_EUNSUPPORTED outside its range (choose_patchnn(); vl3d_patchnn_choice() tells), and the caller falls back to vl3d_patchnn.  `scratch`
+ * as for vl3d_patchnn. */
 int64_t vl3d_gram_major_bytes(int32_t T, int32_t H, int32_t W);
 int vl3d_video_to_gram_major(const float *y, int64_t sc, int64_t st, int64_t sr, int32_t T, int32_t H, int32_t W, float *out,
                              vl3d_stream_t stream);

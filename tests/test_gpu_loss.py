@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import patchnn_rows as PR
 from oracle import vid_oracle as VO
 from videoloop3d_amd import synth
 from videoloop3d_amd import utils_vid as UV_MOD
@@ -226,8 +227,8 @@ def test_g6_get_nn_indices_low_memory(dev, golden):
 
 @pytest.mark.parametrize("variant", ["1", "2", "6", "0x806", "4"])
 def test_patchnn_kernel_variants_agree(dev, variant, monkeypatch):
-    """v1 (strided staging), v2 (pixel-major staging, one location per workgroup), v4 (four locations per workgroup, VALU direct SSD)
-    and v6 = variant 6 (the same workgroup on the half-precision matrix cores with split operands, |x|^2+|y|^2-2x.y like the reference; the
+    """v2 (pixel-major staging, one location per workgroup; variant 1, the removed strided-staging kernel's number, runs it too), v4 (four
+    locations per workgroup, VALU direct SSD) and v6 = variant 6 (the same workgroup on the half-precision matrix cores with split operands, |x|^2+|y|^2-2x.y like the reference; the
     default where it applies; 0x806: its workgroup-wide epilogue also without alpha instead of the per-wave one) pick the same neighbours up
     to exact-distance near-ties."""
     from videoloop3d_amd.utils_vid import _nn_and_fold
@@ -256,6 +257,26 @@ def test_patchnn_matrix_core_tile_counts(dev, tx, ty, ps, s, alpha, monkeypatch)
     y = synth.make_video(ty, H, W, seed=6)
     sg, wg, nng = _nn_and_fold(x.to(dev), y.to(dev), ps, 3, s, 1, alpha, normalize=False)
     nbad, unexplained = nn_mismatch_is_near_tie(x, y, ps, 3, s, 1, alpha, nng)
+    assert unexplained == 0
+    assert nbad <= nng.numel() // 100
+
+
+@pytest.mark.parametrize("case,reaches", PR.NEW_CASES, ids=["-".join(str(v) for v in inst) for _, inst in PR.NEW_CASES])
+def test_patchnn_instantiations_no_other_test_reaches(dev, case, reaches, monkeypatch):
+    """The rows of the launch tables that no other shape of this module launches (tests/test_patchnn_choice_cpu.py shows that, and that with
+    these every row runs): each row first asks the chooser that it reaches the instantiation it is here for, then the criterion of
+    test_patchnn_matrix_core_tile_counts at its 6 x 10 patch locations."""
+    from videoloop3d_amd.utils_vid import _nn_and_fold, patchnn_choice
+    tx, ty, ps, s, alpha, variant = case
+    monkeypatch.setattr(UV_MOD, "KERNEL_VARIANT", variant)
+    rc, c = patchnn_choice(PR.loss_desc(PR.rows_6x10([case[:5]], variant)[0]))
+    assert rc == 0 and PR.instantiation(c) == reaches
+    H, W = PR.frame(ps, s)
+    x = synth.make_video(tx, H, W, seed=5)
+    y = synth.make_video(ty, H, W, seed=6)
+    sg, wg, nng = _nn_and_fold(x.to(dev), y.to(dev), ps, 3, s, 1, alpha, normalize=False)
+    nbad, unexplained = nn_mismatch_is_near_tie(x, y, ps, 3, s, 1, alpha, nng)
+    print(f"{case} -> {reaches}: {nbad} mismatches of {nng.numel()}, {unexplained} unexplained")
     assert unexplained == 0
     assert nbad <= nng.numel() // 100
 

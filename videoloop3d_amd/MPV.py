@@ -62,7 +62,7 @@ def _resize_tiles(tl, h, w, antialias):
 
 
 class _LoopPrologue(torch.autograd.Function):
-    """MPV.py:484-507 between the render and the loss in three launches (csrc/vl3d_loss.hip `loop_*_k`): loop padding
+    """MPV.py:484-507 between the render and the loss in three launches (csrc/vl3d_loop_prologue.hip `loop_*_k`): loop padding
     `cat(rgb, rgb[:pad])`, the scale-invariant gain `(exp(mean(log((mean_f res + .01) / (mean_t rgb.detach() + .01)))) + 3) / 4` and the
     layout the loss takes, [1,3,T+pad,h,w]; the backward folds the pad frames' gradient back and writes the NHWC gradient the render's
     backward reads.  rgb [T,h,w,3] contiguous float32 CUDA; res [F,3,h,w] or None (no gain)."""

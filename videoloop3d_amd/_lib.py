@@ -79,6 +79,18 @@ BWD_ENTRY = {"render": 0, "mask": 1, "adam": 2}
 BWD_FAMILY = {"atomics": 0, "tile": 1, "pair": 2, "pair12": 3}
 
 
+class NNChoice(C.Structure):         # vl3d_nn_choice: which kernel a patch-NN search runs (vl3d_patchnn_choice)
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "tyt", "nl", "nw", "xs", "ch", "runsum", "threads", "kc", "lds_bytes", "scratch_layout")]
+
+
+class FoldChoice(C.Structure):       # vl3d_fold_choice: which kernel a vote-fold runs (vl3d_vote_fold_choice)
+    _fields_ = [(n, C.c_int32) for n in ("staged", "shape", "fw", "fh", "threads", "nb", "lds_bytes")]
+
+
+NN_ENTRY = {"plain": 0, "prepared": 1, "grams": 2}
+NN_LAYOUT = {"gram16": 1, "pixel_major": 2}
+
+
 class Stage1ObjectiveDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("scale_invariant", C.c_int32),
                 ("w_img", C.c_float), ("w_loop", C.c_float), ("w_sparsity", C.c_float), ("w_density", C.c_float),
@@ -137,6 +149,8 @@ SIGNATURES = {
     "vl3d_overcompose_nto0_fwd": ([_I32, _I32, _I32, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P], C.c_int),
     "vl3d_overcompose_nto0_bwd": ([_I32, _I32, _I32, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P], C.c_int),
     "vl3d_patchnn_scratch_bytes": ([C.POINTER(LossDesc)], C.c_int64),
+    "vl3d_patchnn_choice": ([C.POINTER(LossDesc), _I32, _I32, _I32, _I32, _I32, C.POINTER(NNChoice)], C.c_int),
+    "vl3d_vote_fold_choice": ([C.POINTER(LossDesc), _I32, C.POINTER(FoldChoice)], C.c_int),
     "vl3d_patchnn": ([C.POINTER(LossDesc), _P, _P, _P, _P, _P], C.c_int),
     "vl3d_gram_major_bytes": ([_I32, _I32, _I32], C.c_int64),
     "vl3d_video_to_gram_major": ([_P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P], C.c_int),

@@ -1,7 +1,7 @@
 """Drop-in mirror of the reference's utils_vid.py looping-loss operators.
 
 Same names / arguments / error behaviour as /root/reference/utils_vid.py.  The patch search, vote-fold and
-robust loss run in the HIP library (csrc/vl3d_loss.hip); patches are never materialised (no unfoldNd), and
+robust loss run in the HIP library (csrc/vl3d_loss.hip, csrc/vl3d_fold.hip); patches are never materialised (no unfoldNd), and
 the macro-block loop of the reference (a pure memory cap that does not change the result, utils_vid.py:323-342)
 is not needed.
 """
@@ -78,7 +78,7 @@ def _loss_desc(x, y, patch_size, patcht_size, stride, stridet, alpha):
     d.alpha = 0.0 if alpha is None else float(alpha)
     d.x_sc, d.x_st, d.x_sr = x.stride(0), x.stride(1), x.stride(2)
     d.y_sc, d.y_st, d.y_sr = y.stride(0), y.stride(1), y.stride(2)
-    # kernel-variant selector for cross-checks (bits 0-3 pick one of the four patch-NN kernels, every one of them exact; bits 12-15 a
+    # kernel-variant selector for cross-checks (bits 0-3 pick one of the three patch-NN kernels, every one of them exact; bits 12-15 a
     # fold tile shape): the timing-only bits 4-7 never leave this module (the product library refuses them anyway)
     d.variant = int(KERNEL_VARIANT) & ~0xf0
     return d
@@ -98,6 +98,20 @@ def kernel_variant(v):
         yield
     finally:
         KERNEL_VARIANT = old
+
+
+def patchnn_choice(desc, entry="plain", has_scratch=True, x_pitch=0, x_frames=0, y_pitch=0):
+    """which kernel a search with these arguments runs (vl3d_patchnn_choice: the entry points' own decision, no device touched) ->
+    (status, L.NNChoice); status 0 / 1 / 3 is what the entry would return."""
+    out = L.NNChoice()
+    rc = L.lib().vl3d_patchnn_choice(desc, L.NN_ENTRY[entry], int(bool(has_scratch)), int(x_pitch), int(x_frames), int(y_pitch), L.C.byref(out))
+    return rc, out
+
+
+def fold_choice(desc, fused=False):
+    """which kernel vl3d_vote_fold (fused: vl3d_vote_fold_robust*) runs for this descriptor -> (status, L.FoldChoice)."""
+    out = L.FoldChoice()
+    return L.lib().vl3d_vote_fold_choice(desc, int(bool(fused)), L.C.byref(out)), out
 
 
 def _as_video(v, name):
