@@ -81,8 +81,9 @@ typedef struct vl3d_render_desc {
     float pixel_center;    /* 0 (utils_mpi) or 0.5 (pytorch3d pixel centres) */
     float sx, sy, ox, oy;  /* VL3D_COORD_AFFINE only */
     int32_t variant;       /* kernel selector for bitwise cross-checks between EXACT kernels; 0 = default.  Bits 0-3: backward (see
-                            * vl3d_render_bwd); bits 8-11: forward -- 6 = one frame per thread (default for the shipped activations and
-                            * T >= 2: two frames per thread, same bits); bits 12-15: 1 = the two-pass forward with regularisers.  Bits 4-7
+                            * vl3d_render_bwd); bits 8-11: forward -- 6 = one frame and one pixel per thread, 7 = two frames per thread (default for the
+                            * shipped activations and T >= 2: a dense fp32 stack two pixel rows per thread, which share their middle tap
+                            * row; an fp16 or tile-culled one two frames per thread.  Same bits all three); bits 12-15: 1 = the two-pass forward with regularisers.  Bits 4-7
                             * (timing-only ablations, wrong results) exist only in a -DVL3D_VARIANTS measurement build: the product
                             * library returns VL3D_EINVAL for them. */
     /* tile culling on a WINDOW of the stack (a call with a quad map only; all 0 = the stack is the whole plane): the stack passed in is

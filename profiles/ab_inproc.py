@@ -5,7 +5,9 @@ processes differ by up to 10 % on the same box (allocation, clock state), which 
 Prints per variant the median / min of the forward and backward times (HIP events on the launch stream).
 A variant may be listed TWICE (--variants 6,7,6: the frame pairs in 32 x 16 regions, in 64 x 12 regions, and the 32 x 16 ones again): every
 entry is timed as a leg of its own, and the difference between the medians of two legs of the same variant is the harness's own repeatability
-in that run -- the yardstick a gain has to clear (printed as `spread`; every other leg's backward is printed against the first leg's)."""
+in that run -- the yardstick a gain has to clear (printed as `spread`; every other leg's backward is printed against the first leg's).
+Forward legs work the same way (--variants 0x700,0,0x700: frame pairs, the default row pairs, frame pairs again): the last line prints the
+forward medians against the first leg's and the spread of the repeated legs' forward medians."""
 import argparse
 import os
 import statistics
@@ -89,3 +91,8 @@ for i, v in enumerate(variants):
 spread = max([abs(bmed[i] - bmed[j]) for i in range(len(variants)) for j in range(i) if variants[i] == variants[j]], default=None)
 if spread is not None:
     print(f"spread (backward medians of the legs that repeat a variant): {spread:.3f} ms = {100.0 * spread / bmed[0]:.2f} %; a gain counts from 3x that: {3 * spread:.3f} ms")
+    # forward legs (desc->variant bits 8-11, e.g. --variants 0x700,0,0x700): the same yardstick on the forward medians
+    fmed = [statistics.median(f) for f, _ in res]
+    fspread = max(abs(fmed[i] - fmed[j]) for i in range(len(variants)) for j in range(i) if variants[i] == variants[j])
+    print("forward medians against leg 0: " + "  ".join(f"{v:#x} {fmed[i] - fmed[0]:+.3f} ms" for i, v in enumerate(variants) if i)
+          + f"; spread of the repeated legs {fspread:.3f} ms = {100.0 * fspread / fmed[0]:.2f} %")

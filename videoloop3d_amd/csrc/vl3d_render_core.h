@@ -1089,6 +1089,108 @@ __global__ __launch_bounds__(64 * TY, VL3D_FWD2X_MIN_WAVES) void render_fwd2x_k(
     }
 }
 
+// Forward, two pixel ROWS per thread (dense fp32 stacks).  The pixels (x, y) and (x, y+1) almost always have base taps exactly one texel row
+// apart: the lower tap row of the upper pixel IS the upper tap row of the lower pixel, so the thread fetches 3 tap rows x 2 columns = 6 loads
+// for two pixels where render_fwd2_k / render_fwd2x_k issue 8 -- every one still a coalesced 1-KiB wave access, no lane exchange, no LDS, no
+// barrier.  A workgroup of 512 threads covers 64 x 16 pixels of one frame (wave w: rows 2w and 2w+1; 17 tap rows for 16 pixel rows where the
+// 64 x 8 tile fetches 9 for 8).  A lane whose lower pixel does NOT sit one row below (a skipped or repeated texel row where the row pitch is
+// not 1, column drift under rotation, a base tap clamped at the border) fetches the lower pixel's own two upper taps when that pixel is shaded,
+// in a branch a wave without such a lane never enters (tests/test_gpu_fwd2r.py counts those lanes on the host).
+// Per pixel the taps are make_taps2's, every value is blended by shade2 with the weights render_fwd2_k gives it and composited by the
+// statements of its VL3D_COMPOSITE in their order: the bits of render_fwd2_k / render_fwd2x_k.  Two register sets (A/B) over the planes, as there.
+// (One frame per thread: with frames t and t+1 in the thread as well -- four pixels, the plane's coordinate work shared -- hipcc spilled 140
+// bytes per lane at the 128 registers of four waves per SIMD; docs/kernels/K1_render_forward.md.)
+struct Taps2R {
+    Taps2 u, l;        // the upper and the lower pixel's taps: make_taps2 of (px, py) and (px, py + 1)
+    unsigned off2;     // lane offset of the third tap row (against the plane base + dy): l.off; u.off where the frame has no lower pixel
+    bool own;          // l.off != u.off + dy: the lower pixel's upper taps are not the upper pixel's lower ones
+};
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT>
+__global__ __launch_bounds__(512, 4) void render_fwd2r_k(RenderArgs a, int tiles_x, int tiles_y) {      // >= 4 waves per SIMD: <= 128 VGPRs
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_x = b % tiles_x, rest = b / tiles_x;
+    const int tile_y = rest % tiles_y, t = rest / tiles_y;
+    const int x = tile_x * 64 + (threadIdx.x & 63);
+    const int y = tile_y * 16 + (int)(threadIdx.x >> 6) * 2;
+    if (x >= a.W || y >= a.H) return;
+    const bool hasL = y + 1 < a.H;           // odd H: the last row's lower pixel re-reads the upper pixel's rows and is not stored (wave uniform)
+    const float px = (float)(a.col0 + x) + a.pc, pyU = (float)(a.row0 + y) + a.pc, pyL = (float)(a.row0 + y + 1) + a.pc;
+    const size_t frame_b = (size_t)a.Hs * a.Ws * 16;
+    const size_t plane_stride_b = (size_t)a.Tstride * frame_b;
+    const char *plane = reinterpret_cast<const char *>(a.stack) + (size_t)t * frame_b;
+    float TrU = 1.0f, crU = 0.f, cgU = 0.f, cbU = 0.f, AU = 0.f, n1U = 0.f, n2U = 0.f;
+    float TrL = 1.0f, crL = 0.f, cgL = 0.f, cbL = 0.f, AL = 0.f, n1L = 0.f, n2L = 0.f;
+    const TapStep st = make_tap_step<false>(a.Hs, a.Ws);
+    Taps2R tA, tB;
+    f4 vA[6], vB[6];       // tap rows 0, 1, 2 x columns 0, 1: the upper pixel blends [0..3], the lower one [2..5]
+    // the taps of plane d and their six loads.  The prefetch of the next plane is unconditional (past the end it re-reads the last plane), as in render_fwd2_k
+    auto fetch = [&](int d, Taps2R &tp, f4 *v) {
+        float h[VL3D_HN];
+        load_uniform(a.homos + VL3D_HS * d, h);
+        tp.u = make_taps2<COORD, BORDER>(h, px, pyU, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
+        tp.l = make_taps2<COORD, BORDER>(h, px, pyL, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
+        tp.own = hasL && tp.l.off != tp.u.off + st.dy;
+        tp.off2 = hasL ? tp.l.off : tp.u.off;
+        const char *__restrict__ p = plane + (size_t)d * plane_stride_b;
+        v[0] = load_texel<false>(p, tp.u.off);
+        v[1] = load_texel<false>(p + st.dx, tp.u.off);
+        v[2] = load_texel<false>(p + st.dy, tp.u.off);
+        v[3] = load_texel<false>(p + st.dy + st.dx, tp.u.off);
+        v[4] = load_texel<false>(p + st.dy, tp.off2);
+        v[5] = load_texel<false>(p + st.dy + st.dx, tp.off2);
+        asm volatile("" ::: "memory");   // keep the loads here: hipcc otherwise sinks them below the composite
+    };
+#define VL3D_COMPOSITE1(O_, S_)                                                                     \
+    {                                                                                               \
+        const float w = O_.w * Tr##S_;                                                              \
+        cr##S_ += w * O_.x; cg##S_ += w * O_.y; cb##S_ += w * O_.z; A##S_ += w;                     \
+        n1##S_ += O_.w; n2##S_ = fmaf(O_.w, O_.w, n2##S_);                                          \
+        Tr##S_ *= (1.0f - O_.w);                                                                    \
+    }
+    // one plane, both pixels.  The own-taps arm shades on its own: were its two loads joined with the other path in front of ONE shade, the
+    // wait for them would be vmcnt(0) on both paths -- a wait for the prefetch just issued, in every wave.  (The asm comment keeps the arms apart.)
+#define VL3D_COMPOSITE2R(T_, V_, D_)                                                                \
+    {                                                                                               \
+        const f4 oU = shade2<ORDER, RACT, AACT>(T_.u, V_);                                          \
+        VL3D_COMPOSITE1(oU, U)                                                                      \
+        f4 oL;                                                                                      \
+        if (__builtin_amdgcn_ballot_w64(T_.own) != 0ull) {                                          \
+            f4 vl[4] = {V_[2], V_[3], V_[4], V_[5]};                                                \
+            if (T_.own) {                                                                           \
+                const char *__restrict__ p = plane + (size_t)(D_) * plane_stride_b;                 \
+                vl[0] = load_texel<false>(p, T_.l.off);                                             \
+                vl[1] = load_texel<false>(p + st.dx, T_.l.off);                                     \
+            }                                                                                       \
+            oL = shade2<ORDER, RACT, AACT>(T_.l, vl);                                               \
+            asm volatile("; render_fwd2r_k own taps" ::: "memory");                                 \
+        } else {                                                                                    \
+            oL = shade2<ORDER, RACT, AACT>(T_.l, V_ + 2);                                           \
+        }                                                                                           \
+        VL3D_COMPOSITE1(oL, L)                                                                      \
+    }
+    fetch(0, tA, vA);
+    for (int d = 0;; d += 2) {
+        fetch(min(d + 1, a.D - 1), tB, vB);
+        VL3D_COMPOSITE2R(tA, vA, d)
+        if (d + 1 >= a.D) break;
+        fetch(min(d + 2, a.D - 1), tA, vA);
+        VL3D_COMPOSITE2R(tB, vB, d + 1)
+        if (d + 2 >= a.D) break;
+    }
+#undef VL3D_COMPOSITE2R
+#undef VL3D_COMPOSITE1
+    const size_t pix = ((size_t)t * a.H + y) * a.W + x;
+    a.rgb[pix * 3 + 0] = crU; a.rgb[pix * 3 + 1] = cgU; a.rgb[pix * 3 + 2] = cbU;
+    a.alpha[pix] = AU;
+    if (a.asum) { a.asum[pix * 2 + 0] = n1U; a.asum[pix * 2 + 1] = n2U; }
+    if (hasL) {
+        const size_t pl = pix + a.W;
+        a.rgb[pl * 3 + 0] = crL; a.rgb[pl * 3 + 1] = cgL; a.rgb[pl * 3 + 2] = cbL;
+        a.alpha[pl] = AL;
+        if (a.asum) { a.asum[pl * 2 + 0] = n1L; a.asum[pl * 2 + 1] = n2L; }
+    }
+}
+
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
 void launch_fwd2x(const RenderArgs &a, hipStream_t s) {
     constexpr int TY = 8;
@@ -1098,6 +1200,17 @@ void launch_fwd2x(const RenderArgs &a, hipStream_t s) {
         launch_cull_fwd_plan<COORD>(a, TY, tiles_x, tiles_y, s);
         hipLaunchKernelGGL((render_fwd2x_k<COORD, BORDER, ORDER, RACT, AACT, TY, F16, true>), grid, block, 0, s, a, tiles_x, tiles_y);
         return;
+    }
+    // (activate-then-blend under the hard cut -- four activated taps per pixel alive at once -- is the one convention in which hipcc spills the row
+    // pairs at 128 registers, 20 bytes per lane: it keeps the frame pairs)
+    if constexpr (!F16 && !(ORDER == VL3D_ACT_PRE && BORDER == VL3D_BORDER_HARDCUT)) {
+        // dense fp32 stacks: two pixel rows per thread in 64 x 16 tiles of one frame, render_fwd2_k's grid order.  Forward variant 7 keeps
+        // render_fwd2x_k (A/B, bitwise tests)
+        if (a.fwd_variant != 7) {
+            const int tiles_y2 = (a.H + 15) / 16;
+            hipLaunchKernelGGL((render_fwd2r_k<COORD, BORDER, ORDER, RACT, AACT>), dim3((unsigned)(tiles_x * tiles_y2 * a.T)), dim3(512), 0, s, a, tiles_x, tiles_y2);
+            return;
+        }
     }
     hipLaunchKernelGGL((render_fwd2x_k<COORD, BORDER, ORDER, RACT, AACT, TY, F16>), grid, block, 0, s, a, tiles_x, tiles_y);
 }
@@ -2428,8 +2541,8 @@ int launch_t(const RenderArgs &a, hipStream_t s) {
             launch_reg_slots<COORD, BORDER, ORDER, RACT, AACT, F16, false>(a, s);
             return VL3D_OK;
         }
-        // frame pairs (shipped activations, dense stacks, T >= 2); forward variant 6 (desc->variant bits 8..11) keeps the one-frame
-        // kernel (A/B, bitwise tests).  The workgroup-shape variants of round 1 (64x4, 64x16, no XCD remap) measured within the
+        // frame pairs (shipped activations, T >= 2; a dense fp32 stack: row pairs, launch_fwd2x); forward variant 6 (desc->variant bits 8..11)
+        // keeps the one-frame kernel, 7 the frame pairs (A/B, bitwise tests).  The workgroup-shape variants of round 1 (64x4, 64x16, no XCD remap) measured within the
         // noise of the default and are no longer built.
         if constexpr (MASKABLE) {
             if (a.mask) {       // one frame per thread with the fifth channel
