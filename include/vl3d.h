@@ -58,7 +58,7 @@ enum { VL3D_F32 = 0, VL3D_F16 = 1, VL3D_U8 = 2 };
 
 const char *vl3d_last_error(void);
 /* Raised by one whenever an exported signature or the layout of a struct of this header changes (101: the vl3d_adam_window family takes the
- * struct); a caller built against another header compares it before its first call. */
+ * struct; 102: vl3d_render_sh_fwd / _bwd); a caller built against another header compares it before its first call. */
 int vl3d_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -291,6 +291,35 @@ int vl3d_render_bwd(const vl3d_render_desc *desc, const void *stack, const float
                     const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha, const float *grad_reg,
                     const void *reg_state, const float *grad_alpha_sums, float *grad_stack, void *scratch, int64_t scratch_bytes,
                     vl3d_stream_t stream);
+
+/* Stage 1's view-dependent colour head, rgb_mlp_type = "rgb_sh" (csrc/vl3d_render_sh.hip; docs/kernels/K7_stage1.md, "the view-dependent colour head").  Replaces MPI.py:512-513,
+ * 526-537 inside the render MPI.py:452-594: per-pixel ray directions into SphericalHarmoic_RGB (utils_mpi.py:50-61) with the degree-1 basis of
+ * eval_sh_bases (utils_mpi.py:365-383), and its autograd.
+ *   stack    : (D, 1, Hs, Ws, 4)     (R0, G0, B0, alpha logit): coefficient k = 0 of every colour and the alpha, as vl3d_render_fwd reads it
+ *   stack_sh : (D, 1, Hs, Ws, 3, 4)  stack_sh[..., k - 1, c] = coefficient k = 1..3 of colour c; lane 3 is reserved: 0, never read into a value
+ *   homos    : (D, 3, 3)             as vl3d_render_fwd
+ *   ray_m    : device float[9], row-major M = inverse(E)[:3,:3] inverse(K) -- E the ref -> target extrinsic, K the intrinsics of the call
+ * Per output pixel with INTEGER frame indices (x, y) = (col0 + column, row0 + row) (utils.py:182-193: no half pixel, whatever pixel_center says):
+ *     d = normalize(M (x, y, 1)^T),   b = (C0, -C1 d_y, C1 d_z, -C1 d_x),   C0 = 0.28209479177387814, C1 = 0.4886025119029199
+ * Per plane: the taps, hard cut, kept-quad test and tent weights of vl3d_render_fwd's planar convention (the same device functions);
+ *     pre_c = sum_k b_k sample(coef_{c,k}),  pre_a = sample(alpha)  (contracted per tap, before the tent weights: the contraction is linear),
+ *     rgba = (rgb_act(pre_rgb), alpha_act(pre_a)) x coverage, composited front to back as vl3d_render_fwd does.  With stack_sh = 0, alpha and
+ *     alpha_sums hold the bits of vl3d_render_fwd.  M and 2 M give the same bits.  A wave skips a plane that covers none of its 64 pixels.
+ * Forward writes rgb (1,H,W,3), alpha (1,H,W) and alpha_sums (1,H,W,2; may be NULL).  Backward: rgb / alpha the saved outputs, grad_alpha and
+ *     grad_alpha_sums may be NULL; grad_stack and grad_stack_sh are overwritten -- cleared by the entry, then summed with global float atomics
+ *     (per tap with tent weight w: d/d coef_{c,k} += w b_k g_pre_c, d/d alpha += w g_pre_a, g_pre = act'(pre) g_layer; a wave transposes its
+ *     pixels' 16-float texel records through LDS so that one atomic instruction carries whole records of 4 pixels), so the gradient is NOT
+ *     bit-reproducible between runs; lane 3 of grad_stack_sh and every texel no covered sample reads are exactly 0.
+ * Accepted: T = 1, VL3D_F32, (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, VL3D_ACT_POST), every pair of the activation table, D <= 128; quad_keep NULL
+ *     (QH, QW not read) or a map [D][QH][QW] with a POSITIVE grid and desc->cull_* = 0.  VL3D_EUNSUPPORTED: another T, dtype or convention,
+ *     uv_noise_seed != 0, the tile-exact (negative) grid, a cull window.  VL3D_EINVAL: variant != 0, non-positive dims, D > 128, a plane of
+ *     2^28 texels or more, a NULL pointer, stack / stack_sh / their gradients not 16-byte aligned, any other pointer not 4-byte aligned.  Nothing
+ *     is launched after a refusal. */
+int vl3d_render_sh_fwd(const vl3d_render_desc *desc, const float *stack, const float *stack_sh, const float *homos, const float *ray_m,
+                       const uint8_t *quad_keep, int32_t QH, int32_t QW, float *rgb, float *alpha, float *alpha_sums, vl3d_stream_t stream);
+int vl3d_render_sh_bwd(const vl3d_render_desc *desc, const float *stack, const float *stack_sh, const float *homos, const float *ray_m,
+                       const uint8_t *quad_keep, int32_t QH, int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb,
+                       const float *grad_alpha, const float *grad_alpha_sums, float *grad_stack, float *grad_stack_sh, vl3d_stream_t stream);
 
 /* Which kernel a backward call runs, without running it: the value the entry points themselves compute (the same two functions, no device
  * touched, nothing enqueued).  entry: which entry point; has_quad_keep / has_reg_grads (grad_reg or grad_alpha_sums non-NULL) / scratch_bytes:

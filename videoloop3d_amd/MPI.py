@@ -1,7 +1,7 @@
 """MPMesh (stage 1, static MPI) on the MI355X-native render kernels: drop-in for the hot path of the reference's MPI.py.
 
 Mirrors /root/reference/MPI.py:36-131 (constructor), :452-594 (render) and :596-652 (forward) for PLANAR geometry with
-rgb_mlp_type = 'direct' (configs/mpi_base.txt), dense and after sparsify_faces.  As in videoloop3d_amd/MPV.py the texture is the dense plane
+rgb_mlp_type = 'direct' (configs/mpi_base.txt) or 'rgb_sh' (the view-dependent colour head, below), dense and after sparsify_faces.  As in videoloop3d_amd/MPV.py the texture is the dense plane
 stack `stack` (D,1,Hs,Ws,4) (+ `stack_mask` (D,1,Hs,Ws) for the learned loop mask, MPI.py:115-117) instead of the atlas grid, and coverage / UVs
 are the analytic per-plane homography instead of pytorch3d's rasteriser.
   * The loop-mask channel (MPI.py:568-583: sigmoid(mask texture) composited with the DETACHED layer alphas) rides the colour pass as a fifth
@@ -13,7 +13,15 @@ are the analytic per-plane homography instead of pytorch3d's rasteriser.
     reference_state_dict / save_* write the reference's layout (videoloop3d_amd/export.py); both, like the camera set-up, plane_homographies
     and get_lrate / update_step, are shared with MPMeshVid (videoloop3d_amd/plane_model.py).
   * l_smooth / d_smooth / normalize_blendweight_fordepth / variables['mpi' | 'blend_weight' | 'disp_norm' | 'loopmask3d'] (off in every shipped
-    configuration) come from the materialised-layer slow path (videoloop3d_amd/layers.py); direct2sh is out of scope.
+    configuration) come from the materialised-layer slow path (videoloop3d_amd/layers.py).
+  * rgb_mlp_type = 'rgb_sh' (MPI.py:105-110, 512-537; utils_mpi.py:50-61) and direct2sh (MPI.py:273-286, train_3d.py:287-290): every texel holds four
+    degree-1 spherical-harmonics coefficients per colour, contracted per pixel with the basis of its ray direction.  `stack` keeps its meaning
+    -- (R0, G0, B0, alpha logit): coefficient 0 and the alpha, so sparsify_faces, the quad maps, the loop-mask label pass and TileAdam work on it
+    unchanged -- and a second parameter `stack_sh` (D,1,Hs,Ws,3,4) holds coefficients 1..3 (stack_sh[..., k - 1, c]; lane 3 reserved, always 0).
+    render() calls vl3d_render_sh_fwd / _bwd (render.render_planes_sh; docs/kernels/K7_stage1.md, "the view-dependent colour head"); rgb_smooth / a_smooth come from the
+    materialised layers (a completeness path, like d_smooth).  Not built for such a model, each refused with a sentence: atlas_exact,
+    add_uv_noise while training, the crop-aware optimiser, the tile-exact layout, and the reference's 13-channel atlas layout
+    (reference_state_dict / save_mesh / save_texture, init_from_mpi of a reference checkpoint) -- frontal_stack() is the picture save_texture shows.
 Module-level parity: tests/test_gpu_reference_modules.py (the reference's own forward, golden G17), tests/test_gpu_mpv.py (oracle).
 """
 import dataclasses
@@ -25,9 +33,30 @@ import torch.nn as nn
 from . import tiles
 from .MPV import _PixelTerms, sparsity_ratio
 from .plane_model import PlaneModel
-from .render import mask_channel_supported, render_planes, render_planes_with_mask, render_planes_with_regularisers
+from .render import SH_C0, SH_C1, mask_channel_supported, render_planes, render_planes_sh, render_planes_with_mask, render_planes_with_regularisers, sh_basis, sh_ray_matrix
 
 ALPHA_INIT_VAL = -3.     # MPI.py:33
+
+
+# the reference's 13 feature channels of an rgb_sh texel (MPI.py:105-108; SphericalHarmoic_RGB, utils_mpi.py:57-61): channel 4 c + k is coefficient k
+# of colour c, channel 12 the alpha.  Ours is a permutation of them: stack = (k = 0 of r, g, b; alpha), stack_sh[k - 1, c] = coefficient k = 1..3.
+SH_REF_OF_STACK = (0, 4, 8, 12)
+SH_REF_OF_SH = ((1, 5, 9), (2, 6, 10), (3, 7, 11))
+
+
+def sh_from_reference(feat):
+    """reference features [..., 13] -> (stack texels [..., 4], stack_sh texels [..., 3, 4]; lane 3 zero)"""
+    sh = torch.zeros(feat.shape[:-1] + (3, 4), dtype=feat.dtype, device=feat.device)
+    sh[..., :3] = feat[..., torch.tensor(SH_REF_OF_SH, device=feat.device)]
+    return feat[..., list(SH_REF_OF_STACK)], sh
+
+
+def sh_to_reference(stack, stack_sh):
+    """(stack texels [..., 4], stack_sh texels [..., 3, 4]) -> reference features [..., 13]"""
+    feat = torch.empty(stack.shape[:-1] + (13,), dtype=stack.dtype, device=stack.device)
+    feat[..., list(SH_REF_OF_STACK)] = stack
+    feat[..., torch.tensor(SH_REF_OF_SH, device=stack.device)] = stack_sh[..., :3]
+    return feat
 
 
 class _LoopMaskLabel(torch.autograd.Function):
@@ -64,16 +93,28 @@ def crop_aware_pays(stack_shape, view_h, view_w):
 
 class MPMesh(PlaneModel):
     BASE_CONFIG = "mpi_base.txt"
+    RGB_MLP_TYPES = ("direct", "rgb_sh")
 
     def __init__(self, args, H, W, ref_extrin, ref_intrin, near, far, pixel_center=0.5, texel_scale=(1.0, 1.0), atlas_exact=False):
         """atlas_exact=True: sample the stack exactly like the reference samples its atlas of plane cells (MPI.py:75-81, 490-520: cell pitch
         (Aw-1)/(gw*(mpi_w-1)), per-cell sub-texel origin, neighbour-cell bleed) -- videoloop3d_amd/atlas.py, as MPMeshVid(atlas_exact=True).  A
         parity mode for dense weights that come from / go to the reference (MPV.atlas_to_stack / stack_to_atlas): the image and the loop-mask label
-        (a second pass), no fused regularisers, no tile culling; needs args.atlas_grid_h."""
+        (a second pass), no fused regularisers, no tile culling; needs args.atlas_grid_h.
+        args.rgb_mlp_type = 'rgb_sh': initialised AS THE REFERENCE WRITES IT (MPI.py:106-108): all 13 features uniform in [0, 1) and ALPHA_INIT_VAL in
+        its channel 0 -- which is red's first coefficient, stack[..., 0] here; the alpha logit stays uniform."""
         super().__init__(args, H, W, ref_extrin, ref_intrin, near, far, pixel_center, texel_scale, atlas_exact)
         stack = torch.rand((self.mpi_d, 1, self.mpi_h, self.mpi_w, 4))                             # MPI.py:102-103
-        stack[..., -1] = ALPHA_INIT_VAL
+        if self.rgb_mlp_type == "rgb_sh":
+            if self.atlas_exact:
+                raise RuntimeError("atlas_exact is a parity mode of the 4-channel atlas: not built for rgb_mlp_type = 'rgb_sh'")
+            stack[..., 0] = ALPHA_INIT_VAL                                                        # MPI.py:108 (as written: channel 0, not the alpha)
+        else:
+            stack[..., -1] = ALPHA_INIT_VAL
         self.stack = nn.Parameter(stack, requires_grad=True)
+        if self.rgb_mlp_type == "rgb_sh":
+            stack_sh = torch.rand((self.mpi_d, 1, self.mpi_h, self.mpi_w, 3, 4))
+            stack_sh[..., 3] = 0
+            self.stack_sh = nn.Parameter(stack_sh, requires_grad=True)
         self.learn_loop_mask = bool(getattr(args, "learn_loop_mask", False))
         if self.learn_loop_mask:
             self.stack_mask = nn.Parameter(torch.ones((self.mpi_d, 1, self.mpi_h, self.mpi_w)) * ALPHA_INIT_VAL, requires_grad=True)
@@ -95,6 +136,36 @@ class MPMesh(PlaneModel):
         if self.stack.device != dev:
             self._window_opt = None      # optimiser state lives on the old device: the driver asks for a new one
         return out
+
+    @torch.no_grad()
+    def direct2sh(self, keep_picture=False):
+        """MPI.py:273-286 (train_3d.py:287-290 calls it at args.direct2sh_epoch, then asks for a new optimiser): a trained `direct` model becomes
+        an 'rgb_sh' one -- `stack` unchanged, `stack_sh` zeros (MPI.py:279-282).  The colours then read C0 * stack.rgb: the reference does not
+        divide by C0, so its picture changes at the switch, and that is the default here.  keep_picture=True divides the three colour lanes of
+        `stack` by C0, so the render is unchanged (to rounding)."""
+        if self.rgb_mlp_type != "direct":
+            raise RuntimeError(f"direct2sh: the model's colour head is already {self.rgb_mlp_type!r}")
+        if self.atlas_exact:
+            raise RuntimeError("atlas_exact is a parity mode of the 4-channel atlas: not built for rgb_mlp_type = 'rgb_sh'")
+        if getattr(self, "tile_own", None) is not None:
+            raise RuntimeError("direct2sh: the tile-exact layout is not built for the view-dependent colour head: load the checkpoint with "
+                               "init_from_mpi(..., tile_layout='lattice')")
+        self._flush_deferred_updates()
+        self._window_opt = None          # (train_3d.py:290 asks for a new optimiser after this call)
+        if keep_picture:
+            self.stack.data[..., :3] /= SH_C0
+        self.stack_sh = nn.Parameter(torch.zeros(tuple(self.stack.shape[:4]) + (3, 4), dtype=self.stack.dtype, device=self.stack.device), requires_grad=True)
+        self.rgb_mlp_type = "rgb_sh"
+
+    @torch.no_grad()
+    def frontal_stack(self):
+        """(D,1,Hs,Ws,4): the logits seen along d = (0, 0, 1) -- basis (C0, 0, C1, 0): C0 * stack.rgb + C1 * stack_sh[..., 1, :3], plus the alpha
+        logit -- the picture save_texture shows in the reference (MPI.py:242-252); `stack` itself for a direct model."""
+        self._flush_deferred_updates()
+        st = self.stack.detach().clone()
+        if self.rgb_mlp_type == "rgb_sh":
+            st[..., :3] = SH_C0 * st[..., :3] + SH_C1 * self.stack_sh.detach()[..., 1, :3]
+        return st
 
     @torch.no_grad()
     def sparsify_faces(self, erode_num=2, alpha_thresh=0.03, loop_thresh=0.5):
@@ -145,6 +216,8 @@ class MPMesh(PlaneModel):
             sd["self.tile_own"] = self.tile_own
         if self.has_dyn:
             sd["self.has_dyn"] = self.has_dyn
+        if self.rgb_mlp_type != "direct":
+            sd["self.rgb_mlp_type"] = self.rgb_mlp_type
         return sd
 
     # ---- driver hooks of train_3d.py (:159, 185, 284-301, 316-332) ------------------------------------------------------------
@@ -156,6 +229,12 @@ class MPMesh(PlaneModel):
         self._window_opt = None
         if a.optimizer == 'adam':
             crop_aware = getattr(a, "crop_aware_adam", "auto")
+            if self.rgb_mlp_type == "rgb_sh":
+                # the window engine copies and steps `stack` alone: an SH model takes the one-pass Adam over both parameters below (its zero-skip
+                # keeps the texels no view has reached free, in the larger tensor too)
+                if crop_aware is True:
+                    raise RuntimeError("crop_aware_adam = True: the crop-aware optimiser is not built for rgb_mlp_type = 'rgb_sh' (use \"auto\" or False)")
+                crop_aware = False
             if crop_aware == "auto":
                 # the crop-aware engine pays where the optimiser's streams over the WHOLE stack dominate the iteration and a view reaches a minor
                 # part of it: a large stack (>= 768 MB: seven streams of it are >= 1 ms) of which a view's footprint -- the training crop, or the
@@ -198,6 +277,14 @@ class MPMesh(PlaneModel):
         keeps its tile with its own border texels -- the epochs stage 1 trains AFTER the switch-over (train_3d.py:282-285) move the two
         copies of a border sample apart (golden G19 j); "lattice" = neighbouring quads share them."""
         self._window_opt = None          # (the parameters are replaced: the driver asks for a new optimiser)
+        if "stack" not in state_dict and "atlas" in state_dict and state_dict["atlas"].shape[1] != 4:
+            raise RuntimeError(f"init_from_mpi: a reference checkpoint with a {state_dict['atlas'].shape[1]}-channel atlas (rgb_mlp_type = 'rgb_sh'): the "
+                               "reference's atlas layout of a view-dependent model is not read; this package's own checkpoints (state_dict()) are")
+        sh_state = state_dict.get("self.rgb_mlp_type", "rgb_sh" if "stack_sh" in state_dict else "direct")
+        if sh_state not in self.RGB_MLP_TYPES or (sh_state == "rgb_sh") != ("stack_sh" in state_dict):
+            raise RuntimeError(f"init_from_mpi: the state names the colour head {sh_state!r} and {'holds' if 'stack_sh' in state_dict else 'lacks'} stack_sh")
+        if sh_state == "rgb_sh" and self.atlas_exact:
+            raise RuntimeError("atlas_exact is a parity mode of the 4-channel atlas: not built for rgb_mlp_type = 'rgb_sh'")
         if "stack" not in state_dict and "atlas" in state_dict:
             state_dict = self._from_reference_state(state_dict, tile_layout, 1)
             state_dict["stack"] = state_dict["stack"][:, :1]
@@ -219,6 +306,16 @@ class MPMesh(PlaneModel):
                 self.stack.copy_(st.to(dev))
             if "stack_mask" in state_dict and hasattr(self, "stack_mask"):
                 self.stack_mask.copy_(state_dict["stack_mask"].to(dev))
+            if sh_state == "rgb_sh":      # (a model constructed as `direct` is switched over, as direct2sh does)
+                sh = state_dict["stack_sh"]
+                if tuple(sh.shape) != tuple(self.stack.shape[:4]) + (3, 4):
+                    raise RuntimeError(f"checkpoint stack_sh {tuple(sh.shape)} does not match the stack {tuple(self.stack.shape)}: (D,1,Hs,Ws,3,4)")
+                if self.tile_own is not None:
+                    raise RuntimeError("the tile-exact layout is not built for the view-dependent colour head")
+                self.stack_sh = nn.Parameter(sh.to(dev, torch.float32).contiguous(), requires_grad=True)
+            elif hasattr(self, "stack_sh"):
+                del self.stack_sh
+            self.rgb_mlp_type = sh_state
         self._set_texture_geometry(*self.stack.shape[2:4])
         self.spec_mask = dataclasses.replace(self.spec, rgb_act="sigmoid")
         self.is_sparse = bool(state_dict.get("self.is_sparse", False))
@@ -229,7 +326,7 @@ class MPMesh(PlaneModel):
             if hasattr(self, "stack_mask"):
                 del self.stack_mask
 
-    def _layer_variables(self, homos, H, W, extrin, qk):
+    def _layer_variables(self, homos, H, W, extrin, qk, basis=None):
         """the materialised tensors of one view (slow path, videoloop3d_amd/layers.py): `mpi` [1,H,W,K,4] and `loopmask3d` [1,H,W,K,1] in hit-slot
         order (MPI.py:538-548, 575-577), `blend_weight` [1,H,W,K], `disp_norm` [1,H,W] (MPI.py:483-485, 558-561: the disparity of every
         hit normalised between far and near, blended; args.normalize_blendweight_fordepth divides the weights by alpha first)."""
@@ -240,7 +337,8 @@ class MPMesh(PlaneModel):
         from .MPV import ACTIVATES
         from .utils_mpi import overcompose
         a = self.args
-        mpi, planes, cov, (_, _, xm, ym) = LY.materialise(self.stack, homos, H, W, self.spec, ACTIVATES[a.rgb_activate], ACTIVATES[a.alpha_activate], qk)
+        mpi, planes, cov, (_, _, xm, ym) = LY.materialise(self.stack, homos, H, W, self.spec, ACTIVATES[a.rgb_activate], ACTIVATES[a.alpha_activate], qk,
+                                                          stack_sh=self.stack_sh if basis is not None else None, basis=basis)
         bw = overcompose(mpi[..., -1], mpi[..., :-1])[1]                                            # slot order, like the reference's
         bw_planes = overcompose(planes[..., -1], planes[..., :-1])[1]
         if getattr(a, "normalize_blendweight_fordepth", False):
@@ -261,6 +359,14 @@ class MPMesh(PlaneModel):
         B = len(extrin)
         rgbs, alphas, labels, ssums, asums = [], [], [], [], []
         lay = []
+        sh = self.rgb_mlp_type == "rgb_sh"
+        if sh:
+            if self.atlas_exact or getattr(self, "tile_own", None) is not None:
+                raise RuntimeError("rgb_mlp_type = 'rgb_sh' renders the shared-border stack: not built for atlas_exact / the tile-exact layout")
+            if self.training and getattr(self.args, "add_uv_noise", False):
+                raise RuntimeError("add_uv_noise is not built for rgb_mlp_type = 'rgb_sh' (vl3d_render_sh_fwd takes no jitter field)")
+            # rgb_smooth / a_smooth of an SH model come from the materialised layers (a completeness path, like d_smooth)
+            sh_smooth = need_reg and (self.args.rgb_smooth_loss_weight > 0 or self.args.a_smooth_loss_weight > 0)
         # a sparsified model (train_3d.py:282-285: the last epochs of stage 1 train it) renders with its quad map: a sample inside a culled
         # quad is NOT covered by that plane -- no face there in the reference (MPI.py:483-487, 544-548) -- so the slot-ordered smoothness
         # terms skip it and workgroups skip the planes of which they see no kept quad
@@ -272,7 +378,7 @@ class MPMesh(PlaneModel):
         # add_uv_noise with the loop mask (MPI.py:519-522 with :568-572): the colour samples are jittered, the mask is sampled at the PLAIN positions and
         # composited with the jittered samples' alphas -- two positions per layer: the label comes from its own kernel pair (render.loop_mask_label_with_uv_noise)
         noisy_label = self.learn_loop_mask and self.training and bool(getattr(self.args, "add_uv_noise", False))
-        fused_mask = (self.learn_loop_mask and self.stack.is_cuda and mask_channel_supported(self.stack, self.spec) and not noisy_label
+        fused_mask = (self.learn_loop_mask and self.stack.is_cuda and mask_channel_supported(self.stack, self.spec) and not noisy_label and not sh
                       and not self.is_sparse and not self.atlas_exact and not getattr(self.args, "loop_mask_two_pass", False))
         if self.learn_loop_mask and not fused_mask and not self.atlas_exact and not noisy_label:
             if getattr(self, "_mask_buf", None) is None or self._mask_buf.shape != self.stack.shape or self._mask_buf.device != self.stack.device:
@@ -307,13 +413,32 @@ class MPMesh(PlaneModel):
                     lean = not getattr(self.args, "finite_window_grad", False)
                 else:
                     self._flush_deferred_updates()
-            if homos.device.type == "cpu" and self.stack.is_cuda:
+            if sh:
+                ray_m = sh_ray_matrix(extrin[b], intrin[b])
+                if homos.device.type == "cpu" and self.stack.is_cuda:
+                    # homographies and ray matrix as ONE pinned [(D + 1),3,3] upload (see below)
+                    both = torch.cat([homos.detach().to(torch.float32), ray_m[None]]).pin_memory().to(self.stack.device, non_blocking=True)
+                    homos, ray_m = both[:-1], both[-1]
+                else:
+                    homos, ray_m = homos.to(self.stack.device), ray_m.to(self.stack.device)
+            elif homos.device.type == "cpu" and self.stack.is_cuda:
                 # host homographies (a few hundred bytes): through a pinned staging buffer and an asynchronous copy -- a pageable upload blocks
                 # the host until everything queued before it has run (1.7 of the 2.9 ms of a 720p stage-1 iteration, profiles/host_profile_stage1.py)
                 homos = homos.pin_memory().to(self.stack.device, non_blocking=True)
             else:
                 homos = homos.to(self.stack.device)
-            if self.atlas_exact:
+            if sh:
+                out = render_planes_sh(stack, self.stack_sh, homos, ray_m, H, W, spec, quad_keep=qk, with_alpha_sums=need_reg)
+                rgb, alpha = out[0], out[1]
+                basis = sh_basis(ray_m, H, W) if (sh_smooth or need_layers) else None
+                if need_reg:
+                    asums.append(out[2])
+                    if sh_smooth:
+                        from . import layers as LY
+                        from .MPV import ACTIVATES
+                        ssums.append(LY.smoothness_sums(LY.materialise(self.stack, homos, H, W, self.spec, ACTIVATES[self.args.rgb_activate],
+                                                                       ACTIVATES[self.args.alpha_activate], qk, stack_sh=self.stack_sh, basis=basis)[0]))
+            elif self.atlas_exact:
                 from .atlas import render_atlas_exact
                 gh = int(self.args.atlas_grid_h)
                 rgb, alpha = render_atlas_exact(self.stack, homos, H, W, gh, pixel_center=self.spec.pixel_center, rgb_act=self.spec.rgb_act,
@@ -340,7 +465,7 @@ class MPMesh(PlaneModel):
             rgbs.append(rgb)
             alphas.append(alpha)
             if need_layers:
-                lay.append(self._layer_variables(homos, H, W, extrin[b], qk))
+                lay.append(self._layer_variables(homos, H, W, extrin[b], qk, basis if sh else None))
             if noisy_label and not self.atlas_exact:
                 from .render import loop_mask_label_with_uv_noise
                 labels.append(loop_mask_label_with_uv_noise(self.stack_mask, self.stack, homos, H, W, spec)[..., None])      # (spec: this view's jitter field)
@@ -442,7 +567,7 @@ class MPMesh(PlaneModel):
         Falls back to the generic spelling where the head is not built for the call (CPU, several views, materialised-layer terms)."""
         a = self.args
         wts = {k: float(getattr(a, f"{k}_loss_weight", 0) or 0) for k in ("sparsity", "rgb_smooth", "a_smooth", "density", "d_smooth", "l_smooth")}
-        slow = (not self.training or not self.stack.is_cuda or len(tar_extrins) != 1 or getattr(a, "unfused_terms", False)
+        slow = (not self.training or not self.stack.is_cuda or len(tar_extrins) != 1 or getattr(a, "unfused_terms", False) or self.rgb_mlp_type != "direct"
                 or wts["d_smooth"] > 0 or (wts["l_smooth"] > 0 and self.learn_loop_mask) or self.atlas_exact
                 or (self.learn_loop_mask and target_mask is None))
         if slow:

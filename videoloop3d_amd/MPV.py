@@ -375,6 +375,10 @@ class MPMeshVid(PlaneModel):
         every frame.  With a sparsified MPI the quad maps come along: culled quads stay invisible, static quads stay ONE
         texture shared by all frames (their gradient is summed over the frames, as the reference's static atlas sees it),
         dynamic quads are free per frame; without them everything is dynamic ("load static as dynamic", MPV.py:266-288)."""
+        if "stack_sh" in state_dict:
+            # stage 1's view-dependent colour head: the reference's stage-2 head never receives view directions (MPV.py:431-434)
+            raise RuntimeError("init_from_mpi: the stage-1 state holds a view-dependent colour head (stack_sh, rgb_mlp_type = 'rgb_sh'), which stage 2 "
+                               "does not have: pass the frontal picture instead -- dict(mpi.state_dict(), stack=mpi.frontal_stack()) without 'stack_sh'")
         if "stack" not in state_dict and ("atlas" in state_dict or "atlas_dyn" in state_dict):
             # a checkpoint of the REFERENCE: a sparsified one arrives tile for tile (identical weights) or on the tile lattice; the tile size
             # at FULL resolution drives lod() like the reference's (MPV.py:146-151)

@@ -13,7 +13,7 @@ extern "C" void vl3d_set_error(const char *msg) {
     g_err[sizeof(g_err) - 1] = 0;
 }
 extern "C" const char *vl3d_last_error(void) { return g_err; }
-extern "C" int vl3d_version(void) { return 101; }
+extern "C" int vl3d_version(void) { return 102; }
 
 namespace {
 

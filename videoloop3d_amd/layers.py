@@ -70,12 +70,28 @@ def inverse_depth(xm, ym, intrin_mpi, planedepth, extrin):
     return (1.0 / z).float().permute(1, 2, 0)
 
 
-def materialise(stack, homos, H, W, spec, rgb_activate, alpha_activate, quad_keep=None, cull_window=None):
-    """-> (slot-ordered [T,H,W,K,4] = the reference's `mpi`, plane-indexed [T,H,W,D,4], cov [D,H,W], (tx, ty, xm, ym))."""
+def materialise(stack, homos, H, W, spec, rgb_activate, alpha_activate, quad_keep=None, cull_window=None, stack_sh=None, basis=None):
+    """-> (slot-ordered [T,H,W,K,4] = the reference's `mpi`, plane-indexed [T,H,W,D,4], cov [D,H,W], (tx, ty, xm, ym)).
+    stack_sh (D,1,Hs,Ws,3,4) with basis [H,W,4] (render.sh_basis): the view-dependent colour head (MPI.py:526-537) -- the colour logits are
+    sum_k basis_k sample(coefficient k), coefficient 0 in `stack`, 1..3 in `stack_sh`: four sample_planes calls, contracted in torch."""
     Hs, Ws = stack.shape[2:4]
     samp = sample_planes(stack, homos, H, W, spec)                                       # T,D,4,H,W
+    if stack_sh is not None:
+        rgb_pre = samp[:, :, :3] * basis[..., 0]
+        for k in range(3):
+            rgb_pre = rgb_pre + sample_planes(stack_sh[..., k, :], homos, H, W, spec)[:, :, :3] * basis[..., k + 1]
+        samp = torch.cat([rgb_pre, samp[:, :, 3:]], dim=2)
     tx, ty, xm, ym = plane_texel_coords(homos, H, W, spec, stack.device)
     cov = coverage(tx, ty, Hs, Ws, quad_keep, cull_window)
     rgba = torch.cat([rgb_activate(samp[:, :, :3]), alpha_activate(samp[:, :, 3:])], dim=2)
     rgba = (rgba * cov[None, :, None]).permute(0, 3, 4, 1, 2)                            # T,H,W,D,4, plane-indexed
     return to_slots(rgba, cov), rgba, cov, (tx, ty, xm, ym)
+
+
+def smoothness_sums(mpi):
+    """the four sums the smoothness regularisers are made of (MPI.py:609-623, MPV.py:517-531) from slot-ordered layers mpi [T,H,W,K,4]:
+    (sum |dx rgb|, sum |dy rgb|, sum |dx a|, sum |dy a|) over frames, slots and neighbouring pixel pairs -- what the fused renders return as
+    `smooth_sums` without the layer tensor."""
+    c, a = mpi[..., :-1], mpi[..., -1]
+    return torch.stack([(c[:, :, :-1] - c[:, :, 1:]).abs().sum(), (c[:, :-1] - c[:, 1:]).abs().sum(),
+                        (a[:, :, :-1] - a[:, :, 1:]).abs().sum(), (a[:, :-1] - a[:, 1:]).abs().sum()])

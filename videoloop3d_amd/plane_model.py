@@ -26,6 +26,7 @@ def get_new_intrin(old_intrin, new_h_start, new_w_start):
 
 class PlaneModel(nn.Module):
     BASE_CONFIG = None       # the shipped configuration the `rgb_mlp_type` refusal cites
+    RGB_MLP_TYPES = ("direct",)      # the colour heads the class is built for (MPI.py:99-112, MPV.py:107-121)
 
     def __init__(self, args, H, W, ref_extrin, ref_intrin, near, far, pixel_center, texel_scale, atlas_exact):
         """MPI.py:36-63 / MPV.py:26-56: plane set-up and the reference camera; the subclass creates the texture."""
@@ -35,7 +36,8 @@ class PlaneModel(nn.Module):
         self.mpi_h, self.mpi_w = int(args.mpi_h_scale * H), int(args.mpi_w_scale * W)
         self.mpi_d, self.near, self.far = args.mpi_d, near, far
         self.H, self.W = H, W
-        if getattr(args, "rgb_mlp_type", "direct") != "direct":
+        self.rgb_mlp_type = getattr(args, "rgb_mlp_type", "direct")
+        if self.rgb_mlp_type not in self.RGB_MLP_TYPES:
             raise RuntimeError(f"rgbmlp_type = {args.rgb_mlp_type} not supported (shipped configs use 'direct', {self.BASE_CONFIG}:28)")
         ref_extrin, ref_intrin = np.asarray(ref_extrin), np.asarray(ref_intrin)
         assert ref_extrin.shape == (4, 4) and ref_intrin.shape == (3, 3)
@@ -106,19 +108,27 @@ class PlaneModel(nn.Module):
                 "self.tile_own": tile_ref if own else None}
 
     # ---- export to the reference's layout (MPI.py:207-261, MPV.py:290-341) -------------------------------------------------------
+    def _refuse_sh_export(self, what):
+        if self.rgb_mlp_type != "direct":
+            raise RuntimeError(f"{what}: the reference's atlas layout of a view-dependent model (rgb_mlp_type = {self.rgb_mlp_type!r}, 13 channels) is "
+                               "not written; state_dict() is this package's checkpoint and frontal_stack() the (D,1,Hs,Ws,4) picture save_texture shows")
+
     def reference_state_dict(self):
         """the state_dict of the REFERENCE's module for these weights: plane meshes + packed (static / dynamic) atlases."""
+        self._refuse_sh_export("reference_state_dict")
         self._flush_deferred_updates()
         from .export import reference_state_dict
         return reference_state_dict(self)
 
     def save_mesh(self, prefix):
         """MPI.py:223-240, MPV.py:306-323."""
+        self._refuse_sh_export("save_mesh")
         from .export import save_mesh
         return save_mesh(self, prefix, self.reference_state_dict())
 
     def save_texture(self, prefix):
         """MPI.py:242-261, MPV.py:325-341 (dynamic frames as PNG files: no imageio / ffmpeg here)."""
+        self._refuse_sh_export("save_texture")
         from .export import save_texture
         return save_texture(self, prefix, self.reference_state_dict())
 

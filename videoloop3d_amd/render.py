@@ -675,6 +675,98 @@ def render_planes_with_regularisers(stack, homos, H, W, spec: RenderSpec = Rende
                                bool(grad_culled_unwritten), fused_adam)
 
 
+SH_C0, SH_C1 = 0.28209479177387814, 0.4886025119029199      # utils_mpi.py:321-322
+
+
+def sh_ray_matrix(extrin, intrin):
+    """The ray matrix of the view-dependent colour head (MPI.py:512-513 on utils.py:182-193): M = inverse(E)[:3,:3] inverse(K), E [4,4] (or
+    [1,4,4]) the ref -> target extrinsic MPMesh.forward hands to render, K [3,3] the intrinsics of the call (the crop's) -> float32 [3,3] on
+    the host, formed in float64.  Pixel (x, y) of the H x W image (integer indices, no half pixel) looks along d = normalize(M (x, y, 1)^T),
+    in the reference camera's frame."""
+    E = torch.as_tensor(extrin).detach().to("cpu", torch.float64).reshape(4, 4)
+    K = torch.as_tensor(intrin).detach().to("cpu", torch.float64).reshape(3, 3)
+    return (torch.linalg.inv(E)[:3, :3] @ torch.linalg.inv(K)).to(torch.float32)
+
+
+def sh_basis(ray_m, H, W, window=(0, 0)):
+    """the degree-1 basis b = (C0, -C1 d_y, C1 d_z, -C1 d_x) [H,W,4] of every pixel of the H x W window at frame pixel `window` = (row0, col0)
+    (eval_sh_bases, utils_mpi.py:365-383, at the normalised rays of sh_ray_matrix), in torch on ray_m's device: the materialised-layer path and
+    the tests read it; the render kernels form it themselves."""
+    dev, dt = ray_m.device, ray_m.dtype
+    y, x = torch.meshgrid(torch.arange(H, device=dev, dtype=dt) + window[0], torch.arange(W, device=dev, dtype=dt) + window[1], indexing="ij")
+    d = torch.stack([x, y, torch.ones_like(x)], -1) @ ray_m.T
+    d = d / d.norm(dim=-1, keepdim=True)
+    return torch.stack([torch.full_like(d[..., 0], SH_C0), -SH_C1 * d[..., 1], SH_C1 * d[..., 2], -SH_C1 * d[..., 0]], -1)
+
+
+class _RenderPlanesSH(torch.autograd.Function):
+    """render_planes with the view-dependent colour head (vl3d_render_sh_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, stack, stack_sh, homos, ray_m, H, W, spec, row0, col0, quad_keep, with_alpha_sums):
+        ctx.set_materialize_grads(False)
+        L.check_cuda(stack, stack_sh, homos, ray_m)
+        if stack.dim() != 5 or stack.shape[1] != 1 or stack.shape[4] != 4 or stack.dtype != torch.float32:
+            raise RuntimeError(f"render_planes_sh: stack must be float32 (D,1,Hs,Ws,4), got {tuple(stack.shape)} {stack.dtype}")
+        D, _, Hs, Ws, _ = stack.shape
+        if tuple(stack_sh.shape) != (D, 1, Hs, Ws, 3, 4) or stack_sh.dtype != torch.float32 or stack_sh.device != stack.device:
+            raise RuntimeError(f"render_planes_sh: stack_sh must be float32 (D,1,Hs,Ws,3,4) = {(D, 1, Hs, Ws, 3, 4)} on the stack's device, "
+                               f"got {tuple(stack_sh.shape)} {stack_sh.dtype}")
+        if tuple(homos.shape) != (D, 3, 3):
+            raise RuntimeError(f"homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
+        if tuple(ray_m.shape) != (3, 3):
+            raise RuntimeError(f"ray_m must be [3,3] (render.sh_ray_matrix), got {tuple(ray_m.shape)}")
+        if getattr(spec, "tile", (0, 0))[0]:
+            raise RuntimeError("render_planes_sh: the tile-exact layout is not built for the view-dependent colour head")
+        if quad_keep is not None:
+            quad_keep = _quad_map(quad_keep, D)
+        stack, stack_sh = stack.contiguous(), stack_sh.contiguous()
+        homos = homos.detach().to(torch.float32).contiguous()
+        ray_m = ray_m.detach().to(torch.float32).contiguous()
+        rgb, alpha = _out_buffers(None, 1, H, W, stack.device, "render_planes_sh")
+        asum = torch.empty((1, H, W, 2), dtype=torch.float32, device=stack.device) if with_alpha_sums else None
+        ctx.nothing_to_render = H == 0 or W == 0
+        if ctx.nothing_to_render:
+            ctx.save_for_backward(stack, stack_sh)
+            return rgb, alpha, (asum if with_alpha_sums else torch.zeros((0,), dtype=torch.float32, device=stack.device))
+        desc = _desc(stack, H, W, spec, row0, col0)
+        with torch.cuda.device(stack.device):
+            L.check(L.lib().vl3d_render_sh_fwd(desc, L.ptr(stack), L.ptr(stack_sh), L.ptr(homos), L.ptr(ray_m), *_qmap(quad_keep, spec),
+                                               L.ptr(rgb), L.ptr(alpha), L.ptr(asum), L.stream_ptr(stack.device)), "vl3d_render_sh_fwd")
+        ctx.save_for_backward(stack, stack_sh, homos, ray_m, rgb, alpha)
+        ctx.quad_keep, ctx.spec, ctx.desc, ctx.with_alpha_sums = quad_keep, spec, desc, with_alpha_sums
+        return rgb, alpha, (asum if with_alpha_sums else torch.zeros((0,), dtype=torch.float32, device=stack.device))
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_alpha, g_asum):
+        if ctx.nothing_to_render:
+            stack, stack_sh = ctx.saved_tensors
+            return (torch.zeros_like(stack), torch.zeros_like(stack_sh)) + (None,) * 9
+        stack, stack_sh, homos, ray_m, rgb, alpha = ctx.saved_tensors
+        g_rgb = g_rgb.contiguous() if g_rgb is not None else torch.zeros_like(rgb)
+        g_alpha = g_alpha.contiguous() if g_alpha is not None else None
+        g_asum = g_asum.to(torch.float32).contiguous() if (ctx.with_alpha_sums and g_asum is not None) else None
+        g_stack, g_sh = torch.empty_like(stack), torch.empty_like(stack_sh)      # (cleared by the entry: the sums are atomic)
+        with torch.cuda.device(stack.device):
+            L.check(L.lib().vl3d_render_sh_bwd(ctx.desc, L.ptr(stack), L.ptr(stack_sh), L.ptr(homos), L.ptr(ray_m), *_qmap(ctx.quad_keep, ctx.spec),
+                                               L.ptr(rgb), L.ptr(alpha), L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_asum), L.ptr(g_stack), L.ptr(g_sh),
+                                               L.stream_ptr(stack.device)), "vl3d_render_sh_bwd")
+        return (g_stack, g_sh) + (None,) * 9
+
+
+def render_planes_sh(stack, stack_sh, homos, ray_m, H, W, spec: RenderSpec, quad_keep=None, with_alpha_sums=False, window=(0, 0)):
+    """render_planes of a static MPI (T = 1) with the view-dependent colour head of stage 1 (rgb_mlp_type = "rgb_sh"; MPI.py:512-537,
+    utils_mpi.py:50-61): stack (D,1,Hs,Ws,4) = (R0, G0, B0, alpha logit), stack_sh (D,1,Hs,Ws,3,4) with stack_sh[..., k - 1, c] the
+    coefficient k = 1..3 of colour c (lane 3 reserved: 0), homos [D,3,3], ray_m [3,3] on the device (sh_ray_matrix).  Per pixel the colour
+    logits are sum_k b_k sample(coef_k) with the degree-1 basis b of the pixel's normalised ray; everything else as render_planes in the
+    planar convention (RenderSpec.mpv(...), any activation pair, fp32).  `quad_keep` [D,QH,QW]: a tile-culled model (shared borders).
+    -> (rgb [1,H,W,3], alpha [1,H,W]) or, with_alpha_sums, (rgb, alpha, alpha_sums [1,H,W,2]).  Differentiable w.r.t. both stacks; the
+    gradient is summed with float atomics and is not bit-reproducible between runs; lane 3 of stack_sh's gradient is exactly 0."""
+    rgb, alpha, asum = _RenderPlanesSH.apply(stack, stack_sh, homos, ray_m, int(H), int(W), spec, int(window[0]), int(window[1]), quad_keep,
+                                             bool(with_alpha_sums))
+    return (rgb, alpha, asum) if with_alpha_sums else (rgb, alpha)
+
+
 class _RenderPlaneRows(torch.autograd.Function):
     """render_planes of a row band from PER-PLANE local rows (vl3d_render_fwd_plane_rows / _bwd_plane_rows): local row r of plane d is
     plane row plane_row0[d] + r; the gradient comes back in the same local layout, padding rows 0."""

@@ -2,7 +2,8 @@
 
 Mirrors the training part of /root/reference/train_3d.py: the crop dataset over one still image per view (:20-95), `run_iter` (:189-250:
 MPMesh.forward, the loop-mask entropy term, the scale-invariant MSE, the weighted regularisers, backward, step) and the epoch loop
-(:273-318) with its per-epoch tasks -- `sparsify_faces` + a new optimiser at `sparsify_epoch` (:282-285), the quadratic ramp of the
+(:273-318) with its per-epoch tasks -- `sparsify_faces` + a new optimiser at `sparsify_epoch` (:282-285), `direct2sh` + a new optimiser at `direct2sh_epoch`
+(:287-290), the quadratic ramp of the
 density weight (:292-293), the per-iteration learning rate (:303-306), a checkpoint `{'epoch_i', 'network_state_dict'}` every
 `i_weights` epochs (:311-318).  Differences: videos are tensors already on the device (no cv2 / DataLoader: crops are views of resident
 tensors), logging is left to the caller through `on_step`, and the image + loop-mask loss runs in the fused kernel pair of
@@ -197,6 +198,10 @@ def train(nerf, args, videos, poses, intrins, H, W, device="cuda:0", on_step=Non
             module.sparsify_faces(erode_num=int(getattr(args, "sparsify_erode", 2)), alpha_thresh=float(getattr(args, "sparsify_alpha_thresh", 0.03)))
             optimizer = module.get_optimizer()
             sparsified_at = epoch_i
+        if epoch_i == int(getattr(args, "direct2sh_epoch", -1)):                                 # train_3d.py:287-290
+            print("Converting direct to data_sh")
+            module.direct2sh()
+            optimizer = module.get_optimizer()
         pct = float(np.clip(epoch_i / (int(getattr(args, "density_loss_epoch", 0)) + 1), 0, 1))
         args.density_loss_weight = pct * pct * old_density_loss_weight
         for item_i in torch.randperm(len(dataset), generator=generator).tolist():           # DataLoader(dataset, 1, shuffle=True)
