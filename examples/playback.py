@@ -87,6 +87,17 @@ def run(full=False, outdir=None, dev="cuda:0", fps_out=None, trim=False):
             kinds = [k for k, _, _ in RV.path_segments(list(range(N)), rt, 64)]
             out[name]["calls"] = {k: kinds.count(k) for k in sorted(set(kinds))}
             out[name]["route"] = "render_display: uint8 frames stored by the render launches (frames8=)"
+    # the depth map beside the picture (render_video.render_disparity_frames): the float clip frame by frame, the baked models as path calls
+    maps = {}
+    for name, kw in (("float", {}), ("baked", {"baked": baked}), ("baked_pool", {"baked": pool})):
+        RV.render_disparity_frames(model, H, W, ext[:4], intr[:4], rt[:4], **kw)      # untimed
+        sync(); t0 = time.perf_counter()
+        maps[name] = RV.render_disparity_frames(model, H, W, ext, intr, rt, **kw)
+        sync(); dt = time.perf_counter() - t0
+        out[name]["disparity"] = {"frames_per_s": N / dt, "ms_per_frame": dt / N * 1e3, "min": float(maps[name].min()), "max": float(maps[name].max())}
+    out["pool_disparity_equals_baked_disparity"] = bool(torch.equal(maps["baked_pool"], maps["baked"]))
+    out["max_abs_disparity_baked_vs_float"] = float((maps["baked"] - maps["float"]).abs().max())
+    del maps
     mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
     out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
     out["pool_frames_equal_baked_frames"] = bool(torch.equal(frames["baked_pool"], frames["baked"]))

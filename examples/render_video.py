@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The offline renderer (scripts/script_render_video.py) on the device: frames per second of `videoloop3d_amd.render_video.render_frames`
 at 720p, D = 32, a 50-frame loop -- the spiral (a new camera per frame: one launch each, like the reference's loop) and a fixed view (`--v r0`:
-the loop's frames in batched calls).  Synthetic poses and weights."""
+the loop's frames in batched calls).  `--disparity`: also the depth maps of the same frames (`render_video.render_disparity_frames`), with
+the range of the map.  Synthetic poses and weights."""
 import json
 import os
 import sys
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 
-def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0"):
+def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=False):
     from videoloop3d_amd.MPV import MPMeshVid
     from videoloop3d_amd import render_video as RV
     dev = torch.device(dev)
@@ -42,11 +43,25 @@ def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0"):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         out[name] = {"frames": len(rt), "frames_per_s": len(rt) / dt, "ms_per_frame": dt / len(rt) * 1e3}
+        if disparity:
+            RV.render_disparity_frames(model, H, W, ve[:4], vi[:4], rt[:4])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dm = RV.render_disparity_frames(model, H, W, ve, vi, rt)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            out[name]["disparity"] = {"frames_per_s": len(rt) / dt, "ms_per_frame": dt / len(rt) * 1e3, "min": float(dm.min()), "max": float(dm.max()),
+                                      "inverse_far_near": [1.0 / far, 1.0 / near]}
+            del dm
     out["shape"] = f"{H}x{W}, D={planes}, T={frames}, planes {tuple(model.stack.shape[2:4])}, uint8 frames on the device"
     return out
 
 
 if __name__ == "__main__":
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--disparity", action="store_true", help="also render the depth maps of the frames and report their range")
+    a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run()))
+    print(json.dumps(run(disparity=a.disparity)))

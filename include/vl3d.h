@@ -218,6 +218,44 @@ int vl3d_render_fwd_baked_pool_times(const vl3d_render_desc *desc, const int32_t
                                      const float *homos, const vl3d_baked_times *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW,
                                      uint32_t culled_rgba8, void *cull_scratch, const vl3d_baked_out *out, vl3d_stream_t stream);
 
+/* Disparity (csrc/vl3d_render_disp.hip): the depth map beside the picture -- the reference's blend-weighted inverse view depth (MPV.py:385,
+ * 463-466, MPI.py:493-494, 563-566) -- from the float clip, the baked clip and the baked pool, without a layer tensor.  Forward only, no host
+ * synchronisation, kernels of their own: no colour entry above changes.
+ *   The rule.  Planar geometry makes the inverse view depth of plane k under output pixel (x, y) AFFINE in the pixel:
+ *         rho_k(x, y) = fmaf(rows[k][0], x + c, fmaf(rows[k][1], y + c, rows[k][2])),   x + c = (float)(col0 + x) + pixel_center, y likewise,
+ *     rows (D, 3) device fp32, 4-byte aligned, formed on the host (render.depth_rows: row_k = K^-T r3 / (z_k + r3 . t), r3 the third column
+ *     of the ref -> target rotation; any affine renormalisation of rho is folded into the rows, the kernel does not know about it).  With a_k
+ *     the covered alpha of plane k as the colour forward of the same source forms it, T_0 = 1, T_k = prod_{j<k} (1 - a_j), w_k = a_k T_k:
+ *         disp = sum_k w_k rho_k          alpha = sum_k w_k
+ *     one step per plane, nothing contracted but the one spelt fmaf: w = a T; disp = fmaf(w, rho, disp); alpha += w; T *= 1 - a.  Sample
+ *     position, hard cut, kept-quad test, tile-exact quad offset and tent weights are the float forward's own device functions: colour and
+ *     depth agree on every pixel's coverage.  One output pixel and one frame per thread: a frame does not depend, in its last bit, on the
+ *     run or path it is rendered in.  disp (N,H,W) fp32, N = desc->T; alpha (N,H,W) fp32 or NULL (not written).
+ *   desc: the planar convention only -- VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, uv_noise_seed = 0 (else VL3D_EUNSUPPORTED), variant = 0,
+ *     D <= 128.
+ *   vl3d_render_disp_fwd: frames frame0 .. frame0 + desc->T - 1 of a float clip (D, T_alloc, Hs, Ws, 4), fp32 or fp16, read in place as
+ *     vl3d_render_fwd_frames reads it; homos (D, 3, 3).  act_order VL3D_ACT_POST (VL3D_ACT_BAKED: VL3D_EUNSUPPORTED): a_k = alpha_act(the
+ *     bilinear blend of the four taps' alpha logits) * coverage, every alpha_act of the table with either dtype; rgb_act is not read and per
+ *     tap only the alpha lane (4 or 2 bytes) is loaded.  quad_keep NULL = a dense model, else vl3d_render_fwd_frames's map, grid (negative:
+ *     tile-exact layout), desc->cull_* window and vl3d_render_cull_scratch_bytes(desc) of scratch.
+ *   vl3d_render_disp_baked / _baked_pool: the sources of vl3d_render_fwd_baked / _pool and their selection vl3d_baked_frames, unchanged --
+ *     a run under homos (D, 3, 3) and rows (D, 3), or a path under homos (n_cams, D, 3, 3), rows (n_cams, D, 3), frame_cam, frame_t; scratch
+ *     sizes as there.  a_k = the bilinear blend of the decoded alpha bytes (blend<3> of csrc/vl3d_baked_core.h, no activation) * coverage: the
+ *     alpha written here has the bits of the float sink's alpha of the colour entry on the same call.  A tap in a pool block without storage
+ *     reads the alpha byte of culled_rgba8; the pool's output has the bits of the clip entry on the unpacked texels; a path frame whose camera
+ *     or frame is out of range stays unwritten.  There is no loop-time (vl3d_baked_times) form.
+ *   VL3D_EINVAL, nothing launched, with the colour entries' messages: a NULL disp, rows, homos or source, a misaligned source, rows or
+ *     output, D > 128, a run that leaves the clip, whatever check_baked_frames refuses, a bad quad grid. */
+int vl3d_render_disp_fwd(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
+                         const float *rows, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *disp, float *alpha,
+                         vl3d_stream_t stream);
+int vl3d_render_disp_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, const float *rows,
+                           const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW, void *cull_scratch, float *disp,
+                           float *alpha, vl3d_stream_t stream);
+int vl3d_render_disp_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos,
+                                const float *rows, const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                                uint32_t culled_rgba8, void *cull_scratch, float *disp, float *alpha, vl3d_stream_t stream);
+
 /* A viewer package's atlases -> the baked pool (csrc/vl3d_pool_from_atlas.hip; baked.open_viewer_package).  A package IS a baked pool in another
  * order: RGBA8 tiles of th x tw texels of the kept quads, static tiles once (static_atlas, As_h x As_w texels, row-major grid of
  * As_w / tw tiles per row), dynamic tiles per frame (dyn_atlas, Ad_h x Ad_w: the atlas of frame `frame`), culled quads absent.  The

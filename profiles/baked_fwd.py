@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open|trim] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open|trim|disparity] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -36,6 +36,13 @@ texels (the comparison of tests/test_gpu_baked_times.py, bound 1e-5); then the t
 the whole path.  Prints ms per frame (median, min .. max), (b) / (a) -- the condition is (b) median <= (a) median on every storage -- and
 (b) / (c).
 
+The DISPARITY leg (--legs disparity; not part of `all`): the depth map beside the picture (include/vl3d.h "Disparity").  First the float
+entry on the resident fp32 clip: (a) render_frame_run of the whole clip, (b) render_frame_run_disparity of it.  Then the spiral and the three
+storages of the path leg: (a) ONE render_path_baked / _pool call into the float sink, (b) ONE render_path_disparity_baked / _pool call.  The
+disparity call's alpha is compared with the colour call's by torch.equal first (the float entry: its zero pattern); the legs alternate round by
+round under HIP events that span whole calls.  Prints ms per frame (median, min .. max) and (b) / (a); the expectation to check is
+(b) median <= 1.05 (a) median -- the disparity call fetches the same texel lines, writes 8 instead of 16 bytes per pixel and computes less.
+
 The TRIM leg (--legs trim; not part of `all`): BakedPool.trimmed() on the culled pair's model, in whose FLOAT stack, before it is baked, the
 outermost --trim-invisible (0.25) of each plane's kept quads get the alpha logit -12 on the texels they can read and the outermost --trim-frozen
 (0.5) of its dynamic quads repeat frame 0 (the shares of quads and of texels are printed).  The report (blocks, slots, bytes, quads), the ms of
@@ -67,7 +74,7 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open", "trim"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open", "trim", "disparity"])
 ap.add_argument("--trim-invisible", type=float, default=0.25, help="--legs trim: the share of each plane's kept quads (the outermost of its blob) made invisible")
 ap.add_argument("--trim-frozen", type=float, default=0.5, help="--legs trim: the share of each plane's dynamic quads (the outermost) that repeat frame 0")
 ap.add_argument("--poses", type=int, default=120)
@@ -82,8 +89,9 @@ ge.build()
 from videoloop3d_amd import synth  # noqa: E402
 from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, display_frames, loop_times  # noqa: E402
 from videoloop3d_amd.packed import PackedLayout  # noqa: E402
-from videoloop3d_amd.render import (RenderSpec, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool, render_path_baked,  # noqa: E402
-                                    render_path_baked_pool, render_times_baked, render_times_baked_pool)
+from videoloop3d_amd.render import (RenderSpec, depth_rows, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool,  # noqa: E402
+                                    render_frame_run_disparity, render_path_baked, render_path_baked_pool, render_path_disparity_baked,
+                                    render_path_disparity_baked_pool, render_times_baked, render_times_baked_pool)
 from videoloop3d_amd.utils_mpi import compute_homography, make_depths  # noqa: E402
 
 assert torch.cuda.is_available(), "profiles/baked_fwd.py measures on the MI355X"
@@ -229,15 +237,36 @@ if a.legs in ("all", "culled"):
     res["pool_over_dense_culled"] = res["baked_pool"]["ms_median"] / res["baked_culled"]["ms_median"]
     print(f"pool render is {res['pool_over_dense_culled']:.3f}x the dense culled baked render's time (bar: <= 1.05)")
 
-if a.legs in ("path", "display", "times", "trim"):
+if a.legs == "disparity":
+    # the float entry while the fp32 clip is resident: the whole clip as one run, colour against disparity
+    rows1 = depth_rows(tar_e.double() @ torch.linalg.inv(ref_e.double()), Kt, make_depths(D, 1.0, 100.0).flip(0)).to(dev)
+    d_out = (torch.empty((T, H, W), device=dev), torch.empty((T, H, W), device=dev))
+    legs = {"a_colour": lambda: render_frame_run(stack, 0, T, homos, H, W, spec, out=out),
+            "b_disparity": lambda: render_frame_run_disparity(stack, 0, T, homos, rows1, H, W, spec, out=d_out)}
+    for f in legs.values():
+        f()
+    same = torch.equal(out[1] == 0, d_out[1] == 0)
+    ms, per = ab(legs)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    res["disparity"] = {"float": {"alpha_zero_pattern_equal": same, "covered_pixels": float((d_out[1] > 0).float().mean()), "max_disp": float(d_out[0].max()),
+                                  "disparity_over_colour": med["b_disparity"] / med["a_colour"], "expectation_le_1.05": bool(med["b_disparity"] <= 1.05 * med["a_colour"]),
+                                  "legs": {k: {"ms_per_frame_median": med[k] / T, "min": min(ms[k]) / T, "max": max(ms[k]) / T} for k in legs}}}
+    for k in legs:
+        print(f"disparity [float ] {k:12s} {med[k] / T:.4f} ms/frame ({min(ms[k]) / T:.4f} .. {max(ms[k]) / T:.4f}) over {a.rounds} rounds of {per} runs of {T}", flush=True)
+    print(f"disparity [float ] alpha zero pattern equal {same}; (b) / (a) {med['b_disparity'] / med['a_colour']:.3f} -> "
+          f"{'ok' if med['b_disparity'] <= 1.05 * med['a_colour'] else 'ABOVE 1.05'}", flush=True)
+    del d_out, legs
+
+if a.legs in ("path", "display", "times", "trim", "disparity"):
     import math
     del stack, out
     N = a.poses
-    hs = []
+    hs, es = [], []
     for i in range(N):                                    # the spiral of examples/playback.py around the benchmark camera's rotation
         ang = 2 * math.pi * i / N
         e = tar_e.clone()
         e[:3, 3] = torch.tensor([0.05 * math.cos(ang), 0.03 * math.sin(ang), 0.01 * math.sin(2 * ang)])
+        es.append(e)
         hs.append(compute_homography(ref_e[None], Kr[None], e[None], Kt[None], torch.tensor([0., 0., 1.]).expand(1, D, 3),
                                      make_depths(D, 1.0, 100.0).flip(0)[None])[0])
     path_homos = torch.stack(hs).float().to(dev)          # [N, D, 3, 3]
@@ -277,6 +306,34 @@ if a.legs == "path":
         print(f"path [{name:6s}] bit-equal {same}; loop {ml / N:.4f} ms/frame ({min(ms['loop']) / N:.4f} .. {max(ms['loop']) / N:.4f}), "
               f"path {mp / N:.4f} ms/frame ({min(ms['path']) / N:.4f} .. {max(ms['path']) / N:.4f}) over {a.rounds} rounds of {per} paths of {N}; "
               f"path / loop {mp / ml:.3f} -> {'ok' if mp <= ml else 'MISSED'}")
+if a.legs == "disparity":
+    to_ref = torch.linalg.inv(ref_e.double())
+    path_rows = depth_rows(torch.stack([e.double() @ to_ref for e in es]), Kt, make_depths(D, 1.0, 100.0).flip(0)).to(dev)      # [N, D, 3]
+    o_c = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    o_d = (torch.empty((N, H, W), device=dev), torch.empty((N, H, W), device=dev))
+    storages = {
+        "dense": (lambda: render_path_baked(baked, cam, ts, path_homos, H, W, spec, out=o_c),
+                  lambda: render_path_disparity_baked(baked, cam, ts, path_homos, path_rows, H, W, spec, out=o_d)),
+        "culled": (lambda: render_path_baked(dense, cam, ts, path_homos, H, W, spec, out=o_c, quad_keep=qk),
+                   lambda: render_path_disparity_baked(dense, cam, ts, path_homos, path_rows, H, W, spec, out=o_d, quad_keep=qk)),
+        "pool": (lambda: render_path_baked_pool(lay, pool, cam, ts, path_homos, H, W, spec, out=o_c, **kwp),
+                 lambda: render_path_disparity_baked_pool(lay, pool, cam, ts, path_homos, path_rows, H, W, spec, out=o_d, **kwp)),
+    }
+    res["disparity"]["poses"] = N
+    for name, (colour, disparity) in storages.items():
+        o_c[1].fill_(-1.0), o_d[1].fill_(-2.0)
+        colour()
+        disparity()
+        same = torch.equal(o_c[1], o_d[1])
+        ms, per = ab({"a_colour": colour, "b_disparity": disparity})
+        ma, mb = statistics.median(ms["a_colour"]), statistics.median(ms["b_disparity"])
+        res["disparity"][name] = {"alpha_bit_equal": same, "covered_pixels": float((o_d[1] > 0).float().mean()), "max_disp": float(o_d[0].max()),
+                                  "colour_ms_per_frame": {"median": ma / N, "min": min(ms["a_colour"]) / N, "max": max(ms["a_colour"]) / N},
+                                  "disparity_ms_per_frame": {"median": mb / N, "min": min(ms["b_disparity"]) / N, "max": max(ms["b_disparity"]) / N},
+                                  "disparity_over_colour": mb / ma, "expectation_le_1.05": bool(mb <= 1.05 * ma)}
+        print(f"disparity [{name:6s}] alpha bit-equal {same}; colour {ma / N:.4f} ms/frame ({min(ms['a_colour']) / N:.4f} .. {max(ms['a_colour']) / N:.4f}), "
+              f"disparity {mb / N:.4f} ms/frame ({min(ms['b_disparity']) / N:.4f} .. {max(ms['b_disparity']) / N:.4f}) over {a.rounds} rounds of {per} paths of {N}; "
+              f"(b) / (a) {mb / ma:.3f} -> {'ok' if mb <= 1.05 * ma else 'ABOVE 1.05'}", flush=True)
 if a.legs == "display":
     o_f = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
     f_a, f_3, f_4 = (torch.empty((N, H, W, c), dtype=torch.uint8, device=dev) for c in (3, 3, 4))

@@ -353,6 +353,12 @@ class MPMesh(PlaneModel):
             mask3d = LY.to_slots((lab * cov[None, :, None]).permute(0, 3, 4, 1, 2), cov)
         return mpi, bw, disp, mask3d
 
+    def _disparity_runs(self, ts):
+        """the one frame of a stage-1 model (the rgb_sh head included: its alpha lives in `stack`)"""
+        if ts is not None:
+            raise RuntimeError("render_disparity: a stage-1 model has one frame (ts=None)")
+        return [(self.stack.detach(), 0, 1)]
+
     def render(self, H, W, extrin, intrin, need_reg=False, need_layers=False, cat_label=True):
         """MPI.py:452-594 -> (rgbl [B,H,W,3|4], variables).  One fused render per view (the kernels share one camera per call).
         need_layers: also materialise `mpi` / `blend_weight` / `disp_norm` / `loopmask3d` (slow path; no shipped configuration reads them)."""

@@ -644,6 +644,22 @@ class MPMeshVid(PlaneModel):
             return self.stack
         return self.stack[:, torch.as_tensor(ts, device=self.stack.device).long()]
 
+    def _disparity_runs(self, ts):
+        """a dense, sparsified or tile-exact model: every run of consecutive frames of `ts` where it lies in the clip; a packed model: the
+        requested frames unpacked, as its evaluation render unpacks them (packed.unpack_frames), read as one run"""
+        tl = list(range(self.frm_num)) if ts is None else [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        if not tl or min(tl) < 0 or max(tl) >= self.frm_num:
+            raise IndexError(f"render_disparity: frames {tl} outside the model's {self.frm_num}")
+        if self.packed is not None:
+            return [(self.packed.unpack_frames(self.stack_pool.data, tl), 0, len(tl))]
+        clip, runs = self.stack.detach(), []
+        for t in tl:
+            if runs and runs[-1][1] + runs[-1][2] == t:
+                runs[-1] = (clip, runs[-1][1], runs[-1][2] + 1)
+            else:
+                runs.append((clip, t, 1))
+        return runs
+
     def render(self, H, W, extrin, intrin, ts, need_layers=False, need_smooth=False):
         """MPV.py:351-475 -> (rgb [T',H,W,3], variables).  `variables['mpi']`/`['blend_weight']` (the warped per-layer
         rgba, only consumed by the smoothness/sparsity regularisers) are materialised on demand with the unfused operators."""

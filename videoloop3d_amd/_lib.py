@@ -111,6 +111,10 @@ SIGNATURES = {
     "vl3d_render_fwd_baked_times": ([C.POINTER(RenderDesc), _P, _I32, _P, C.POINTER(BakedTimes), _P, _I32, _I32, _P, C.POINTER(BakedOut), _P], C.c_int),
     "vl3d_render_fwd_baked_pool_times": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, C.POINTER(BakedTimes), _P, _I32, _I32, C.c_uint32, _P,
                                           C.POINTER(BakedOut), _P], C.c_int),
+    "vl3d_render_disp_fwd": ([C.POINTER(RenderDesc), _P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_disp_baked": ([C.POINTER(RenderDesc), _P, _I32, _P, _P, C.POINTER(BakedFrames), _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
+    "vl3d_render_disp_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, C.POINTER(BakedFrames), _P, _I32, _I32, C.c_uint32, _P,
+                                     _P, _P, _P], C.c_int),
     "vl3d_pool_from_atlas_rgba8": ([_I32] * 8 + [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, C.c_uint32, _P, _P], C.c_int),
     "vl3d_baked_trim_scratch_bytes": ([_I32, _I32, _I32], C.c_int64),
     "vl3d_baked_trim_classify": ([_I32] * 4 + [_P, _P, _I64, C.c_uint32, _P, _I64, _P, _P, _P], C.c_int),

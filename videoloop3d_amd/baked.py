@@ -94,6 +94,11 @@ class _Camera:
         for name in ("ref_extrin", "ref_intrin_mpi", "planedepth"):
             setattr(self, name, getattr(module, name).detach().clone())
 
+    def depth_rows(self, extrins_to_ref, intrins):
+        """the affine rows of the planes' inverse view depth (render.depth_rows) under ref -> target extrinsics [C,4,4] / intrinsics [C,3,3]"""
+        from .render import depth_rows
+        return depth_rows(extrins_to_ref, intrins, self.planedepth)
+
 
 def path_cameras(camera, view_extrins, view_intrins):
     """the DISTINCT cameras of a path: (view_extrins [N,4,4] world-to-camera, view_intrins [N,3,3], host float tensors) -> (cam_of: for every
@@ -173,6 +178,42 @@ class _Baked:
         if bg is not None:
             rgb = rgb * alpha[..., None] + bg[None, None, None] * (-alpha[..., None] + 1)
         return rgb.permute(0, 3, 1, 2), alpha
+
+    @torch.no_grad()
+    def render_disparity(self, H, W, extrins, intrins, ts, max_batch=64):
+        """The depth maps of a camera path on the baked texels (render.render_path_disparity_baked / _pool; include/vl3d.h "Disparity"): N poses
+        (extrins [N,4,4] world-to-camera, intrins [N,3,3]), output frame i showing frame ts[i] -> (disp [N,H,W], alpha [N,H,W]) float32 on the
+        device: per pixel the colour composite's own blend weights (alpha has the bits of render_path's) times the inverse view depth of every
+        plane.  Equal poses share a camera (path_cameras); chunks of at most `max_batch` frames go as render_video.path_segments says -- a
+        chunk that is one run as one run call, any other as one path call -- with the same bits either way."""
+        from .render_video import path_segments
+        extrins = torch.as_tensor(extrins, dtype=torch.float32).cpu()
+        intrins = torch.as_tensor(intrins, dtype=torch.float32).cpu()
+        tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        n, dev = len(tl), self.device
+        if not (len(extrins) == len(intrins) == n):
+            raise RuntimeError(f"render_disparity: one pose and one frame per output frame ({len(extrins)} extrins, {len(intrins)} intrins, {n} frames)")
+        disp = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        alpha = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        if n == 0:
+            return disp, alpha
+        cam_of, homos = path_cameras(self.camera, extrins, intrins)
+        first = [cam_of.index(c) for c in range(len(homos))]      # a pose of every distinct camera
+        rows = self.camera.depth_rows(self.extrins_to_ref(extrins[first]), intrins[first])
+        both = torch.cat([homos.to(torch.float32).reshape(-1), rows.reshape(-1)])      # homographies and rows of every camera: one pinned copy
+        if dev.type == "cuda":
+            both = both.pin_memory().to(dev, non_blocking=True)
+        homos, rows = both[:homos.numel()].view(homos.shape), both[homos.numel():].view(rows.shape)
+        for kind, c0, c1 in path_segments(cam_of, tl, max_batch):
+            out = (disp[c0:c1], alpha[c0:c1])
+            if kind == "run":
+                if not (0 <= tl[c0] and tl[c1 - 1] < self.frm_num):
+                    raise IndexError(f"frame index {tl[c0]} .. {tl[c1 - 1]} outside the clip of {self.frm_num} frames")
+                self._disparity_run(tl[c0], c1 - c0, homos[cam_of[c0]], rows[cam_of[c0]], H, W, out)
+            else:
+                lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras: a slice of the path's
+                self._disparity_path([c - lo for c in cam_of[c0:c1]], tl[c0:c1], homos[lo:hi], rows[lo:hi], H, W, out)
+        return disp, alpha
 
     def display_bg(self):
         """bg_color parsed for the display frames: 3 floats, or None; "random" -- one draw per call, a float composite -- is refused."""
@@ -262,6 +303,14 @@ class BakedMPV(_Baked):
         return render_times_baked(self.texels, frame_cam, frame_time, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
                                   cull_scratch=cull_scratch, **display)
 
+    def _disparity_run(self, frame0, n, homos, rows, H, W, out):
+        from .render import render_frame_run_disparity_baked
+        return render_frame_run_disparity_baked(self.texels, frame0, n, homos, rows, H, W, self.spec, quad_keep=self.quad_keep, out=out)
+
+    def _disparity_path(self, frame_cam, frame_t, homos, rows, H, W, out):
+        from .render import render_path_disparity_baked
+        return render_path_disparity_baked(self.texels, frame_cam, frame_t, homos, rows, H, W, self.spec, quad_keep=self.quad_keep, out=out)
+
 
 class BakedPool(_Baked):
     """bake_pool(module)'s product: the playback model of a tile-culled model without a dense clip.  pool [n_slots * 64, 4] uint8 on the device
@@ -307,6 +356,16 @@ class BakedPool(_Baked):
         from .render import render_times_baked_pool
         return render_times_baked_pool(self.layout, self.pool, frame_cam, frame_time, homos, H, W, self.spec, out=out, quad_keep=self.quad_keep,
                                        culled_rgba8=self.culled_rgba8, cull_scratch=cull_scratch, **display)
+
+    def _disparity_run(self, frame0, n, homos, rows, H, W, out):
+        from .render import render_frame_run_disparity_baked_pool
+        return render_frame_run_disparity_baked_pool(self.layout, self.pool, frame0, n, homos, rows, H, W, self.spec, out=out,
+                                                     quad_keep=self.quad_keep, culled_rgba8=self.culled_rgba8)
+
+    def _disparity_path(self, frame_cam, frame_t, homos, rows, H, W, out):
+        from .render import render_path_disparity_baked_pool
+        return render_path_disparity_baked_pool(self.layout, self.pool, frame_cam, frame_t, homos, rows, H, W, self.spec, out=out,
+                                                quad_keep=self.quad_keep, culled_rgba8=self.culled_rgba8)
 
     @torch.no_grad()
     def unpack_frames(self, frames):

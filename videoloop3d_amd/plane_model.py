@@ -189,6 +189,47 @@ class PlaneModel(nn.Module):
             cache[name] = (key, buf.detach().to(dev))
         return cache[name][1]
 
+    # ---- disparity ---------------------------------------------------------------------------------------------------------
+    def _disparity_runs(self, ts):
+        """the requested frames as runs read in place: [(clip [D,T,Hs,Ws,4] on the device, frame0, n)], in the order of `ts`"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def render_disparity(self, H, W, extrin, intrin, ts=None, normalise=False, by_alpha=False):
+        """The depth map beside the picture (MPV.py:385, 463-466; MPI.py:493-494, 563-566: `disp_norm`): per pixel the colour composite's own
+        blend weights times the inverse view depth of every plane, from the render kernels (render.render_frame_run_disparity) -- no layer
+        tensor, for every layout render() takes in evaluation.  extrin ([4,4] or [B,4,4]) / intrin ([3,3] or [B,3,3]): the ref -> target
+        extrinsics and the intrinsics render() receives; `ts`: the frames of a video model (None: all).  normalise: stage 1's normalisation
+        between far and near (MPI.py:494); by_alpha: the weights divided by alpha (normalize_blendweight_fordepth, MPI.py:564-565).
+        -> (disp [N,H,W], alpha [N,H,W]) float32, N = views x frames.  Forward only."""
+        from .render import depth_rows, render_frame_run_disparity
+        if self.atlas_exact:
+            raise RuntimeError("render_disparity: atlas_exact is a parity mode of the reference's atlas sampling; the disparity kernels sample the "
+                               "plane stack (build the model without atlas_exact)")
+        if self.spec.act_order != "post":
+            raise RuntimeError("render_disparity: a model under the bake rule shows its baked texels: bake it (baked.bake / bake_pool) and call the "
+                               "playback model's render_disparity")
+        self._flush_deferred_updates()
+        extrin, intrin = torch.as_tensor(extrin).detach().cpu(), torch.as_tensor(intrin).detach().cpu()
+        extrin, intrin = extrin.reshape(-1, 4, 4), intrin.reshape(-1, 3, 3)
+        if len(intrin) != len(extrin):
+            raise RuntimeError(f"render_disparity: {len(extrin)} extrinsics and {len(intrin)} intrinsics")
+        qk = self.quad_keep if (self.is_sparse and getattr(self, "quad_keep", None) is not None) else None
+        runs = self._disparity_runs(ts)
+        disps, alphas = [], []
+        for b in range(len(extrin)):
+            homos = self.plane_homographies(extrin[b:b + 1], intrin[b:b + 1])
+            rows = depth_rows(extrin[b], intrin[b], self.planedepth, (self.near, self.far) if normalise else None)
+            for clip, frame0, n in runs:
+                d, a = render_frame_run_disparity(clip, frame0, n, homos.to(clip.device), rows, H, W, self.spec, quad_keep=qk)
+                disps.append(d)
+                alphas.append(a)
+        disp = disps[0] if len(disps) == 1 else torch.cat(disps)
+        alpha = alphas[0] if len(alphas) == 1 else torch.cat(alphas)
+        if by_alpha:
+            disp = disp / alpha.clamp_min(1e-10)
+        return disp, alpha
+
     # ---- render --------------------------------------------------------------------------------------------------------------
     def _composite_bg(self, rgb, alpha):
         """MPI.py:550-556, MPV.py:455-461 (as written): the render over args.bg_color ("" = none, "random" = one draw per call, "r#g#b")."""

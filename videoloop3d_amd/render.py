@@ -639,6 +639,141 @@ def render_times_baked_pool(layout, pool, frame_cam, frame_time, homos, H, W, sp
     return _baked_render(who, src, n, 0, path, homos, H, W, spec, out, frames8, bg, cull_scratch, by_time=True)
 
 
+# ---- disparity (include/vl3d.h "Disparity"; csrc/vl3d_render_disp.hip) -------------------------------------------------------------------
+def depth_rows(extrin, intrin, planedepth, normalise=None):
+    """The affine rows of the inverse view depth (MPV.py:385, MPI.py:493: 1 / zbuf of the planar mesh): for the ref -> target extrinsic
+    E = [R | t] that render() receives, the intrinsics K of the call (a crop's are the shifted ones) and plane depths z_k (plane 0 nearest),
+        rho_k(x, y) = row_k . (x + c, y + c, 1),   row_k = (K^-T r3) / (z_k + r3 . t),   r3 the third COLUMN of R, c the pixel centre,
+    formed on the host in float64.  extrin [4,4] with intrin [3,3] -> float32 [D,3]; extrin [C,4,4] with intrin [C,3,3] (or one [3,3] for all
+    cameras) -> [C,D,3].  `normalise` = (near, far): stage 1's normalisation (MPI.py:494), (rho - 1 / far) / (1 / near - 1 / far), folded into
+    the rows -- it is affine in rho, so the kernels do not know about it."""
+    E = torch.as_tensor(extrin).detach().to("cpu", torch.float64)
+    K = torch.as_tensor(intrin).detach().to("cpu", torch.float64)
+    z = torch.as_tensor(planedepth).detach().to("cpu", torch.float64).reshape(-1)
+    single = E.dim() == 2
+    if tuple(E.shape[-2:]) != (4, 4) or E.dim() not in (2, 3) or tuple(K.shape[-2:]) != (3, 3) or K.dim() not in (2, 3):
+        raise RuntimeError(f"depth_rows: extrin [4,4] or [C,4,4] and intrin [3,3] or [C,3,3], got {tuple(E.shape)} and {tuple(K.shape)}")
+    E = E.reshape(-1, 4, 4)
+    K = K.reshape(-1, 3, 3)
+    if K.shape[0] not in (1, E.shape[0]) or (single and K.shape[0] != 1):
+        raise RuntimeError(f"depth_rows: {E.shape[0]} extrinsics and {K.shape[0]} intrinsics")
+    r3, t = E[:, :3, 2], E[:, :3, 3]
+    num = (torch.linalg.inv(K).transpose(-1, -2) @ r3[..., None])[..., 0].expand(E.shape[0], 3)      # K^-T r3, [C,3]
+    rows = num[:, None, :] / (z[None, :] + (r3 * t).sum(-1)[:, None])[..., None]                      # [C,D,3]
+    if normalise is not None:
+        near, far = float(normalise[0]), float(normalise[1])
+        rows = rows.clone()
+        rows[..., 2] -= 1.0 / far
+        rows = rows / (1.0 / near - 1.0 / far)
+    rows = rows.to(torch.float32)
+    return rows[0] if single else rows
+
+
+def _disp_buffers(out, n, H, W, device, who):
+    """(disp [n,H,W], alpha [n,H,W]) float32: fresh, or the caller's `out` pair checked."""
+    if out is None:
+        return torch.empty((n, H, W), dtype=torch.float32, device=device), torch.empty((n, H, W), dtype=torch.float32, device=device)
+    disp, alpha = out
+    for b in (disp, alpha):
+        if not isinstance(b, torch.Tensor) or b.device != device or b.dtype != torch.float32 or tuple(b.shape) != (n, H, W) or not b.is_contiguous():
+            raise RuntimeError(f"{who}: `out` must be contiguous float32 (disp [n,H,W], alpha [n,H,W]) = [{n},{H},{W}] on the model's device")
+    return disp, alpha
+
+
+def _disp_rows(who, rows, homos, device):
+    """rows [D,3] beside homos [D,3,3], or [C,D,3] beside [C,D,3,3], as contiguous float32 on `device`"""
+    if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != tuple(homos.shape[:-2]) + (3,):
+        raise RuntimeError(f"{who}: rows must be {list(homos.shape[:-2]) + [3]} beside homos {list(homos.shape)} (render.depth_rows), "
+                           f"got {tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+    return rows.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def render_frame_run_disparity(stack, frame0, nframes, homos, rows, H, W, spec: RenderSpec, quad_keep=None, out=None):
+    """The disparity map of frames frame0 .. frame0 + nframes - 1 of the float clip `stack` [D,T,Hs,Ws,4] (float32 / float16), read in place
+    as render_frame_run reads it (vl3d_render_disp_fwd): per pixel sum_k w_k rho_k with the colour composite's own blend weights w_k and
+    rho_k = rows[k] . (x + c, y + c, 1) (depth_rows) -> (disp [n,H,W], alpha [n,H,W]) float32.  The planar convention only (RenderSpec.mpv(),
+    sample-then-activate), every alpha_act; `quad_keep` [D,QH,QW]: a tile-culled model.  Forward only."""
+    who = "render_frame_run_disparity"
+    L.check_cuda(stack, homos)
+    if stack.dim() != 5 or stack.shape[4] != 4 or not stack.is_contiguous() or stack.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"{who}: a contiguous float32 / float16 clip [D,T,Hs,Ws,4]")
+    D, T = stack.shape[:2]
+    _check_run(who, frame0, nframes, T, homos, D, "clip of")
+    if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
+        raise RuntimeError("RenderSpec.tile (tile-exact layout) belongs to a tile-culled model: pass its quad_keep map")
+    homos = homos.detach().to(torch.float32).contiguous()
+    rows = _disp_rows(who, rows, homos, stack.device)
+    desc = _desc(stack, H, W, spec, 0, 0)
+    desc.T = int(nframes)
+    disp, alpha = _disp_buffers(out, int(nframes), H, W, stack.device, who)
+    with torch.cuda.device(stack.device):
+        qk = None if quad_keep is None else _quad_map(quad_keep, D)
+        cull = None if qk is None else _cull_scratch(desc, stack.device)
+        L.check(L.lib().vl3d_render_disp_fwd(desc, L.ptr(stack), int(frame0), int(T), L.ptr(homos), L.ptr(rows), *_qmap(qk, spec), L.ptr(cull),
+                                             L.ptr(disp), L.ptr(alpha), L.stream_ptr(stack.device)), "vl3d_render_disp_fwd")
+    return disp, alpha
+
+
+def _baked_disparity(who, src, n, frame0, path, homos, rows, H, W, spec, out, cull_scratch=None):
+    """the one call of the four baked disparity renders: _baked_render with `rows` beside the homographies and (disp, alpha) for a sink"""
+    dev = src.device
+    homos = homos.detach().to(torch.float32).contiguous()
+    rows = _disp_rows(who, rows, homos, dev)
+    desc = _desc_dims(src.dims[0], n, src.dims[1], src.dims[2], H, W, spec, L.STACK_DTYPE["u8"])
+    sel, entry = L.BakedFrames(frame0=int(frame0)), src.entry.replace("vl3d_render_fwd_", "vl3d_render_disp_")
+    if path is not None:
+        sel.n_cams, sel.frame_cam, sel.frame_t = path[0], path[1][0].data_ptr(), path[1][1].data_ptr()
+    disp, alpha = _disp_buffers(out, n, H, W, dev, who)
+    with torch.cuda.device(dev):
+        cull = None
+        if src.qk is not None:
+            cull = _cull_scratch(desc, dev) if path is None else _path_cull_scratch(desc, path[0], dev, cull_scratch, who)
+        grid = (0, 0) if src.qk is None else _qgrid(src.qk, spec)
+        L.check(getattr(L.lib(), entry)(desc, *src.head, L.ptr(homos), L.ptr(rows), sel, L.ptr(src.qk), *grid, *src.culled, L.ptr(cull),
+                                        L.ptr(disp), L.ptr(alpha), L.stream_ptr(dev)), entry)
+    return disp, alpha
+
+
+def render_frame_run_disparity_baked(baked, frame0, nframes, homos, rows, H, W, spec: RenderSpec, quad_keep=None, out=None):
+    """render_frame_run_disparity on the baked clip of a playback model (vl3d_render_disp_baked): `baked`, the frames, `homos`, `quad_keep` as
+    render_frame_run_baked takes them, `rows` [D,3] (depth_rows).  Alpha is the bilinear blend of the decoded alpha bytes, nothing activated:
+    the alpha returned has the bits of render_frame_run_baked's.  -> (disp [n,H,W], alpha [n,H,W]) float32."""
+    who = "render_frame_run_disparity_baked"
+    T, src = _baked_dense(who, baked, homos, spec, quad_keep)
+    _check_run(who, frame0, nframes, T, homos, src.dims[0], "clip of")
+    return _baked_disparity(who, src, int(nframes), frame0, None, homos, rows, H, W, spec, out)
+
+
+def render_frame_run_disparity_baked_pool(layout, pool, frame0, nframes, homos, rows, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8):
+    """render_frame_run_disparity_baked from the baked POOL (vl3d_render_disp_baked_pool): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
+    render_frame_run_baked_pool takes them (a tap in a block without storage reads the alpha byte of culled_rgba8) -> the bits of
+    render_frame_run_disparity_baked on the unpacked texels."""
+    who = "render_frame_run_disparity_baked_pool"
+    T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
+    _check_run(who, frame0, nframes, T, homos, src.dims[0], "model's")
+    return _baked_disparity(who, src, int(nframes), frame0, None, homos, rows, H, W, spec, out)
+
+
+def render_path_disparity_baked(baked, frame_cam, frame_t, homos, rows, H, W, spec: RenderSpec, quad_keep=None, out=None, cull_scratch=None):
+    """The disparity maps of a camera path on the baked clip, one plan launch plus one render launch (vl3d_render_disp_baked with a path
+    selection): output frame i is frame frame_t[i] seen by camera frame_cam[i] of `homos` [C,D,3,3] and `rows` [C,D,3]; the indices are
+    range-checked here before they are uploaded (IndexError), as render_path_baked checks them.  -> (disp [N,H,W], alpha [N,H,W]) float32,
+    frame i bit-equal to render_frame_run_disparity_baked(baked, frame_t[i], 1, homos[frame_cam[i]], rows[frame_cam[i]], ...)."""
+    who = "render_path_disparity_baked"
+    T, src = _baked_dense(who, baked, homos, spec, quad_keep)
+    n, path = _check_path(who, frame_cam, frame_t, T, homos, src.dims[0], src.device)
+    return _baked_disparity(who, src, n, 0, path, homos, rows, H, W, spec, out, cull_scratch)
+
+
+def render_path_disparity_baked_pool(layout, pool, frame_cam, frame_t, homos, rows, H, W, spec: RenderSpec, out=None, *, quad_keep, culled_rgba8,
+                                     cull_scratch=None):
+    """render_path_disparity_baked from the baked POOL (vl3d_render_disp_baked_pool with a path selection)."""
+    who = "render_path_disparity_baked_pool"
+    T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
+    n, path = _check_path(who, frame_cam, frame_t, T, homos, src.dims[0], src.device)
+    return _baked_disparity(who, src, n, 0, path, homos, rows, H, W, spec, out, cull_scratch)
+
+
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,
                   fused_adam=None):
     """stack (D,T,Hs,Ws,4) pre-activation fp32 (plane 0 = nearest), homos [D,3,3] (target pixel -> plane pixel).

@@ -308,6 +308,32 @@ def render_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64
     return res
 
 
+@torch.no_grad()
+def render_disparity_frames(nerf, H, W, view_extrins, view_intrins, render_t, max_batch=64, baked=None):
+    """The depth maps of the frames render_frames renders: for every output frame the blend-weighted inverse view depth (MPV.py:385, 463-466)
+    from the disparity kernels -> float32 [N,H,W] on the model's device.  The float model: runs of frames with one camera are one call of
+    its `render_disparity` (at most `max_batch` frames; consecutive frames are read where they lie in the clip).  `baked` (baked.BakedMPV /
+    baked.BakedPool): the playback model's `render_disparity` -- chunks of `max_batch` frames as path or run calls (`path_segments`)."""
+    view_extrins = torch.as_tensor(np.asarray(view_extrins), dtype=torch.float32)
+    view_intrins = torch.as_tensor(np.asarray(view_intrins), dtype=torch.float32)
+    render_t = np.asarray(render_t).astype(np.int64).reshape(-1)[:len(view_extrins)]
+    n = len(render_t)
+    if baked is not None:
+        return baked.render_disparity(H, W, view_extrins[:n], view_intrins[:n], render_t, max_batch=max_batch)[0]
+    module = getattr(nerf, "module", nerf)
+    ref_inv = module._on(view_extrins.device, "ref_extrin")[None, ...].inverse().to(view_extrins.dtype)
+    out, i = [], 0
+    while i < n:
+        j = i + 1
+        while j < n and j - i < max_batch and torch.equal(view_extrins[j], view_extrins[i]) and torch.equal(view_intrins[j], view_intrins[i]):
+            j += 1
+        out.append(module.render_disparity(H, W, view_extrins[i:i + 1] @ ref_inv, view_intrins[i:i + 1], ts=render_t[i:j].tolist())[0])
+        i = j
+    if not out:
+        return torch.empty((0, H, W), dtype=torch.float32)
+    return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+
 def render_video(nerf, args, poses_bounds, ckpt=None, v="", t="", f=-1, render_scaling=1., factor=None):
     """The whole of script_render_video.evaluate() but the files: poses -> selection -> (optional) checkpoint -> frames.
     `nerf`: an MPMeshVid built with `reference_camera(...)` of the same poses; `ckpt`: a path or a loaded dict with 'network_state_dict'."""
