@@ -318,7 +318,12 @@ int vl3d_baked_trim_move(int32_t D, int32_t T, int32_t Hs, int32_t Ws, const int
  *   3  one frame per thread in 64 x 16 regions, the owner table built one texel per thread
  *   4  = 3 with the 3x3 gather everywhere (reference for the 2x2 gather of no-minification tiles, which must equal it bit for bit)
  *   5  one frame per thread in 32 x 16 regions (shipped planar convention; = 3 elsewhere)
- *   6 / 7  two frames per thread in 32 x 16 / 64 x 12 regions wherever 0 takes frame pairs WITHOUT regularisers; = 3 elsewhere
+ *   6 / 7  two frames per thread in 32 x 16 / 64 x 12 regions wherever 0 takes frame pairs WITHOUT regularisers; = 3 elsewhere.  7 is the
+ *      64 x 12 kernel that reads the per-call owner table (one uint16 per plane texel in `scratch`)
+ *   8  two frames per thread in 64 x 12 regions WITHOUT the owner table wherever 0 takes frame pairs without regularisers: every gather
+ *      thread computes its texel's owner pixel itself, the table region of `scratch` is not touched; = 0 elsewhere.  vl3d_render_bwd_choice
+ *      reports VL3D_BWD_PAIR12, 64 x 12 for 7 and 8 alike.  0 takes 8's kernel for fp32 stacks outside VL3D_COORD_UTILS_MPI and 7's otherwise (as measured:
+ *      BWD_PAIR12_AUTO_OWNERLESS_*, csrc/vl3d_render_bwd_choice.h)
  *   every other value = 3.  All of them produce the same gradient bits.
  * vl3d_render_bwd_mask: 3 / 4 the 64 x 16 regions, 1 atomics, every other value flat 64 x 8 regions (its default).  vl3d_render_bwd_adam: a
  * dense model (variant 0 only) rides the 32 x 16 frame pairs; a tile-culled one 32 x 16 one-frame regions, 64 x 16 with variant 3.

@@ -16,7 +16,8 @@ enum BwdPolicy : int {
     BWD_FLAT8,         // one frame per thread, flat 64 x 8 regions
     BWD_NARROW32,      // one frame per thread, 32 x 16 regions
     BWD_PAIRS32,       // frame pairs in 32 x 16 regions wherever BWD_AUTO takes frame pairs
-    BWD_PAIRS64X12,    // frame pairs in 64 x 12 regions wherever BWD_AUTO takes frame pairs
+    BWD_PAIRS64X12,    // frame pairs in 64 x 12 regions wherever BWD_AUTO takes frame pairs, WITH the owner table (render_bwd_pair12_k)
+    BWD_PAIRS64X12O,   // ... without the owner table (render_bwd_pair12o_k): every gather thread computes its texel's owner pixel
 };
 struct BwdSetting {
     BwdPolicy policy;
@@ -26,7 +27,8 @@ struct BwdSetting {
 
 // (entry point, desc->variant & 0xf) -> policy.  `tile_ok`: the caller passed vl3d_render_bwd_scratch_bytes() of scratch and no uv noise
 // (add_uv_noise: a jittered tap can leave the 1-pixel halo the owner-computes kernels stage -- the atomics kernel takes the call).
-//   vl3d_render_bwd (dense or with a quad map): 0 auto, 1 atomics, 2 flat 64 x 8, 5 narrow 32 x 16, 6 / 7 pairs 32 x 16 / 64 x 12, every other value 64 x 16
+//   vl3d_render_bwd (dense or with a quad map): 0 auto, 1 atomics, 2 flat 64 x 8, 5 narrow 32 x 16, 6 / 7 / 8 pairs 32 x 16 / 64 x 12 with the owner table / 64 x 12 without it,
+//                             every other value 64 x 16
 //   vl3d_render_bwd_mask:     1 atomics, 3 / 4 the 16 rows, every other value the flat 64 x 8 regions: 512 threads at that instantiation's
 //                             128-register budget are TWO workgroups per CU -- stage-1 iterations +3.3 % at the reference's crop, +2 % for a
 //                             720p frame (profiles/r05d_s1_mask_rows.txt), same bits
@@ -42,7 +44,7 @@ inline BwdSetting bwd_setting_of(int entry, int bv, bool tile_ok, bool has_quad_
     } else if (entry == VL3D_BWD_ENTRY_MASK) {
         s.policy = (bv == 3 || bv == 4) ? BWD_TILE16 : BWD_FLAT8;
     } else {
-        s.policy = bv == 0 ? BWD_AUTO : bv == 2 ? BWD_FLAT8 : bv == 5 ? BWD_NARROW32 : bv == 6 ? BWD_PAIRS32 : bv == 7 ? BWD_PAIRS64X12 : BWD_TILE16;
+        s.policy = bv == 0 ? BWD_AUTO : bv == 2 ? BWD_FLAT8 : bv == 5 ? BWD_NARROW32 : bv == 6 ? BWD_PAIRS32 : bv == 7 ? BWD_PAIRS64X12 : bv == 8 ? BWD_PAIRS64X12O : BWD_TILE16;
     }
     return s;
 }
@@ -70,12 +72,20 @@ inline int64_t bwd_max_tiles(int H, int W) {
     return tiles;
 }
 
+// what BWD_AUTO takes where rule 4 gives it the 64 x 12 frame pairs: the kernel without the owner table (true) or with it, by the stack's
+// texel type.  In process on one resident cfg3 stack (profiles/ab_inproc.py --variants 7,8,7): fp32 11.995 -> 11.634 ms (-3.0 %, 26x the
+// spread of the repeated leg); fp16 9.194 -> 9.457 ms (+2.9 %: half the bytes per texel, and the owner arithmetic is no longer hidden).
+// Measured under the planar convention; the utils_mpi cross-check convention keeps the table kernel whatever the type (its texel coordinates
+// cost a reciprocal more, and two of its table-free instantiations spill 12 bytes at the 80-register budget where the table kernel's do not)
+constexpr bool BWD_PAIR12_AUTO_OWNERLESS_F32 = true, BWD_PAIR12_AUTO_OWNERLESS_F16 = false;
+
 // ---- the choice -------------------------------------------------------------------------------------------------------------------------
 struct BwdChoice {
     int family;        // VL3D_BWD_ATOMICS | _TILE (render_bwd_tile_k) | _PAIR (render_bwd_pair_k) | _PAIR12 (render_bwd_pair12_k)
     BwdShape shape;    // (unread for VL3D_BWD_ATOMICS)
     bool reg, mask, adam, cull, f16;      // the instantiation: layer regularisers' 128-register build, fifth channel, fused step, quad map, fp16 texels
     bool owner4;       // the owner table is built four texels per thread (bwd_owner_table4_k)
+    bool ownerless;    // VL3D_BWD_PAIR12 only: no owner table (render_bwd_pair12o_k behind bwd_zero_unowned_k).  Internal: vl3d_bwd_choice does not show it
 };
 
 // what the launch switches on: the instantiations differ in these (CULL and F16 are arguments of the chosen launch)
@@ -95,13 +105,17 @@ struct BwdFacts {
 
 // First match wins.  The figures are the measurements each rule rests on.
 inline BwdChoice choose_bwd(const BwdFacts &f) {
-    const BwdPolicy p = f.set.policy;
     const bool sig = f.ract == VL3D_ACT_SIGMOID && f.aact == VL3D_ACT_SIGMOID;
+    // rule 4's own test (its comment is there): the calls that take the plain frame pairs
+    const bool fits = (int64_t)f.Hs * 100 <= (int64_t)f.H * 107 || (int64_t)f.Ws * 100 <= (int64_t)f.W * 107;
+    const bool plain_pairs = sig && f.T >= 2 && !f.qk && !f.adam && !f.mask && !f.reg && fits;
+    // variant 8 names a kernel of rule 4 only: everywhere else it is the default (6 and 7, older, are variant 3 there)
+    const BwdPolicy p = f.set.policy == BWD_PAIRS64X12O && !plain_pairs ? BWD_AUTO : f.set.policy;
     // the convention stage 1 and stage 2 ship (MPI.py / MPV.py planar path, sigmoid / sigmoid, fp32): the loop-mask channel, the fused step
     // and the narrow / flat one-frame shapes are built for it alone (the last three with 9-float plane records)
     const bool shipped = f.coord == VL3D_COORD_AFFINE && f.border == VL3D_BORDER_HARDCUT && f.order == VL3D_ACT_POST && sig && !f.f16;
     const bool shipped9 = shipped && f.plane_record == 9;
-    BwdChoice c{VL3D_BWD_TILE, BWD_64X16, false, false, false, false, false, false};
+    BwdChoice c{VL3D_BWD_TILE, BWD_64X16, false, false, false, false, false, false, false};
     // (a single frame: four texels per thread; the fused optimiser step keeps its per-texel records)
     c.owner4 = f.T == 1 && !f.adam && f.set.owner4;
     // 0
@@ -127,11 +141,15 @@ inline BwdChoice choose_bwd(const BwdFacts &f) {
         // 13.9 ms pairs): crops of a larger stack and the reference's 1.1x stacks keep the 64 x 16 tile kernel.
         // Two region shapes: 64 x 12 (62 x 10 owned, 768 threads; render_bwd_pair12_k) is the default, 32 x 16 the kernel it replaced there
         // (variant 6 keeps it: the A/B partner and the reference of the bitwise tests; variant 7 forces the 64 x 12 regions).
-        const bool fits = (int64_t)f.Hs * 100 <= (int64_t)f.H * 107 || (int64_t)f.Ws * 100 <= (int64_t)f.W * 107;
-        if ((p == BWD_AUTO || p == BWD_PAIRS32 || p == BWD_PAIRS64X12) && !f.reg && fits) {
+        // The 64 x 12 regions come with the owner table (render_bwd_pair12_k, variant 7) and without it (render_bwd_pair12o_k, variant 8: the
+        // gather computes each texel's owner pixel -- VALU the kernel has to spare for memory instructions it has not); BWD_PAIR12_AUTO_OWNERLESS_*
+        // say which of the two the default takes (docs/kernels/K2_render_backward.md, "64 x 12 pairs without the owner table").
+        if ((p == BWD_AUTO || p == BWD_PAIRS32 || p == BWD_PAIRS64X12 || p == BWD_PAIRS64X12O) && !f.reg && fits) {
             c.family = p == BWD_PAIRS32 ? VL3D_BWD_PAIR : VL3D_BWD_PAIR12;
             c.shape = p == BWD_PAIRS32 ? BWD_32X16 : BWD_64X12;
             c.f16 = f.f16;
+            c.ownerless = p == BWD_PAIRS64X12O ||
+                          (p == BWD_AUTO && f.coord != VL3D_COORD_UTILS_MPI && (f.f16 ? BWD_PAIR12_AUTO_OWNERLESS_F16 : BWD_PAIR12_AUTO_OWNERLESS_F32));
             return c;
         }
         // 5: with the layer regularisers the pair kernel wins at every stack size (round 3, in process: 15.7 ms against 20.0 ms for the

@@ -1934,15 +1934,37 @@ constexpr int PROWS = 16;      // region rows.  The region width PW is a templat
 // accumulators, two stores.  sg0 / sg1: staged gradients of frames t and t+1, st: staged texel coordinates (this plane's buffers).
 // ADAM: the owner applies the optimiser's step where it would have stored the gradient (vl3d_render_bwd_adam): (d, t0) = the plane and the
 // pair's first frame.
-template <int ORDER, int RACT, int AACT, bool F16, bool ADAM = false, int PW = 32, int PR = PROWS>
+// OWNERLESS (render_bwd_pair12o_k): no owner table -- the gather thread computes the texel's owner pixel itself, with the table pass's function
+// on the table pass's inputs (owner_pixel on the plan's inverse homography `hi`, rintf, clamp to the frame): the texel is this tile's iff that
+// pixel lies in the tile's interior [ix0, ix1] x [iy0, iy1], and its slot is the table's.  e0 / oplane / my_tile are not read.
+template <int ORDER, int RACT, int AACT, bool F16, bool ADAM = false, int PW = 32, int PR = PROWS, bool OWNERLESS = false>
 __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const float4 *sg0, const float4 *sg1, const float2 *st, int X0, int Y0,
                                                   int ww, int wh, bool apart, unsigned my_tile, unsigned e0, const unsigned short *oplane,
                                                   const char *plane0, char *gplane0, size_t f1, size_t frame_b, bool has1, int col, int row,
-                                                  int d = 0, int t0 = 0) {
+                                                  int d = 0, int t0 = 0, const float *hi = nullptr, int ix0 = 0, int ix1 = 0, int iy0 = 0,
+                                                  int iy1 = 0) {
     const unsigned win0 = (unsigned)(Y0 * a.Ws + X0);
+    // OWNERLESS: the frame's last column and row as floats in SGPRs (a conversion is a vector instruction: its result would hold a VGPR each)
+    [[maybe_unused]] float wmax = 0.0f, hmax = 0.0f;
+    if constexpr (OWNERLESS) {
+        wmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(a.W - 1))));
+        hmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(a.H - 1))));
+    }
     auto gather = [&](unsigned e, int wx, int wy, unsigned tix) {
         constexpr int SLOT_BITS = PW == 64 ? 10 : 9;      // PW * PR slots of the region (bwd_owner_table_k)
-        if ((e >> SLOT_BITS) != my_tile) return;
+        if constexpr (OWNERLESS) {      // (the table kernels' statements below stay as they were: their instantiations compile to the code they had)
+            // the window's origin as the compiler cannot see through: it otherwise forms (float)col0 and (float)row0 once per kernel and holds
+            // them in two VGPRs across the sweep, where this kernel has none to spare (80: two workgroups per CU) -- two conversions per texel
+            int c0 = a.col0, r0 = a.row0;
+            asm volatile("" : "+s"(c0), "+s"(r0));
+            float qx, qy;
+            owner_pixel(hi, (float)(X0 + wx), (float)(Y0 + wy), a.pc, c0, r0, qx, qy);
+            const int rx = (int)fminf(fmaxf(rintf(qx), 0.0f), wmax), ry = (int)fminf(fmaxf(rintf(qy), 0.0f), hmax);      // clamped to the frame, as the table pass
+            if (rx < ix0 || rx > ix1 || ry < iy0 || ry > iy1) return;
+            e = (unsigned)((ry - iy0 + BWD_HALO) * PW + (rx - ix0 + BWD_HALO));      // the table's slot, no tile code above it
+        } else {
+            if ((e >> SLOT_BITS) != my_tile) return;
+        }
         const int lc = (int)(e & ((1u << SLOT_BITS) - 1u));
         const f2 tau = f2{(float)(X0 + wx), (float)(Y0 + wy)};
         f4 acc0 = f4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
@@ -2006,14 +2028,16 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
                 const int wy = wy0 + r, wx = wxb + c;
                 if (c < necp && wx < ww && wy < rmain) {
                     const unsigned tix = win0 + (unsigned)(wy * a.Ws + wx);
-                    gather(oplane[tix], wx, wy, tix);
+                    if constexpr (OWNERLESS) gather(0u, wx, wy, tix);
+                    else gather(oplane[tix], wx, wy, tix);
                 }
             }
     }
     for (int wy = row + PR; wy < wh; wy += PR)
         for (int wx = col; wx < ww; wx += PW) {
             const unsigned tix = win0 + (unsigned)(wy * a.Ws + wx);
-            gather(oplane[tix], wx, wy, tix);
+            if constexpr (OWNERLESS) gather(0u, wx, wy, tix);
+            else gather(oplane[tix], wx, wy, tix);
         }
 }
 
@@ -2262,10 +2286,115 @@ __global__ __launch_bounds__(P12W * P12ROWS, 6) void render_bwd_pair12_k(RenderA
     }
 }
 
+// ... without the owner table (`variant` 8).  render_bwd_pair12_k has VALU to spare (active in 60-66 % of the SIMD cycles) and no memory to
+// spare: the table costs it one 2-byte load per thread and plane at the texture path's full per-instruction price, re-read by every frame
+// pair (1 of its 9.2 read instructions per wave and plane, 1.17 GB of FETCH_SIZE at cfg3), and the pre-pass 59 MB of stores; fp32 cfg3
+// 12.00 -> 11.63 ms in process, fp16 stacks 9.19 -> 9.46 (docs/kernels/K2_render_backward.md).  Here the gather thread computes its texel's owner pixel with
+// the table pass's own function on the table pass's inputs (pair_gather_plane<..., OWNERLESS>): the nine inverse-homography floats of the plane
+// arrive as scalar loads with the forward homography, the tile's interior is formed once per workgroup as bwd_windows_k forms it.  Same
+// partition of the texels, so the same gradient bits.  The sweep is render_bwd_pair12_k's, statement for statement; a kernel of its own because
+// tests/test_bwd_pair12_resources_cpu.py pins that one's six template parameters, and it stays the A/B partner.
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
+__global__ __launch_bounds__(P12W * P12ROWS, 6) void render_bwd_pair12o_k(RenderArgs a) {      // 6 waves per SIMD = 2 workgroups per CU: <= 80 VGPRs
+    constexpr int PW = P12W, PR = P12ROWS, PNT = PW * PR;
+    if (!reinterpret_cast<const int *>(a.plan)[0]) return;
+    __shared__ float4 s_g[2][2][PNT];   // [buffer][frame][pixel]
+    __shared__ float2 s_t[2][PNT];
+    const int tid = threadIdx.x, col = tid & (PW - 1), row = tid / PW;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_x = bid % a.tiles_x, rest = bid / a.tiles_x;
+    const int tile_y = rest % a.tiles_y, t0 = (rest / a.tiles_y) * 2;
+    const bool has1 = t0 + 1 < a.T;          // odd T: the last pair sweeps frame t0 twice and stores it once
+    const int rx0 = tile_x * (PW - 2) - 1, ry0 = tile_y * (PR - 2) - 1;
+    const int x = rx0 + col, y = ry0 + row;
+    const bool inimg = (x >= 0) && (x < a.W) && (y >= 0) && (y < a.H);
+    const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
+    // the pixels this tile owns (bwd_windows_k's ix0 .. iy1): a texel is gathered here iff its owner pixel is one of them
+    const int ix0 = tile_x * (PW - 2), ix1 = min(ix0 + (PW - 2) - 1, a.W - 1), iy0 = tile_y * (PR - 2), iy1 = min(iy0 + (PR - 2) - 1, a.H - 1);
+    constexpr size_t TEXB = F16 ? 8 : 16;
+    const size_t frame_b = (size_t)a.Hs * a.Ws * TEXB;
+    const size_t plane_stride_b = (size_t)a.T * frame_b;
+    const char *plane0 = reinterpret_cast<const char *>(a.stack) + (size_t)t0 * frame_b;
+    char *gplane0 = reinterpret_cast<char *>(a.g_stack) + (size_t)t0 * frame_b;
+    const size_t f1 = has1 ? frame_b : 0;
+    float Gr0 = 0.f, Gg0 = 0.f, Gb0 = 0.f, gA0 = 0.f, S0 = 0.f, Gr1 = 0.f, Gg1 = 0.f, Gb1 = 0.f, gA1 = 0.f, S1 = 0.f;
+    if (inimg) {
+        size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
+        Gr0 = a.g_rgb[pix * 3 + 0]; Gg0 = a.g_rgb[pix * 3 + 1]; Gb0 = a.g_rgb[pix * 3 + 2];
+        gA0 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
+        S0 = dot3p(Gr0, a.rgb[pix * 3 + 0], Gg0, a.rgb[pix * 3 + 1], Gb0, a.rgb[pix * 3 + 2], gA0 * a.alpha[pix]);
+        if (has1) pix += (size_t)a.H * a.W;
+        Gr1 = a.g_rgb[pix * 3 + 0]; Gg1 = a.g_rgb[pix * 3 + 1]; Gb1 = a.g_rgb[pix * 3 + 2];
+        gA1 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
+        S1 = dot3p(Gr1, a.rgb[pix * 3 + 0], Gg1, a.rgb[pix * 3 + 1], Gb1, a.rgb[pix * 3 + 2], gA1 * a.alpha[pix]);
+    }
+    float Tr0 = 1.0f, P0 = 0.0f, Tr1 = 1.0f, P1 = 0.0f;
+    const TapStep st = make_tap_step<F16>(a.Hs, a.Ws);
+    const unsigned my_tile_id = (unsigned)(tile_y * a.tiles_x + tile_x);
+    const cint_p wrec = (cint_p)a.plan + plan_win_off(a.D) + (size_t)my_tile_id * a.D * 4;
+    typedef typename TapVal<F16, ORDER>::type tapv_t;
+    const f4 ex = f4{0.f, 0.f, 0.f, 0.f};      // (no regularisers: VL3D_PAIR_GRAD's extra term, as in render_bwd_pair_k<REG = false>)
+    for (int d = 0; d < a.D; ++d, plane0 += plane_stride_b, gplane0 += plane_stride_b) {
+        float h[VL3D_HN], hi[9];
+        load_uniform(a.homos + VL3D_HS * d, h);
+        load_uniform(a.plan + PLAN_HDR + PLAN_REC * d, hi);      // the plan's inverse texel homography (bwd_plan_k): scalar loads, as h
+        const int X0 = wrec[4 * d], Y0 = wrec[4 * d + 1], wwh = wrec[4 * d + 2];
+        const int ww = wwh & 0xffff, wh = (wwh >> 16) & 0x3fff;
+        const bool apart = (wwh & 0x40000000) != 0;
+        const int buf = d & 1;
+        // sweep: one set of taps, two frames
+        float2 tc = make_float2(0.f, 0.f);
+        float4 gv0 = make_float4(0.f, 0.f, 0.f, 0.f), gv1 = gv0;
+        if (inimg) {
+            const Taps2 tp = make_taps2<COORD, BORDER>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
+            tapv_t tv0[4], tv1[4];
+            load_taps2<F16>(plane0, tp, st, tv0);
+            load_taps2<F16>(plane0 + f1, tp, st, tv1);
+            f4 pre0, pre1;
+            const f4 o0 = shade2<ORDER, RACT, AACT>(tp, tv0, &pre0);
+            const f4 o1 = shade2<ORDER, RACT, AACT>(tp, tv1, &pre1);
+            VL3D_PAIR_GRAD(o0, pre0, Gr0, Gg0, Gb0, gA0, S0, P0, Tr0, gv0, ex)
+            VL3D_PAIR_GRAD(o1, pre1, Gr1, Gg1, Gb1, gA1, S1, P1, Tr1, gv1, ex)
+            tc = make_float2(tp.tx, tp.ty);
+            if (!(tp.cov > 0.0f)) { gv0 = make_float4(0.f, 0.f, 0.f, 0.f); gv1 = gv0; }
+        }
+        s_t[buf][tid] = tc;
+        s_g[buf][0][tid] = gv0;
+        s_g[buf][1][tid] = gv1;
+        __syncthreads();
+        // gather: one set of weights, two accumulators; the owner of every texel computed in place
+        pair_gather_plane<ORDER, RACT, AACT, F16, false, PW, PR, true>(a, s_g[buf][0], s_g[buf][1], s_t[buf], X0, Y0, ww, wh, apart, 0u, 0u, nullptr,
+                                                                       plane0, gplane0, f1, frame_b, has1, col, row, d, t0, hi, ix0, ix1, iy0, iy1);
+    }
+}
+
 #undef VL3D_PAIR_GRAD
 
+// The pre-pass of render_bwd_pair12o_k: bwd_owner_table_k's zero fill alone -- the same `safe` test on the same owner pixel, the same thread ->
+// texel mapping and frame loop (other mappings: round 3, 15.8 -> 19.4 ms on a 1.1x stack), no table entry, no shuffles, no table stores.  Dense
+// stacks without the fused step or a loop mask: the frame pairs' calls (choose_bwd rule 4).
+__global__ __launch_bounds__(256) void bwd_zero_unowned_k(RenderArgs a) {
+    if (!reinterpret_cast<const int *>(a.plan)[0]) return;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int d = blockIdx.z;
+    if (x >= a.Ws || y >= a.Hs) return;
+    float qx, qy;      // (no quad map on this path: a texel's lattice position is its coordinate, as in the gather)
+    owner_pixel(a.plan + PLAN_HDR + PLAN_REC * d, (float)x, (float)y, a.pc, a.col0, a.row0, qx, qy);
+    const bool safe = (qx > 0.5f) && (qx < (float)a.W - 1.5f) && (qy > 0.5f) && (qy < (float)a.H - 1.5f);
+    if (safe) return;
+    const size_t frame = (size_t)a.Hs * a.Ws;
+    if (a.g_f16) {
+        float2 *g = reinterpret_cast<float2 *>(a.g_stack) + (size_t)d * a.T * frame + (size_t)y * a.Ws + x;
+        for (int t = 0; t < a.T; ++t, g += frame) *g = make_float2(0.f, 0.f);
+    } else {
+        float4 *g = reinterpret_cast<float4 *>(a.g_stack) + (size_t)d * a.T * frame + (size_t)y * a.Ws + x;
+        for (int t = 0; t < a.T; ++t, g += frame) *g = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
-void launch_pair12(const RenderArgs &a, hipStream_t s, const BwdChoice &) {
+void launch_pair12(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
     constexpr int SHAPE = BWD_64X12, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
     static_assert(P12W == BWD_REGIONS[SHAPE].width && P12ROWS == BWD_REGIONS[SHAPE].rows, "render_bwd_pair12_k's region is not the shape table's");
     RenderArgs b = a;
@@ -2273,10 +2402,15 @@ void launch_pair12(const RenderArgs &a, hipStream_t s, const BwdChoice &) {
     const int nwin = b.tiles_x * b.tiles_y * a.D;
     hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
                        reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
+    const dim3 grid((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), block(P12W * P12ROWS);
+    if (c.ownerless) {      // no owner table: the scratch's table region is not touched
+        hipLaunchKernelGGL(bwd_zero_unowned_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b);
+        hipLaunchKernelGGL((render_bwd_pair12o_k<COORD, BORDER, ORDER, RACT, AACT, F16>), grid, block, 0, s, b);
+        return;
+    }
     hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
                        const_cast<unsigned short *>(a.owner), P12W, bwd_slot_bits(SHAPE));
-    hipLaunchKernelGGL((render_bwd_pair12_k<COORD, BORDER, ORDER, RACT, AACT, F16>),
-                       dim3((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), dim3(P12W * P12ROWS), 0, s, b);
+    hipLaunchKernelGGL((render_bwd_pair12_k<COORD, BORDER, ORDER, RACT, AACT, F16>), grid, block, 0, s, b);
 }
 
 // =====================================================================================================
@@ -2435,7 +2569,7 @@ void launch_tile(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, REG, F16, false, false, false, RWT>), grid, block, 0, s, b);
 }
 
-// one signature for the three launch templates (the frame pairs read nothing of the choice: their instantiation is all of it)
+// one signature for the three launch templates (the 32 x 16 frame pairs read nothing of the choice: their instantiation is all of it; the 64 x 12 ones read `ownerless`)
 using BwdLauncher = void (*)(const RenderArgs &, hipStream_t, const BwdChoice &);
 
 // what choose_bwd() reads: a call's arguments and a compiled convention -- launch_t passes its template constants, vl3d_render_bwd_choice()
