@@ -737,6 +737,35 @@ void launch_reg_slots(const RenderArgs &a, hipStream_t s) {
 
 constexpr int TILE_X = 64, TILE_Y = 4;
 
+// The backward sweeps take the planes behind plane d from the stored forward outputs: (S - P) / (1 - a_d) = T_d sum_{j>d} a_j q_j prod_{d<i<j} (1 - a_i).
+// At a_d == 1 that quotient is 0 / 0 while the term is not: d w_j / d a_d = -w_j / (1 - a_d) stays finite as the weights behind an opaque
+// plane vanish.  A sigmoid alpha multiplies it by a (1 - a) = 0; the other activations (identity: a decoded viewer package, alpha 255 / 255)
+// do not.  This is the sum itself for one pixel, by a look-ahead over the planes behind -- `plane` is plane d + 1 at the pixel's frame.
+// Short of a_d == 1 the quotient amplifies the rounding of S and P -- stored fp32 outputs and a running fp32 sum, about 1e-7 together -- by
+// 1 / (1 - a_d), and without the factor a (1 - a) of a sigmoid nothing takes that back: with the look-ahead at a_d == 1 alone the gradient was
+// 5.3e-4 from the fp64 statement where an opaque texel block blends in with weight 1 - 2^-10, and 5.7 (of a gradient of 1) on a perspective view,
+// where the four weights of an opaque block sum to 1 - 6e-8 (docs/kernels/K2_render_backward.md, "Parity with the fp64 oracle").  So the
+// look-ahead takes every pixel with 1 - a_d < BEHIND_QUOTIENT_FROM (negative included: relu and abs alphas above 1); above it the quotient
+// amplifies by 8 at the most: measured 1.2e-6.
+// Only those pixels pay for it, and only in the instantiations without a sigmoid alpha; the sigmoid ones keep their code.
+constexpr float BEHIND_QUOTIENT_FROM = 0.125f;
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool CULL>
+__device__ __forceinline__ float composite_behind(const RenderArgs &a, int d, const char *plane, size_t plane_stride_b, float px, float py, TapStep st,
+                                               float Gr, float Gg, float Gb, float gA, unsigned uv_seed) {
+    float Tb = 1.0f, C = 0.0f;
+    for (int j = d + 1; j < a.D; ++j, plane += plane_stride_b) {
+        const Taps2 tp = make_taps2<COORD, BORDER>(a.homos + VL3D_HS * j, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy,
+                                                   CULL ? plane_cull(a, j) : QuadCull{nullptr, 0, 0, 0.f, 0.f, 0.f, 0.f, 0}, UvNoise{uv_seed, j});
+        if (tp.cov == 0.0f) continue;
+        typename TapVal<F16, ORDER>::type tv[4];
+        load_taps2<F16>(plane, tp, st, tv);
+        const f4 o = shade2<ORDER, RACT, AACT>(tp, tv);
+        C = fmaf(o.w * Tb, dot3p(Gr, o.x, Gg, o.y, Gb, o.z, gA), C);
+        Tb *= 1.0f - o.w;
+    }
+    return C;
+}
+
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool MASK = false>
 __global__ __launch_bounds__(TILE_X *TILE_Y) void render_bwd_k(RenderArgs a) {
     if (a.plan && reinterpret_cast<const int *>(a.plan)[0]) return;   // the tile path owns this call
@@ -761,6 +790,7 @@ __global__ __launch_bounds__(TILE_X *TILE_Y) void render_bwd_k(RenderArgs a) {
     const TapStep st = make_tap_step<F16>(a.Hs, a.Ws), gst = make_tap_step<false>(a.Hs, a.Ws);
     const float gL = MASK ? a.g_label[pix] : 0.0f;
     const size_t mframe = (size_t)a.Hs * a.Ws;
+    [[maybe_unused]] const size_t plane_stride_b = (size_t)a.T * a.Hs * a.Ws * TEXB;
     for (int d = 0; d < a.D; ++d, plane += (size_t)a.T * a.Hs * a.Ws * TEXB, gplane += (size_t)a.T * a.Hs * a.Ws * TEXB) {
         const Taps2 tp = make_taps2<COORD, BORDER>(a.homos + VL3D_HS * d, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d), UvNoise{a.uv_seed, d});
         if (tp.cov == 0.0f) continue;
@@ -782,8 +812,15 @@ __global__ __launch_bounds__(TILE_X *TILE_Y) void render_bwd_k(RenderArgs a) {
         }
         P = fmaf(w, q, P);
         const float om = 1.0f - o.w;
-        // dL/da_k = T_k q_k - (sum_{j>k} w_j q_j)/(1-a_k); everything behind a fully opaque plane has zero weight
-        const float behind = (om > 1e-12f) ? (S - P) * fast_rcp(om) : 0.0f;
+        // dL/da_k = T_k q_k - (sum_{j>k} w_j q_j)/(1-a_k); behind a fully opaque plane every weight is zero -- and under a sigmoid so is da/ds
+        float behind;
+        if constexpr (AACT != VL3D_ACT_SIGMOID) {
+            behind = om >= BEHIND_QUOTIENT_FROM ? (S - P) * fast_rcp(om)
+                                                : Tr * composite_behind<COORD, BORDER, ORDER, RACT, AACT, F16, true>(a, d, plane + plane_stride_b, plane_stride_b, px, py, st,
+                                                                                                                      Gr, Gg, Gb, gA, a.uv_seed);
+        } else {
+            behind = (om > 1e-12f) ? (S - P) * fast_rcp(om) : 0.0f;
+        }
         f4 go = f4{w * Gr, w * Gg, w * Gb, fmaf(Tr, q, -behind) + fmaf(gN2, o.w, gN1)};   // grad wrt activated (c, a)
         Tr *= om;
         if (a.g_reg) {   // smoothness regularisers: the signs the forward stored (hit-slot order)
@@ -1788,7 +1825,14 @@ __global__ __launch_bounds__(RWT *ROWS, ((REG || MASK || (CULL && COORD == VL3D_
             if constexpr (MASK) gm = gL * w * (msig * (1.0f - msig));
             P = fmaf(w, q, P);
             const float om = 1.0f - o.w;
-            const float behind = (om > 1e-12f) ? (S - P) * fast_rcp(om) : 0.0f;
+            float behind;
+            if constexpr (AACT != VL3D_ACT_SIGMOID) {      // (composite_behind: the quotient is no good near an opaque plane)
+                behind = om >= BEHIND_QUOTIENT_FROM ? (S - P) * fast_rcp(om)
+                                                    : Tr * composite_behind<COORD, BORDER, ORDER, RACT, AACT, F16, CULL>(a, d, plane + plane_stride_b, plane_stride_b, px, py, st,
+                                                                                                                          Gr, Gg, Gb, gA, 0u);
+            } else {
+                behind = (om > 1e-12f) ? (S - P) * fast_rcp(om) : 0.0f;
+            }
             // grad wrt activated (c, a); spelt exactly like VL3D_PAIR_GRAD of the frame-pair kernels (compared bit for bit)
             if constexpr (REG) sg.w += fmaf(gN2, o.w, gN1);
             gval = make_float4(fmaf(w, Gr, sg.x), fmaf(w, Gg, sg.y), fmaf(w, Gb, sg.z), fmaf(Tr, q, -behind) + sg.w);
@@ -2043,8 +2087,11 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
 
 // composite backward of one plane for one frame: o = activated sample (alpha already 0 where uncovered), pre = the
 // value before the activation, extra = the regularisers' part of the gradient w.r.t. the activated layer value (0 without them)
+// (the frame pairs are built and chosen for sigmoid / sigmoid alone -- launch_t's SIG, choose_bwd's `sig` -- where da/ds = a (1 - a) takes the
+// quotient's pole at a == 1 back; another alpha activation needs composite_behind here as in the one-frame sweeps)
 #define VL3D_PAIR_GRAD(o, pre, Gr, Gg, Gb, gA, S, P, Tr, gv, ex)                                                               \
     {                                                                                                                          \
+        static_assert(AACT == VL3D_ACT_SIGMOID, "frame pairs: sigmoid alpha only (see composite_behind)");                     \
         const float q = dot3p(Gr, o.x, Gg, o.y, Gb, o.z, gA);                                                                  \
         const float w = o.w * Tr;                                                                                              \
         P = fmaf(w, q, P);                                                                                                     \
