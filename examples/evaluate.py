@@ -3,7 +3,8 @@
 the reference's factor-2 frames (360 x 640), D = 32, a 50-frame loop, 2 test views with 60-frame gt clips (the model's own loop, its first 10
 frames again, plus noise of up to +-6 levels; the left half of every plane is static in time, so the loop mask has a static region).  Prints
 one JSON line: the dataset row of metrics.txt and the wall time of each stage (render, loop mask, static + dyn statistics, NN metrics per
-patch configuration), of a second run after a warm-up run.  Synthetic poses and weights."""
+patch configuration), of a second run after a warm-up run.  `--gt-y4m A.y4m,B.y4m`: the ground-truth clips come from YUV4MPEG2 files, one per
+test view (`y4m.videos_from_y4m`; frames of H x W), instead of the synthetic ones.  Synthetic poses and weights."""
 import json
 import os
 import sys
@@ -16,12 +17,19 @@ import numpy as np
 import torch
 
 
-def run(H=360, W=640, planes=32, frames=50, gt_frames=60, views=2, dev="cuda:0"):
+def run(H=360, W=640, planes=32, frames=50, gt_frames=60, views=2, dev="cuda:0", gt_y4m=None):
     from videoloop3d_amd import evaluations as E
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth
     from videoloop3d_amd.MPV import MPMeshVid
     dev = torch.device(dev)
+    gt_clips = None
+    if gt_y4m:
+        from videoloop3d_amd import y4m
+        gt_clips = y4m.videos_from_y4m(gt_y4m, dev)
+        views, gt_frames = len(gt_clips), len(gt_clips[0])
+        if any(tuple(c.shape[1:3]) != (H, W) for c in gt_clips):
+            raise ValueError(f"--gt-y4m: frames of {H} x {W} expected, got {[tuple(c.shape[1:3]) for c in gt_clips]}")
     rng = np.random.RandomState(3)
     rows = []
     for v in range(views):      # an LLFF poses_bounds array of full-resolution (2H x 2W) views: small rotations, positions on an arc
@@ -44,11 +52,13 @@ def run(H=360, W=640, planes=32, frames=50, gt_frames=60, views=2, dev="cuda:0")
         model.stack[:, :, :, :half] = model.stack[:, :1, :, :half].clone()
     vext = RV.pose2extrin_np(poses)
     videos = []
-    for v in range(views):
+    for v in range(0 if gt_clips is None else views, views):
         own = RV.render_frames(model, H, W, np.repeat(vext[v:v + 1], frames, 0), np.repeat(intrins[v:v + 1], frames, 0), np.arange(frames))
         clip = torch.cat([own, own[:gt_frames - frames]]).long()
         noise = (synth.hash_uniform(tuple(clip.shape), 70 + v, device=dev) * 13).long() - 6
         videos.append((clip + noise).clamp(0, 255).to(torch.uint8).cpu().numpy())
+    if gt_clips is not None:
+        videos = gt_clips
     out = {}
     with tempfile.TemporaryDirectory() as d:
         for rep in range(2):      # the first run warms up (code objects, allocator); the second is reported
@@ -70,6 +80,10 @@ def run(H=360, W=640, planes=32, frames=50, gt_frames=60, views=2, dev="cuda:0")
 
 
 if __name__ == "__main__":
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gt-y4m", default=None, metavar="A.y4m,B.y4m", help="ground-truth clips from YUV4MPEG2 files, one per test view")
+    a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run()))
+    print(json.dumps(run(gt_y4m=a.gt_y4m)))

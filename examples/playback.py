@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 
-def run(full=False, outdir=None, dev="cuda:0", fps_out=None, trim=False):
+def run(full=False, outdir=None, dev="cuda:0", fps_out=None, trim=False, y4m=None):
     from videoloop3d_amd import render_video as RV
     from videoloop3d_amd import synth, tiles
     from videoloop3d_amd.baked import bake, bake_pool, culled_texel_rgba8, open_viewer_package
@@ -87,6 +87,11 @@ def run(full=False, outdir=None, dev="cuda:0", fps_out=None, trim=False):
             kinds = [k for k, _, _ in RV.path_segments(list(range(N)), rt, 64)]
             out[name]["calls"] = {k: kinds.count(k) for k in sorted(set(kinds))}
             out[name]["route"] = "render_display: uint8 frames stored by the render launches (frames8=)"
+    if y4m:      # the baked spiral as a file any player opens (render_video.write_video: chunks of 64 frames through a y4m.Y4MWriter)
+        sync(); t0 = time.perf_counter()
+        n = RV.write_video(y4m, model, H, W, ext, intr, rt, fps=25, baked=baked)
+        dt = time.perf_counter() - t0
+        out["y4m"] = {"path": y4m, "frames": n, "bytes": os.path.getsize(y4m), "frames_per_s": n / dt}
     # the depth map beside the picture (render_video.render_disparity_frames): the float clip frame by frame, the baked models as path calls
     maps = {}
     for name, kw in (("float", {}), ("baked", {"baked": baked}), ("baked_pool", {"baked": pool})):
@@ -170,8 +175,9 @@ if __name__ == "__main__":
     ap.add_argument("--full", action="store_true")
     ap.add_argument("--out", default=None, help="directory for the viewer package (default: a temporary one)")
     ap.add_argument("--fps-out", type=float, default=None, help="also play the spiral retimed from 25 fps to this display rate (default: off)")
+    ap.add_argument("--y4m", default=None, metavar="PATH", help="also write the baked spiral to PATH as a YUV4MPEG2 (.y4m) file")
     ap.add_argument("--trim", action="store_true", help="also trim the pool (BakedPool.trimmed) and write the package with its quad maps")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run(a.full, a.out, fps_out=a.fps_out, trim=a.trim)))
+    print(json.dumps(run(a.full, a.out, fps_out=a.fps_out, trim=a.trim, y4m=a.y4m)))

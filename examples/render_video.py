@@ -2,7 +2,8 @@
 """The offline renderer (scripts/script_render_video.py) on the device: frames per second of `videoloop3d_amd.render_video.render_frames`
 at 720p, D = 32, a 50-frame loop -- the spiral (a new camera per frame: one launch each, like the reference's loop) and a fixed view (`--v r0`:
 the loop's frames in batched calls).  `--disparity`: also the depth maps of the same frames (`render_video.render_disparity_frames`), with
-the range of the map.  Synthetic poses and weights."""
+the range of the map.  `--y4m PATH`: also write the spiral to PATH as a YUV4MPEG2 file (`render_video.write_video`: any player opens it) and
+report the frames per second to the file.  Synthetic poses and weights."""
 import json
 import os
 import sys
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 
-def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=False):
+def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=False, y4m=None):
     from videoloop3d_amd.MPV import MPMeshVid
     from videoloop3d_amd import render_video as RV
     dev = torch.device(dev)
@@ -53,6 +54,13 @@ def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=Fa
             out[name]["disparity"] = {"frames_per_s": len(rt) / dt, "ms_per_frame": dt / len(rt) * 1e3, "min": float(dm.min()), "max": float(dm.max()),
                                       "inverse_far_near": [1.0 / far, 1.0 / near]}
             del dm
+        if y4m and name == "spiral":
+            del fr
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = RV.write_video(y4m, model, H, W, ve, vi, rt, fps=25)
+            dt = time.perf_counter() - t0      # (write_video returns with the file closed)
+            out[name]["y4m"] = {"path": y4m, "frames": n, "bytes": os.path.getsize(y4m), "frames_per_s": n / dt}
     out["shape"] = f"{H}x{W}, D={planes}, T={frames}, planes {tuple(model.stack.shape[2:4])}, uint8 frames on the device"
     return out
 
@@ -61,7 +69,8 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--disparity", action="store_true", help="also render the depth maps of the frames and report their range")
+    ap.add_argument("--y4m", default=None, metavar="PATH", help="also write the spiral to PATH as a YUV4MPEG2 (.y4m) file")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run(disparity=a.disparity)))
+    print(json.dumps(run(disparity=a.disparity, y4m=a.y4m)))

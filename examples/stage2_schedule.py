@@ -41,7 +41,7 @@ def make_views(V, H, W, frames, dev):
 
 
 def run(views=8, epochs=2, planes=32, frames=50, clip=75, smooth=0.2, levels=3, dev="cuda:0", sparsify=False, fused=True, bwd_variant=0, generic_objective=False,
-        tile_exact=False):
+        tile_exact=False, gt_y4m=None):
     """tile_exact (with sparsify): the model in the TILE-EXACT layout a sparsified reference checkpoint is loaded into (every quad owns its tile,
     border texels included: 12 x 12 texels per quad of the 396 x 704 planes, MPI.py:296-313) instead of the shared-border pitch-1 stack."""
     from videoloop3d_amd.MPV import MPMeshVid
@@ -62,7 +62,15 @@ def run(views=8, epochs=2, planes=32, frames=50, clip=75, smooth=0.2, levels=3, 
         add_intrin_noise=True, mpi_h_verts=36, mpi_w_verts=64,
         generic_objective=bool(generic_objective),      # True: forward + weighted_total instead of MPMeshVid.objective (A/B)
         fused_adam_backward=bool(fused))      # dense models: the optimiser step inside the render backward (vl3d_render_bwd_adam)
+    if gt_y4m:      # the views' clips from YUV4MPEG2 files, one per view, frames of 360 x 640 (y4m.videos_from_y4m); the poses stay synthetic
+        from videoloop3d_amd import y4m
+        files = [p for p in gt_y4m.split(",") if p]
+        views = len(files)
     poses, intrins, vids = make_views(views, H, W, clip, dev)
+    if gt_y4m:
+        vids = y4m.videos_from_y4m(files, dev, layout="float")
+        if any(tuple(v.shape[-2:]) != (H, W) for v in vids):
+            raise ValueError(f"--gt-y4m: frames of {H} x {W} expected, got {[tuple(v.shape[-2:]) for v in vids]}")
     K = intrins[0].numpy()
     model = MPMeshVid(args, H, W, np.eye(4), K, 1.0, 100.0, device=dev).to(dev).train()
     if bwd_variant:      # A/B of the backward kernels (include/vl3d.h: desc->variant bits 0-3)
@@ -242,8 +250,9 @@ if __name__ == "__main__":
     ap.add_argument("--two-kernels", action="store_true", help="dense model: vl3d_render_bwd + the step kernel instead of the step inside the backward")
     ap.add_argument("--bwd-variant", type=int, default=0)
     ap.add_argument("--generic-objective", action="store_true", help="forward + weighted_total instead of MPMeshVid.objective")
+    ap.add_argument("--gt-y4m", default=None, metavar="A.y4m,B.y4m", help="the views' clips from YUV4MPEG2 files (one per view, 360 x 640) instead of synthetic ones")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
     print(json.dumps(run(a.views, a.epochs, sparsify=a.sparsify, fused=not a.two_kernels, bwd_variant=a.bwd_variant, generic_objective=a.generic_objective,
-                         tile_exact=a.tile_exact)))
+                         tile_exact=a.tile_exact, gt_y4m=a.gt_y4m)))

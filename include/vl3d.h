@@ -869,6 +869,49 @@ int64_t vl3d_eval_scratch_bytes(const vl3d_eval_desc *desc);
 int vl3d_eval_view(const vl3d_eval_desc *desc, const uint8_t *gt, const uint8_t *pred, const uint8_t *mask, int64_t mask_ones,
                    int64_t *sse, double *ssim_sum, int32_t *gt_min, double *dyn_sum, void *scratch, vl3d_stream_t stream);
 
+/* ---- Video I/O: 8-bit RGB frames <-> planar Y'CbCr as a YUV4MPEG2 payload holds it (docs/kernels/K10_video_io.md) ------------------------
+ * The reference reads and writes its clips through cv2 / imageio (dataloader.py, script_render_video.py:149); this project has neither and
+ * moves frames as .y4m files (videoloop3d_amd/y4m.py), whose only arithmetic is this conversion.  THE RULE is stated once, in integers, by
+ * y4m.rgb8_to_yuv8 / y4m.yuv8_to_rgb8; both entries store its bytes, byte for byte, on either path:
+ *   encode   byte = clamp((c0 R + c1 G + c2 B + offset 2^16 + 2^15) >> 16, 0, 255) with the integer rows of vl3d_video_coefs; 4:2:0 chroma
+ *            takes the SUMS of the 2 x 2 block (coordinates clamped at the right / bottom edge of an odd frame) and shifts by 18; chroma
+ *            planes are ceil(H/2) x ceil(W/2), centre sited.  The fourth channel of RGBA frames is not read.
+ *   decode   chroma upsampled bilinearly as 16 x chroma with clamped indices: per axis weights (3, 1) / 4 on the own sample and the
+ *            neighbour on the side of the luma coordinate's parity; siting_x LEFT horizontally (4, 0) / 4 on even and (2, 2) / 4 on odd
+ *            columns; 4:4:4: 16 c.  byte = clamp((cy (Y - y0) + cu (U16 - 2048) + cv (V16 - 2048) + 2^20) >> 21, 0, 255), int32 throughout.
+ *            Sink U8: uint8 [N,H,W,channels], a fourth channel is 255.  Sink F32: float [N,3,H,W] = byte / 255 (IEEE division).
+ * Frames: frame n of plane p starts at p + n * frame_stride; rows are tight (W bytes of luma, cw of chroma); the RGB side is dense.
+ * Two paths, the same bytes: WIDE -- a thread owns 16 luma pixels of 2 rows (1 row at 4:4:4) and moves them in 16- and 8-byte accesses,
+ * taken when W is a multiple of 16, H even (4:2:0), and every pointer and the stride are aligned for it; BYTE -- everything else, one
+ * byte per access.  desc->path = 1 forces the byte path; vl3d_video_choice tells which one a call takes (pure: nothing is launched).
+ * VL3D_EINVAL, nothing launched: a NULL descriptor, plane or frame pointer; channels outside {3, 4} (F32 sink: 3); N, H or W < 1; an unknown
+ * chroma, siting_x, matrix, full_range, sink or path; frame_stride below the frame's H W + 2 ch cw bytes; N H W above 2^31 - 1 (the grid
+ * limit); an F32 sink that is not 4-byte aligned. */
+enum { VL3D_CHROMA_444 = 0, VL3D_CHROMA_420 = 1 };
+enum { VL3D_SITING_CENTER = 0, VL3D_SITING_LEFT = 1 };      /* horizontal siting read by the decode (C420jpeg / C420mpeg2); the encode is centre sited */
+enum { VL3D_MATRIX_BT601 = 0, VL3D_MATRIX_BT709 = 1 };
+enum { VL3D_SINK_U8 = 0, VL3D_SINK_F32 = 1 };
+enum { VL3D_VIDEO_PATH_AUTO = 0, VL3D_VIDEO_PATH_BYTE = 1 };
+typedef struct vl3d_video_desc {
+    int32_t N, H, W, channels;                       /* frames, luma size, channels of the RGB side (3 / 4) */
+    int32_t chroma, siting_x, matrix, full_range;    /* VL3D_CHROMA_*, VL3D_SITING_* (decode only), VL3D_MATRIX_*, 0 limited / 1 full */
+    int32_t sink, path;                              /* decode: VL3D_SINK_*; VL3D_VIDEO_PATH_* */
+    uint8_t *y, *u, *v;                              /* frame 0 of each plane (read by the decode, written by the encode) */
+    int64_t frame_stride;                            /* bytes from a frame of a plane to the next, the same for all three */
+} vl3d_video_desc;
+typedef struct vl3d_video_path {
+    int32_t wide;                                    /* 1: the wide path, 0: the byte path */
+    int32_t strip, rows;                             /* luma pixels a thread owns: strip columns x rows */
+    int32_t threads, blocks;                         /* the launch: workgroup size, workgroups */
+} vl3d_video_path;
+/* The rule's integers for (matrix, full_range), as the kernels use them -- enc[12]: the 3 x 3 rows at 2^16 (Y, U, V), then the three offsets;
+ * dec[10]: per output channel (cy at 2^21, cu, cv at 2^17), then y0.  Pure host code. */
+int vl3d_video_coefs(int32_t matrix, int32_t full_range, int32_t *enc, int32_t *dec);
+/* rgb: the dense RGB side of the call (read by the encode, written by the decode); decode: 0 vl3d_rgb8_to_yuv8, 1 vl3d_yuv8_to_rgb. */
+int vl3d_video_choice(const vl3d_video_desc *desc, const void *rgb, int32_t decode, vl3d_video_path *out);
+int vl3d_rgb8_to_yuv8(const vl3d_video_desc *desc, const uint8_t *rgb, vl3d_stream_t stream);
+int vl3d_yuv8_to_rgb(const vl3d_video_desc *desc, void *rgb, vl3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

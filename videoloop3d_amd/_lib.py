@@ -98,6 +98,15 @@ class Stage1ObjectiveDesc(C.Structure):
                 ("smooth_coef", C.c_float * 4)]
 
 
+class VideoDesc(C.Structure):       # vl3d_video_desc: 72 bytes (10 x int32, 3 pointers, int64)
+    _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "channels", "chroma", "siting_x", "matrix", "full_range", "sink", "path")] \
+        + [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("frame_stride", C.c_int64)]
+
+
+class VideoChoice(C.Structure):     # vl3d_video_path: which path a video conversion takes (vl3d_video_choice)
+    _fields_ = [(n, C.c_int32) for n in ("wide", "strip", "rows", "threads", "blocks")]
+
+
 # symbol -> argtypes; every symbol include/vl3d.h declares must be listed here (tests/test_abi.py checks).
 SIGNATURES = {
     "vl3d_last_error": ([], C.c_char_p),
@@ -183,6 +192,10 @@ SIGNATURES = {
     "vl3d_robust_bwd": ([_I64, _P, _P, _I32, _F, _F, _P, _F, _P, _P], C.c_int),
     "vl3d_eval_scratch_bytes": ([C.POINTER(EvalDesc)], C.c_int64),
     "vl3d_eval_view": ([C.POINTER(EvalDesc), _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], C.c_int),
+    "vl3d_video_coefs": ([_I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+    "vl3d_video_choice": ([C.POINTER(VideoDesc), _P, _I32, C.POINTER(VideoChoice)], C.c_int),
+    "vl3d_rgb8_to_yuv8": ([C.POINTER(VideoDesc), _P, _P], C.c_int),
+    "vl3d_yuv8_to_rgb": ([C.POINTER(VideoDesc), _P, _P], C.c_int),
 }
 
 _lib = None

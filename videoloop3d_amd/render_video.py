@@ -347,3 +347,25 @@ def render_video(nerf, args, poses_bounds, ckpt=None, v="", t="", f=-1, render_s
         getattr(nerf, "module", nerf).init_from_mpi(sd['network_state_dict'])
     H, W = int(round(2 * intrins[0, 1, 2])), int(round(2 * intrins[0, 0, 2]))
     return render_frames(nerf, H, W, pose2extrin_np(vp), vi, rt)
+
+
+@torch.no_grad()
+def write_video(path, nerf, H, W, view_extrins, view_intrins, render_t, fps=25, baked=None, fractional=False, max_batch=64, **writer_kw):
+    """The files of script_render_video.evaluate() (`imageio.mimwrite(..., fps=25)`, script_render_video.py:149), as YUV4MPEG2: the frames of
+    `render_frames(nerf, H, W, view_extrins, view_intrins, render_t, baked=, fractional=)` written to `path` by a y4m.Y4MWriter, a segment
+    of at most `max_batch` frames at a time -- the path may be of any length, no more than two segments of it exist at once (the one being
+    rendered and the one on its way to the file).  `fps`: the rate in the file's header, a number or (n, d); with `fractional=True` it is
+    the display rate the loop times were made for (`retime(n, fps, ...)`).  `writer_kw`: chroma, matrix, full_range of the writer.
+    Returns the number of frames written."""
+    from .y4m import Y4MWriter
+    view_extrins = torch.as_tensor(np.asarray(view_extrins), dtype=torch.float32)
+    view_intrins = torch.as_tensor(np.asarray(view_intrins), dtype=torch.float32)
+    render_t = np.asarray(render_t, dtype=np.float64 if fractional else np.int64).reshape(-1)
+    n = min(len(render_t), len(view_extrins))      # script_render_video.py:129 loops over the poses
+    seg = max(1, int(max_batch))
+    with Y4MWriter(path, W, H, fps=fps, chunk=seg, **writer_kw) as out:
+        for i in range(0, n, seg):
+            j = min(n, i + seg)
+            out.write(render_frames(nerf, H, W, view_extrins[i:j], view_intrins[i:j], render_t[i:j], max_batch=seg, baked=baked,
+                                    fractional=fractional))
+    return n
