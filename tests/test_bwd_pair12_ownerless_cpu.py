@@ -1,42 +1,30 @@
-"""The 64 x 12 frame-pair backward without the owner table (render_bwd_pair12o_k, `variant` 8), without a GPU: what hipcc gives every
+"""The 64 x 12 frame-pair backward without the owner table (render_bwd_pair_k<..., BWD_64X12, OWNERLESS>, `variant` 8), without a GPU: what hipcc gives every
 instantiation of it -- the shape is only worth having while TWO 768-thread workgroups share a CU, the budget worked out in
 tests/test_bwd_pair12_resources_cpu.py: no scratch, at most 80 registers (6 waves per SIMD), at most half a CU's LDS -- and what the library's
 chooser says of variant 8: the 64 x 12 frame pairs wherever the default takes them, the default's own choice everywhere else."""
 import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "videoloop3d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from pair_kernel_resources import HIPCC, LDS_PER_CU, SHAPE_64X12, VGPR_BUDGET_64X12 as VGPR_BUDGET, pair_kernels
 
-VGPR_BUDGET = 80                 # 6 waves per SIMD: floor(512 / 80) = 6, floor(512 / 88) = 5
-LDS_PER_CU = 160 * 1024
+
+def ownerless_kernels(unit):
+    return [k for k in pair_kernels(unit) if k.shape == SHAPE_64X12 and k.ownerless]
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
 def test_ownerless_pair12_backward_fits_two_workgroups_per_cu():
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-             "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only"]
-    out = subprocess.run([HIPCC] + flags + ["-c", os.path.join(CSRC, "vl3d_render_c3_mpv_sig.hip"), "-o", os.devnull],
-                         capture_output=True, text=True).stderr
-    blocks = [b for b in re.split(r"remark: Function Name: ", out) if re.match(r"\w*render_bwd_pair12o_k", b)]
-    names = {b.split()[0] for b in blocks}
-    # fp32 and fp16 stacks of the shipped planar convention: render_bwd_pair12o_k<1,1,1,1,1,false> and <...,true>
-    assert any("ILi1ELi1ELi1ELi1ELi1ELb0EE" in n for n in names), f"the fp32 instantiation is missing: {sorted(names)}"
-    assert any("ILi1ELi1ELi1ELi1ELi1ELb1EE" in n for n in names), f"the fp16 instantiation is missing: {sorted(names)}"
-    for b in blocks:
-        name = b.split()[0]
-        num = lambda key: int(re.search(key + r": (\d+)", b).group(1))
-        vgprs, agprs, scratch = num("VGPRs"), num("AGPRs"), num(r"ScratchSize \[bytes/lane\]")
-        lds, occupancy = num(r"LDS Size \[bytes/block\]"), num(r"Occupancy \[waves/SIMD\]")
-        print(f"{name}: VGPRs {vgprs} AGPRs {agprs} scratch {scratch} LDS {lds} occupancy {occupancy}")
-        assert scratch == 0, name
-        assert vgprs + agprs <= VGPR_BUDGET, f"{name}: {vgprs} + {agprs} registers allocate more than 80: fewer than 6 waves per SIMD, one workgroup per CU"
-        assert lds <= LDS_PER_CU // 2, name
+    mine = ownerless_kernels("vl3d_render_c3_mpv_sig.hip")
+    # fp32 and fp16 stacks of the shipped planar convention: render_bwd_pair_k<1,1,1,1,1,false | true,false,false,BWD_64X12,true>
+    assert any(k.conv == (1, 1, 1, 1, 1) and not k.f16 for k in mine), f"the fp32 instantiation is missing: {sorted(k.name for k in mine)}"
+    assert any(k.conv == (1, 1, 1, 1, 1) and k.f16 for k in mine), f"the fp16 instantiation is missing: {sorted(k.name for k in mine)}"
+    for k in mine:
+        print(f"{k.name}: VGPRs {k.vgprs} AGPRs {k.agprs} scratch {k.scratch} LDS {k.lds} occupancy {k.occupancy}")
+        assert k.scratch == 0, k.name
+        assert k.vgprs + k.agprs <= VGPR_BUDGET, f"{k.name}: {k.vgprs} + {k.agprs} registers allocate more than 80: fewer than 6 waves per SIMD, one workgroup per CU"
+        assert k.lds <= LDS_PER_CU // 2, k.name
 
 
 # the other translation units that instantiate the kernel (sigmoid / sigmoid conventions): utils_mpi (zeros / pre, zeros / post, hardcut / pre),
@@ -51,26 +39,19 @@ def test_ownerless_pair12_backward_in_the_other_units():
     instantiation policy auto can take -- fp32 stacks of the planar coordinate convention (COORD = 1, F16 = false): plain, per-plane records,
     bake rule.  The instantiations only `variant` 8 reaches are NOT all clean, and this pins how far: hipcc spills <0,0,0,.,.,true> 12,
     <0,0,0,.,.,false> 12, <0,0,1,.,.,false> 20, <0,1,0,.,.,false> 16 and the baked fp16 <1,1,2,.,.,true> 12 bytes per lane at the 80-register
-    budget (render_bwd_pair12_k spills 12 / 0 / 0 / 8 / 0 there, and 8 in <0,1,0,.,.,true>) -- the reason the default keeps the table kernel
+    budget (with the owner table 12 / 0 / 0 / 8 / 0 there, and 8 in <0,1,0,.,.,true>) -- the reason the default keeps the table kernel
     for them (csrc/vl3d_render_bwd_choice.h).  More than 20 bytes anywhere is a regression."""
     from concurrent.futures import ThreadPoolExecutor
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-             "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only"]
-    run = lambda u: subprocess.run([HIPCC] + flags + ["-c", os.path.join(CSRC, u), "-o", os.devnull], capture_output=True, text=True).stderr
     with ThreadPoolExecutor(len(OTHER_UNITS)) as ex:
-        outs = list(ex.map(run, OTHER_UNITS))
+        found = list(ex.map(ownerless_kernels, OTHER_UNITS))
     seen = 0
-    for unit, out in zip(OTHER_UNITS, outs):
-        blocks = [b for b in re.split(r"remark: Function Name: ", out) if re.match(r"\w*render_bwd_pair12o_k", b)]
-        assert len({b.split()[0] for b in blocks}) == 2, f"{unit}: an fp32 and an fp16 instantiation"
-        for b in blocks:
-            name = b.split()[0]
-            num = lambda key: int(re.search(key + r": (\d+)", b).group(1))
-            vgprs, agprs, scratch, lds = num("VGPRs"), num("AGPRs"), num(r"ScratchSize \[bytes/lane\]"), num(r"LDS Size \[bytes/block\]")
-            print(f"{unit} {name}: VGPRs {vgprs} AGPRs {agprs} scratch {scratch} LDS {lds}")
-            assert vgprs + agprs <= VGPR_BUDGET and lds <= LDS_PER_CU // 2, name
-            default_can_take = "pair12o_kILi1E" in name and name.endswith("Lb0EEEvN18vl3d_render_detail10RenderArgsE")
-            assert scratch == 0 if default_can_take else scratch <= 20, f"{unit} {name}: {scratch} bytes of scratch"
+    for unit, mine in zip(OTHER_UNITS, found):
+        assert len({k.name for k in mine}) == 2 and {k.f16 for k in mine} == {False, True}, f"{unit}: an fp32 and an fp16 instantiation"
+        for k in mine:
+            print(f"{unit} {k.name}: VGPRs {k.vgprs} AGPRs {k.agprs} scratch {k.scratch} LDS {k.lds}")
+            assert k.vgprs + k.agprs <= VGPR_BUDGET and k.lds <= LDS_PER_CU // 2, k.name
+            default_can_take = k.conv[0] == 1 and not k.f16
+            assert k.scratch == 0 if default_can_take else k.scratch <= 20, f"{unit} {k.name}: {k.scratch} bytes of scratch"
             seen += 1
     assert seen == 2 * len(OTHER_UNITS)
 

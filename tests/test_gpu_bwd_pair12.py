@@ -1,5 +1,5 @@
-"""The frame-pair backward in 64 x 12-pixel regions (render_bwd_pair12_k, `variant` 7; the default wherever it measured faster) against the
-frame-pair backward in 32 x 16-pixel regions (render_bwd_pair_k, `variant` 6): per frame the same arithmetic in the same order, so the
+"""The frame-pair backward in 64 x 12-pixel regions (render_bwd_pair_k<..., BWD_64X12>, `variant` 7; the default wherever it measured faster) against the
+frame-pair backward in 32 x 16-pixel regions (the same kernel's BWD_32X16 instantiation, `variant` 6): per frame the same arithmetic in the same order, so the
 gradient has the SAME BITS -- over ragged and exact tile grids, frames smaller than one region, even and odd T, fp32 and fp16 stacks, stacks at
 the frame's size and at the 1.07x edge of the pair dispatch, with and without an alpha gradient, in both coordinate conventions."""
 import math

@@ -1,5 +1,5 @@
-"""The 64 x 12 frame-pair backward WITHOUT the owner table (render_bwd_pair12o_k, `variant` 8) against the two frame-pair kernels that read
-the table (render_bwd_pair12_k, `variant` 7; render_bwd_pair_k in 32 x 16 regions, `variant` 6).  The gather computes every texel's owner
+"""The 64 x 12 frame-pair backward WITHOUT the owner table (render_bwd_pair_k<..., BWD_64X12, OWNERLESS>, `variant` 8) against the two frame-pair kernels that read
+the table (the same kernel without OWNERLESS in 64 x 12 regions, `variant` 7, and in 32 x 16 regions, `variant` 6).  The gather computes every texel's owner
 pixel with the function the table pass uses, on the same inputs, so the partition of the texels -- and with it every bit of the gradient -- is
 the table kernels': one tile / a ragged grid / a frame smaller than a region, even and odd T, fp32 and fp16 stacks, stacks at the frame's
 size and at the 1.07x edge of the pair dispatch (windows wider and taller than the region: the strip and extra-row passes), a near-unit view
@@ -212,8 +212,8 @@ def test_the_owner_table_is_not_touched(dev):
                                                         ("utils_mpi", torch.float16, False)], ids=["mpv-f32", "mpv-f16", "utils_mpi-f32", "utils_mpi-f16"])
 def test_which_kernel_the_default_runs(dev, spec_name, dtype, table_free):
     """the exported choice reads (pair12, 64, 12) for both 64 x 12 kernels, so the default (variant 0) is told apart by what it leaves in a
-    scratch full of 0xA5: the table region untouched for fp32 stacks of the planar convention (render_bwd_pair12o_k), every entry written
-    for fp16 stacks and for the utils_mpi convention (render_bwd_pair12_k) -- csrc/vl3d_render_bwd_choice.h, BWD_PAIR12_AUTO_OWNERLESS_*"""
+    scratch full of 0xA5: the table region untouched for fp32 stacks of the planar convention (the OWNERLESS kernel), every entry written
+    for fp16 stacks and for the utils_mpi convention (the table kernel) -- csrc/vl3d_render_bwd_choice.h, BWD_PAIR12_AUTO_OWNERLESS_*"""
     D, T, H, W = 3, 2, 23, 70
     stack, homos, g_rgb, g_a, kw = _scene(dev, spec_name, H, W, 1.0, T, dtype, "half_degree", D)
     table_bytes = (D * H * W + 16 * W + 64) * 2

@@ -16,8 +16,8 @@ enum BwdPolicy : int {
     BWD_FLAT8,         // one frame per thread, flat 64 x 8 regions
     BWD_NARROW32,      // one frame per thread, 32 x 16 regions
     BWD_PAIRS32,       // frame pairs in 32 x 16 regions wherever BWD_AUTO takes frame pairs
-    BWD_PAIRS64X12,    // frame pairs in 64 x 12 regions wherever BWD_AUTO takes frame pairs, WITH the owner table (render_bwd_pair12_k)
-    BWD_PAIRS64X12O,   // ... without the owner table (render_bwd_pair12o_k): every gather thread computes its texel's owner pixel
+    BWD_PAIRS64X12,    // frame pairs in 64 x 12 regions wherever BWD_AUTO takes frame pairs, WITH the owner table (render_bwd_pair_k<..., BWD_64X12>)
+    BWD_PAIRS64X12O,   // ... without the owner table (its OWNERLESS instantiation): every gather thread computes its texel's owner pixel
 };
 struct BwdSetting {
     BwdPolicy policy;
@@ -81,11 +81,11 @@ constexpr bool BWD_PAIR12_AUTO_OWNERLESS_F32 = true, BWD_PAIR12_AUTO_OWNERLESS_F
 
 // ---- the choice -------------------------------------------------------------------------------------------------------------------------
 struct BwdChoice {
-    int family;        // VL3D_BWD_ATOMICS | _TILE (render_bwd_tile_k) | _PAIR (render_bwd_pair_k) | _PAIR12 (render_bwd_pair12_k)
+    int family;        // VL3D_BWD_ATOMICS | _TILE (render_bwd_tile_k) | _PAIR | _PAIR12 (render_bwd_pair_k in 32 x 16 | 64 x 12 regions)
     BwdShape shape;    // (unread for VL3D_BWD_ATOMICS)
     bool reg, mask, adam, cull, f16;      // the instantiation: layer regularisers' 128-register build, fifth channel, fused step, quad map, fp16 texels
     bool owner4;       // the owner table is built four texels per thread (bwd_owner_table4_k)
-    bool ownerless;    // VL3D_BWD_PAIR12 only: no owner table (render_bwd_pair12o_k behind bwd_zero_unowned_k).  Internal: vl3d_bwd_choice does not show it
+    bool ownerless;    // VL3D_BWD_PAIR12 only: no owner table (render_bwd_pair_k<..., OWNERLESS> behind bwd_zero_unowned_k).  Internal: vl3d_bwd_choice does not show it
 };
 
 // what the launch switches on: the instantiations differ in these (CULL and F16 are arguments of the chosen launch)
@@ -139,9 +139,9 @@ inline BwdChoice choose_bwd(const BwdFacts &f) {
         // than the frame (+7 %) -- full frames and row bands (dist.render_band: full width, rows = band + halo) of a stack at the frame's
         // resolution.  Beyond that the extra gather passes of the small tiles cost more than the pairs save (1.1x: 13.3 ms tile kernel,
         // 13.9 ms pairs): crops of a larger stack and the reference's 1.1x stacks keep the 64 x 16 tile kernel.
-        // Two region shapes: 64 x 12 (62 x 10 owned, 768 threads; render_bwd_pair12_k) is the default, 32 x 16 the kernel it replaced there
+        // Two region shapes: 64 x 12 (62 x 10 owned, 768 threads) is the default, 32 x 16 the kernel it replaced there
         // (variant 6 keeps it: the A/B partner and the reference of the bitwise tests; variant 7 forces the 64 x 12 regions).
-        // The 64 x 12 regions come with the owner table (render_bwd_pair12_k, variant 7) and without it (render_bwd_pair12o_k, variant 8: the
+        // The 64 x 12 regions come with the owner table (variant 7) and without it (render_bwd_pair_k's OWNERLESS instantiations, variant 8: the
         // gather computes each texel's owner pixel -- VALU the kernel has to spare for memory instructions it has not); BWD_PAIR12_AUTO_OWNERLESS_*
         // say which of the two the default takes (docs/kernels/K2_render_backward.md, "64 x 12 pairs without the owner table").
         if ((p == BWD_AUTO || p == BWD_PAIRS32 || p == BWD_PAIRS64X12 || p == BWD_PAIRS64X12O) && !f.reg && fits) {

@@ -1956,37 +1956,36 @@ __global__ __launch_bounds__(RWT *ROWS, ((REG || MASK || (CULL && COORD == VL3D_
 
 
 // =====================================================================================================
-// Backward, two frames per thread (dense stacks, no layer regularisers).  render_bwd_tile_k is VALU-issue bound, and almost
-// half of its instruction stream does not depend on the frame: the sweep's homography / divide / base tap / tents / coverage /
-// offset, the gather's owner decode and all of its tent weights.  A workgroup of this kernel owns a 30 x 14-pixel tile of
-// frames t and t+1 (32 x 16 region, 512 threads, 2 workgroups per CU at <= 128 VGPRs): one set of coordinates and weights,
-// two composite states, two staged gradients, two accumulators, two stores.  Per frame the arithmetic is that of
-// render_bwd_tile_k in the same order (same bits).  Pre-pass kernels, owner table and window records are shared (region
-// width 32 in the owner table's slots).
-//
-// Region shape: 32 x 16 pixels (30 x 14 owned).  Round 2 measured the flat 64 x 8 alternative in process on one resident stack
-// (profiles/ab_inproc.py): the memory pattern alone prefers 1-KiB row segments (profiles/microbench/rw_bw.hip `bwd_like`: 4.51 vs
-// 4.18 TB/s of algorithmic bytes), but its halo (x1.38 instead of x1.22 pixels swept per pixel owned) costs more than that:
-// 12.58 vs 11.96 ms.  An L2 prefetch of the next plane's tap rows in front of the barrier (4-byte LDS-DMA loads): +0.5 ms.
-constexpr int PROWS = 16;      // region rows.  The region width PW is a template parameter (PW * 16 threads): 32 is shipped; 64 -- 992-byte owner
-// segments, x1.18 instead of x1.22 pixels swept per pixel owned, but ONE 1024-thread workgroup per CU (80 KB LDS, <= 128 VGPRs) -- was built and
-// measured in round 4 (same bits): cfg3 13.3 against 12.6-12.9 ms, reference geometry 16.3 against 15.9, fused schedule 201 against 214 it/s:
-// with a single workgroup per CU nothing runs while its 16 waves meet at the per-plane barrier.  Not instantiated.
+// Backward, two frames per thread (dense stacks).  render_bwd_tile_k is VALU-issue bound, and almost half of its instruction stream
+// does not depend on the frame: the sweep's homography / divide / base tap / tents / coverage / offset, the gather's owner decode and
+// all of its tent weights.  A workgroup of render_bwd_pair_k owns one tile of frames t and t+1: one set of coordinates and weights,
+// two composite states, two staged gradients, two accumulators, two stores.  Per frame the arithmetic is that of render_bwd_tile_k in
+// the same order (same bits); pre-pass kernels, owner table and window records are shared.  One kernel, three uses (their earlier names and
+// measurements: docs/kernels/K2_render_backward.md, "one kernel, three uses", rounds 2, 4 and 7, "64 x 12 pairs without the owner table"):
+//   SHAPE = BWD_32X16 (30 x 14 owned, 512 threads, 2 workgroups per CU at <= 128 VGPRs): with the layer regularisers (REG), with the fused
+//     optimiser step (ADAM), and `variant` 6.  Measured against flat 64 x 8 regions (x1.38 instead of x1.22 pixels swept per pixel owned:
+//     12.58 vs 11.96 ms) and 64 x 16 ones (ONE 1024-thread workgroup per CU, idle at the per-plane barrier: 13.3 vs 12.6-12.9 ms).
+//   SHAPE = BWD_64X12 (62 x 10 owned, 768 threads; plain only, `variant` 7): 992- instead of 480-byte owner row segments (the pattern alone
+//     4.06 against 3.82 TB/s, profiles/microbench/rw_bw.hip w) and still TWO workgroups per CU (2 x 60 KB of LDS, <= 80 VGPRs for 6 waves per
+//     SIMD) at x1.24 swept per owned.  10-bit slots, 3 + 3 bits of tile code: tiles that share a code are 80 pixel rows apart.
+//   OWNERLESS (64 x 12 only, `variant` 8): no owner table, whose 2-byte load per thread and plane is 1.17 GB of fetches at cfg3 in a kernel
+//     with VALU to spare and no memory to spare.  The gather thread computes its texel's owner pixel with the table pass's function on the
+//     table pass's inputs (owner_pixel on the plan's inverse homography, rintf, clamp to the frame): the texel is this tile's iff that pixel
+//     lies in the tile's interior [ix0, ix1] x [iy0, iy1], and its slot is the table's -- the same partition, the same gradient bits; fp32
+//     cfg3 12.00 -> 11.63 ms, fp16 stacks 9.19 -> 9.46.  All of it sits behind `if constexpr`: the table kernels compile to the code they had.
+constexpr int pair_min_waves(int shape) { return shape == BWD_64X12 ? 6 : VL3D_PAIR_MIN_WAVES; }      // waves per SIMD the launch bound asks for
 
 // gather of one plane for a frame pair: every texel of the tile's window that the owner table assigns to this tile sums its taps
 // from the 3 x 3 (or, where pixels are >= 1 texel apart, 2 x 2) staged pixels around its owner pixel -- one set of weights, two
 // accumulators, two stores.  sg0 / sg1: staged gradients of frames t and t+1, st: staged texel coordinates (this plane's buffers).
 // ADAM: the owner applies the optimiser's step where it would have stored the gradient (vl3d_render_bwd_adam): (d, t0) = the plane and the
-// pair's first frame.
-// OWNERLESS (render_bwd_pair12o_k): no owner table -- the gather thread computes the texel's owner pixel itself, with the table pass's function
-// on the table pass's inputs (owner_pixel on the plan's inverse homography `hi`, rintf, clamp to the frame): the texel is this tile's iff that
-// pixel lies in the tile's interior [ix0, ix1] x [iy0, iy1], and its slot is the table's.  e0 / oplane / my_tile are not read.
-template <int ORDER, int RACT, int AACT, bool F16, bool ADAM = false, int PW = 32, int PR = PROWS, bool OWNERLESS = false>
+// pair's first frame.  OWNERLESS reads hinv and the interior, and not e0 / oplane / my_tile; the table kernels the reverse.
+template <int ORDER, int RACT, int AACT, bool F16, bool ADAM, BwdShape SHAPE, bool OWNERLESS>
 __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const float4 *sg0, const float4 *sg1, const float2 *st, int X0, int Y0,
                                                   int ww, int wh, bool apart, unsigned my_tile, unsigned e0, const unsigned short *oplane,
                                                   const char *plane0, char *gplane0, size_t f1, size_t frame_b, bool has1, int col, int row,
-                                                  int d = 0, int t0 = 0, const float *hi = nullptr, int ix0 = 0, int ix1 = 0, int iy0 = 0,
-                                                  int iy1 = 0) {
+                                                  int d, int t0, const float *hinv, int ix0, int ix1, int iy0, int iy1) {
+    constexpr int PW = BWD_REGIONS[SHAPE].width, PR = BWD_REGIONS[SHAPE].rows;
     const unsigned win0 = (unsigned)(Y0 * a.Ws + X0);
     // OWNERLESS: the frame's last column and row as floats in SGPRs (a conversion is a vector instruction: its result would hold a VGPR each)
     [[maybe_unused]] float wmax = 0.0f, hmax = 0.0f;
@@ -1995,14 +1994,14 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
         hmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(a.H - 1))));
     }
     auto gather = [&](unsigned e, int wx, int wy, unsigned tix) {
-        constexpr int SLOT_BITS = PW == 64 ? 10 : 9;      // PW * PR slots of the region (bwd_owner_table_k)
+        constexpr int SLOT_BITS = bwd_slot_bits(SHAPE);      // PW * PR slots of the region (bwd_owner_table_k)
         if constexpr (OWNERLESS) {      // (the table kernels' statements below stay as they were: their instantiations compile to the code they had)
             // the window's origin as the compiler cannot see through: it otherwise forms (float)col0 and (float)row0 once per kernel and holds
             // them in two VGPRs across the sweep, where this kernel has none to spare (80: two workgroups per CU) -- two conversions per texel
             int c0 = a.col0, r0 = a.row0;
             asm volatile("" : "+s"(c0), "+s"(r0));
             float qx, qy;
-            owner_pixel(hi, (float)(X0 + wx), (float)(Y0 + wy), a.pc, c0, r0, qx, qy);
+            owner_pixel(hinv, (float)(X0 + wx), (float)(Y0 + wy), a.pc, c0, r0, qx, qy);
             const int rx = (int)fminf(fmaxf(rintf(qx), 0.0f), wmax), ry = (int)fminf(fmaxf(rintf(qy), 0.0f), hmax);      // clamped to the frame, as the table pass
             if (rx < ix0 || rx > ix1 || ry < iy0 || ry > iy1) return;
             e = (unsigned)((ry - iy0 + BWD_HALO) * PW + (rx - ix0 + BWD_HALO));      // the table's slot, no tile code above it
@@ -2109,10 +2108,11 @@ __device__ __forceinline__ void pair_gather_plane(const RenderArgs &a, const flo
 // sparsity-sum gradient is gN1 + gN2 a_k.  Until round 3 this was a kernel of its own (render_bwd_pair_reg_k: 2-pixel halo, the
 // neighbours' layer values through a second LDS stage, sampling pipelined one plane ahead, 128 VGPRs, 18.2 ms at cfg3 against 12.0
 // without the regularisers -- VALU bound on re-deriving signs the forward had already formed).
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool REG = false, bool ADAM = false, int PW = 32>
-__global__ __launch_bounds__(PW * PROWS, VL3D_PAIR_MIN_WAVES) void render_bwd_pair_k(RenderArgs a) {      // >= 4 waves per SIMD (2 workgroups per CU at PW = 32): <= 128 VGPRs
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool REG, bool ADAM, BwdShape SHAPE, bool OWNERLESS>
+__global__ __launch_bounds__(BWD_REGIONS[SHAPE].width * BWD_REGIONS[SHAPE].rows, pair_min_waves(SHAPE)) void render_bwd_pair_k(RenderArgs a) {
+    // 32 x 16: >= 4 waves per SIMD = 2 workgroups per CU: <= 128 VGPRs; 64 x 12: 6 waves per SIMD = 2 workgroups per CU: <= 80 VGPRs
+    constexpr int PW = BWD_REGIONS[SHAPE].width, PR = BWD_REGIONS[SHAPE].rows, PNT = PW * PR, SLOT_BITS = bwd_slot_bits(SHAPE);
     static_assert(PW == 32 || PW == 64, "region width");
-    constexpr int PNT = PW * PROWS;
     if (!reinterpret_cast<const int *>(a.plan)[0]) return;
     __shared__ float4 s_g[2][2][PNT];   // [buffer][frame][pixel]
     __shared__ float2 s_t[2][PNT];
@@ -2121,10 +2121,15 @@ __global__ __launch_bounds__(PW * PROWS, VL3D_PAIR_MIN_WAVES) void render_bwd_pa
     const int tile_x = bid % a.tiles_x, rest = bid / a.tiles_x;
     const int tile_y = rest % a.tiles_y, t0 = (rest / a.tiles_y) * 2;
     const bool has1 = t0 + 1 < a.T;          // odd T: the last pair sweeps frame t0 twice and stores it once
-    const int rx0 = tile_x * (PW - 2) - 1, ry0 = tile_y * (PROWS - 2) - 1;
+    const int rx0 = tile_x * (PW - 2) - 1, ry0 = tile_y * (PR - 2) - 1;
     const int x = rx0 + col, y = ry0 + row;
     const bool inimg = (x >= 0) && (x < a.W) && (y >= 0) && (y < a.H);
     const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
+    // OWNERLESS: the pixels this tile owns (bwd_windows_k's ix0 .. iy1): a texel is gathered here iff its owner pixel is one of them
+    int ix0 = 0, ix1 = 0, iy0 = 0, iy1 = 0;
+    if constexpr (OWNERLESS) {      // (formed in here: in the open, REG's clamp shares its a.W - 1 and the REG instantiations compile differently)
+        ix0 = tile_x * (PW - 2); ix1 = min(ix0 + (PW - 2) - 1, a.W - 1); iy0 = tile_y * (PR - 2); iy1 = min(iy0 + (PR - 2) - 1, a.H - 1);
+    }
     constexpr size_t TEXB = F16 ? 8 : 16;
     const size_t frame_b = (size_t)a.Hs * a.Ws * TEXB;
     const size_t plane_stride_b = (size_t)a.T * frame_b;
@@ -2168,20 +2173,26 @@ __global__ __launch_bounds__(PW * PROWS, VL3D_PAIR_MIN_WAVES) void render_bwd_pa
     float Tr0 = 1.0f, P0 = 0.0f, Tr1 = 1.0f, P1 = 0.0f;
     const TapStep st = make_tap_step<F16>(a.Hs, a.Ws);
     const unsigned my_tile_id = (unsigned)(tile_y * a.tiles_x + tile_x);
-    // 9-bit slots (PW = 32): 4 + 3 bits of tile code; 10-bit slots (PW = 64): 3 + 3 (bwd_owner_table_k)
-    const unsigned my_tile = (unsigned)((tile_y & (PW == 64 ? 7 : 15)) << 3 | (tile_x & 7));
+    // the 16-bit table entry's tile code above the slot: 9-bit slots 4 + 3 bits (y, x), 10-bit slots 3 + 3 (bwd_owner_table_k)
+    const unsigned my_tile = (unsigned)((tile_y & ((1 << (16 - 3 - SLOT_BITS)) - 1)) << 3 | (tile_x & 7));
     const unsigned toff_thread = (unsigned)(row * a.Ws + col);
     const cint_p wrec = (cint_p)a.plan + plan_win_off(a.D) + (size_t)my_tile_id * a.D * 4;
     typedef typename TapVal<F16, ORDER>::type tapv_t;
     for (int d = 0; d < a.D; ++d, plane0 += plane_stride_b, gplane0 += plane_stride_b) {
         float h[VL3D_HN];
+        float hinv[9];
         load_uniform(a.homos + VL3D_HS * d, h);
+        if constexpr (OWNERLESS) load_uniform(a.plan + PLAN_HDR + PLAN_REC * d, hinv);      // the plan's inverse texel homography (bwd_plan_k): scalar loads, as h
         const int X0 = wrec[4 * d], Y0 = wrec[4 * d + 1], wwh = wrec[4 * d + 2];
         const int ww = wwh & 0xffff, wh = (wwh >> 16) & 0x3fff;
         const bool apart = (wwh & 0x40000000) != 0;
         const int buf = d & 1;
-        const unsigned short *oplane = a.owner + (size_t)d * a.Hs * a.Ws;
-        const unsigned e0 = oplane[(unsigned)(Y0 * a.Ws + X0) + toff_thread];     // unconditional (padded table), arrives in the shadow of the sweep
+        const unsigned short *oplane = nullptr;
+        unsigned e0 = 0u;
+        if constexpr (!OWNERLESS) {
+            oplane = a.owner + (size_t)d * a.Hs * a.Ws;
+            e0 = oplane[(unsigned)(Y0 * a.Ws + X0) + toff_thread];     // unconditional (padded table), arrives in the shadow of the sweep
+        }
         // sign words of this group of four planes (own, left, upper; two frames): requested with the taps of its first plane
         if constexpr (REG) if (reg_on && (d & 3) == 0 && !VL3D_REGAB(16)) {      // uniform
             const uint2 *w = sgp;      // (advanced by one group of planes below: no 64-bit multiply per group)
@@ -2229,195 +2240,14 @@ __global__ __launch_bounds__(PW * PROWS, VL3D_PAIR_MIN_WAVES) void render_bwd_pa
         s_g[buf][1][tid] = gv1;
         __syncthreads();
         // (3) gather: one set of weights, two accumulators
-        pair_gather_plane<ORDER, RACT, AACT, F16, ADAM, PW>(a, s_g[buf][0], s_g[buf][1], s_t[buf], X0, Y0, ww, wh, apart, my_tile, e0, oplane, plane0,
-                                                        gplane0, f1, frame_b, has1, col, row, d, t0);
-    }
-}
-
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16, bool REG = false, bool ADAM = false>
-void launch_pair(const RenderArgs &a, hipStream_t s, const BwdChoice &) {
-    constexpr int SHAPE = BWD_32X16, PW = BWD_REGIONS[SHAPE].width, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
-    static_assert(PROWS == BWD_REGIONS[SHAPE].rows, "render_bwd_pair_k's rows are not the shape table's");
-    RenderArgs b = a;
-    b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
-    const int nwin = b.tiles_x * b.tiles_y * a.D;
-    hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
-                       reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
-    hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
-                       const_cast<unsigned short *>(a.owner), PW, bwd_slot_bits(SHAPE));
-    hipLaunchKernelGGL((render_bwd_pair_k<COORD, BORDER, ORDER, RACT, AACT, F16, REG, ADAM, PW>),
-                       dim3((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), dim3(PW * PROWS), 0, s, b);
-}
-
-// Frame pairs in 64 x 12-pixel regions (62 x 10 owned, 768 threads): the plain pair kernel -- no layer regularisers, no fused optimiser
-// step -- in the shape its memory pattern prefers.  The owner's row segments are 992 bytes instead of 480 (fp16 stacks: 496 instead of 240):
-// profiles/microbench/rw_bw.hip w reads 4.06 against 3.82 TB/s for the pattern alone (8-byte texels 3.81 against 2.94).  Unlike the two
-// 64-wide shapes built before it keeps TWO workgroups per CU (2 x 768 threads, 2 x 60 KB of LDS, <= 80 VGPRs for 6 waves per SIMD) -- 64 x 16 x 2
-// ran alone on its CU -- at x1.24 pixels swept per pixel owned -- 64 x 8 x 2 swept x1.38.  Per frame the arithmetic is render_bwd_pair_k's,
-// instruction for instruction (same bits); the pre-pass kernels are shared (region width 64, 10-bit slots, 3 + 3 bits of tile code: tiles
-// that share a code are 8 steps = 80 pixel rows apart, more than the 48 of the flat 64 x 8 one-frame regions that use the same code).
-// A kernel of its own: render_bwd_pair_k's schedule is what tests/test_kernel_schedule_canary.py pins, and its template parameters stay.
-constexpr int P12W = 64, P12ROWS = 12;
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
-__global__ __launch_bounds__(P12W * P12ROWS, 6) void render_bwd_pair12_k(RenderArgs a) {      // 6 waves per SIMD = 2 workgroups per CU: <= 80 VGPRs
-    constexpr int PW = P12W, PR = P12ROWS, PNT = PW * PR;
-    if (!reinterpret_cast<const int *>(a.plan)[0]) return;
-    __shared__ float4 s_g[2][2][PNT];   // [buffer][frame][pixel]
-    __shared__ float2 s_t[2][PNT];
-    const int tid = threadIdx.x, col = tid & (PW - 1), row = tid / PW;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_x = bid % a.tiles_x, rest = bid / a.tiles_x;
-    const int tile_y = rest % a.tiles_y, t0 = (rest / a.tiles_y) * 2;
-    const bool has1 = t0 + 1 < a.T;          // odd T: the last pair sweeps frame t0 twice and stores it once
-    const int rx0 = tile_x * (PW - 2) - 1, ry0 = tile_y * (PR - 2) - 1;
-    const int x = rx0 + col, y = ry0 + row;
-    const bool inimg = (x >= 0) && (x < a.W) && (y >= 0) && (y < a.H);
-    const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
-    constexpr size_t TEXB = F16 ? 8 : 16;
-    const size_t frame_b = (size_t)a.Hs * a.Ws * TEXB;
-    const size_t plane_stride_b = (size_t)a.T * frame_b;
-    const char *plane0 = reinterpret_cast<const char *>(a.stack) + (size_t)t0 * frame_b;
-    char *gplane0 = reinterpret_cast<char *>(a.g_stack) + (size_t)t0 * frame_b;
-    const size_t f1 = has1 ? frame_b : 0;
-    float Gr0 = 0.f, Gg0 = 0.f, Gb0 = 0.f, gA0 = 0.f, S0 = 0.f, Gr1 = 0.f, Gg1 = 0.f, Gb1 = 0.f, gA1 = 0.f, S1 = 0.f;
-    if (inimg) {
-        size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
-        Gr0 = a.g_rgb[pix * 3 + 0]; Gg0 = a.g_rgb[pix * 3 + 1]; Gb0 = a.g_rgb[pix * 3 + 2];
-        gA0 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
-        S0 = dot3p(Gr0, a.rgb[pix * 3 + 0], Gg0, a.rgb[pix * 3 + 1], Gb0, a.rgb[pix * 3 + 2], gA0 * a.alpha[pix]);
-        if (has1) pix += (size_t)a.H * a.W;
-        Gr1 = a.g_rgb[pix * 3 + 0]; Gg1 = a.g_rgb[pix * 3 + 1]; Gb1 = a.g_rgb[pix * 3 + 2];
-        gA1 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
-        S1 = dot3p(Gr1, a.rgb[pix * 3 + 0], Gg1, a.rgb[pix * 3 + 1], Gb1, a.rgb[pix * 3 + 2], gA1 * a.alpha[pix]);
-    }
-    float Tr0 = 1.0f, P0 = 0.0f, Tr1 = 1.0f, P1 = 0.0f;
-    const TapStep st = make_tap_step<F16>(a.Hs, a.Ws);
-    const unsigned my_tile_id = (unsigned)(tile_y * a.tiles_x + tile_x);
-    const unsigned my_tile = (unsigned)((tile_y & 7) << 3 | (tile_x & 7));      // 10-bit slots: 3 + 3 bits of tile code (bwd_owner_table_k)
-    const unsigned toff_thread = (unsigned)(row * a.Ws + col);
-    const cint_p wrec = (cint_p)a.plan + plan_win_off(a.D) + (size_t)my_tile_id * a.D * 4;
-    typedef typename TapVal<F16, ORDER>::type tapv_t;
-    const f4 ex = f4{0.f, 0.f, 0.f, 0.f};      // (no regularisers: VL3D_PAIR_GRAD's extra term, as in render_bwd_pair_k<REG = false>)
-    for (int d = 0; d < a.D; ++d, plane0 += plane_stride_b, gplane0 += plane_stride_b) {
-        float h[VL3D_HN];
-        load_uniform(a.homos + VL3D_HS * d, h);
-        const int X0 = wrec[4 * d], Y0 = wrec[4 * d + 1], wwh = wrec[4 * d + 2];
-        const int ww = wwh & 0xffff, wh = (wwh >> 16) & 0x3fff;
-        const bool apart = (wwh & 0x40000000) != 0;
-        const int buf = d & 1;
-        const unsigned short *oplane = a.owner + (size_t)d * a.Hs * a.Ws;
-        const unsigned e0 = oplane[(unsigned)(Y0 * a.Ws + X0) + toff_thread];     // unconditional (padded table), arrives in the shadow of the sweep
-        // sweep: one set of taps, two frames
-        float2 tc = make_float2(0.f, 0.f);
-        float4 gv0 = make_float4(0.f, 0.f, 0.f, 0.f), gv1 = gv0;
-        if (inimg) {
-            const Taps2 tp = make_taps2<COORD, BORDER>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
-            tapv_t tv0[4], tv1[4];
-            load_taps2<F16>(plane0, tp, st, tv0);
-            load_taps2<F16>(plane0 + f1, tp, st, tv1);
-            f4 pre0, pre1;
-            const f4 o0 = shade2<ORDER, RACT, AACT>(tp, tv0, &pre0);
-            const f4 o1 = shade2<ORDER, RACT, AACT>(tp, tv1, &pre1);
-            VL3D_PAIR_GRAD(o0, pre0, Gr0, Gg0, Gb0, gA0, S0, P0, Tr0, gv0, ex)
-            VL3D_PAIR_GRAD(o1, pre1, Gr1, Gg1, Gb1, gA1, S1, P1, Tr1, gv1, ex)
-            tc = make_float2(tp.tx, tp.ty);
-            if (!(tp.cov > 0.0f)) { gv0 = make_float4(0.f, 0.f, 0.f, 0.f); gv1 = gv0; }
-        }
-        s_t[buf][tid] = tc;
-        s_g[buf][0][tid] = gv0;
-        s_g[buf][1][tid] = gv1;
-        __syncthreads();
-        // gather: one set of weights, two accumulators
-        pair_gather_plane<ORDER, RACT, AACT, F16, false, PW, PR>(a, s_g[buf][0], s_g[buf][1], s_t[buf], X0, Y0, ww, wh, apart, my_tile, e0, oplane, plane0,
-                                                                 gplane0, f1, frame_b, has1, col, row, d, t0);
-    }
-}
-
-// ... without the owner table (`variant` 8).  render_bwd_pair12_k has VALU to spare (active in 60-66 % of the SIMD cycles) and no memory to
-// spare: the table costs it one 2-byte load per thread and plane at the texture path's full per-instruction price, re-read by every frame
-// pair (1 of its 9.2 read instructions per wave and plane, 1.17 GB of FETCH_SIZE at cfg3), and the pre-pass 59 MB of stores; fp32 cfg3
-// 12.00 -> 11.63 ms in process, fp16 stacks 9.19 -> 9.46 (docs/kernels/K2_render_backward.md).  Here the gather thread computes its texel's owner pixel with
-// the table pass's own function on the table pass's inputs (pair_gather_plane<..., OWNERLESS>): the nine inverse-homography floats of the plane
-// arrive as scalar loads with the forward homography, the tile's interior is formed once per workgroup as bwd_windows_k forms it.  Same
-// partition of the texels, so the same gradient bits.  The sweep is render_bwd_pair12_k's, statement for statement; a kernel of its own because
-// tests/test_bwd_pair12_resources_cpu.py pins that one's six template parameters, and it stays the A/B partner.
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
-__global__ __launch_bounds__(P12W * P12ROWS, 6) void render_bwd_pair12o_k(RenderArgs a) {      // 6 waves per SIMD = 2 workgroups per CU: <= 80 VGPRs
-    constexpr int PW = P12W, PR = P12ROWS, PNT = PW * PR;
-    if (!reinterpret_cast<const int *>(a.plan)[0]) return;
-    __shared__ float4 s_g[2][2][PNT];   // [buffer][frame][pixel]
-    __shared__ float2 s_t[2][PNT];
-    const int tid = threadIdx.x, col = tid & (PW - 1), row = tid / PW;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_x = bid % a.tiles_x, rest = bid / a.tiles_x;
-    const int tile_y = rest % a.tiles_y, t0 = (rest / a.tiles_y) * 2;
-    const bool has1 = t0 + 1 < a.T;          // odd T: the last pair sweeps frame t0 twice and stores it once
-    const int rx0 = tile_x * (PW - 2) - 1, ry0 = tile_y * (PR - 2) - 1;
-    const int x = rx0 + col, y = ry0 + row;
-    const bool inimg = (x >= 0) && (x < a.W) && (y >= 0) && (y < a.H);
-    const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
-    // the pixels this tile owns (bwd_windows_k's ix0 .. iy1): a texel is gathered here iff its owner pixel is one of them
-    const int ix0 = tile_x * (PW - 2), ix1 = min(ix0 + (PW - 2) - 1, a.W - 1), iy0 = tile_y * (PR - 2), iy1 = min(iy0 + (PR - 2) - 1, a.H - 1);
-    constexpr size_t TEXB = F16 ? 8 : 16;
-    const size_t frame_b = (size_t)a.Hs * a.Ws * TEXB;
-    const size_t plane_stride_b = (size_t)a.T * frame_b;
-    const char *plane0 = reinterpret_cast<const char *>(a.stack) + (size_t)t0 * frame_b;
-    char *gplane0 = reinterpret_cast<char *>(a.g_stack) + (size_t)t0 * frame_b;
-    const size_t f1 = has1 ? frame_b : 0;
-    float Gr0 = 0.f, Gg0 = 0.f, Gb0 = 0.f, gA0 = 0.f, S0 = 0.f, Gr1 = 0.f, Gg1 = 0.f, Gb1 = 0.f, gA1 = 0.f, S1 = 0.f;
-    if (inimg) {
-        size_t pix = ((size_t)t0 * a.H + y) * a.W + x;
-        Gr0 = a.g_rgb[pix * 3 + 0]; Gg0 = a.g_rgb[pix * 3 + 1]; Gb0 = a.g_rgb[pix * 3 + 2];
-        gA0 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
-        S0 = dot3p(Gr0, a.rgb[pix * 3 + 0], Gg0, a.rgb[pix * 3 + 1], Gb0, a.rgb[pix * 3 + 2], gA0 * a.alpha[pix]);
-        if (has1) pix += (size_t)a.H * a.W;
-        Gr1 = a.g_rgb[pix * 3 + 0]; Gg1 = a.g_rgb[pix * 3 + 1]; Gb1 = a.g_rgb[pix * 3 + 2];
-        gA1 = a.g_alpha ? a.g_alpha[pix] : 0.0f;
-        S1 = dot3p(Gr1, a.rgb[pix * 3 + 0], Gg1, a.rgb[pix * 3 + 1], Gb1, a.rgb[pix * 3 + 2], gA1 * a.alpha[pix]);
-    }
-    float Tr0 = 1.0f, P0 = 0.0f, Tr1 = 1.0f, P1 = 0.0f;
-    const TapStep st = make_tap_step<F16>(a.Hs, a.Ws);
-    const unsigned my_tile_id = (unsigned)(tile_y * a.tiles_x + tile_x);
-    const cint_p wrec = (cint_p)a.plan + plan_win_off(a.D) + (size_t)my_tile_id * a.D * 4;
-    typedef typename TapVal<F16, ORDER>::type tapv_t;
-    const f4 ex = f4{0.f, 0.f, 0.f, 0.f};      // (no regularisers: VL3D_PAIR_GRAD's extra term, as in render_bwd_pair_k<REG = false>)
-    for (int d = 0; d < a.D; ++d, plane0 += plane_stride_b, gplane0 += plane_stride_b) {
-        float h[VL3D_HN], hi[9];
-        load_uniform(a.homos + VL3D_HS * d, h);
-        load_uniform(a.plan + PLAN_HDR + PLAN_REC * d, hi);      // the plan's inverse texel homography (bwd_plan_k): scalar loads, as h
-        const int X0 = wrec[4 * d], Y0 = wrec[4 * d + 1], wwh = wrec[4 * d + 2];
-        const int ww = wwh & 0xffff, wh = (wwh >> 16) & 0x3fff;
-        const bool apart = (wwh & 0x40000000) != 0;
-        const int buf = d & 1;
-        // sweep: one set of taps, two frames
-        float2 tc = make_float2(0.f, 0.f);
-        float4 gv0 = make_float4(0.f, 0.f, 0.f, 0.f), gv1 = gv0;
-        if (inimg) {
-            const Taps2 tp = make_taps2<COORD, BORDER>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
-            tapv_t tv0[4], tv1[4];
-            load_taps2<F16>(plane0, tp, st, tv0);
-            load_taps2<F16>(plane0 + f1, tp, st, tv1);
-            f4 pre0, pre1;
-            const f4 o0 = shade2<ORDER, RACT, AACT>(tp, tv0, &pre0);
-            const f4 o1 = shade2<ORDER, RACT, AACT>(tp, tv1, &pre1);
-            VL3D_PAIR_GRAD(o0, pre0, Gr0, Gg0, Gb0, gA0, S0, P0, Tr0, gv0, ex)
-            VL3D_PAIR_GRAD(o1, pre1, Gr1, Gg1, Gb1, gA1, S1, P1, Tr1, gv1, ex)
-            tc = make_float2(tp.tx, tp.ty);
-            if (!(tp.cov > 0.0f)) { gv0 = make_float4(0.f, 0.f, 0.f, 0.f); gv1 = gv0; }
-        }
-        s_t[buf][tid] = tc;
-        s_g[buf][0][tid] = gv0;
-        s_g[buf][1][tid] = gv1;
-        __syncthreads();
-        // gather: one set of weights, two accumulators; the owner of every texel computed in place
-        pair_gather_plane<ORDER, RACT, AACT, F16, false, PW, PR, true>(a, s_g[buf][0], s_g[buf][1], s_t[buf], X0, Y0, ww, wh, apart, 0u, 0u, nullptr,
-                                                                       plane0, gplane0, f1, frame_b, has1, col, row, d, t0, hi, ix0, ix1, iy0, iy1);
+        pair_gather_plane<ORDER, RACT, AACT, F16, ADAM, SHAPE, OWNERLESS>(a, s_g[buf][0], s_g[buf][1], s_t[buf], X0, Y0, ww, wh, apart, my_tile, e0, oplane,
+                                                                          plane0, gplane0, f1, frame_b, has1, col, row, d, t0, hinv, ix0, ix1, iy0, iy1);
     }
 }
 
 #undef VL3D_PAIR_GRAD
 
-// The pre-pass of render_bwd_pair12o_k: bwd_owner_table_k's zero fill alone -- the same `safe` test on the same owner pixel, the same thread ->
+// The pre-pass of render_bwd_pair_k<..., OWNERLESS>: bwd_owner_table_k's zero fill alone -- the same `safe` test on the same owner pixel, the same thread ->
 // texel mapping and frame loop (other mappings: round 3, 15.8 -> 19.4 ms on a 1.1x stack), no table entry, no shuffles, no table stores.  Dense
 // stacks without the fused step or a loop mask: the frame pairs' calls (choose_bwd rule 4).
 __global__ __launch_bounds__(256) void bwd_zero_unowned_k(RenderArgs a) {
@@ -2438,26 +2268,6 @@ __global__ __launch_bounds__(256) void bwd_zero_unowned_k(RenderArgs a) {
         float4 *g = reinterpret_cast<float4 *>(a.g_stack) + (size_t)d * a.T * frame + (size_t)y * a.Ws + x;
         for (int t = 0; t < a.T; ++t, g += frame) *g = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-}
-
-template <int COORD, int BORDER, int ORDER, int RACT, int AACT, bool F16>
-void launch_pair12(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
-    constexpr int SHAPE = BWD_64X12, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
-    static_assert(P12W == BWD_REGIONS[SHAPE].width && P12ROWS == BWD_REGIONS[SHAPE].rows, "render_bwd_pair12_k's region is not the shape table's");
-    RenderArgs b = a;
-    b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
-    const int nwin = b.tiles_x * b.tiles_y * a.D;
-    hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
-                       reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
-    const dim3 grid((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), block(P12W * P12ROWS);
-    if (c.ownerless) {      // no owner table: the scratch's table region is not touched
-        hipLaunchKernelGGL(bwd_zero_unowned_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b);
-        hipLaunchKernelGGL((render_bwd_pair12o_k<COORD, BORDER, ORDER, RACT, AACT, F16>), grid, block, 0, s, b);
-        return;
-    }
-    hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
-                       const_cast<unsigned short *>(a.owner), P12W, bwd_slot_bits(SHAPE));
-    hipLaunchKernelGGL((render_bwd_pair12_k<COORD, BORDER, ORDER, RACT, AACT, F16>), grid, block, 0, s, b);
 }
 
 // =====================================================================================================
@@ -2590,21 +2400,47 @@ __global__ __launch_bounds__(512) void render_fwd_reg_k(RenderArgs a, int tiles_
 }
 
 // ---- launch templates ---------------------------------------------------------------------------------------------
+// What every owner-computes launch starts with, for the regions of `shape`: the tile grid of their interiors (returned in the arguments the
+// kernels take), each (tile, plane)'s texel window, then who owns each texel -- the owner table with its zero fill, one or four texels per
+// thread, or for a table-free kernel the zero fill alone (the scratch's table region is not touched).  choose_bwd sets `owner4` for single
+// frames of the one-frame kernels and `ownerless` for the 64 x 12 frame pairs only.
+template <int COORD>
+RenderArgs bwd_prepass(const RenderArgs &a, hipStream_t s, int shape, const BwdChoice &c) {
+    const int rw = BWD_REGIONS[shape].width, slot_bits = bwd_slot_bits(shape), rh = BWD_HALO, iw = bwd_interior_w(shape), ih = bwd_interior_h(shape);
+    RenderArgs b = a;
+    b.tiles_x = (a.W + iw - 1) / iw; b.tiles_y = (a.H + ih - 1) / ih;
+    const int nwin = b.tiles_x * b.tiles_y * a.D;
+    hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, iw, ih, rh, b.tiles_x, b.tiles_y,
+                       reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
+    if (c.ownerless)
+        hipLaunchKernelGGL(bwd_zero_unowned_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b);
+    else if (c.owner4)
+        hipLaunchKernelGGL(bwd_owner_table4_k, dim3(((a.Ws + 3) / 4 + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, iw, ih, rh,
+                           const_cast<unsigned short *>(a.owner), rw, slot_bits);
+    else
+        hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, iw, ih, rh, b.tiles_x,
+                           const_cast<unsigned short *>(a.owner), rw, slot_bits);
+    return b;
+}
+
+// frame pairs: the 64 x 12 regions are built with the owner table and without it, the 32 x 16 ones with it
+template <int COORD, int BORDER, int ORDER, int RACT, int AACT, BwdShape SHAPE, bool F16, bool REG = false, bool ADAM = false>
+void launch_pairs(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
+    const RenderArgs b = bwd_prepass<COORD>(a, s, SHAPE, c);
+    const dim3 grid((unsigned)(b.tiles_x * b.tiles_y * ((a.T + 1) / 2))), block(BWD_REGIONS[SHAPE].width * BWD_REGIONS[SHAPE].rows);
+    if constexpr (SHAPE == BWD_64X12) {
+        if (c.ownerless) {
+            hipLaunchKernelGGL((render_bwd_pair_k<COORD, BORDER, ORDER, RACT, AACT, F16, REG, ADAM, SHAPE, true>), grid, block, 0, s, b);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((render_bwd_pair_k<COORD, BORDER, ORDER, RACT, AACT, F16, REG, ADAM, SHAPE, false>), grid, block, 0, s, b);
+}
+
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, int SHAPE, bool REG, bool F16 = false, bool MASK = false, bool ADAM = false>
 void launch_tile(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
-    constexpr int RWT = BWD_REGIONS[SHAPE].width, ROWS = BWD_REGIONS[SHAPE].rows, RH = BWD_HALO, IW = bwd_interior_w(SHAPE), IH = bwd_interior_h(SHAPE);
-    constexpr int SLOT_BITS = bwd_slot_bits(SHAPE);
-    RenderArgs b = a;
-    b.tiles_x = (a.W + IW - 1) / IW; b.tiles_y = (a.H + IH - 1) / IH;
-    const int nwin = b.tiles_x * b.tiles_y * a.D;
-    hipLaunchKernelGGL((bwd_windows_k<COORD>), dim3((nwin + 255) / 256), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x, b.tiles_y,
-                       reinterpret_cast<int *>(const_cast<float *>(a.plan)) + plan_win_off(a.D));
-    if (c.owner4)
-        hipLaunchKernelGGL(bwd_owner_table4_k, dim3(((a.Ws + 3) / 4 + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH,
-                           const_cast<unsigned short *>(a.owner), RWT, SLOT_BITS);
-    else
-        hipLaunchKernelGGL(bwd_owner_table_k, dim3((a.Ws + 63) / 64, (a.Hs + 3) / 4, a.D), dim3(256), 0, s, b, IW, IH, RH, b.tiles_x,
-                           const_cast<unsigned short *>(a.owner), RWT, SLOT_BITS);
+    constexpr int RWT = BWD_REGIONS[SHAPE].width, ROWS = BWD_REGIONS[SHAPE].rows;
+    const RenderArgs b = bwd_prepass<COORD>(a, s, SHAPE, c);
     const dim3 grid((unsigned)(b.tiles_x * b.tiles_y * a.T)), block(RWT * ROWS);
     if constexpr (ADAM) {      // (tile-culled models only, with the regularisers' instantiation)
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, true, false, true, false, true, RWT>), grid, block, 0, s, b);
@@ -2616,7 +2452,7 @@ void launch_tile(const RenderArgs &a, hipStream_t s, const BwdChoice &c) {
         hipLaunchKernelGGL((render_bwd_tile_k<COORD, BORDER, ORDER, RACT, AACT, ROWS, REG, F16, false, false, false, RWT>), grid, block, 0, s, b);
 }
 
-// one signature for the three launch templates (the 32 x 16 frame pairs read nothing of the choice: their instantiation is all of it; the 64 x 12 ones read `ownerless`)
+// one signature for the two launch templates
 using BwdLauncher = void (*)(const RenderArgs &, hipStream_t, const BwdChoice &);
 
 // what choose_bwd() reads: a call's arguments and a compiled convention -- launch_t passes its template constants, vl3d_render_bwd_choice()
@@ -2665,11 +2501,11 @@ int launch_t(const RenderArgs &a, hipStream_t s) {
                 VL3D_BWD_CASE(MASKABLE, (VL3D_BWD_TILE, BWD_64X16, false, true), launch_tile<VL3D_CONV, BWD_64X16, false, false, true>)
                 VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_32X16, true, false, true), launch_tile<VL3D_CONV, BWD_32X16, true, false, false, true>)
                 VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_64X16, true, false, true), launch_tile<VL3D_CONV, BWD_64X16, true, false, false, true>)
-                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_PAIR, BWD_32X16, true, false, true), launch_pair<VL3D_CONV, false, true, true>)
-                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_PAIR, BWD_32X16, false, false, true), launch_pair<VL3D_CONV, false, false, true>)
-                VL3D_BWD_CASE(SIG, (VL3D_BWD_PAIR, BWD_32X16, false), launch_pair<VL3D_CONV, F16>)
-                VL3D_BWD_CASE(SIG, (VL3D_BWD_PAIR12, BWD_64X12, false), launch_pair12<VL3D_CONV, F16>)
-                VL3D_BWD_CASE(SIG && COORD != VL3D_COORD_UTILS_MPI, (VL3D_BWD_PAIR, BWD_32X16, true), launch_pair<VL3D_CONV, F16, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_PAIR, BWD_32X16, true, false, true), launch_pairs<VL3D_CONV, BWD_32X16, false, true, true>)
+                VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_PAIR, BWD_32X16, false, false, true), launch_pairs<VL3D_CONV, BWD_32X16, false, false, true>)
+                VL3D_BWD_CASE(SIG, (VL3D_BWD_PAIR, BWD_32X16, false), launch_pairs<VL3D_CONV, BWD_32X16, F16>)
+                VL3D_BWD_CASE(SIG, (VL3D_BWD_PAIR12, BWD_64X12, false), launch_pairs<VL3D_CONV, BWD_64X12, F16>)
+                VL3D_BWD_CASE(SIG && COORD != VL3D_COORD_UTILS_MPI, (VL3D_BWD_PAIR, BWD_32X16, true), launch_pairs<VL3D_CONV, BWD_32X16, F16, true>)
                 VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_32X16, true), launch_tile<VL3D_CONV, BWD_32X16, true, false>)
                 VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_32X16, false), launch_tile<VL3D_CONV, BWD_32X16, false, false>)
                 VL3D_BWD_CASE(SHIPPED9, (VL3D_BWD_TILE, BWD_64X8, false), launch_tile<VL3D_CONV, BWD_64X8, false, false>)

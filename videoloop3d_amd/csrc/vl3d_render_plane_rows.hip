@@ -17,6 +17,7 @@ using namespace vl3d_render_detail;
 
 constexpr int PR_COORD = VL3D_COORD_AFFINE, PR_BORDER = VL3D_BORDER_HARDCUT, PR_ORDER = VL3D_ACT_POST;
 constexpr int PR_RACT = VL3D_ACT_SIGMOID, PR_AACT = VL3D_ACT_SIGMOID;
+constexpr int PROWS = BWD_REGIONS[BWD_32X16].rows;      // region rows of its frame pairs: the dense render's 32 x 16 regions
 
 // make_taps2 with the tap offset taken in the plane's local rows: local base row = global base row - r0, clamped into [0, R - 2] (a no-op
 // for every sample of a band whose windows the planner built; it keeps a wrong table inside the allocation)
