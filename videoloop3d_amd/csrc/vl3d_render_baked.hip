@@ -100,11 +100,16 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
     float Tr[NF], cr[NF], cg[NF], cb[NF], A[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) { Tr[f] = 1.0f; cr[f] = cg[f] = cb[f] = A[f] = 0.0f; }
-    BakedTaps vA[NS], vB[NS];
+    struct Slot {
+        Taps2 t;
+        BakedTaps v[NS];
+    } sA, sB;
     struct Owner;      // a type of this kernel instantiation alone: its own copy of the composite (vl3d_baked_core.h)
     std::conditional_t<IS_TIME, BakedCompositeAt<Owner>, const BakedComposite<NF, Owner>> composite(Tr, cr, cg, cb, A);
     if constexpr (IS_TIME) composite.fr = frac;
-    auto fetch = [&](int d, Taps2 &t, BakedTaps *v) {
+    auto fetch = [&](int d, Slot &s) {
+        Taps2 &t = s.t;
+        BakedTaps *v = s.v;
         float h[VL3D_HN];
         load_uniform(homos + VL3D_HS * d, h);
         if constexpr (CULL) t = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
@@ -113,38 +118,11 @@ __global__ __launch_bounds__(512) void render_fwd_baked_k(RenderArgs a, int tile
         for (int f = 0; f < NS; ++f) v[f] = load_baked(base[f] + (size_t)d * plane_stride_b, t, row_b);
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
-    Taps2 tA, tB;
-    if constexpr (CULL) {
-        // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps2)
-        PlaneList list(a.cull_masks, tile);
-        int dA = list.next();
-        if (dA >= 0) {
-            fetch(dA, tA, vA);
-            for (;;) {
-                const int dB = list.next();
-                fetch(dB < 0 ? dA : dB, tB, vB);      // unconditional prefetch (re-reads the current plane past the end)
-                composite(tA, vA);
-                if (dB < 0) break;
-                const int dC = list.next();
-                fetch(dC < 0 ? dB : dC, tA, vA);
-                composite(tB, vB);
-                if (dC < 0) break;
-                dA = dC;
-            }
-        }
-    } else {
-        // two register sets (A / B): the taps of plane d + 1 are in flight while plane d is composited; the prefetch is unconditional
-        // (past the end it re-reads the last plane), as in the float forward
-        fetch(0, tA, vA);
-        for (int d = 0;; d += 2) {
-            fetch(min(d + 1, a.D - 1), tB, vB);
-            composite(tA, vA);
-            if (d + 1 >= a.D) break;
-            fetch(min(d + 2, a.D - 1), tA, vA);
-            composite(tB, vB);
-            if (d + 2 >= a.D) break;
-        }
-    }
+    auto step = [&](const Slot &s, int) { composite(s.t, s.v); };
+    // the workgroup's plane list (cull_fwd_plan_k; a pixel inside a culled quad is uncovered, make_taps2) or every plane: walk_planes
+    // (vl3d_render_core.h), the float forward's walk
+    if constexpr (CULL) walk_planes(ListedPlanes(a.cull_masks, tile), sA, sB, fetch, step);
+    else walk_planes(DensePlanes{a.D}, sA, sB, fetch, step);
     composite.store(a, out, t0, x, y, has1);
 }
 

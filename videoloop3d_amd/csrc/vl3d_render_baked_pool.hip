@@ -91,10 +91,15 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
     float Tr[NF], cr[NF], cg[NF], cb[NF], A[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) { Tr[f] = 1.0f; cr[f] = cg[f] = cb[f] = A[f] = 0.0f; }
-    BakedTaps vA[NS], vB[NS];
+    struct Slot {
+        TapsI t;
+        BakedTaps v[NS];
+    } sA, sB;
     struct Owner;      // a type of this kernel instantiation alone: its own copy of the composite (vl3d_baked_core.h)
     const BakedComposite<NF, Owner> state(Tr, cr, cg, cb, A);
-    auto fetch = [&](int d, TapsI &t, BakedTaps *v) {
+    auto fetch = [&](int d, Slot &s) {
+        TapsI &t = s.t;
+        BakedTaps *v = s.v;
         float h[VL3D_HN];
         load_uniform(homos + VL3D_HS * d, h);
         t = make_taps_i<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
@@ -131,29 +136,15 @@ __global__ __launch_bounds__(512) void render_fwd_baked_pool_k(RenderArgs a, Poo
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
     // (an uncovered pixel's composite step changes no bit of the state -- see fetch --: skipped)
-    auto composite_if = [&](const TapsI &t, const BakedTaps *v) {
-        if (t.cov != 0.0f) {
-            if constexpr (IS_TIME) state(t, v, frac);
-            else state(t, v);
+    auto composite_if = [&](const Slot &s, int) {
+        if (s.t.cov != 0.0f) {
+            if constexpr (IS_TIME) state(s.t, s.v, frac);
+            else state(s.t, s.v);
         }
     };
-    // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps_i)
-    PlaneList list(a.cull_masks, tile);
-    TapsI tA, tB;
-    const int dA = list.next();
-    if (dA >= 0) {
-        fetch(dA, tA, vA);
-        for (;;) {      // two register sets: the next listed plane is fetched before the current one is composited; nothing is fetched past the end
-            const int dB = list.next();
-            if (dB >= 0) fetch(dB, tB, vB);
-            composite_if(tA, vA);
-            if (dB < 0) break;
-            const int dC = list.next();
-            if (dC >= 0) fetch(dC, tA, vA);
-            composite_if(tB, vB);
-            if (dC < 0) break;
-        }
-    }
+    // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps_i).  Two register sets: the next
+    // listed plane is fetched before the current one is composited; nothing is fetched past the end (walk_planes_cond, vl3d_render_core.h)
+    walk_planes_cond(ListedPlanes(a.cull_masks, tile), sA, sB, fetch, composite_if);
     state.store(a, out, t0, x, y, NF == 2 && has1);
 }
 

@@ -922,6 +922,60 @@ struct PlaneList {
     }
 };
 
+// The plane walk of the forward kernels, written once: front to back with two register sets (slots A / B: a plane's taps and tap values), so
+// that the taps of the next plane are in flight while the current one is composited, without register copies.
+//   fetch(d, slot&)       issues the loads of plane d into a slot and ends with asm volatile("" ::: "memory"): the fence keeps the loads
+//                         there -- hipcc otherwise sinks them below the composite.
+//   step(const slot&, d)  composites plane d from a slot.
+// The prefetch is unconditional: past the end it re-reads a plane (the dense sequence its last one, the listed sequence the current one).
+// With a branch around the loads hipcc merges the two paths' counters and waits with vmcnt(0), i.e. for the taps it has just issued as
+// well.  walk_planes_cond is the sibling that fetches nothing past the end (the pool kernels, whose fetch is a dependent chain of loads).
+// Callers: the baked clip and pool kernels and the disparity kernels.  The float colour kernels below (render_fwd2_k, render_fwd2x_k,
+// render_fwd2r_k, render_fwd_reg_k; render_fwd_plane_rows_k) still spell the same walk out: moved onto the helper, hipcc contracts other
+// multiply-add pairs of their composite into fma and their pictures lose bits they are tested to share (docs/kernels/K1_render_forward.md).
+struct DensePlanes {       // planes 0 .. D-1, D >= 1
+    int D;
+    static constexpr bool never_empty = true;
+    __device__ __forceinline__ int first() const { return 0; }
+    __device__ __forceinline__ int next(int d) const { return d + 1; }
+    __device__ __forceinline__ bool has(int d) const { return d < D; }
+    __device__ __forceinline__ int prefetch(int, int dn) const { return min(dn, D - 1); }
+};
+struct ListedPlanes : PlaneList {      // the planes of a workgroup's PlaneList
+    using PlaneList::PlaneList;
+    static constexpr bool never_empty = false;
+    __device__ __forceinline__ int first() { return PlaneList::next(); }
+    __device__ __forceinline__ int next(int) { return PlaneList::next(); }
+    __device__ __forceinline__ bool has(int d) const { return d >= 0; }
+    __device__ __forceinline__ int prefetch(int d, int dn) const { return dn < 0 ? d : dn; }
+};
+template <bool PAST_END, class Planes, class Slot, class Fetch, class Step>
+__device__ __forceinline__ void walk_planes_as(Planes planes, Slot &sA, Slot &sB, const Fetch &fetch, const Step &step) {
+    int dA = planes.first();
+    if (Planes::never_empty || planes.has(dA)) {
+        fetch(dA, sA);
+        for (;;) {
+            const int dB = planes.next(dA);
+            if (PAST_END || planes.has(dB)) fetch(planes.prefetch(dA, dB), sB);
+            step(sA, dA);
+            if (!planes.has(dB)) break;
+            const int dC = planes.next(dB);
+            if (PAST_END || planes.has(dC)) fetch(planes.prefetch(dB, dC), sA);
+            step(sB, dB);
+            if (!planes.has(dC)) break;
+            dA = dC;
+        }
+    }
+}
+template <class Planes, class Slot, class Fetch, class Step>
+__device__ __forceinline__ void walk_planes(Planes planes, Slot &sA, Slot &sB, const Fetch &fetch, const Step &step) {
+    walk_planes_as<true>(planes, sA, sB, fetch, step);
+}
+template <class Planes, class Slot, class Fetch, class Step>
+__device__ __forceinline__ void walk_planes_cond(Planes planes, Slot &sA, Slot &sB, const Fetch &fetch, const Step &step) {
+    walk_planes_as<false>(planes, sA, sB, fetch, step);
+}
+
 template <int COORD, int BORDER, int ORDER, int RACT, int AACT, int TY, bool SWZ, bool F16, bool CULL = false, bool MASK = false>
 __global__ __launch_bounds__(64 * TY) void render_fwd2_k(RenderArgs a, int tiles_x, int tiles_y) {
     static_assert(!(MASK && (CULL || F16)), "the loop-mask channel: dense fp32 stage-1 stacks");

@@ -104,48 +104,27 @@ __global__ __launch_bounds__(512) void render_disp_fwd_k(RenderArgs a, DispArgs 
     const char *plane = reinterpret_cast<const char *>(a.stack) + (size_t)t * frame_b;
     const TapStep st = make_tap_step<F16>(a.Hs, a.Ws);
     typedef typename AlphaLane<F16>::type lane_t;
-    lane_t vA[4], vB[4];
-    Taps2 tA, tB;
-    float rA, rB;
+    struct Slot {
+        Taps2 t;
+        lane_t v[4];
+        float rho;
+    } sA, sB;
     DispComposite c;
-    auto fetch = [&](int d, Taps2 &tp, lane_t (&v)[4], float &rho) {
+    auto fetch = [&](int d, Slot &s) {
+        Taps2 &tp = s.t;
         float h[VL3D_HN];
         load_uniform(a.homos + VL3D_HS * d, h);
         if constexpr (CULL) tp = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
         else tp = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
-        rho = plane_rho(o.rows, d, px, py);
-        load_alpha_taps<F16>(plane + (size_t)d * plane_stride_b, tp, st, v);
+        s.rho = plane_rho(o.rows, d, px, py);
+        load_alpha_taps<F16>(plane + (size_t)d * plane_stride_b, tp, st, s.v);
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
-    if constexpr (CULL) {
-        // the workgroup's plane list (cull_fwd_plan_k); a pixel inside a culled quad is uncovered (make_taps2)
-        PlaneList list(a.cull_masks, tile_y * tiles_x + tile_x);
-        int dA = list.next();
-        if (dA >= 0) {
-            fetch(dA, tA, vA, rA);
-            for (;;) {
-                const int dB = list.next();
-                fetch(dB < 0 ? dA : dB, tB, vB, rB);      // unconditional prefetch (re-reads the current plane past the end)
-                c.logits(tA, vA, o.alpha_act, rA);
-                if (dB < 0) break;
-                const int dC = list.next();
-                fetch(dC < 0 ? dB : dC, tA, vA, rA);
-                c.logits(tB, vB, o.alpha_act, rB);
-                if (dC < 0) break;
-                dA = dC;
-            }
-        }
-    } else {
-        fetch(0, tA, vA, rA);
-        for (int d = 0;; d += 2) {      // past the end the prefetch re-reads the last plane, as in the colour forward
-            fetch(min(d + 1, a.D - 1), tB, vB, rB);
-            c.logits(tA, vA, o.alpha_act, rA);
-            if (d + 1 >= a.D) break;
-            fetch(min(d + 2, a.D - 1), tA, vA, rA);
-            c.logits(tB, vB, o.alpha_act, rB);
-            if (d + 2 >= a.D) break;
-        }
-    }
+    auto step = [&](const Slot &s, int) { c.logits(s.t, s.v, o.alpha_act, s.rho); };
+    // the workgroup's plane list (cull_fwd_plan_k; a pixel inside a culled quad is uncovered, make_taps2) or every plane: the colour forward's
+    // walk (walk_planes, vl3d_render_core.h)
+    if constexpr (CULL) walk_planes(ListedPlanes(a.cull_masks, tile_y * tiles_x + tile_x), sA, sB, fetch, step);
+    else walk_planes(DensePlanes{a.D}, sA, sB, fetch, step);
     c.store(a, o, t, x, y);
 }
 
@@ -182,47 +161,25 @@ __global__ __launch_bounds__(512) void render_disp_baked_k(RenderArgs a, DispArg
     const size_t frame_b = (size_t)a.Hs * a.Ws * 4;
     const size_t plane_stride_b = (size_t)a.Tstride * frame_b;
     const char *base = reinterpret_cast<const char *>(a.stack) + (size_t)src_t * frame_b;
-    BakedTaps vA, vB;
-    Taps2 tA, tB;
-    float rA, rB;
+    struct Slot {
+        Taps2 t;
+        BakedTaps v;
+        float rho;
+    } sA, sB;
     DispComposite c;
-    auto fetch = [&](int d, Taps2 &tp, BakedTaps &v, float &rho) {
+    auto fetch = [&](int d, Slot &s) {
+        Taps2 &tp = s.t;
         float h[VL3D_HN];
         load_uniform(homos + VL3D_HS * d, h);
         if constexpr (CULL) tp = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
         else tp = make_taps2<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy);
-        rho = plane_rho(rows, d, px, py);
-        v = load_baked(base + (size_t)d * plane_stride_b, tp, row_b);
+        s.rho = plane_rho(rows, d, px, py);
+        s.v = load_baked(base + (size_t)d * plane_stride_b, tp, row_b);
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
-    if constexpr (CULL) {
-        PlaneList list(a.cull_masks, tile);
-        int dA = list.next();
-        if (dA >= 0) {
-            fetch(dA, tA, vA, rA);
-            for (;;) {
-                const int dB = list.next();
-                fetch(dB < 0 ? dA : dB, tB, vB, rB);      // unconditional prefetch (re-reads the current plane past the end)
-                c.baked(tA, vA, rA);
-                if (dB < 0) break;
-                const int dC = list.next();
-                fetch(dC < 0 ? dB : dC, tA, vA, rA);
-                c.baked(tB, vB, rB);
-                if (dC < 0) break;
-                dA = dC;
-            }
-        }
-    } else {
-        fetch(0, tA, vA, rA);
-        for (int d = 0;; d += 2) {
-            fetch(min(d + 1, a.D - 1), tB, vB, rB);
-            c.baked(tA, vA, rA);
-            if (d + 1 >= a.D) break;
-            fetch(min(d + 2, a.D - 1), tA, vA, rA);
-            c.baked(tB, vB, rB);
-            if (d + 2 >= a.D) break;
-        }
-    }
+    auto step = [&](const Slot &s, int) { c.baked(s.t, s.v, s.rho); };
+    if constexpr (CULL) walk_planes(ListedPlanes(a.cull_masks, tile), sA, sB, fetch, step);
+    else walk_planes(DensePlanes{a.D}, sA, sB, fetch, step);
     c.store(a, o, t0, x, y);
 }
 
@@ -266,15 +223,19 @@ __global__ __launch_bounds__(512) void render_disp_baked_pool_k(RenderArgs a, Di
     const float px = (float)(a.col0 + x) + a.pc, py = (float)(a.row0 + y) + a.pc;
     const size_t frame_b = (size_t)src_t * SLOT_B;      // src_t in [0, T_model): slot + src_t is a slot of a dynamic block
     const size_t bplane_n = (size_t)p.tiles_y * p.tiles_x;
-    BakedTaps vA, vB;
-    TapsI tA, tB;
-    float rA, rB;
+    struct Slot {
+        TapsI t;
+        BakedTaps v;
+        float rho;
+    } sA, sB;
     DispComposite c;
-    auto fetch = [&](int d, TapsI &tp, BakedTaps &v, float &rho) {
+    auto fetch = [&](int d, Slot &s) {
+        TapsI &tp = s.t;
+        BakedTaps &v = s.v;
         float h[VL3D_HN];
         load_uniform(homos + VL3D_HS * d, h);
         tp = make_taps_i<VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT>(h, px, py, a.Hs, a.Ws, a.sx, a.sy, a.ox, a.oy, plane_cull(a, d));
-        rho = plane_rho(rows, d, px, py);
+        s.rho = plane_rho(rows, d, px, py);
         v = BakedTaps{u2w{0u, 0u}, u2w{0u, 0u}};
         // an uncovered pixel leaves the composite state untouched bit for bit (a = 0): nothing is fetched, and the step is skipped
         if (tp.cov != 0.0f) {
@@ -297,21 +258,11 @@ __global__ __launch_bounds__(512) void render_disp_baked_pool_k(RenderArgs a, Di
         }
         asm volatile("" ::: "memory");      // keep the loads here: hipcc otherwise sinks them below the composite
     };
-    PlaneList list(a.cull_masks, tile);
-    const int dA = list.next();
-    if (dA >= 0) {
-        fetch(dA, tA, vA, rA);
-        for (;;) {      // two register sets: the next listed plane is fetched before the current one is composited; nothing is fetched past the end
-            const int dB = list.next();
-            if (dB >= 0) fetch(dB, tB, vB, rB);
-            if (tA.cov != 0.0f) c.baked(tA, vA, rA);
-            if (dB < 0) break;
-            const int dC = list.next();
-            if (dC >= 0) fetch(dC, tA, vA, rA);
-            if (tB.cov != 0.0f) c.baked(tB, vB, rB);
-            if (dC < 0) break;
-        }
-    }
+    auto step = [&](const Slot &s, int) {
+        if (s.t.cov != 0.0f) c.baked(s.t, s.v, s.rho);
+    };
+    // two register sets: the next listed plane is fetched before the current one is composited; nothing is fetched past the end
+    walk_planes_cond(ListedPlanes(a.cull_masks, tile), sA, sB, fetch, step);
     c.store(a, o, t0, x, y);
 }
 
