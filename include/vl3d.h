@@ -364,6 +364,35 @@ int vl3d_render_sh_bwd(const vl3d_render_desc *desc, const float *stack, const f
                        const uint8_t *quad_keep, int32_t QH, int32_t QW, const float *rgb, const float *alpha, const float *grad_rgb,
                        const float *grad_alpha, const float *grad_alpha_sums, float *grad_stack, float *grad_stack_sh, vl3d_stream_t stream);
 
+/* Camera gradients (csrc/vl3d_render_cam.hip): d loss / d homos of vl3d_render_fwd's picture and of vl3d_warp_fwd's -- what the reference's
+ * autograd passes through grid_sample's grid to `homos` (utils_mpi.py:159-176) and on to extrinsics and intrinsics (compute_homography).
+ * Per output pixel (u, v) = (col0 + x + c, row0 + y + c), c = desc->pixel_center, plane d, frame t: (X, Y, Z) = H_d (u, v, 1),
+ * tx = sx X / Z + ox, ty = sy Y / Z + oy (VL3D_COORD_UTILS_MPI: sx = (Ws - 1) / Ws, sy = (Hs - 1) / Hs, ox = oy = 0); x0 = floor(tx), fx = tx - x0:
+ * floor carries no gradient, fx does (ATen's grid_sample rule); a tap outside the texture counts as 0, as in the forward:
+ *     ds/dtx = (S10 - S00)(1 - fy) + (S11 - S01) fy,   ds/dty = (S01 - S00)(1 - fx) + (S11 - S10) fx      per channel
+ * (the taps are the activated texels under VL3D_ACT_PRE).  g_pre, the gradient with respect to the sampled values of (pixel, plane, frame), is
+ * the quantity vl3d_render_bwd scatters with the tent weights -- the same device functions decide coverage, kept quads, the composite
+ * backward from the saved rgb / alpha and act' --, zero where the plane does not cover the pixel; coverage and quad membership are step
+ * functions and carry no gradient.  With g_tx = sum_t sum_c g_pre_c ds_c/dtx, a = g_tx sx / Z, b = g_ty sy / Z, e = -(g_tx sx X + g_ty sy Y) / Z^2:
+ *     grad_homos[d] = sum over pixels of (a, b, e)^T (u, v, 1)         [D][3][3], overwritten
+ * No float atomics: sums over the wave's lanes, then the workgroup's waves, one [D][9] partial per workgroup in `scratch`, and a finish kernel
+ * that adds the partials in a fixed order in fp64.  Two calls give identical bits.  grad_alpha may be NULL.
+ * Accepted: VL3D_F32 stacks, any T >= 1, D <= 128; (VL3D_COORD_AFFINE, VL3D_BORDER_HARDCUT, VL3D_ACT_POST) and (VL3D_COORD_UTILS_MPI,
+ *     VL3D_BORDER_ZEROS, VL3D_ACT_PRE); every pair of the activation table; row0 / col0 windows; quad_keep NULL (QH, QW not read) or a map
+ *     [D][QH][QW] with a POSITIVE grid and desc->cull_* = 0.  VL3D_EUNSUPPORTED: fp16 stacks, any other convention (VL3D_COORD_AFFINE_PLANES,
+ *     VL3D_ACT_BAKED included), the tile-exact (negative) grid, a cull window, uv_noise_seed != 0.  VL3D_EINVAL: variant != 0, non-positive dims,
+ *     D > 128, a plane of 2^28 texels or more, a NULL pointer, stack not 16-byte aligned, any other pointer not 4-byte aligned, scratch_bytes
+ *     below vl3d_render_bwd_homos_scratch_bytes(desc).  Nothing is launched after a refusal.
+ * vl3d_warp_bwd_homos: the same for vl3d_warp_fwd (images (N, C, Hs, Ws), grad_out (N, C, h, w), c = 0, the utils_mpi coordinates): g_pre is
+ *     the upstream gradient of image n itself; grad_homos [N][3][3], overwritten.  VL3D_EINVAL as vl3d_warp_bwd, plus alignment and scratch. */
+int64_t vl3d_render_bwd_homos_scratch_bytes(const vl3d_render_desc *desc);
+int vl3d_render_bwd_homos(const vl3d_render_desc *desc, const void *stack, const float *homos, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                          const float *rgb, const float *alpha, const float *grad_rgb, const float *grad_alpha,
+                          float *grad_homos /* [D][3][3], overwritten */, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
+int64_t vl3d_warp_bwd_homos_scratch_bytes(int32_t N, int32_t h, int32_t w);
+int vl3d_warp_bwd_homos(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t h, int32_t w, const float *homos, const float *images,
+                        const float *grad_out, float *grad_homos /* [N][3][3] */, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
+
 /* Which kernel a backward call runs, without running it: the value the entry points themselves compute (the same two functions, no device
  * touched, nothing enqueued).  entry: which entry point; has_quad_keep / has_reg_grads (grad_reg or grad_alpha_sums non-NULL) / scratch_bytes:
  * as the call would pass them (scratch_bytes 0 = scratch NULL); fused_step: vl3d_render_bwd_adam (entry VL3D_BWD_ENTRY_ADAM) only.  Refusals

@@ -230,6 +230,40 @@ class PlaneModel(nn.Module):
             disp = disp / alpha.clamp_min(1e-10)
         return disp, alpha
 
+    # ---- cameras ---------------------------------------------------------------------------------------------------------
+    def render_cameras(self, H, W, extrins, intrins, ts=None):
+        """The picture as a function of the stack AND of the cameras: extrins [B,4,4] (ref -> target) and intrins [B,3,3], float64 tensors
+        that may require a gradient (poses.CameraDeltas) -> (rgb [B*T',H,W,3], alpha [B*T',H,W]), T' = len(ts) (None: every frame).
+        Per camera: plane_homographies in its torch spelling (the autograd graph from the pose to the homographies, on the poses' device),
+        then render.render_planes, whose backward returns d loss / d homos (vl3d_render_bwd_homos) beside the stack gradient.  With `ts`
+        the frames are gathered (stack[:, ts]): a refinement renders a few frames of a few views, not a training step's crop.  No
+        regularisers, no background colour, no fused optimiser step -- render() / forward() are the training path and stay as they are.
+        Refused: atlas_exact, packed models, the tile-exact layout, the view-dependent colour head (rgb_sh)."""
+        from .render import render_planes
+        who = "render_cameras"
+        if self.atlas_exact:
+            raise RuntimeError(f"{who}: atlas_exact is a parity mode of the reference's atlas sampling; the camera gradient is built on the plane stack")
+        if getattr(self, "packed", None) is not None:
+            raise RuntimeError(f"{who}: a packed model has no dense stack to differentiate through (unpack_() it first)")
+        if self.tile_own is not None:
+            raise RuntimeError(f"{who}: the camera gradient is not built for the tile-exact layout")
+        if self.rgb_mlp_type != "direct":
+            raise RuntimeError(f"{who}: the camera gradient is not built for the view-dependent colour head (rgb_mlp_type = {self.rgb_mlp_type!r})")
+        self._flush_deferred_updates()
+        extrins, intrins = torch.as_tensor(extrins), torch.as_tensor(intrins)
+        extrins, intrins = extrins.reshape(-1, 4, 4), intrins.reshape(-1, 3, 3).to(extrins.dtype)
+        if len(intrins) != len(extrins):
+            raise RuntimeError(f"{who}: {len(extrins)} extrinsics and {len(intrins)} intrinsics")
+        stack = self.stack if ts is None else self.stack[:, torch.as_tensor(ts, dtype=torch.long, device=self.stack.device)]
+        qk = self.quad_keep if (self.is_sparse and getattr(self, "quad_keep", None) is not None) else None
+        rgbs, alphas = [], []
+        for b in range(len(extrins)):
+            homos = self.plane_homographies(extrins[b:b + 1], intrins[b:b + 1])
+            rgb, alpha = render_planes(stack, homos.to(stack.device), H, W, self.spec, quad_keep=qk)
+            rgbs.append(rgb)
+            alphas.append(alpha)
+        return (rgbs[0], alphas[0]) if len(rgbs) == 1 else (torch.cat(rgbs), torch.cat(alphas))
+
     # ---- render --------------------------------------------------------------------------------------------------------------
     def _composite_bg(self, rgb, alpha):
         """MPI.py:550-556, MPV.py:455-461 (as written): the render over args.bg_color ("" = none, "random" = one draw per call, "r#g#b")."""

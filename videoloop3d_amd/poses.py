@@ -1,0 +1,122 @@
+"""Camera refinement on the camera-differentiable render (render.render_planes with `homos.requires_grad`, PlaneModel.render_cameras).
+
+The inputs of this method are asynchronous hand-held captures whose poses come from COLMAP; both stages take them as given.  A photometric
+refinement needs d loss / d homographies from the render kernels (vl3d_render_bwd_homos) and, on the host, the small differentiable chain
+pose -> homographies (utils_mpi.compute_homography, plain torch as in the reference).  Everything here is host-side float64 torch: a pose is
+six numbers."""
+import torch
+import torch.nn as nn
+
+
+def _hat(w):
+    """[..., 3] -> the cross-product matrices [..., 3, 3]"""
+    z = torch.zeros_like(w[..., 0])
+    return torch.stack([torch.stack([z, -w[..., 2], w[..., 1]], -1), torch.stack([w[..., 2], z, -w[..., 0]], -1),
+                        torch.stack([-w[..., 1], w[..., 0], z], -1)], -2)
+
+
+def se3_exp(xi):
+    """the exponential of the twist xi [..., 6] = (rotation vector w, translation v) -> [..., 4, 4] in float64: exp [[w^, v], [0, 0]] =
+    [[R, V v], [0, 1]] with R = I + A w^ + B w^2, V = I + B w^ + C w^2, A = sin t / t, B = (1 - cos t) / t^2, C = (t - sin t) / t^3, t = |w|.
+    Differentiable everywhere: below t^2 = 1e-4 the three coefficients are their series in t^2 (next term below 3e-16), so neither the value
+    nor the gradient divides by t at 0."""
+    xi = xi.to(torch.float64)
+    w, v = xi[..., :3], xi[..., 3:]
+    t2 = (w * w).sum(-1)
+    small = t2 < 1e-4
+    t2s = torch.where(small, torch.ones_like(t2), t2)      # (the closed forms are evaluated away from 0 only: no NaN in the unused branch's gradient)
+    t = torch.sqrt(t2s)
+    A = torch.where(small, 1 - t2 / 6 + t2 * t2 / 120 - t2 ** 3 / 5040, torch.sin(t) / t)
+    B = torch.where(small, 0.5 - t2 / 24 + t2 * t2 / 720 - t2 ** 3 / 40320, (1 - torch.cos(t)) / t2s)
+    C = torch.where(small, 1.0 / 6 - t2 / 120 + t2 * t2 / 5040 - t2 ** 3 / 362880, (t - torch.sin(t)) / (t2s * t))
+    W = _hat(w)
+    W2 = W @ W
+    eye = torch.eye(3, dtype=torch.float64, device=xi.device).expand(W.shape)
+    R = eye + A[..., None, None] * W + B[..., None, None] * W2
+    V = eye + B[..., None, None] * W + C[..., None, None] * W2
+    top = torch.cat([R, V @ v[..., None]], -1)
+    bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=xi.device).expand(top.shape[:-2] + (1, 4))
+    return torch.cat([top, bottom], -2)
+
+
+def pose_error(extrin, true_extrin):
+    """(rotation angle in radians, translation norm) of extrin @ inverse(true_extrin), float64"""
+    r = torch.as_tensor(extrin).to(torch.float64) @ torch.inverse(torch.as_tensor(true_extrin).to(torch.float64))
+    cos = ((r[..., 0, 0] + r[..., 1, 1] + r[..., 2, 2]) - 1) / 2
+    skew = torch.stack([r[..., 2, 1] - r[..., 1, 2], r[..., 0, 2] - r[..., 2, 0], r[..., 1, 0] - r[..., 0, 1]], -1).norm(dim=-1) / 2
+    return torch.atan2(skew, cos), r[..., :3, 3].norm(dim=-1)
+
+
+class CameraDeltas(nn.Module):
+    """per-view corrections of given cameras: a twist xi [V,6] (float64, on the host, zero at the start) applied on the left of the extrinsics,
+    and with `learn_focal` a log focal scale per view."""
+
+    def __init__(self, n_views, learn_focal=False):
+        super().__init__()
+        self.xi = nn.Parameter(torch.zeros((int(n_views), 6), dtype=torch.float64))
+        self.log_focal = nn.Parameter(torch.zeros(int(n_views), dtype=torch.float64)) if learn_focal else None
+
+    def extrins(self, base, idx=None):
+        """se3_exp(xi[idx]) @ base[idx]: base [V,4,4] -> [len(idx),4,4] float64"""
+        idx = torch.arange(len(self.xi)) if idx is None else torch.as_tensor(idx, dtype=torch.long)
+        return se3_exp(self.xi[idx]) @ torch.as_tensor(base).to(torch.float64)[idx]
+
+    def intrins(self, base, idx=None):
+        """base [V,3,3] with the focal entries (the upper-left 2 x 2 block) scaled by exp(log_focal[idx]) -> [len(idx),3,3] float64"""
+        idx = torch.arange(len(self.xi)) if idx is None else torch.as_tensor(idx, dtype=torch.long)
+        K = torch.as_tensor(base).to(torch.float64)[idx]
+        if self.log_focal is None:
+            return K
+        s = torch.exp(self.log_focal[idx])[:, None, None]
+        block = torch.zeros((3, 3), dtype=torch.float64)
+        block[:2, :2] = 1
+        return K * (1 + block * (s - 1))
+
+
+def refine_loop(render, targets, extrins, intrins, steps=60, lr=5e-5, learn_focal=False, params=()):
+    """Adam on a CameraDeltas over `render(extrins [V,4,4], intrins [V,3,3]) -> rgb`, a picture shaped like `targets`: the mean squared error
+    against `targets`.  `params`: further tensors to train beside the cameras (the stack), at the same rate.
+    -> (refined extrinsics [V,4,4], refined intrinsics [V,3,3], losses [steps]) -- float64 host tensors and a list of floats."""
+    extrins, intrins = torch.as_tensor(extrins).detach().cpu().to(torch.float64), torch.as_tensor(intrins).detach().cpu().to(torch.float64)
+    deltas = CameraDeltas(len(extrins), learn_focal)
+    groups = [dict(params=list(deltas.parameters()), lr=lr)]
+    if len(params):
+        groups.append(dict(params=list(params), lr=lr))
+    opt = torch.optim.Adam(groups)
+    history = []
+    for _ in range(int(steps)):
+        opt.zero_grad(set_to_none=True)
+        rgb = render(deltas.extrins(extrins), deltas.intrins(intrins))
+        loss = ((rgb - targets) ** 2).mean()
+        loss.backward()
+        opt.step()
+        history.append(loss.detach().item())
+    with torch.no_grad():
+        return deltas.extrins(extrins).clone(), deltas.intrins(intrins).clone(), history
+
+
+def refine_cameras(model, targets, extrins, intrins, ts=None, steps=60, lr=5e-5, train_stack=False, crop=None, learn_focal=False):
+    """Photometric refinement of the cameras of a PlaneModel (MPMesh / MPMeshVid): Adam on a CameraDeltas, the mean squared error of
+    model.render_cameras against `targets` [V,T',H,W,3] (T' = the frames `ts`; 1 for a static model).  extrins [V,4,4] (ref -> target) and
+    intrins [V,3,3]: the cameras to start from.  The stack is frozen unless `train_stack` (then trained beside the cameras, at `lr`).  crop (row0, col0, h, w): compare that window of the frames only (a shifted principal point, utils.py:196-200).
+    -> (refined extrinsics [V,4,4], refined intrinsics [V,3,3], loss history) -- float64 host tensors and a list of floats."""
+    from .plane_model import get_new_intrin
+    V, Tn, H, W = (int(v) for v in targets.shape[:4])
+    dev = model.stack.device
+    tgt = targets.to(dev, torch.float32)
+    r0 = c0 = 0
+    if crop is not None:
+        r0, c0, H, W = (int(v) for v in crop)
+        tgt = tgt[:, :, r0:r0 + H, c0:c0 + W]
+    tgt = tgt.reshape(V * Tn, H, W, 3)
+
+    def render(E, K):
+        return model.render_cameras(H, W, E, get_new_intrin(K, r0, c0), ts=ts)[0]
+
+    stack = model.stack
+    was = stack.requires_grad
+    stack.requires_grad_(bool(train_stack))
+    try:
+        return refine_loop(render, tgt, extrins, intrins, steps, lr, learn_focal, [stack] if train_stack else ())
+    finally:
+        stack.requires_grad_(was)

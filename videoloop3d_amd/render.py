@@ -171,6 +171,11 @@ class _RenderPlanes(torch.autograd.Function):
         if getattr(spec, "tile", (0, 0))[0] and quad_keep is None:
             raise RuntimeError("RenderSpec.tile (tile-exact layout) belongs to a tile-culled model: pass its quad_keep map")
         stack = stack.contiguous()
+        # the camera gradient (vl3d_render_bwd_homos): only when `homos` asks for one -- otherwise nothing below changes, launch for launch
+        ctx.cam = bool(ctx.needs_input_grad[1])
+        if ctx.cam:
+            _check_camera_grad(stack, spec, with_reg, fused_adam, quad_keep, cull_window)
+            ctx.homos_like = (homos.dtype, homos.device)
         homos = homos.detach().to(torch.float32).contiguous()
         D, T = stack.shape[:2]
         if spec.coord_mode == "affine_planes":
@@ -229,12 +234,26 @@ class _RenderPlanes(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_sums, g_asum):
         if ctx.nothing_to_render:
-            return (torch.zeros_like(ctx.saved_tensors[0]),) + (None,) * 11
+            return (torch.zeros_like(ctx.saved_tensors[0]), torch.zeros((ctx.saved_tensors[0].shape[0], 3, 3), dtype=ctx.homos_like[0],
+                                                                        device=ctx.homos_like[1]) if ctx.cam else None) + (None,) * 10
         stack, homos, rgb, alpha = ctx.saved_tensors
         g_reg = g_sums.to(torch.float32).contiguous() if (ctx.with_reg and g_sums is not None) else None
         g_asum = g_asum.to(torch.float32).contiguous() if (ctx.with_reg and g_asum is not None) else None
         g_rgb = g_rgb.contiguous() if g_rgb is not None else torch.zeros_like(rgb)
         g_alpha = g_alpha.contiguous() if g_alpha is not None else None
+        g_homos = None
+        if ctx.cam:
+            # beside the stack backward, from the same saved outputs and output gradients; [D,3,3] in the dtype and on the device of the `homos` passed in
+            gh = torch.empty((stack.shape[0], 3, 3), dtype=torch.float32, device=stack.device)
+            with torch.cuda.device(stack.device):
+                nb = int(L.lib().vl3d_render_bwd_homos_scratch_bytes(ctx.desc))
+                cam_scratch = torch.empty((nb + 3) // 4, dtype=torch.float32, device=stack.device)
+                L.check(L.lib().vl3d_render_bwd_homos(ctx.desc, L.ptr(stack), L.ptr(homos), *_qmap(ctx.quad_keep, ctx.spec), L.ptr(rgb), L.ptr(alpha),
+                                                      L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(gh), L.ptr(cam_scratch), nb, L.stream_ptr(stack.device)),
+                        "vl3d_render_bwd_homos")
+            g_homos = gh.to(device=ctx.homos_like[1], dtype=ctx.homos_like[0])
+            if not ctx.needs_input_grad[0]:      # a frozen stack (pose refinement): no stack backward at all
+                return (None, g_homos) + (None,) * 10
         global LAST_BWD_SCRATCH, LAST_BWD_CALL
         LAST_BWD_CALL = (ctx.desc, "render" if ctx.fused_adam is None else "adam",
                          (ctx.quad_keep if ctx.fused_adam is None else ctx.fused_adam.quad_keep) is not None, g_reg is not None or g_asum is not None,
@@ -255,7 +274,32 @@ class _RenderPlanes(torch.autograd.Function):
                                             L.ptr(g_rgb), L.ptr(g_alpha), L.ptr(g_reg), L.ptr(ctx.reg_state), L.ptr(g_asum), L.ptr(g_stack),
                                             L.ptr(scratch), nscratch, L.stream_ptr(stack.device)), "vl3d_render_bwd")
         LAST_BWD_SCRATCH = scratch
-        return (g_stack,) + (None,) * 11
+        return (g_stack, g_homos) + (None,) * 10
+
+
+def _check_camera_grad(stack, spec, with_reg, fused_adam, quad_keep, cull_window):
+    """what render_planes refuses when `homos` requires a gradient: what vl3d_render_bwd_homos is not built for (include/vl3d.h), and the two
+    callers whose camera gradient would be wrong rather than missing."""
+    who = "render_planes: homos.requires_grad (the camera gradient)"
+    if with_reg:
+        raise RuntimeError(f"{who} is not built for the regulariser sums: they depend on the coordinates too, and their camera gradient does not exist")
+    if fused_adam is not None:
+        raise RuntimeError(f"{who} cannot ride the fused optimiser step: vl3d_render_bwd_adam rewrites the texels the camera gradient reads")
+    if spec.coord_mode == "affine_planes":
+        raise RuntimeError(f"{who} is not built for per-plane records (coord_mode 'affine_planes')")
+    if stack.dtype != torch.float32:
+        raise RuntimeError(f"{who} is built for float32 stacks only, got {stack.dtype}")
+    if getattr(spec, "tile", (0, 0))[0]:
+        raise RuntimeError(f"{who} is not built for the tile-exact layout (RenderSpec.tile)")
+    if getattr(spec, "uv_noise_seed", 0):
+        raise RuntimeError(f"{who} is not built for add_uv_noise (uv_noise_seed = 0)")
+    if cull_window is not None and quad_keep is not None:
+        raise RuntimeError(f"{who} takes the whole plane: no cull_window")
+    if int(spec.variant) != 0:
+        raise RuntimeError(f"{who} has no kernel variants (spec.variant = 0)")
+    conv = (spec.coord_mode, spec.border, spec.act_order)
+    if conv not in (("affine", "hardcut", "post"), ("utils_mpi", "zeros", "pre")):
+        raise RuntimeError(f"{who} is built for the planar convention (affine, hardcut, post) and the utils_mpi one (utils_mpi, zeros, pre), got {conv}")
 
 
 def mask_channel_supported(stack, spec):
@@ -266,7 +310,8 @@ def mask_channel_supported(stack, spec):
 
 class _RenderPlanesMask(torch.autograd.Function):
     """render (+ layer regularisers) with stage 1's loop mask as a fifth composited channel (MPI.py:568-583): one forward and one backward
-    sweep over the stack for colours, regularisers and label; the label's gradient reaches the mask texture only (detached weights)."""
+    sweep over the stack for colours, regularisers and label; the label's gradient reaches the mask texture only (detached weights).
+    `homos` gets no gradient here: render_planes is the camera-differentiable entry."""
 
     @staticmethod
     def forward(ctx, stack, mask, homos, H, W, spec, with_reg):
@@ -557,7 +602,8 @@ def render_frame_run_baked(baked, frame0, nframes, homos, H, W, spec: RenderSpec
     activated, times 255, truncated (baked.bake_texels) -- filtered bilinearly AFTER the activation, as a player filters the exported 8-bit
     atlases; nothing is activated behind the blend, so spec.rgb_act / alpha_act / act_order are not read.  Coverage (hard cut, culled quads,
     tile-exact layout) is decided by the float kernels' own code.  The planar convention only (RenderSpec.mpv()); forward only -- a baked
-    model is not trained: inputs that require a gradient are refused.  -> (rgb [n,H,W,3], alpha [n,H,W]) float32.
+    model is not trained: inputs that require a gradient are refused (`homos` included: render_planes is the camera-differentiable entry).
+    -> (rgb [n,H,W,3], alpha [n,H,W]) float32.
     `frames8` (uint8 [n,H,W,3|4] on the device): the DISPLAY frames instead -- baked.display_frames(rgb, alpha, bg, channels), byte for byte,
     written by the render launch (the display sink of vl3d_baked_out); no float output exists and `frames8` is returned.  `bg`: the background
     colour, 3 floats, or None."""
@@ -788,7 +834,10 @@ def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0
     `grad_culled_unwritten` (with quad_keep): the consumer of the stack gradient never reads texels no kept quad can read (WindowAdam / TileAdam
     skip them), so the backward leaves those slots UNDEFINED instead of zero-filling them (VL3D_GRAD_CULLED_UNWRITTEN, include/vl3d.h).
     `fused_adam`: an optim.WindowAdam(fused_backward=True) whose pending window leaf `stack` is -- the backward then takes its step
-    (vl3d_render_bwd_adam) and the leaf receives no gradient."""
+    (vl3d_render_bwd_adam) and the leaf receives no gradient.
+    This is the camera-differentiable entry: when `homos` requires a gradient the backward also returns d loss / d homos
+    (vl3d_render_bwd_homos: float32 stacks, the planar and the utils_mpi convention, dense or a shared-border quad map, no cull_window, no
+    fused step; anything else raises here).  The regulariser, loop-mask, view-dependent, plane-rows, packed and baked renders are not."""
     rgb, alpha, _, _ = _RenderPlanes.apply(stack, homos, int(H), int(W), spec, int(window[0]), int(window[1]), False, quad_keep, cull_window,
                                            bool(grad_culled_unwritten), fused_adam)
     return rgb, alpha
@@ -835,7 +884,8 @@ def sh_basis(ray_m, H, W, window=(0, 0)):
 
 
 class _RenderPlanesSH(torch.autograd.Function):
-    """render_planes with the view-dependent colour head (vl3d_render_sh_fwd / _bwd)."""
+    """render_planes with the view-dependent colour head (vl3d_render_sh_fwd / _bwd).  `homos` and `ray_m` get no gradient here:
+    render_planes is the camera-differentiable entry."""
 
     @staticmethod
     def forward(ctx, stack, stack_sh, homos, ray_m, H, W, spec, row0, col0, quad_keep, with_alpha_sums):
@@ -904,7 +954,8 @@ def render_planes_sh(stack, stack_sh, homos, ray_m, H, W, spec: RenderSpec, quad
 
 class _RenderPlaneRows(torch.autograd.Function):
     """render_planes of a row band from PER-PLANE local rows (vl3d_render_fwd_plane_rows / _bwd_plane_rows): local row r of plane d is
-    plane row plane_row0[d] + r; the gradient comes back in the same local layout, padding rows 0."""
+    plane row plane_row0[d] + r; the gradient comes back in the same local layout, padding rows 0.  `homos` gets no gradient here:
+    render_planes is the camera-differentiable entry."""
 
     @staticmethod
     def forward(ctx, local, homos, plane_row0, H, W, Hs, spec, row0, col0):
@@ -965,7 +1016,8 @@ def render_plane_rows(local, homos, plane_row0, H, W, Hs, spec: RenderSpec, wind
 def render_planes_packed(layout, pool, frames, homos, H, W, spec: RenderSpec, quad_keep, culled_alpha, out=None, frames_dev=None):
     """The forward of a PACKED tile-culled model straight from its pool (videoloop3d_amd/packed.py; the reference renders a sparsified model
     from its tile lists, MPV.py:389-449): rgb [n,H,W,3], alpha [n,H,W] for the chosen `frames` -- the bits of the culled render of the
-    unpacked frames, without ever building them.  No gradient (evaluation renders; training goes through the optimiser's window copy).
+    unpacked frames, without ever building them.  No gradient (evaluation renders; training goes through the optimiser's window copy;
+    render_planes is the camera-differentiable entry).
     `out`: (rgb, alpha) buffers to write into; `frames_dev`: the same frame indices as an int32 device tensor (a caller rendering a long path
     uploads them once instead of per call)."""
     L.check_cuda(pool, homos, quad_keep, layout.blocks)

@@ -72,26 +72,37 @@ class _Warp(torch.autograd.Function):
         with torch.cuda.device(images.device):
             L.check(L.lib().vl3d_warp_fwd(B * D, C, Hs, Ws, h, w, L.ptr(hm), L.ptr(img), L.ptr(out),
                                           L.stream_ptr(images.device)), "vl3d_warp_fwd")
-        ctx.save_for_backward(hm)
+        cam = ctx.needs_input_grad[0]      # the camera gradient reads the images again
+        ctx.save_for_backward(hm, img if cam else None)
+        ctx.homos_like = (homos.dtype, homos.device, tuple(homos.shape)) if cam else None
         ctx.dims = (B, D, C, Hs, Ws, h, w)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        (hm,) = ctx.saved_tensors
+        hm, img = ctx.saved_tensors
         B, D, C, Hs, Ws, h, w = ctx.dims
         g = g.contiguous()
-        gi = torch.empty((B, D, C, Hs, Ws), dtype=torch.float32, device=g.device)
+        gh = gi = None
         with torch.cuda.device(g.device):
-            L.check(L.lib().vl3d_warp_bwd(B * D, C, Hs, Ws, h, w, L.ptr(hm), L.ptr(g), L.ptr(gi),
-                                          L.stream_ptr(g.device)), "vl3d_warp_bwd")
-        return None, gi, None, None
+            if ctx.needs_input_grad[0]:
+                gh = torch.empty((B * D, 3, 3), dtype=torch.float32, device=g.device)
+                nb = int(L.lib().vl3d_warp_bwd_homos_scratch_bytes(B * D, h, w))
+                scratch = torch.empty((nb + 3) // 4, dtype=torch.float32, device=g.device)
+                L.check(L.lib().vl3d_warp_bwd_homos(B * D, C, Hs, Ws, h, w, L.ptr(hm), L.ptr(img), L.ptr(g), L.ptr(gh), L.ptr(scratch), nb,
+                                                    L.stream_ptr(g.device)), "vl3d_warp_bwd_homos")
+                gh = gh.reshape(ctx.homos_like[2]).to(device=ctx.homos_like[1], dtype=ctx.homos_like[0])
+            if ctx.needs_input_grad[1]:
+                gi = torch.empty((B, D, C, Hs, Ws), dtype=torch.float32, device=g.device)
+                L.check(L.lib().vl3d_warp_bwd(B * D, C, Hs, Ws, h, w, L.ptr(hm), L.ptr(g), L.ptr(gi),
+                                              L.stream_ptr(g.device)), "vl3d_warp_bwd")
+        return gh, gi, None, None
 
 
 def warp_homography(h, w, homos: torch.Tensor, images: torch.Tensor) -> torch.Tensor:
     """utils_mpi.py:159-176: homos [B,D,3,3], images [B,D,C,Hs,Ws] -> [B,D,C,h,w]
-    (bilinear, zeros padding, texel = p*(size-1)/size).  Differentiable w.r.t. `images` only, like the
-    geometry-free use in the reference (utils_mpi.py:292, MPV.py:354)."""
+    (bilinear, zeros padding, texel = p*(size-1)/size).  Differentiable w.r.t. `images` and, when it requires a
+    gradient, w.r.t. `homos` (grid_sample's grid gradient in the reference; vl3d_warp_bwd_homos)."""
     return _Warp.apply(homos, images, int(h), int(w))
 
 
