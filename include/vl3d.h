@@ -393,6 +393,27 @@ int64_t vl3d_warp_bwd_homos_scratch_bytes(int32_t N, int32_t h, int32_t w);
 int vl3d_warp_bwd_homos(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t h, int32_t w, const float *homos, const float *images,
                         const float *grad_out, float *grad_homos /* [N][3][3] */, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
 
+/* Camera normal equations (csrc/vl3d_render_cam_normal.hip): the Gauss-Newton system of the photometric residual r = rgb - target of
+ * vl3d_render_fwd's picture in P camera parameters theta, for Levenberg-Marquardt steps on the host (videoloop3d_amd/poses.py).  The kernel
+ * knows nothing about poses: the host chain supplies the tangent homographies dhomos [P][D][3][3], dhomos[k] = dH / d theta_k, 1 <= P <= 8.
+ * Per output pixel (u, v) (window and pixel centre as in the camera gradient), plane d, parameter k: (X, Y, Z) = H_d (u, v, 1),
+ * (dX, dY, dZ)_k = dhomos[k][d] (u, v, 1),
+ *     dtx_{d,k} = sx (dX_k - (X / Z) dZ_k) / Z,   dty_{d,k} = sy (dY_k - (Y / Z) dZ_k) / Z        (sx, sy as in the camera gradient)
+ * Per frame t and colour channel c: g_pre^(c) is the composite backward with upstream gradient e_c (alpha gradient 0), by the device functions
+ * of the camera gradient -- the (S - P) rcp(1 - a) form with its look-ahead, S_c = rgb_c the saved forward picture; coverage and quad
+ * membership carry no gradient; ds/dtx, ds/dty are the tent-slope contractions of the camera gradient:
+ *     J[t,p,c,k] = sum_d sum_ch g_pre^(c)_{d,ch} (ds_ch/dtx dtx_{d,k} + ds_ch/dty dty_{d,k}),     r[t,p,c] = rgb - target
+ *     out = A [P][P] = sum_{t,p,c} w J_k J_l (symmetric, both triangles written),  b [P] = sum w J_k r,  cost = sum w r^2      float64, overwritten
+ * with w = weight[t,p] (T,H,W), 1 if weight is NULL.  No float atomics: sums over rows of 16 lanes, LDS slots with one writer each, one
+ * fp64 partial per workgroup in `scratch`, a finish kernel that adds the partials in a fixed order in fp64.  Two calls give identical bits.
+ * Accepted: exactly what vl3d_render_bwd_homos accepts; everything it refuses is refused here with the same codes.  In addition VL3D_EINVAL:
+ *     P < 1 or P > 8, a NULL dhomos / rgb / target / out, out or scratch not 8-byte aligned, scratch_bytes below
+ *     vl3d_render_cam_normal_scratch_bytes(desc, P).  Nothing is launched after a refusal, and `out` is not written. */
+int64_t vl3d_render_cam_normal_scratch_bytes(const vl3d_render_desc *desc, int32_t P);
+int vl3d_render_cam_normal(const vl3d_render_desc *desc, const void *stack, const float *homos, const float *dhomos, int32_t P,
+                           const uint8_t *quad_keep, int32_t QH, int32_t QW, const float *rgb, const float *target, const float *weight,
+                           double *out /* double[P*P + P + 1] */, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
+
 /* Which kernel a backward call runs, without running it: the value the entry points themselves compute (the same two functions, no device
  * touched, nothing enqueued).  entry: which entry point; has_quad_keep / has_reg_grads (grad_reg or grad_alpha_sums non-NULL) / scratch_bytes:
  * as the call would pass them (scratch_bytes 0 = scratch NULL); fused_step: vl3d_render_bwd_adam (entry VL3D_BWD_ENTRY_ADAM) only.  Refusals

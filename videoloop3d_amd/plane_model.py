@@ -167,6 +167,16 @@ class PlaneModel(nn.Module):
         return compute_homography(eye, self._on(dev, "ref_intrin_mpi")[None].to(extrin.dtype), extrin, intrin.to(dev), normal,
                                   self._on(dev, "planedepth")[None].to(extrin.dtype))[0].float()
 
+    def homography_chain(self, extrin, intrin):
+        """plane_homographies' torch spelling in the dtype of `extrin`, not rounded to float32: the differentiable chain pose -> homographies
+        whose Jacobian poses.camera_tangents takes in float64.  (A method of its own: plane_homographies is also borrowed as a plain function
+        by objects that are no PlaneModel.)"""
+        dev = extrin.device
+        eye = torch.eye(4, dtype=extrin.dtype, device=dev)[None]
+        normal = torch.tensor([0., 0., 1.], dtype=extrin.dtype, device=dev).expand(1, self.mpi_d, 3)
+        return compute_homography(eye, self._on(dev, "ref_intrin_mpi")[None].to(extrin.dtype), extrin, intrin.to(dev), normal,
+                                  self._on(dev, "planedepth")[None].to(extrin.dtype))[0]
+
     def _host_np(self, name):
         """numpy mirror of a (small, constant) camera buffer, refreshed when the buffer changes."""
         buf = getattr(self, name)
@@ -263,6 +273,33 @@ class PlaneModel(nn.Module):
             rgbs.append(rgb)
             alphas.append(alpha)
         return (rgbs[0], alphas[0]) if len(rgbs) == 1 else (torch.cat(rgbs), torch.cat(alphas))
+
+    def camera_normal_equations(self, H, W, extrin, intrin, target, ts=None, learn_focal=False, weight=None, window=(0, 0)):
+        """The Gauss-Newton system of one view's photometric residual in its camera (render.render_normal_equations): extrin [4,4]
+        (ref -> target) and intrin [3,3] of the view, target [T',H,W,3] (T' = len(ts); None: every frame), weight [T',H,W] or None,
+        `window` (row0, col0) of the frame the target covers.  The unknowns are a left twist of the extrinsic and, with `learn_focal`, a log
+        focal scale (poses.camera_tangents) -> (A [P,P], b [P], cost) float64 on the stack's device, P = 6 or 7.  The stack is read only.
+        Refused: what render_cameras refuses."""
+        from .poses import camera_tangents
+        from .render import render_normal_equations
+        who = "camera_normal_equations"
+        if self.atlas_exact:
+            raise RuntimeError(f"{who}: atlas_exact is a parity mode of the reference's atlas sampling; the normal equations are built on the plane stack")
+        if getattr(self, "packed", None) is not None:
+            raise RuntimeError(f"{who}: a packed model has no dense stack to differentiate through (unpack_() it first)")
+        if self.tile_own is not None:
+            raise RuntimeError(f"{who}: the normal equations are not built for the tile-exact layout")
+        if self.rgb_mlp_type != "direct":
+            raise RuntimeError(f"{who}: the normal equations are not built for the view-dependent colour head (rgb_mlp_type = {self.rgb_mlp_type!r})")
+        self._flush_deferred_updates()
+        homos, dhomos = camera_tangents(self, extrin, intrin, learn_focal)
+        stack = self.stack.detach()
+        if ts is not None:
+            stack = stack[:, torch.as_tensor(ts, dtype=torch.long, device=stack.device)]
+        qk = self.quad_keep if (self.is_sparse and getattr(self, "quad_keep", None) is not None) else None
+        dev = stack.device
+        return render_normal_equations(stack, homos.to(dev), dhomos.to(dev), torch.as_tensor(target).to(dev), H, W, self.spec, window=window, quad_keep=qk,
+                                       weight=None if weight is None else torch.as_tensor(weight).to(dev))
 
     # ---- render --------------------------------------------------------------------------------------------------------------
     def _composite_bg(self, rgb, alpha):

@@ -3,7 +3,11 @@
 The inputs of this method are asynchronous hand-held captures whose poses come from COLMAP; both stages take them as given.  A photometric
 refinement needs d loss / d homographies from the render kernels (vl3d_render_bwd_homos) and, on the host, the small differentiable chain
 pose -> homographies (utils_mpi.compute_homography, plain torch as in the reference).  Everything here is host-side float64 torch: a pose is
-six numbers."""
+six numbers.
+
+Second order: the render kernels also form the normal equations of the photometric residual in the camera parameters (vl3d_render_cam_normal
+from the tangents of the homographies, camera_tangents), and refine_cameras_gn takes Levenberg-Marquardt steps on them -- no learning rate,
+and a pose covariance at the end."""
 import torch
 import torch.nn as nn
 
@@ -120,3 +124,94 @@ def refine_cameras(model, targets, extrins, intrins, ts=None, steps=60, lr=5e-5,
         return refine_loop(render, tgt, extrins, intrins, steps, lr, learn_focal, [stack] if train_stack else ())
     finally:
         stack.requires_grad_(was)
+
+
+# ---- Gauss-Newton / Levenberg-Marquardt on the normal equations of the render (vl3d_render_cam_normal) ---------------------------------
+def _focal_scaled(K, log_focal):
+    """K [3,3] with the focal entries (the upper-left 2 x 2 block) scaled by exp(log_focal): CameraDeltas.intrins' rule for one view"""
+    block = torch.zeros((3, 3), dtype=torch.float64)
+    block[:2, :2] = 1
+    return K * (1 + block * (torch.exp(log_focal) - 1))
+
+
+def camera_tangents(model, extrin, intrin, learn_focal=False):
+    """The homographies of one view of a PlaneModel and their tangents in the camera parameters theta = (left twist xi in R^6[, log focal
+    scale]) at theta = 0: E(theta) = se3_exp(xi) E, the focal entries of K scaled by exp(log focal) as CameraDeltas.intrins scales them.
+    extrin [4,4] (ref -> target), intrin [3,3].  The Jacobian of the model's float64 homography chain (PlaneModel.homography_chain) on the
+    host, by forward-mode autograd, rounded to float32 once.
+    -> (homos [D,3,3] float32, dhomos [P,D,3,3] float32), P = 6 or 7: what render.render_normal_equations takes."""
+    E = torch.as_tensor(extrin).detach().cpu().to(torch.float64).reshape(4, 4)
+    K = torch.as_tensor(intrin).detach().cpu().to(torch.float64).reshape(3, 3)
+    P = 7 if learn_focal else 6
+
+    def chain(theta):
+        Kt = _focal_scaled(K, theta[6]) if learn_focal else K
+        return model.homography_chain((se3_exp(theta[:6]) @ E)[None], Kt[None])
+
+    theta0 = torch.zeros(P, dtype=torch.float64)
+    with torch.enable_grad():
+        jac = torch.autograd.functional.jacobian(chain, theta0, vectorize=True, strategy="forward-mode")      # [D,3,3,P]
+    with torch.no_grad():
+        homos = chain(theta0)
+    return homos.float(), jac.permute(3, 0, 1, 2).contiguous().float()
+
+
+def gn_loop(system, extrin, intrin, steps=5, damping=1e-3, learn_focal=False):
+    """Levenberg-Marquardt on one camera over `system(extrin [4,4], intrin [3,3]) -> (A [P,P], b [P], cost)`, the normal equations of a
+    residual in theta = (left twist[, log focal scale]) at that camera (float64 host tensors and a float).  Per step
+    delta = -(A + lambda diag A)^-1 b, E <- se3_exp(delta_xi) E, the focal entries scaled by exp(delta_f).  lambda starts at `damping`; a step
+    whose cost is not below the last accepted one is undone and lambda multiplied by 10, an accepted step divides it by 10, down to `damping`.
+    -> (extrin, intrin, costs: the cost at every evaluated point, A and cost at the last accepted point)."""
+    E, K = extrin, intrin
+    A, b, cost = system(E, K)
+    costs, lam = [cost], float(damping)
+    for _ in range(int(steps)):
+        delta = -torch.linalg.solve(A + lam * torch.diag(torch.diagonal(A)), b)
+        E_try = se3_exp(delta[:6]) @ E
+        K_try = _focal_scaled(K, delta[6]) if learn_focal else K
+        A_try, b_try, cost_try = system(E_try, K_try)
+        costs.append(cost_try)
+        if cost_try < cost:
+            E, K, A, b, cost = E_try, K_try, A_try, b_try, cost_try
+            lam = max(lam / 10, float(damping))
+        else:      # undone: the same point, more damping
+            lam *= 10
+    return E, K, costs, A, cost
+
+
+def refine_cameras_gn(model, targets, extrins, intrins, ts=None, steps=5, damping=1e-3, learn_focal=False, crop=None, weight=None):
+    """Photometric refinement of the cameras of a PlaneModel by Levenberg-Marquardt (gn_loop) on the normal equations the render kernels
+    form (PlaneModel.camera_normal_equations): no learning rate.  targets [V,T',H,W,3], extrins [V,4,4], intrins [V,3,3], `ts`, `crop` as
+    refine_cameras takes them; weight [V,T',H,W] or None: per-pixel weights of the residual (cropped like the targets).  The views are
+    independent blocks and run one after the other, in float64 on the host.  The stack is frozen and untouched.
+    -> (extrinsics [V,4,4], intrinsics [V,3,3], cost history per view (a list of lists: the cost at every evaluated point), covariance [V,P,P])
+    -- float64 host tensors; covariance = sigma^2 A^-1 at the last accepted point, sigma^2 = cost / (N - P), N the count of weighted residuals
+    (pixels of non-zero weight x 3 colour channels; without weights frames x pixels x 3)."""
+    from .plane_model import get_new_intrin
+    extrins = torch.as_tensor(extrins).detach().cpu().to(torch.float64).reshape(-1, 4, 4).clone()
+    intrins = torch.as_tensor(intrins).detach().cpu().to(torch.float64).reshape(-1, 3, 3).clone()
+    V, Tn, H, W = (int(v) for v in targets.shape[:4])
+    if len(extrins) != V or len(intrins) != V:
+        raise RuntimeError(f"refine_cameras_gn: {V} views of targets, {len(extrins)} extrinsics and {len(intrins)} intrinsics")
+    dev = model.stack.device
+    tgt = torch.as_tensor(targets).to(dev, torch.float32)
+    wgt = None if weight is None else torch.as_tensor(weight).to(dev, torch.float32)
+    r0 = c0 = 0
+    if crop is not None:
+        r0, c0, H, W = (int(v) for v in crop)
+        tgt = tgt[:, :, r0:r0 + H, c0:c0 + W]
+        wgt = None if wgt is None else wgt[:, :, r0:r0 + H, c0:c0 + W]
+    P = 7 if learn_focal else 6
+    history, covs = [], []
+    for v in range(V):
+        t_v, w_v = tgt[v].contiguous(), None if wgt is None else wgt[v].contiguous()
+        n_res = 3.0 * (float(Tn * H * W) if w_v is None else float((w_v != 0).sum()))
+
+        def system(E, K):
+            A, b, cost = model.camera_normal_equations(H, W, E, get_new_intrin(K, r0, c0), t_v, ts=ts, learn_focal=learn_focal, weight=w_v)
+            return A.cpu(), b.cpu(), float(cost)
+
+        extrins[v], intrins[v], costs, A, cost = gn_loop(system, extrins[v], intrins[v], steps, damping, learn_focal)
+        history.append(costs)
+        covs.append(cost / max(n_res - P, 1.0) * torch.linalg.inv(A))
+    return extrins, intrins, history, torch.stack(covs)

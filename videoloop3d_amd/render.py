@@ -843,6 +843,71 @@ def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0
     return rgb, alpha
 
 
+def render_normal_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, weight=None, rgb=None):
+    """The Gauss-Newton system of the photometric residual rgb - target in P camera parameters (vl3d_render_cam_normal, include/vl3d.h
+    "Camera normal equations"): stack (D,T,Hs,Ws,4) float32, homos [D,3,3], dhomos [P,D,3,3] = d homos / d theta_k (1 <= P <= 8;
+    poses.camera_tangents), target [T,H,W,3], weight [T,H,W] or None (1), `window` and `quad_keep` as render_planes takes them.
+    -> (A [P,P], b [P], cost) float64 tensors on the stack's device: A = sum w J^T J (symmetric), b = sum w J^T r, cost = sum w r^2 over
+    frames, pixels and colour channels.  `rgb`: the forward picture [T,H,W,3] of the same arguments if the caller holds it; otherwise the
+    existing forward runs here.  Not an autograd function: nothing it returns carries a graph.  It takes what the camera gradient takes
+    (float32 stacks, the planar and the utils_mpi convention, dense or a shared-border quad map) and refuses the rest."""
+    who = "render_normal_equations"
+    L.check_cuda(stack, homos, dhomos, target)
+    if spec.coord_mode == "affine_planes":
+        raise RuntimeError(f"{who} is not built for per-plane records (coord_mode 'affine_planes')")
+    if stack.dtype != torch.float32:
+        raise RuntimeError(f"{who} is built for float32 stacks only, got {stack.dtype}")
+    if getattr(spec, "tile", (0, 0))[0]:
+        raise RuntimeError(f"{who} is not built for the tile-exact layout (RenderSpec.tile)")
+    if getattr(spec, "uv_noise_seed", 0):
+        raise RuntimeError(f"{who} is not built for add_uv_noise (uv_noise_seed = 0)")
+    if int(spec.variant) != 0:
+        raise RuntimeError(f"{who} has no kernel variants (spec.variant = 0)")
+    conv = (spec.coord_mode, spec.border, spec.act_order)
+    if conv not in (("affine", "hardcut", "post"), ("utils_mpi", "zeros", "pre")):
+        raise RuntimeError(f"{who} is built for the planar convention (affine, hardcut, post) and the utils_mpi one (utils_mpi, zeros, pre), got {conv}")
+    if stack.dim() != 5 or stack.shape[4] != 4:
+        raise RuntimeError(f"{who}: the plane stack must be (D,T,Hs,Ws,4), got {tuple(stack.shape)}")
+    D, T = int(stack.shape[0]), int(stack.shape[1])
+    H, W = int(H), int(W)
+    if T < 1 or H < 1 or W < 1:
+        raise RuntimeError(f"{who}: nothing to fit on an empty picture (T = {T}, H = {H}, W = {W})")
+    if tuple(homos.shape) != (D, 3, 3):
+        raise RuntimeError(f"{who}: homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
+    if dhomos.dim() != 4 or tuple(dhomos.shape[1:]) != (D, 3, 3) or not 1 <= dhomos.shape[0] <= 8:
+        raise RuntimeError(f"{who}: dhomos must be [P,D,3,3] = [1..8,{D},3,3], got {tuple(dhomos.shape)}")
+    if tuple(target.shape) != (T, H, W, 3):
+        raise RuntimeError(f"{who}: target must be [T,H,W,3] = [{T},{H},{W},3], got {tuple(target.shape)}")
+    if weight is not None:
+        L.check_cuda(weight)
+        if tuple(weight.shape) != (T, H, W):
+            raise RuntimeError(f"{who}: weight must be [T,H,W] = [{T},{H},{W}], got {tuple(weight.shape)}")
+        weight = weight.detach().to(torch.float32).contiguous()
+    if rgb is not None:
+        L.check_cuda(rgb)
+        if tuple(rgb.shape) != (T, H, W, 3):
+            raise RuntimeError(f"{who}: rgb must be the forward picture [T,H,W,3] = [{T},{H},{W},3], got {tuple(rgb.shape)}")
+    P = int(dhomos.shape[0])
+    stack = stack.detach().contiguous()
+    homos = homos.detach().to(torch.float32).contiguous()
+    dhomos = dhomos.detach().to(torch.float32).contiguous()
+    target = target.detach().to(torch.float32).contiguous()
+    if quad_keep is not None:
+        quad_keep = _quad_map(quad_keep, D)
+    if rgb is None:
+        with torch.no_grad():
+            rgb, _ = render_planes(stack, homos, H, W, spec, window=window, quad_keep=quad_keep)
+    rgb = rgb.detach().to(torch.float32).contiguous()
+    desc = _desc(stack, H, W, spec, int(window[0]), int(window[1]))
+    out = torch.empty(P * P + P + 1, dtype=torch.float64, device=stack.device)
+    with torch.cuda.device(stack.device):
+        nb = int(L.lib().vl3d_render_cam_normal_scratch_bytes(desc, P))
+        scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=stack.device)
+        L.check(L.lib().vl3d_render_cam_normal(desc, L.ptr(stack), L.ptr(homos), L.ptr(dhomos), P, *_qmap(quad_keep, spec), L.ptr(rgb), L.ptr(target),
+                                               L.ptr(weight), L.ptr(out), L.ptr(scratch), nb, L.stream_ptr(stack.device)), "vl3d_render_cam_normal")
+    return out[:P * P].view(P, P), out[P * P:P * P + P], out[P * P + P]
+
+
 def render_planes_with_smoothness(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None):
     """render_planes plus the raw sums of the layer-space smoothness regularisers (MPV.py:517-531), differentiable:
     returns (rgb, alpha, sums[4]) with sums = (sum|dx rgb|, sum|dy rgb|, sum|dx a|, sum|dy a|) over frames, planes and
