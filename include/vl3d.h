@@ -414,6 +414,31 @@ int vl3d_render_cam_normal(const vl3d_render_desc *desc, const void *stack, cons
                            const uint8_t *quad_keep, int32_t QH, int32_t QW, const float *rgb, const float *target, const float *weight,
                            double *out /* double[P*P + P + 1] */, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
 
+/* Camera registration (csrc/vl3d_render_cam_register.hip): the normal equations above for a target that is a CAPTURED clip of the view, not the
+ * model's own picture frame for frame -- the same loop started at an unknown time, exposed differently.  C[t,p,c] is the saved forward picture
+ * `rgb`, J[t,p,c,k] the per-pixel Jacobian exactly as vl3d_render_cam_normal forms it (the same device functions, coverage rules and tent
+ * slopes), g = exp(log_gain), beta = bias: the point at which the system is evaluated.
+ *   mode = VL3D_CAM_PER_FRAME:      r[t,p,c] = g C + beta - I[t,p,c];   column k < P: g J[t,p,c,k];  target (T,H,W,3), weight (T,H,W) or NULL
+ *   mode = VL3D_CAM_LONG_EXPOSURE:  Cm[p,c] = (1 / T) sum_t C,  Jm[p,c,k] = (1 / T) sum_t J,  r[p,c] = g Cm + beta - I[p,c];  column k < P: g Jm;
+ *                                   target (H,W,3) -- the temporal mean of the clip --, weight (H,W) or NULL
+ *   photo = 1: two more unknowns, the log gain and the bias: column P is g C (g Cm), column P + 1 is 1.  photo = 0: (log_gain, bias) still
+ *              shape the residual and the columns, but are not unknowns.
+ *     out = A [Q][Q] = sum w col_k col_l (both triangles written),  b [Q] = sum w col_k r,  cost = sum w r^2,   Q = P + 2 photo;
+ *     double[Q*Q + Q + 1], overwritten.
+ * A long exposure of a clip equals the loop's only when the clip spans whole loop periods: a caveat of the method, not of the kernel.
+ * The reduction is vl3d_render_cam_normal's: no float atomics, one fp64 partial per workgroup in `scratch`, a finish kernel that adds them in a
+ * fixed order; two calls give identical bits; at T = 1 the two modes give identical bits.
+ * Accepted: exactly what vl3d_render_cam_normal accepts; everything it refuses is refused here with the same codes.  In addition VL3D_EINVAL:
+ *     mode or photo outside {0, 1}, a non-finite log_gain or bias (or exp(log_gain) not a finite float), P < 1 or P > 8, a NULL or misaligned
+ *     pointer, scratch_bytes below vl3d_render_cam_register_scratch_bytes(desc, P, photo) (0 for arguments it refuses).  Nothing is launched
+ *     after a refusal, and `out` is not written. */
+enum { VL3D_CAM_PER_FRAME = 0, VL3D_CAM_LONG_EXPOSURE = 1 };
+int64_t vl3d_render_cam_register_scratch_bytes(const vl3d_render_desc *desc, int32_t P, int32_t photo);
+int vl3d_render_cam_register(const vl3d_render_desc *desc, const void *stack, const float *homos, const float *dhomos, int32_t P,
+                             const uint8_t *quad_keep, int32_t QH, int32_t QW, const float *rgb, const float *target, const float *weight,
+                             int32_t mode, int32_t photo, float log_gain, float bias,
+                             double *out /* double[Q*Q + Q + 1] */, void *scratch, int64_t scratch_bytes, vl3d_stream_t stream);
+
 /* Which kernel a backward call runs, without running it: the value the entry points themselves compute (the same two functions, no device
  * touched, nothing enqueued).  entry: which entry point; has_quad_keep / has_reg_grads (grad_reg or grad_alpha_sums non-NULL) / scratch_bytes:
  * as the call would pass them (scratch_bytes 0 = scratch NULL); fused_step: vl3d_render_bwd_adam (entry VL3D_BWD_ENTRY_ADAM) only.  Refusals

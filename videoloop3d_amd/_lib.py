@@ -141,6 +141,8 @@ SIGNATURES = {
     "vl3d_warp_bwd_homos": ([_I32] * 6 + [_P, _P, _P, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_cam_normal_scratch_bytes": ([C.POINTER(RenderDesc), _I32], C.c_int64),
     "vl3d_render_cam_normal": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
+    "vl3d_render_cam_register_scratch_bytes": ([C.POINTER(RenderDesc), _I32, _I32], C.c_int64),
+    "vl3d_render_cam_register": ([C.POINTER(RenderDesc), _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _I64, _P], C.c_int),
     "vl3d_render_bwd_adam": ([C.POINTER(RenderDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(AdamWindow), _P], C.c_int),
     "vl3d_render_reg_state_bytes": ([C.POINTER(RenderDesc)], C.c_int64),
     "vl3d_tie_static_grad": ([_I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, _P], C.c_int),

@@ -301,6 +301,35 @@ class PlaneModel(nn.Module):
         return render_normal_equations(stack, homos.to(dev), dhomos.to(dev), torch.as_tensor(target).to(dev), H, W, self.spec, window=window, quad_keep=qk,
                                        weight=None if weight is None else torch.as_tensor(weight).to(dev))
 
+    def camera_register_equations(self, H, W, extrin, intrin, target, ts=None, learn_focal=False, weight=None, window=(0, 0), long_exposure=False,
+                                  brightness=None):
+        """The Gauss-Newton system of registering one view against a captured clip (render.render_register_equations): camera_normal_equations
+        with `long_exposure` (target [H,W,3], the clip's temporal mean, against the mean of the frames `ts`; weight [H,W] or None) and
+        `brightness` = (log_gain, bias), two more unknowns after the camera's, evaluated at that point (None: none)
+        -> (A [Q,Q], b [Q], cost) float64 on the stack's device, Q = P (+ 2 with `brightness`).  The stack is read only.
+        Refused: what camera_normal_equations refuses."""
+        from .poses import camera_tangents
+        from .render import render_register_equations
+        who = "camera_register_equations"
+        if self.atlas_exact:
+            raise RuntimeError(f"{who}: atlas_exact is a parity mode of the reference's atlas sampling; the normal equations are built on the plane stack")
+        if getattr(self, "packed", None) is not None:
+            raise RuntimeError(f"{who}: a packed model has no dense stack to differentiate through (unpack_() it first)")
+        if self.tile_own is not None:
+            raise RuntimeError(f"{who}: the normal equations are not built for the tile-exact layout")
+        if self.rgb_mlp_type != "direct":
+            raise RuntimeError(f"{who}: the normal equations are not built for the view-dependent colour head (rgb_mlp_type = {self.rgb_mlp_type!r})")
+        self._flush_deferred_updates()
+        homos, dhomos = camera_tangents(self, extrin, intrin, learn_focal)
+        stack = self.stack.detach()
+        if ts is not None:
+            stack = stack[:, torch.as_tensor(ts, dtype=torch.long, device=stack.device)]
+        qk = self.quad_keep if (self.is_sparse and getattr(self, "quad_keep", None) is not None) else None
+        dev = stack.device
+        return render_register_equations(stack, homos.to(dev), dhomos.to(dev), torch.as_tensor(target).to(dev), H, W, self.spec, window=window,
+                                         quad_keep=qk, weight=None if weight is None else torch.as_tensor(weight).to(dev),
+                                         long_exposure=long_exposure, brightness=brightness)
+
     # ---- render --------------------------------------------------------------------------------------------------------------
     def _composite_bg(self, rgb, alpha):
         """MPI.py:550-556, MPV.py:455-461 (as written): the render over args.bg_color ("" = none, "random" = one draw per call, "r#g#b")."""

@@ -7,7 +7,14 @@ six numbers.
 
 Second order: the render kernels also form the normal equations of the photometric residual in the camera parameters (vl3d_render_cam_normal
 from the tangents of the homographies, camera_tangents), and refine_cameras_gn takes Levenberg-Marquardt steps on them -- no learning rate,
-and a pose covariance at the end."""
+and a pose covariance at the end.
+
+Captured clips: a clip of a view is the same loop started at an unknown time and exposed differently, so a per-frame residual against it has no
+meaning and a brightness offset would be absorbed into the pose.  register_cameras fits the temporal mean of the rendered frames to the temporal
+mean of the clip (stage 1's statistic, train_3d.py:52-56) with a log gain and a bias per view (train_3d.py:217, MPV.py:499-504), on the normal
+equations of vl3d_render_cam_register."""
+import dataclasses
+
 import torch
 import torch.nn as nn
 
@@ -215,3 +222,101 @@ def refine_cameras_gn(model, targets, extrins, intrins, ts=None, steps=5, dampin
         history.append(costs)
         covs.append(cost / max(n_res - P, 1.0) * torch.linalg.inv(A))
     return extrins, intrins, history, torch.stack(covs)
+
+
+# ---- registration against a captured clip: long exposure and a brightness fit (vl3d_render_cam_register) ------------------------------------
+@dataclasses.dataclass
+class Registration:
+    """what register_cameras returns, float64 host tensors: extrinsics [V,4,4], intrinsics [V,3,3], log_gain [V] and bias [V] (the clip is
+    exp(log_gain) picture + bias; zeros without the brightness fit), costs (per view: the cost at every evaluated point), covariance [V,Q,Q] of
+    theta = (twist[, log focal][, log gain, bias]) at the last accepted point."""
+    extrinsics: torch.Tensor
+    intrinsics: torch.Tensor
+    log_gain: torch.Tensor
+    bias: torch.Tensor
+    costs: list
+    covariance: torch.Tensor
+
+
+def register_loop(system, extrin, intrin, steps=8, damping=1e-3, learn_focal=False, fit_brightness=True, log_gain=0.0, bias=0.0):
+    """gn_loop with two more unknowns: Levenberg-Marquardt on one camera and, with `fit_brightness`, the log gain a and the bias beta of its
+    clip, over `system(extrin [4,4], intrin [3,3], a, beta) -> (A [Q,Q], b [Q], cost)` in theta = (left twist[, log focal scale][, a, beta])
+    at that point (float64 host tensors and a float).  Per step delta = -(A + lambda diag A)^-1 b, E <- se3_exp(delta_xi) E, the focal entries
+    scaled by exp(delta_f), a <- a + delta_a, beta <- beta + delta_beta; the accept / reject rule and the damping schedule are gn_loop's.
+    -> (extrin, intrin, a, beta, costs: the cost at every evaluated point, A and cost at the last accepted point)."""
+    E, K, a, beta = extrin, intrin, float(log_gain), float(bias)
+    A, b, cost = system(E, K, a, beta)
+    costs, lam = [cost], float(damping)
+    n_cam = 7 if learn_focal else 6
+    for _ in range(int(steps)):
+        delta = -torch.linalg.solve(A + lam * torch.diag(torch.diagonal(A)), b)
+        E_try = se3_exp(delta[:6]) @ E
+        K_try = _focal_scaled(K, delta[6]) if learn_focal else K
+        a_try, beta_try = (a + float(delta[n_cam]), beta + float(delta[n_cam + 1])) if fit_brightness else (a, beta)
+        A_try, b_try, cost_try = system(E_try, K_try, a_try, beta_try)
+        costs.append(cost_try)
+        if cost_try < cost:
+            E, K, a, beta, A, b, cost = E_try, K_try, a_try, beta_try, A_try, b_try, cost_try
+            lam = max(lam / 10, float(damping))
+        else:      # undone: the same point, more damping
+            lam *= 10
+    return E, K, a, beta, costs, A, cost
+
+
+def register_cameras(model, clips, extrins, intrins, ts=None, steps=8, damping=1e-3, learn_focal=False, crop=None, weight=None, long_exposure=True,
+                     fit_brightness=True):
+    """Register the cameras of captured clips against a PlaneModel: refine_cameras_gn for targets that are NOT the model's own frames.  A
+    captured clip of a view is the same loop started at an unknown time, possibly with another frame count, and exposed differently, so
+      * `long_exposure`: the residual is taken between the temporal mean of the rendered frames (`ts`; None: every frame) and the temporal mean
+        of the clip -- clips [V,F,H,W,3] or a list of V clips [F_v,H,W,3], any F.  The two means describe the same picture only when the clip
+        spans whole loop periods: a caveat of the method.  Without it the residual is per frame, and F must be the number of rendered frames;
+      * `fit_brightness`: a log gain and a bias per view are fitted beside the camera (clip = exp(log_gain) picture + bias), instead of being
+        absorbed into the pose.
+    Levenberg-Marquardt (register_loop) on PlaneModel.camera_register_equations, the views one after the other, in float64 on the host; the
+    stack is frozen and untouched.  weight: per-pixel weights, [V,H,W] with `long_exposure`, else [V,F,H,W]; `crop`, `learn_focal`, `steps`,
+    `damping` as refine_cameras_gn takes them.
+    -> Registration; covariance = sigma^2 A^-1, sigma^2 = cost / (N - Q), N the count of weighted residuals (pixels of non-zero weight x 3;
+    with `long_exposure` the pixels of ONE picture)."""
+    from .plane_model import get_new_intrin
+    who = "register_cameras"
+    extrins = torch.as_tensor(extrins).detach().cpu().to(torch.float64).reshape(-1, 4, 4).clone()
+    intrins = torch.as_tensor(intrins).detach().cpu().to(torch.float64).reshape(-1, 3, 3).clone()
+    clips = [torch.as_tensor(c) for c in clips] if isinstance(clips, (list, tuple)) else list(torch.as_tensor(clips))
+    V = len(clips)
+    if len(extrins) != V or len(intrins) != V:
+        raise RuntimeError(f"{who}: {V} clips, {len(extrins)} extrinsics and {len(intrins)} intrinsics")
+    if weight is not None and len(weight) != V:
+        raise RuntimeError(f"{who}: {V} clips and {len(weight)} weight maps")
+    dev = model.stack.device
+    n_frames = int(model.stack.shape[1]) if ts is None else len(ts)
+    P = 7 if learn_focal else 6
+    Q = P + (2 if fit_brightness else 0)
+    history, covs, gains, biases = [], [], [], []
+    for v in range(V):
+        clip = clips[v].to(dev, torch.float32)
+        if clip.dim() != 4 or clip.shape[-1] != 3 or clip.shape[0] < 1:
+            raise RuntimeError(f"{who}: clip {v} must be [F,H,W,3], got {tuple(clip.shape)}")
+        if not long_exposure and clip.shape[0] != n_frames:
+            raise RuntimeError(f"{who}: without long_exposure clip {v} needs the {n_frames} rendered frames, got {clip.shape[0]}")
+        t_v = clip.double().mean(0).float() if long_exposure else clip      # the long exposure: the clip's temporal mean
+        w_v = None if weight is None else torch.as_tensor(weight[v]).to(dev, torch.float32)
+        H, W = (int(s) for s in clip.shape[1:3])
+        r0 = c0 = 0
+        if crop is not None:
+            r0, c0, H, W = (int(s) for s in crop)
+            t_v = t_v[..., r0:r0 + H, c0:c0 + W, :]
+            w_v = None if w_v is None else w_v[..., r0:r0 + H, c0:c0 + W]
+        t_v, w_v = t_v.contiguous(), None if w_v is None else w_v.contiguous()
+        n_res = 3.0 * (float(t_v.numel() // 3) if w_v is None else float((w_v != 0).sum()))
+
+        def system(E, K, a, beta):
+            A, b, cost = model.camera_register_equations(H, W, E, get_new_intrin(K, r0, c0), t_v, ts=ts, learn_focal=learn_focal, weight=w_v,
+                                                         long_exposure=long_exposure, brightness=(a, beta) if fit_brightness else None)
+            return A.cpu(), b.cpu(), float(cost)
+
+        extrins[v], intrins[v], a, beta, costs, A, cost = register_loop(system, extrins[v], intrins[v], steps, damping, learn_focal, fit_brightness)
+        history.append(costs)
+        gains.append(a)
+        biases.append(beta)
+        covs.append(cost / max(n_res - Q, 1.0) * torch.linalg.inv(A))
+    return Registration(extrins, intrins, torch.tensor(gains, dtype=torch.float64), torch.tensor(biases, dtype=torch.float64), history, torch.stack(covs))

@@ -3,6 +3,7 @@
 Host-side mirror of the chain MPV.py:351-454 (planar geometry) / utils_mpi.py:159-176 + 92-107 of the
 reference, behind a torch.autograd.Function.  The arithmetic lives in csrc/vl3d_render.hip.
 """
+import math
 import types
 from dataclasses import dataclass
 
@@ -843,15 +844,10 @@ def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0
     return rgb, alpha
 
 
-def render_normal_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, weight=None, rgb=None):
-    """The Gauss-Newton system of the photometric residual rgb - target in P camera parameters (vl3d_render_cam_normal, include/vl3d.h
-    "Camera normal equations"): stack (D,T,Hs,Ws,4) float32, homos [D,3,3], dhomos [P,D,3,3] = d homos / d theta_k (1 <= P <= 8;
-    poses.camera_tangents), target [T,H,W,3], weight [T,H,W] or None (1), `window` and `quad_keep` as render_planes takes them.
-    -> (A [P,P], b [P], cost) float64 tensors on the stack's device: A = sum w J^T J (symmetric), b = sum w J^T r, cost = sum w r^2 over
-    frames, pixels and colour channels.  `rgb`: the forward picture [T,H,W,3] of the same arguments if the caller holds it; otherwise the
-    existing forward runs here.  Not an autograd function: nothing it returns carries a graph.  It takes what the camera gradient takes
-    (float32 stacks, the planar and the utils_mpi convention, dense or a shared-border quad map) and refuses the rest."""
-    who = "render_normal_equations"
+def _cam_system_args(who, stack, homos, dhomos, target, H, W, spec, window, quad_keep, weight, rgb, per_frame):
+    """what render_normal_equations and render_register_equations check and prepare: -> (stack, homos, dhomos, target, weight, rgb, quad_keep,
+    desc, P), contiguous float32 on the stack's device; `rgb` is the forward picture (rendered here if the caller gave none).  per_frame:
+    target [T,H,W,3] and weight [T,H,W]; otherwise one picture, [H,W,3] and [H,W]."""
     L.check_cuda(stack, homos, dhomos, target)
     if spec.coord_mode == "affine_planes":
         raise RuntimeError(f"{who} is not built for per-plane records (coord_mode 'affine_planes')")
@@ -876,12 +872,14 @@ def render_normal_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec
         raise RuntimeError(f"{who}: homos must be [D,3,3] = [{D},3,3], got {tuple(homos.shape)}")
     if dhomos.dim() != 4 or tuple(dhomos.shape[1:]) != (D, 3, 3) or not 1 <= dhomos.shape[0] <= 8:
         raise RuntimeError(f"{who}: dhomos must be [P,D,3,3] = [1..8,{D},3,3], got {tuple(dhomos.shape)}")
-    if tuple(target.shape) != (T, H, W, 3):
-        raise RuntimeError(f"{who}: target must be [T,H,W,3] = [{T},{H},{W},3], got {tuple(target.shape)}")
+    frames, lead = ((T,), "T,") if per_frame else ((), "")
+    dims = ",".join(str(v) for v in frames + (H, W))
+    if tuple(target.shape) != frames + (H, W, 3):
+        raise RuntimeError(f"{who}: target must be [{lead}H,W,3] = [{dims},3], got {tuple(target.shape)}")
     if weight is not None:
         L.check_cuda(weight)
-        if tuple(weight.shape) != (T, H, W):
-            raise RuntimeError(f"{who}: weight must be [T,H,W] = [{T},{H},{W}], got {tuple(weight.shape)}")
+        if tuple(weight.shape) != frames + (H, W):
+            raise RuntimeError(f"{who}: weight must be [{lead}H,W] = [{dims}], got {tuple(weight.shape)}")
         weight = weight.detach().to(torch.float32).contiguous()
     if rgb is not None:
         L.check_cuda(rgb)
@@ -899,6 +897,20 @@ def render_normal_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec
             rgb, _ = render_planes(stack, homos, H, W, spec, window=window, quad_keep=quad_keep)
     rgb = rgb.detach().to(torch.float32).contiguous()
     desc = _desc(stack, H, W, spec, int(window[0]), int(window[1]))
+    return stack, homos, dhomos, target, weight, rgb, quad_keep, desc, P
+
+
+def render_normal_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, weight=None, rgb=None):
+    """The Gauss-Newton system of the photometric residual rgb - target in P camera parameters (vl3d_render_cam_normal, include/vl3d.h
+    "Camera normal equations"): stack (D,T,Hs,Ws,4) float32, homos [D,3,3], dhomos [P,D,3,3] = d homos / d theta_k (1 <= P <= 8;
+    poses.camera_tangents), target [T,H,W,3], weight [T,H,W] or None (1), `window` and `quad_keep` as render_planes takes them.
+    -> (A [P,P], b [P], cost) float64 tensors on the stack's device: A = sum w J^T J (symmetric), b = sum w J^T r, cost = sum w r^2 over
+    frames, pixels and colour channels.  `rgb`: the forward picture [T,H,W,3] of the same arguments if the caller holds it; otherwise the
+    existing forward runs here.  Not an autograd function: nothing it returns carries a graph.  It takes what the camera gradient takes
+    (float32 stacks, the planar and the utils_mpi convention, dense or a shared-border quad map) and refuses the rest."""
+    who = "render_normal_equations"
+    stack, homos, dhomos, target, weight, rgb, quad_keep, desc, P = _cam_system_args(who, stack, homos, dhomos, target, H, W, spec, window, quad_keep,
+                                                                                  weight, rgb, per_frame=True)
     out = torch.empty(P * P + P + 1, dtype=torch.float64, device=stack.device)
     with torch.cuda.device(stack.device):
         nb = int(L.lib().vl3d_render_cam_normal_scratch_bytes(desc, P))
@@ -906,6 +918,34 @@ def render_normal_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec
         L.check(L.lib().vl3d_render_cam_normal(desc, L.ptr(stack), L.ptr(homos), L.ptr(dhomos), P, *_qmap(quad_keep, spec), L.ptr(rgb), L.ptr(target),
                                                L.ptr(weight), L.ptr(out), L.ptr(scratch), nb, L.stream_ptr(stack.device)), "vl3d_render_cam_normal")
     return out[:P * P].view(P, P), out[P * P:P * P + P], out[P * P + P]
+
+
+def render_register_equations(stack, homos, dhomos, target, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, weight=None, rgb=None,
+                              long_exposure=False, brightness=None):
+    """The Gauss-Newton system of registering a view against a CAPTURED clip (vl3d_render_cam_register, include/vl3d.h "Camera registration"):
+    render_normal_equations with two additions.  `long_exposure`: the residual is taken on the temporal mean of the T rendered frames against
+    ONE picture, target [H,W,3] (the clip's temporal mean; weight [H,W] or None) -- a clip of the same loop started at an unknown time has no
+    frame-for-frame residual, its long exposure has one when it spans whole loop periods.  Otherwise target [T,H,W,3], weight [T,H,W].
+    `brightness` = (log_gain, bias): the residual is exp(log_gain) picture + bias - target, and the log gain and the bias are two more unknowns
+    after the P camera parameters, evaluated at that point; None: no brightness unknowns (gain 1, bias 0).
+    -> (A [Q,Q], b [Q], cost) float64 on the stack's device, Q = P + 2 with `brightness`, else P.  Everything else -- stack, homos, dhomos,
+    `window`, `quad_keep`, `rgb`, what is refused -- as render_normal_equations."""
+    who = "render_register_equations"
+    photo = brightness is not None
+    log_gain, bias = (float(brightness[0]), float(brightness[1])) if photo else (0.0, 0.0)
+    if not (math.isfinite(log_gain) and math.isfinite(bias)):
+        raise RuntimeError(f"{who}: brightness = (log_gain, bias) must be finite, got {(log_gain, bias)}")
+    stack, homos, dhomos, target, weight, rgb, quad_keep, desc, P = _cam_system_args(who, stack, homos, dhomos, target, H, W, spec, window, quad_keep,
+                                                                                  weight, rgb, per_frame=not long_exposure)
+    Q = P + 2 * int(photo)
+    out = torch.empty(Q * Q + Q + 1, dtype=torch.float64, device=stack.device)
+    with torch.cuda.device(stack.device):
+        nb = int(L.lib().vl3d_render_cam_register_scratch_bytes(desc, P, int(photo)))
+        scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=stack.device)
+        L.check(L.lib().vl3d_render_cam_register(desc, L.ptr(stack), L.ptr(homos), L.ptr(dhomos), P, *_qmap(quad_keep, spec), L.ptr(rgb), L.ptr(target),
+                                                 L.ptr(weight), 1 if long_exposure else 0, int(photo), log_gain, bias, L.ptr(out), L.ptr(scratch), nb,
+                                                 L.stream_ptr(stack.device)), "vl3d_render_cam_register")
+    return out[:Q * Q].view(Q, Q), out[Q * Q:Q * Q + Q], out[Q * Q + Q]
 
 
 def render_planes_with_smoothness(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None):
