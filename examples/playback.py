@@ -103,6 +103,13 @@ def run(full=False, outdir=None, dev="cuda:0", fps_out=None, trim=False, y4m=Non
     out["pool_disparity_equals_baked_disparity"] = bool(torch.equal(maps["baked_pool"], maps["baked"]))
     out["max_abs_disparity_baked_vs_float"] = float((maps["baked"] - maps["float"]).abs().max())
     del maps
+    # colour and 16-bit depth of every frame from one render launch per chunk (render_video.render_rgbd_frames)
+    for name, model_b in (("baked", baked), ("baked_pool", pool)):
+        RV.render_rgbd_frames(model_b, H, W, ext[:4], intr[:4], rt[:4])      # untimed
+        sync(); t0 = time.perf_counter()
+        RV.render_rgbd_frames(model_b, H, W, ext, intr, rt)
+        sync(); dt = time.perf_counter() - t0
+        out[name]["rgbd"] = {"frames_per_s": N / dt, "ms_per_frame": dt / N * 1e3}
     mse = float(((frames["float"].float() - frames["baked"].float()) / 255).pow(2).mean())
     out["psnr_baked_vs_float_dB"] = float("inf") if mse == 0 else -10 * np.log10(mse)
     out["pool_frames_equal_baked_frames"] = bool(torch.equal(frames["baked_pool"], frames["baked"]))

@@ -3,7 +3,9 @@
 at 720p, D = 32, a 50-frame loop -- the spiral (a new camera per frame: one launch each, like the reference's loop) and a fixed view (`--v r0`:
 the loop's frames in batched calls).  `--disparity`: also the depth maps of the same frames (`render_video.render_disparity_frames`), with
 the range of the map.  `--y4m PATH`: also write the spiral to PATH as a YUV4MPEG2 file (`render_video.write_video`: any player opens it) and
-report the frames per second to the file.  Synthetic poses and weights."""
+report the frames per second to the file.  `--baked --rgbd DIR`: bake the model (`baked.bake`) and write the spiral as RGB-D -- colour and depth of
+every frame from one render launch (`render_video.write_rgbd`): DIR/rgb.y4m and the 16-bit depth DIR/depth/%04d.pgm (binary PGM, maxval 65535:
+an opaque pixel of the nearest plane 65535, an uncovered pixel 0).  Synthetic poses and weights."""
 import json
 import os
 import sys
@@ -15,7 +17,7 @@ import numpy as np
 import torch
 
 
-def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=False, y4m=None):
+def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=False, y4m=None, rgbd=None):
     from videoloop3d_amd.MPV import MPMeshVid
     from videoloop3d_amd import render_video as RV
     dev = torch.device(dev)
@@ -61,6 +63,16 @@ def run(H=720, W=1280, planes=32, frames=50, views=8, dev="cuda:0", disparity=Fa
             n = RV.write_video(y4m, model, H, W, ve, vi, rt, fps=25)
             dt = time.perf_counter() - t0      # (write_video returns with the file closed)
             out[name]["y4m"] = {"path": y4m, "frames": n, "bytes": os.path.getsize(y4m), "frames_per_s": n / dt}
+        if rgbd and name == "spiral":
+            from videoloop3d_amd.baked import bake
+            playback = bake(model)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = RV.write_rgbd(os.path.join(rgbd, "rgb.y4m"), os.path.join(rgbd, "depth"), playback, H, W, ve, vi, rt, fps=25)
+            dt = time.perf_counter() - t0
+            first = RV.read_pgm16(os.path.join(rgbd, "depth", "0000.pgm"))
+            out[name]["rgbd"] = {"dir": rgbd, "frames": n, "frames_per_s": n / dt, "depth_levels_frame_0": [int(first.min()), int(first.max())]}
+            del playback
     out["shape"] = f"{H}x{W}, D={planes}, T={frames}, planes {tuple(model.stack.shape[2:4])}, uint8 frames on the device"
     return out
 
@@ -70,7 +82,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--disparity", action="store_true", help="also render the depth maps of the frames and report their range")
     ap.add_argument("--y4m", default=None, metavar="PATH", help="also write the spiral to PATH as a YUV4MPEG2 (.y4m) file")
+    ap.add_argument("--baked", action="store_true", help="bake the model to its 8-bit playback form (needed by --rgbd)")
+    ap.add_argument("--rgbd", default=None, metavar="DIR", help="with --baked: write the spiral as DIR/rgb.y4m and DIR/depth/%%04d.pgm (16-bit depth)")
     a = ap.parse_args()
+    if a.rgbd and not a.baked:
+        ap.error("--rgbd renders the playback model: pass --baked")
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run(disparity=a.disparity, y4m=a.y4m)))
+    print(json.dumps(run(disparity=a.disparity, y4m=a.y4m, rgbd=a.rgbd)))

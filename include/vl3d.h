@@ -243,7 +243,7 @@ int vl3d_render_fwd_baked_pool_times(const vl3d_render_desc *desc, const int32_t
  *     sizes as there.  a_k = the bilinear blend of the decoded alpha bytes (blend<3> of csrc/vl3d_baked_core.h, no activation) * coverage: the
  *     alpha written here has the bits of the float sink's alpha of the colour entry on the same call.  A tap in a pool block without storage
  *     reads the alpha byte of culled_rgba8; the pool's output has the bits of the clip entry on the unpacked texels; a path frame whose camera
- *     or frame is out of range stays unwritten.  There is no loop-time (vl3d_baked_times) form.
+ *     or frame is out of range stays unwritten.  There is no loop-time (vl3d_baked_times) form here: "RGB-D" below has it.
  *   VL3D_EINVAL, nothing launched, with the colour entries' messages: a NULL disp, rows, homos or source, a misaligned source, rows or
  *     output, D > 128, a run that leaves the clip, whatever check_baked_frames refuses, a bad quad grid. */
 int vl3d_render_disp_fwd(const vl3d_render_desc *desc, const void *stack, int32_t frame0, int32_t T_alloc, const float *homos,
@@ -255,6 +255,47 @@ int vl3d_render_disp_baked(const vl3d_render_desc *desc, const uint8_t *baked, i
 int vl3d_render_disp_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos,
                                 const float *rows, const vl3d_baked_frames *sel, const uint8_t *quad_keep, int32_t QH, int32_t QW,
                                 uint32_t culled_rgba8, void *cull_scratch, float *disp, float *alpha, vl3d_stream_t stream);
+
+/* RGB-D (csrc/vl3d_render_rgbd.hip): the picture of "Baked playback" AND the depth map of "Disparity" from ONE render launch -- one walk of
+ * the planes, one fetch of the texels, one per-plane alpha -- for a run, a camera path and a path in loop time, which has no other depth
+ * entry.  Forward only, no host synchronisation, kernels of their own: no entry above changes.
+ *   The rule.  Per covered (pixel, plane) the colour statements of vl3d_render_fwd_baked (at a loop time: of vl3d_render_fwd_baked_times, every
+ *     channel c_K = fmaf(f, b1_K - b0_K, b0_K), alpha included), nothing contracted, and with the SAME w = a T one more accumulator,
+ *         disp = fmaf(w, rho_k, disp),   rho_k = fmaf(rows[k][0], x + c, fmaf(rows[k][1], y + c, rows[k][2]))        ("Disparity")
+ *     rows (D, 3) for a run, (n_cams, D, 3) for a path, device fp32, 4-byte aligned (render.depth_rows; any normalisation folded in).
+ *     Frame pairs per thread for a run of two or more frames, one output frame along a path, one output and two source frames at a loop time.
+ *   Bit for bit: rgb and alpha are the float sink of the colour entry on the same call; frames its display sink; disp of a run or a path is
+ *     vl3d_render_disp_baked(_pool) on the same call; a loop time with f == 0 has the bits of path frame (cam, t0), disp included, and equal
+ *     texels in both frames give the same bits at any f; the pool has the bits of the clip entry on the unpacked texels; a frame does not
+ *     depend on the run or path it is rendered in.
+ *   Source, scratch and quad map: vl3d_render_rgbd_baked takes what vl3d_render_fwd_baked takes, vl3d_render_rgbd_baked_pool what
+ *     vl3d_render_fwd_baked_pool takes; D <= 128.  Selection: exactly one of sel (vl3d_baked_frames: a run or a camera path) and times
+ *     (vl3d_baked_times), the other NULL; a workgroup whose camera, frame or time is out of range returns before any load or store.
+ *   Sink (vl3d_rgbd_out), exactly one of two.  FLOAT: rgb (N,H,W,3), alpha (N,H,W), disp (N,H,W) fp32, all three, 4-byte aligned; frames =
+ *     depth16 = bg = NULL.  DISPLAY: frames / channels / bg by the rules of vl3d_baked_out's display sink, and depth16 (N,H,W) uint16, 2-byte
+ *     aligned, every operation rounded on its own:
+ *         depth16 = (uint16) trunc(65535 * min(max(disp, 0), 1))
+ *     not divided by alpha and not composited over the background: a pixel no plane covers reads 0, which is far.  The normalisation of disp
+ *     to [0, 1] is the caller's, folded into rows (render.depth_rows(normalise=(near, far))).  One two-byte store per pixel: a wave's 64
+ *     levels are 128 contiguous bytes.
+ *   VL3D_EINVAL, nothing launched: what the colour entry of the same source and vl3d_render_disp_baked(_pool) refuse, with their messages
+ *     (a descriptor outside the planar convention is VL3D_EINVAL here, as in the colour entries); both or neither of sel / times; both sinks or
+ *     neither; a float sink without disp (or without rgb or alpha); a display sink without depth16 (or without frames); a misaligned depth16,
+ *     rgb, alpha, disp, rows or homos; a bg with the float sink. */
+typedef struct vl3d_rgbd_out {
+    float *rgb, *alpha, *disp;             /* the float sink: all three */
+    uint8_t *frames;                       /* the display sink: vl3d_baked_out's frames ... */
+    int32_t channels;
+    const float *bg;                       /* ... its background: host float[3] or NULL ... */
+    uint16_t *depth16;                     /* ... and the 16-bit depth (N,H,W) */
+} vl3d_rgbd_out;                           /* 56 bytes */
+int vl3d_render_rgbd_baked(const vl3d_render_desc *desc, const uint8_t *baked, int32_t T_alloc, const float *homos, const float *rows,
+                           const vl3d_baked_frames *sel, const vl3d_baked_times *times, const uint8_t *quad_keep, int32_t QH, int32_t QW,
+                           void *cull_scratch, const vl3d_rgbd_out *out, vl3d_stream_t stream);
+int vl3d_render_rgbd_baked_pool(const vl3d_render_desc *desc, const int32_t *blocks, const uint8_t *pool, int32_t T_model, const float *homos,
+                                const float *rows, const vl3d_baked_frames *sel, const vl3d_baked_times *times, const uint8_t *quad_keep,
+                                int32_t QH, int32_t QW, uint32_t culled_rgba8, void *cull_scratch, const vl3d_rgbd_out *out,
+                                vl3d_stream_t stream);
 
 /* A viewer package's atlases -> the baked pool (csrc/vl3d_pool_from_atlas.hip; baked.open_viewer_package).  A package IS a baked pool in another
  * order: RGBA8 tiles of th x tw texels of the kept quads, static tiles once (static_atlas, As_h x As_w texels, row-major grid of

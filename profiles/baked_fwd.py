@@ -2,7 +2,7 @@
 """In-process A/B of the float forward against the baked forward at cfg3 (D = 32, T = 50, 720p; docs/kernels/K9_baked_playback.md).
 Both stacks are resident (fp32 23.6 GB + RGBA8 5.9 GB), both renders take the same homographies, the legs alternate round by round under
 HIP events on the launch stream; the float leg is the yardstick (the same kernel the parent commit ships, timed in this process).
-  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open|trim|disparity] [--out FILE]
+  python profiles/baked_fwd.py [--warm 20] [--iters 100] [--rounds 10] [--D 32 --T 50 --H 720 --W 1280] [--legs all|dense|culled|path|display|times|open|trim|disparity|rgbd] [--out FILE]
 Prints per leg: ms per call (median / min over the rounds), Mpix/s, and the fraction of 8 TB/s its ALGORITHMIC bytes amount to -- per pixel
 and frame one texel per plane and 16 bytes of output: 16 D + 16 (float), 4 D + 16 (baked).
 
@@ -43,6 +43,13 @@ disparity call's alpha is compared with the colour call's by torch.equal first (
 round under HIP events that span whole calls.  Prints ms per frame (median, min .. max) and (b) / (a); the expectation to check is
 (b) median <= 1.05 (a) median -- the disparity call fetches the same texel lines, writes 8 instead of 16 bytes per pixel and computes less.
 
+The RGBD leg (--legs rgbd; not part of `all`): colour AND depth from one launch (include/vl3d.h "RGB-D") on the same spiral and storages.  Per
+storage and sink -- float (rgb, alpha, disp) and display (RGB8 + D16) -- (a) the colour path call plus the disparity path call of the same
+source, the entries an RGB-D frame costs without it (for the display sink: the colour call's frames8 sink plus the fp32 disparity call; the
+16-bit quantisation in torch that a consumer adds today is NOT counted), against (b) one RGB-D call.  (b)'s outputs are compared bit for
+bit with (a)'s first.  A fourth pair: the loop-time RGB-D call (60 Hz times) against the loop-time colour call alone -- there is no depth twin.  ms per frame with
+min..max, (b) / (a), bytes written per frame.
+
 The TRIM leg (--legs trim; not part of `all`): BakedPool.trimmed() on the culled pair's model, in whose FLOAT stack, before it is baked, the
 outermost --trim-invisible (0.25) of each plane's kept quads get the alpha logit -12 on the texels they can read and the outermost --trim-frozen
 (0.5) of its dynamic quads repeat frame 0 (the shares of quads and of texels are printed).  The report (blocks, slots, bytes, quads), the ms of
@@ -74,7 +81,7 @@ ap.add_argument("--D", type=int, default=32)
 ap.add_argument("--T", type=int, default=50)
 ap.add_argument("--H", type=int, default=720)
 ap.add_argument("--W", type=int, default=1280)
-ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open", "trim", "disparity"])
+ap.add_argument("--legs", default="all", choices=["all", "dense", "culled", "path", "display", "times", "open", "trim", "disparity", "rgbd"])
 ap.add_argument("--trim-invisible", type=float, default=0.25, help="--legs trim: the share of each plane's kept quads (the outermost of its blob) made invisible")
 ap.add_argument("--trim-frozen", type=float, default=0.5, help="--legs trim: the share of each plane's dynamic quads (the outermost) that repeat frame 0")
 ap.add_argument("--poses", type=int, default=120)
@@ -91,7 +98,8 @@ from videoloop3d_amd.baked import BakedPool, bake_texels, culled_texel_rgba8, di
 from videoloop3d_amd.packed import PackedLayout  # noqa: E402
 from videoloop3d_amd.render import (RenderSpec, depth_rows, render_frame_run, render_frame_run_baked, render_frame_run_baked_pool,  # noqa: E402
                                     render_frame_run_disparity, render_path_baked, render_path_baked_pool, render_path_disparity_baked,
-                                    render_path_disparity_baked_pool, render_times_baked, render_times_baked_pool)
+                                    render_path_disparity_baked_pool, render_rgbd_baked, render_rgbd_baked_pool, render_times_baked,
+                                    render_times_baked_pool)
 from videoloop3d_amd.utils_mpi import compute_homography, make_depths  # noqa: E402
 
 assert torch.cuda.is_available(), "profiles/baked_fwd.py measures on the MI355X"
@@ -257,7 +265,7 @@ if a.legs == "disparity":
           f"{'ok' if med['b_disparity'] <= 1.05 * med['a_colour'] else 'ABOVE 1.05'}", flush=True)
     del d_out, legs
 
-if a.legs in ("path", "display", "times", "trim", "disparity"):
+if a.legs in ("path", "display", "times", "trim", "disparity", "rgbd"):
     import math
     del stack, out
     N = a.poses
@@ -334,6 +342,56 @@ if a.legs == "disparity":
         print(f"disparity [{name:6s}] alpha bit-equal {same}; colour {ma / N:.4f} ms/frame ({min(ms['a_colour']) / N:.4f} .. {max(ms['a_colour']) / N:.4f}), "
               f"disparity {mb / N:.4f} ms/frame ({min(ms['b_disparity']) / N:.4f} .. {max(ms['b_disparity']) / N:.4f}) over {a.rounds} rounds of {per} paths of {N}; "
               f"(b) / (a) {mb / ma:.3f} -> {'ok' if mb <= 1.05 * ma else 'ABOVE 1.05'}", flush=True)
+if a.legs == "rgbd":
+    to_ref = torch.linalg.inv(ref_e.double())
+    path_rows = depth_rows(torch.stack([e.double() @ to_ref for e in es]), Kt, make_depths(D, 1.0, 100.0).flip(0), normalise=(1.0, 100.0)).to(dev)
+    tau = loop_times([i * 25.0 / 60.0 for i in range(N)], T)
+    o_c = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
+    o_d = (torch.empty((N, H, W), device=dev), torch.empty((N, H, W), device=dev))
+    o_r = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev), torch.empty((N, H, W), device=dev))
+    f_c, f_r = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+    d16 = torch.empty((N, H, W), dtype=torch.uint16, device=dev)
+    srcs = {
+        "dense": (lambda **o: render_path_baked(baked, cam, ts, path_homos, H, W, spec, **o),
+                  lambda: render_path_disparity_baked(baked, cam, ts, path_homos, path_rows, H, W, spec, out=o_d),
+                  lambda **o: render_rgbd_baked(baked, path_homos, path_rows, H, W, spec, **o),
+                  lambda **o: render_times_baked(baked, cam, tau, path_homos, H, W, spec, **o)),
+        "culled": (lambda **o: render_path_baked(dense, cam, ts, path_homos, H, W, spec, quad_keep=qk, **o),
+                   lambda: render_path_disparity_baked(dense, cam, ts, path_homos, path_rows, H, W, spec, out=o_d, quad_keep=qk),
+                   lambda **o: render_rgbd_baked(dense, path_homos, path_rows, H, W, spec, quad_keep=qk, **o),
+                   lambda **o: render_times_baked(dense, cam, tau, path_homos, H, W, spec, quad_keep=qk, **o)),
+        "pool": (lambda **o: render_path_baked_pool(lay, pool, cam, ts, path_homos, H, W, spec, **kwp, **o),
+                 lambda: render_path_disparity_baked_pool(lay, pool, cam, ts, path_homos, path_rows, H, W, spec, out=o_d, **kwp),
+                 lambda **o: render_rgbd_baked_pool(lay, pool, path_homos, path_rows, H, W, spec, **kwp, **o),
+                 lambda **o: render_times_baked_pool(lay, pool, cam, tau, path_homos, H, W, spec, **kwp, **o)),
+    }
+    px = H * W
+    res["rgbd"] = {"poses": N, "bytes_written_per_frame": {"float_rgbd": px * 20, "float_colour_plus_disparity": px * (16 + 8),
+                                                           "display_rgbd": px * 5, "display_colour_plus_disparity": px * (3 + 8)}}
+    for name, (colour, disparity, rgbd, times) in srcs.items():
+        # the outputs first: (b) has (a)'s bits
+        colour(out=o_c), disparity(), rgbd(path=(cam, ts), out=o_r)
+        same_f = torch.equal(o_r[0], o_c[0]) and torch.equal(o_r[1], o_c[1]) and torch.equal(o_r[2], o_d[0])
+        colour(frames8=f_c), rgbd(path=(cam, ts), frames8=f_r, depth16=d16)
+        same_d = torch.equal(f_r, f_c) and all(torch.equal(d16[i].to(torch.int32), (65535 * o_d[0][i].clamp(0, 1)).to(torch.int32)) for i in range(0, N, 17))
+        pairs = {
+            "float": {"a_colour_then_disparity": lambda: (colour(out=o_c), disparity()), "b_rgbd": lambda: rgbd(path=(cam, ts), out=o_r)},
+            "display": {"a_colour8_then_disparity": lambda: (colour(frames8=f_c), disparity()),
+                        "b_rgbd": lambda: rgbd(path=(cam, ts), frames8=f_r, depth16=d16)},
+            "times_float": {"a_colour_times_alone": lambda: times(out=o_c), "b_rgbd_times": lambda: rgbd(times=(cam, tau), out=o_r)},
+            "times_display": {"a_colour8_times_alone": lambda: times(frames8=f_c),
+                              "b_rgbd_times": lambda: rgbd(times=(cam, tau), frames8=f_r, depth16=d16)},
+        }
+        res["rgbd"][name] = {"float_bit_equal": same_f, "display_bit_equal": same_d, "covered_pixels": float((o_d[1] > 0).float().mean())}
+        for pair, legs in pairs.items():
+            ms, per = ab(legs)
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            first = next(iter(legs))
+            res["rgbd"][name][pair] = {k: {"ms_per_frame_median": med[k] / N, "min": min(ms[k]) / N, "max": max(ms[k]) / N, "over_a": med[k] / med[first]}
+                                       for k in legs}
+            print(f"rgbd [{name:6s} | {pair:13s}] bit-equal float {same_f} display {same_d}; " +
+                  "; ".join(f"{k} {med[k] / N:.4f} ms/frame ({min(ms[k]) / N:.4f} .. {max(ms[k]) / N:.4f}) x{med[k] / med[first]:.3f}" for k in legs) +
+                  f" over {a.rounds} rounds of {per} paths of {N}", flush=True)
 if a.legs == "display":
     o_f = (torch.empty((N, H, W, 3), device=dev), torch.empty((N, H, W), device=dev))
     f_a, f_3, f_4 = (torch.empty((N, H, W, c), dtype=torch.uint8, device=dev) for c in (3, 3, 4))

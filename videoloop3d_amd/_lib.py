@@ -71,6 +71,10 @@ class BakedOut(C.Structure):         # vl3d_baked_out: the float sink (rgb, alph
     _fields_ = [("rgb", _P), ("alpha", _P), ("frames", _P), ("channels", C.c_int32), ("bg", _P)]
 
 
+class RgbdOut(C.Structure):          # vl3d_rgbd_out: the float sink (rgb, alpha, disp) or the display sink (frames, channels, bg, depth16); 56 bytes
+    _fields_ = [("rgb", _P), ("alpha", _P), ("disp", _P), ("frames", _P), ("channels", C.c_int32), ("bg", _P), ("depth16", _P)]
+
+
 class BwdChoice(C.Structure):       # vl3d_bwd_choice: which kernel a backward call runs (vl3d_render_bwd_choice)
     _fields_ = [(n, C.c_int32) for n in ("family", "width", "rows", "reg", "mask", "adam", "cull", "f16", "owner4", "gather9")]
 
@@ -124,6 +128,10 @@ SIGNATURES = {
     "vl3d_render_disp_baked": ([C.POINTER(RenderDesc), _P, _I32, _P, _P, C.POINTER(BakedFrames), _P, _I32, _I32, _P, _P, _P, _P], C.c_int),
     "vl3d_render_disp_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, C.POINTER(BakedFrames), _P, _I32, _I32, C.c_uint32, _P,
                                      _P, _P, _P], C.c_int),
+    "vl3d_render_rgbd_baked": ([C.POINTER(RenderDesc), _P, _I32, _P, _P, C.POINTER(BakedFrames), C.POINTER(BakedTimes), _P, _I32, _I32, _P,
+                                C.POINTER(RgbdOut), _P], C.c_int),
+    "vl3d_render_rgbd_baked_pool": ([C.POINTER(RenderDesc), _P, _P, _I32, _P, _P, C.POINTER(BakedFrames), C.POINTER(BakedTimes), _P, _I32, _I32,
+                                     C.c_uint32, _P, C.POINTER(RgbdOut), _P], C.c_int),
     "vl3d_pool_from_atlas_rgba8": ([_I32] * 8 + [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, C.c_uint32, _P, _P], C.c_int),
     "vl3d_baked_trim_scratch_bytes": ([_I32, _I32, _I32], C.c_int64),
     "vl3d_baked_trim_classify": ([_I32] * 4 + [_P, _P, _I64, C.c_uint32, _P, _I64, _P, _P, _P], C.c_int),

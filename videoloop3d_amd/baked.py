@@ -94,10 +94,11 @@ class _Camera:
         for name in ("ref_extrin", "ref_intrin_mpi", "planedepth"):
             setattr(self, name, getattr(module, name).detach().clone())
 
-    def depth_rows(self, extrins_to_ref, intrins):
-        """the affine rows of the planes' inverse view depth (render.depth_rows) under ref -> target extrinsics [C,4,4] / intrinsics [C,3,3]"""
+    def depth_rows(self, extrins_to_ref, intrins, normalise=None):
+        """the affine rows of the planes' inverse view depth (render.depth_rows) under ref -> target extrinsics [C,4,4] / intrinsics [C,3,3];
+        `normalise` = (near, far): folded into the rows"""
         from .render import depth_rows
-        return depth_rows(extrins_to_ref, intrins, self.planedepth)
+        return depth_rows(extrins_to_ref, intrins, self.planedepth, normalise)
 
 
 def path_cameras(camera, view_extrins, view_intrins):
@@ -118,7 +119,8 @@ class _Baked:
     """what BakedMPV and BakedPool share: camera, background and the module's eval forward over runs of consecutive frames.  A subclass has
     `device`, `frm_num`, `bg_color`, `camera`, `_run(frame0, n, homos, H, W, out)`: its render of a run of frames, read in place, and
     `_path(frame_cam, frame_t, homos [C,D,3,3], H, W, out)`: its render of a camera path; both take `frames8=`, `bg=` for the display frames.
-    `_times(frame_cam, frame_time, homos, H, W, out)`: the path in loop time (`fractional=True`), float32 times in [0, frm_num)."""
+    `_times(frame_cam, frame_time, homos, H, W, out)`: the path in loop time (`fractional=True`), float32 times in [0, frm_num).
+    `_rgbd(homos, rows, H, W, run= | path= | times=, out= | frames8=, depth16=, bg=)`: its RGB-D render (render.render_rgbd_baked / _pool)."""
 
     def extrins_to_ref(self, tar_extrins):
         """world-to-camera poses -> reference-camera-to-target transforms, as MPMeshVid.forward forms them (MPV.py:481)."""
@@ -214,6 +216,76 @@ class _Baked:
                 lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras: a slice of the path's
                 self._disparity_path([c - lo for c in cam_of[c0:c1]], tl[c0:c1], homos[lo:hi], rows[lo:hi], H, W, out)
         return disp, alpha
+
+    @torch.no_grad()
+    def render_rgbd(self, H, W, extrins, intrins, ts, fractional=False, normalise=True, display=False, channels=3, out=None, max_batch=64):
+        """RGB-D frames of a camera path, colour and depth from ONE render launch per chunk (render.render_rgbd_baked / _pool; include/vl3d.h
+        "RGB-D"): N poses (extrins [N,4,4] world-to-camera, intrins [N,3,3]), output frame i showing frame ts[i] of the clip -- or, with
+        `fractional`, the model at the real loop time ts[i] (loop_times reduces it), which no other depth entry renders.
+        -> (rgb [N,H,W,3], alpha [N,H,W], disp [N,H,W]) float32 on the device: rgb and alpha with the bits of render_path before its
+        background, disp with the bits of render_disparity under the same rows; or, with `display`, (frames8 uint8 [N,H,W,channels], depth16
+        uint16 [N,H,W]): render_display's bytes and trunc(65535 clip(disp, 0, 1)), not divided by alpha, 0 where no plane covers the pixel.
+        `normalise`: True maps the inverse depth of the nearest plane to 1 and of the farthest to 0 (folded into the rows,
+        render.depth_rows(normalise=(near, far))), a (near, far) pair names the range, False leaves the inverse view depth as it is
+        (render_disparity's).  `out`: the caller's triple or pair, written in place.  Chunks of at most `max_batch` frames go as
+        render_video.path_segments says -- one run call or one path call, the same bits either way; every chunk of loop times is one call."""
+        from .render_video import path_segments
+        extrins = torch.as_tensor(extrins, dtype=torch.float32).cpu()
+        intrins = torch.as_tensor(intrins, dtype=torch.float32).cpu()
+        if fractional:
+            tl = loop_times(torch.as_tensor(ts).reshape(-1).tolist(), self.frm_num)
+        else:
+            tl = [int(t) for t in torch.as_tensor(ts).reshape(-1).tolist()]
+        n, dev = len(tl), self.device
+        if not (len(extrins) == len(intrins) == n):
+            raise RuntimeError(f"render_rgbd: one pose and one frame per output frame ({len(extrins)} extrins, {len(intrins)} intrins, {n} frames)")
+        if display:
+            if channels not in (3, 4):
+                raise ValueError(f"render_rgbd: channels must be 3 (RGB8) or 4 (RGBA8), got {channels}")
+            bg = self.display_bg()
+            shapes = (((n, H, W, channels), torch.uint8), ((n, H, W), torch.uint16))
+        else:
+            bg = None
+            shapes = (((n, H, W, 3), torch.float32), ((n, H, W), torch.float32), ((n, H, W), torch.float32))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in shapes)
+        elif len(out) != len(shapes) or any(b.dtype != d or tuple(b.shape) != s or not b.is_contiguous() or b.device != dev
+                                           for b, (s, d) in zip(out, shapes)):
+            raise RuntimeError(f"render_rgbd: `out` must be contiguous tensors {[(s, str(d)) for s, d in shapes]} on the model's device")
+        if n == 0:
+            return tuple(out)
+        if normalise is True:
+            z = self.camera.planedepth.detach().double().reshape(-1)
+            normalise = (float(z.min()), float(z.max()))
+        elif normalise is False:
+            normalise = None
+        cam_of, homos = path_cameras(self.camera, extrins, intrins)
+        first = [cam_of.index(c) for c in range(len(homos))]      # a pose of every distinct camera
+        rows = self.camera.depth_rows(self.extrins_to_ref(extrins[first]), intrins[first], normalise)
+        both = torch.cat([homos.to(torch.float32).reshape(-1), rows.reshape(-1)])      # homographies and rows of every camera: one pinned copy
+        if dev.type == "cuda":
+            both = both.pin_memory().to(dev, non_blocking=True)
+        homos, rows = both[:homos.numel()].view(homos.shape), both[homos.numel():].view(rows.shape)
+
+        def sink(c0, c1):
+            part = tuple(b[c0:c1] for b in out)
+            return dict(frames8=part[0], depth16=part[1], bg=bg) if display else dict(out=part)
+
+        if fractional:
+            chunk = max(1, min(int(max_batch), n))
+            segs = [("times", c0, min(n, c0 + chunk)) for c0 in range(0, n, chunk)]
+        else:
+            segs = path_segments(cam_of, tl, max_batch)
+        for kind, c0, c1 in segs:
+            if kind == "run":
+                if not (0 <= tl[c0] and tl[c1 - 1] < self.frm_num):
+                    raise IndexError(f"frame index {tl[c0]} .. {tl[c1 - 1]} outside the clip of {self.frm_num} frames")
+                self._rgbd(homos[cam_of[c0]], rows[cam_of[c0]], H, W, run=(tl[c0], c1 - c0), **sink(c0, c1))
+            else:
+                lo, hi = min(cam_of[c0:c1]), max(cam_of[c0:c1]) + 1      # the chunk's cameras: a slice of the path's
+                sel = ([c - lo for c in cam_of[c0:c1]], tl[c0:c1])
+                self._rgbd(homos[lo:hi], rows[lo:hi], H, W, **{"times" if kind == "times" else "path": sel}, **sink(c0, c1))
+        return tuple(out)
 
     def display_bg(self):
         """bg_color parsed for the display frames: 3 floats, or None; "random" -- one draw per call, a float composite -- is refused."""
@@ -311,6 +383,10 @@ class BakedMPV(_Baked):
         from .render import render_path_disparity_baked
         return render_path_disparity_baked(self.texels, frame_cam, frame_t, homos, rows, H, W, self.spec, quad_keep=self.quad_keep, out=out)
 
+    def _rgbd(self, homos, rows, H, W, **sel_and_sink):
+        from .render import render_rgbd_baked
+        return render_rgbd_baked(self.texels, homos, rows, H, W, self.spec, quad_keep=self.quad_keep, **sel_and_sink)
+
 
 class BakedPool(_Baked):
     """bake_pool(module)'s product: the playback model of a tile-culled model without a dense clip.  pool [n_slots * 64, 4] uint8 on the device
@@ -366,6 +442,11 @@ class BakedPool(_Baked):
         from .render import render_path_disparity_baked_pool
         return render_path_disparity_baked_pool(self.layout, self.pool, frame_cam, frame_t, homos, rows, H, W, self.spec, out=out,
                                                 quad_keep=self.quad_keep, culled_rgba8=self.culled_rgba8)
+
+    def _rgbd(self, homos, rows, H, W, **sel_and_sink):
+        from .render import render_rgbd_baked_pool
+        return render_rgbd_baked_pool(self.layout, self.pool, homos, rows, H, W, self.spec, quad_keep=self.quad_keep, culled_rgba8=self.culled_rgba8,
+                                      **sel_and_sink)
 
     @torch.no_grad()
     def unpack_frames(self, frames):

@@ -821,6 +821,93 @@ def render_path_disparity_baked_pool(layout, pool, frame_cam, frame_t, homos, ro
     return _baked_disparity(who, src, n, 0, path, homos, rows, H, W, spec, out, cull_scratch)
 
 
+# ---- RGB-D (include/vl3d.h "RGB-D"; csrc/vl3d_render_rgbd.hip) ----------------------------------------------------------------------------
+def _rgbd_float_out(out, n, H, W, device, who):
+    """(rgb [n,H,W,3], alpha [n,H,W], disp [n,H,W]) float32: fresh, or the caller's `out` triple checked."""
+    if out is None:
+        return _out_buffers(None, n, H, W, device, who) + (torch.empty((n, H, W), dtype=torch.float32, device=device),)
+    if len(out) != 3:
+        raise RuntimeError(f"{who}: `out` is (rgb [n,H,W,3], alpha [n,H,W], disp [n,H,W])")
+    for b, shape in zip(out, ((n, H, W, 3), (n, H, W), (n, H, W))):
+        if not isinstance(b, torch.Tensor) or b.device != device or b.dtype != torch.float32 or tuple(b.shape) != shape or not b.is_contiguous():
+            raise RuntimeError(f"{who}: `out` must be contiguous float32 (rgb [n,H,W,3], alpha [n,H,W], disp [n,H,W]) with n,H,W = {n},{H},{W} "
+                               "on the model's device")
+    return tuple(out)
+
+
+def _depth16_out(depth16, n, H, W, device, who):
+    """the 16-bit depth of the display sink: uint16 [n,H,W] contiguous on `device`"""
+    if (not isinstance(depth16, torch.Tensor) or depth16.device != device or depth16.dtype != torch.uint16 or tuple(depth16.shape) != (n, H, W)
+            or not depth16.is_contiguous()):
+        raise RuntimeError(f"{who}: `depth16` must be contiguous uint16 [n,H,W] = [{n},{H},{W}] on the model's device")
+    return depth16
+
+
+def _baked_rgbd(who, src, T, homos, rows, H, W, spec, run, path, times, out, frames8, depth16, bg, cull_scratch):
+    """the one call of the two RGB-D renders: the selection (exactly one of run / path / times) checked by the colour wrappers' own checks, the
+    sink (float triple, or frames8 with depth16) and the entry of the source `src` (_baked_dense / _baked_pool)"""
+    if sum(v is not None for v in (run, path, times)) != 1:
+        raise ValueError(f"{who}: exactly one of run=(frame0, n), path=(frame_cam, frame_t) and times=(frame_cam, frame_time)")
+    if (frames8 is None) != (depth16 is None):
+        raise ValueError(f"{who}: the display sink is `frames8=` AND `depth16=` (uint8 colour frames, uint16 depth): pass both or neither")
+    _check_bg(who, frames8, bg)
+    dev, D = src.device, src.dims[0]
+    sel = tsel = None
+    if run is not None:
+        frame0, n = int(run[0]), int(run[1])
+        _check_run(who, frame0, n, T, homos, D, "model's" if src.culled else "clip of")
+        sel, n_cams = L.BakedFrames(frame0=frame0), None
+    elif path is not None:
+        n, (n_cams, idx) = _check_path(who, path[0], path[1], T, homos, D, dev)
+        sel = L.BakedFrames(frame0=0, n_cams=n_cams, frame_cam=idx[0].data_ptr(), frame_t=idx[1].data_ptr())
+    else:
+        n, (n_cams, idx) = _check_times(who, times[0], times[1], T, homos, D, dev)
+        tsel = L.BakedTimes(n_cams=n_cams, frame_cam=idx[0].data_ptr(), frame_time=idx[1].data_ptr())
+    homos = homos.detach().to(torch.float32).contiguous()
+    rows = _disp_rows(who, rows, homos, dev)
+    desc = _desc_dims(D, n, src.dims[1], src.dims[2], H, W, spec, L.STACK_DTYPE["u8"])
+    sink, entry = L.RgbdOut(), src.entry.replace("vl3d_render_fwd_", "vl3d_render_rgbd_")
+    if frames8 is not None:
+        sink.channels, bgc = _display_out(out, frames8, bg, n, H, W, dev, who)
+        ret = (frames8, _depth16_out(depth16, n, H, W, dev, who))
+        sink.frames, sink.bg, sink.depth16 = frames8.data_ptr(), (None if bgc is None else L.C.addressof(bgc)), depth16.data_ptr()
+    else:
+        ret = _rgbd_float_out(out, n, H, W, dev, who)
+        sink.rgb, sink.alpha, sink.disp = (b.data_ptr() for b in ret)
+    with torch.cuda.device(dev):
+        cull = None
+        if src.qk is not None:
+            cull = _cull_scratch(desc, dev) if n_cams is None else _path_cull_scratch(desc, n_cams, dev, cull_scratch, who)
+        grid = (0, 0) if src.qk is None else _qgrid(src.qk, spec)
+        L.check(getattr(L.lib(), entry)(desc, *src.head, L.ptr(homos), L.ptr(rows), sel, tsel, L.ptr(src.qk), *grid, *src.culled, L.ptr(cull), sink,
+                                        L.stream_ptr(dev)), entry)
+    return ret
+
+
+def render_rgbd_baked(baked, homos, rows, H, W, spec: RenderSpec, *, run=None, path=None, times=None, quad_keep=None, out=None, frames8=None,
+                      depth16=None, bg=None, cull_scratch=None):
+    """RGB-D frames of the baked clip in ONE render launch (vl3d_render_rgbd_baked): the picture of render_frame_run_baked / render_path_baked /
+    render_times_baked and the disparity map of render_*_disparity_baked from one walk of the planes.  Exactly one selection, by keyword:
+    `run` = (frame0, n) under homos [D,3,3] and rows [D,3]; `path` = (frame_cam, frame_t) or `times` = (frame_cam, frame_time) under homos
+    [C,D,3,3] and rows [C,D,3] (depth_rows), checked as the colour wrappers check them.  -> (rgb [n,H,W,3], alpha [n,H,W], disp [n,H,W])
+    float32 (`out`: the caller's triple): rgb and alpha bit-equal to the colour wrapper, disp of a run or a path to the disparity wrapper; a
+    loop time has no other depth entry.  `frames8` (uint8 [n,H,W,3|4]) WITH `depth16` (uint16 [n,H,W]): the display sink instead -- the
+    colour wrapper's display frames (over `bg`) and depth16 = trunc(65535 clip(disp, 0, 1)), not divided by alpha, 0 where nothing covers
+    the pixel; normalise disp into [0, 1] through the rows (depth_rows(normalise=(near, far))).  -> (frames8, depth16).  Forward only."""
+    who = "render_rgbd_baked"
+    T, src = _baked_dense(who, baked, homos, spec, quad_keep)
+    return _baked_rgbd(who, src, T, homos, rows, H, W, spec, run, path, times, out, frames8, depth16, bg, cull_scratch)
+
+
+def render_rgbd_baked_pool(layout, pool, homos, rows, H, W, spec: RenderSpec, *, run=None, path=None, times=None, quad_keep, culled_rgba8, out=None,
+                           frames8=None, depth16=None, bg=None, cull_scratch=None):
+    """render_rgbd_baked from the baked POOL (vl3d_render_rgbd_baked_pool): `layout`, `pool`, `quad_keep`, `culled_rgba8` as
+    render_frame_run_baked_pool takes them -> the bits of render_rgbd_baked on the unpacked texels."""
+    who = "render_rgbd_baked_pool"
+    T, src = _baked_pool(who, layout, pool, homos, spec, quad_keep, culled_rgba8)
+    return _baked_rgbd(who, src, T, homos, rows, H, W, spec, run, path, times, out, frames8, depth16, bg, cull_scratch)
+
+
 def render_planes(stack, homos, H, W, spec: RenderSpec = RenderSpec(), window=(0, 0), quad_keep=None, cull_window=None, grad_culled_unwritten=False,
                   fused_adam=None):
     """stack (D,T,Hs,Ws,4) pre-activation fp32 (plane 0 = nearest), homos [D,3,3] (target pixel -> plane pixel).

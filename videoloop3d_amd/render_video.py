@@ -334,6 +334,68 @@ def render_disparity_frames(nerf, H, W, view_extrins, view_intrins, render_t, ma
     return out[0] if len(out) == 1 else torch.cat(out, 0)
 
 
+@torch.no_grad()
+def render_rgbd_frames(baked, H, W, view_extrins, view_intrins, render_t, max_batch=64, fractional=False, normalise=True, display=True, channels=3):
+    """RGB-D frames of the playback model beside render_disparity_frames: colour and depth of every output frame from ONE render launch per
+    chunk (baked.BakedMPV / BakedPool .render_rgbd; include/vl3d.h "RGB-D") -> (frames8 uint8 [N,H,W,channels], depth16 uint16 [N,H,W]) on the
+    model's device, or with display=False (rgb [N,H,W,3], alpha [N,H,W], disp [N,H,W]) float32.  `fractional`: render_t are real loop times
+    (`retime(...)`) -- the only depth at a fractional time.  `normalise`: as render_rgbd takes it (True: nearest plane 1, farthest 0)."""
+    view_extrins = torch.as_tensor(np.asarray(view_extrins), dtype=torch.float32)
+    view_intrins = torch.as_tensor(np.asarray(view_intrins), dtype=torch.float32)
+    render_t = np.asarray(render_t, dtype=np.float64 if fractional else np.int64).reshape(-1)[:len(view_extrins)]
+    n = len(render_t)
+    return baked.render_rgbd(H, W, view_extrins[:n], view_intrins[:n], render_t, fractional=fractional, normalise=normalise, display=display,
+                             channels=channels, max_batch=max_batch)
+
+
+def write_pgm16(path, depth16):
+    """one depth frame [H,W] (uint16 tensor or array) as a binary PGM of maxval 65535: "P5\\nW H\\n65535\\n", then the samples most significant
+    byte first, as the format demands -- the byte swap happens here, on the host."""
+    a = depth16.detach().cpu().numpy() if isinstance(depth16, torch.Tensor) else np.asarray(depth16)
+    if a.dtype != np.uint16 or a.ndim != 2:
+        raise ValueError(f"write_pgm16: one frame [H,W] of uint16, got {a.shape} {a.dtype}")
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n65535\n" % (a.shape[1], a.shape[0]))
+        f.write(a.astype(">u2").tobytes())
+
+
+def read_pgm16(path):
+    """write_pgm16's file back -> uint16 array [H,W]"""
+    with open(path, "rb") as f:
+        raw = f.read()
+    head = raw.split(b"\n", 3)
+    if len(head) != 4 or head[0] != b"P5" or head[2] != b"65535":
+        raise ValueError(f"read_pgm16: {path} is not a binary PGM of maxval 65535")
+    w, h = (int(v) for v in head[1].split())
+    if len(head[3]) != 2 * w * h:
+        raise ValueError(f"read_pgm16: {path} holds {len(head[3])} sample bytes, {w} x {h} x 2 expected")
+    return np.frombuffer(head[3], dtype=">u2").reshape(h, w).astype(np.uint16)
+
+
+@torch.no_grad()
+def write_rgbd(y4m_path, depth_dir, baked, H, W, view_extrins, view_intrins, render_t, fps=25, fractional=False, normalise=True, max_batch=64,
+               **writer_kw):
+    """write_video for RGB-D frames: the colour frames of render_rgbd_frames to `y4m_path` through y4m.Y4MWriter and the 16-bit depth of
+    frame i to `depth_dir`/%04d.pgm (write_pgm16), a segment of at most `max_batch` frames at a time.  Returns the number of frames."""
+    from .y4m import Y4MWriter
+    view_extrins = torch.as_tensor(np.asarray(view_extrins), dtype=torch.float32)
+    view_intrins = torch.as_tensor(np.asarray(view_intrins), dtype=torch.float32)
+    render_t = np.asarray(render_t, dtype=np.float64 if fractional else np.int64).reshape(-1)
+    n = min(len(render_t), len(view_extrins))
+    seg = max(1, int(max_batch))
+    os.makedirs(depth_dir, exist_ok=True)
+    with Y4MWriter(y4m_path, W, H, fps=fps, chunk=seg, **writer_kw) as out:
+        for i in range(0, n, seg):
+            j = min(n, i + seg)
+            frames8, depth16 = render_rgbd_frames(baked, H, W, view_extrins[i:j], view_intrins[i:j], render_t[i:j], max_batch=seg,
+                                                  fractional=fractional, normalise=normalise)
+            out.write(frames8)
+            host = depth16.cpu()
+            for k in range(j - i):
+                write_pgm16(os.path.join(depth_dir, "%04d.pgm" % (i + k)), host[k])
+    return n
+
+
 def render_video(nerf, args, poses_bounds, ckpt=None, v="", t="", f=-1, render_scaling=1., factor=None):
     """The whole of script_render_video.evaluate() but the files: poses -> selection -> (optional) checkpoint -> frames.
     `nerf`: an MPMeshVid built with `reference_camera(...)` of the same poses; `ckpt`: a path or a loaded dict with 'network_state_dict'."""
