@@ -112,11 +112,13 @@ __global__ __launch_bounds__(256) void overcompose_fwd_k(int64_t P, int D, int C
     for (int c = 0; c < C; ++c) rgb[p * C + c] = acc[c];
 }
 
-// Backward without any division: back-to-front recurrence R_{k-1} = a_k q'_k + (1-a_k) R_k is not possible
-// with a per-plane upstream gradient on the blend weights, so use the generic two-sweep form:
-//   w_k = a_k T_k ; given gw_k := dL/dw_k (= g_rgb . c_k + g_bw_k):
-//   dL/da_k = T_k gw_k - sum_{j>k} gw_j w_j / (1 - a_k)        (exact 0/0 -> handled by direct product below)
-// The suffix sum is accumulated back-to-front; (1-a_k)==0 falls back to an explicit product over planes.
+// Backward without a division or a special case, in two sweeps.  With w_k = a_k T_k and gw_k := dL/dw_k = g_rgb . c_k + g_bw_k (the
+// per-plane upstream gradient on the blend weights is just one more term of gw_k):
+//   dL/da_k = T_k (gw_k - R_k),   R_k = sum_{j>k} gw_j a_j prod_{k<m<j} (1 - a_m)   (what the planes behind k lose when a_k grows)
+//   back to front:  R_{D-1} = 0,  R_{k-1} = a_k gw_k + (1 - a_k) R_k
+//   front to back:  T_0 = 1,      T_{k+1} = T_k (1 - a_k)
+// Every intermediate is a sum of terms of the result, so an opaque plane (1 - a_k == 0), a nearly opaque one and a total
+// transmittance that underflows cost nothing.  R_k is parked in g_alpha between the sweeps: the same thread writes and reads it.
 __global__ __launch_bounds__(256) void overcompose_bwd_k(int64_t P, int D, int C, const float *__restrict__ alpha,
                                                          const float *__restrict__ content,
                                                          const float *__restrict__ g_rgb, const float *__restrict__ g_bw,
@@ -127,43 +129,27 @@ __global__ __launch_bounds__(256) void overcompose_bwd_k(int64_t P, int D, int C
     const float *ct = content + p * D * C;
     float G[8];
     for (int c = 0; c < C; ++c) G[c] = g_rgb[p * C + c];
-    // forward sweep: T_D (total transmittance) and per-plane content grads
-    float Tr = 1.f;
-    for (int d = 0; d < D; ++d) {
-        const float w = a[d] * Tr;
-        for (int c = 0; c < C; ++c) g_content[(p * D + d) * C + c] = w * G[c];
-        Tr *= (1.f - a[d]);
-    }
-    // backward sweep: maintain T_{k} by dividing out (1-a_{k}) when safe, else recompute the prefix product
-    float suffix = 0.f;        // sum_{j>k} gw_j w_j
-    float Tk1 = Tr;            // T_{k+1}
+    // back to front: R_k
+    float R = 0.f;
     for (int d = D - 1; d >= 0; --d) {
-        const float om = 1.f - a[d];
-        float Tk;
-        if (fabsf(om) > 1e-6f) {
-            Tk = Tk1 / om;
-        } else {
-            Tk = 1.f;
-            for (int j = 0; j < d; ++j) Tk *= (1.f - a[j]);
-        }
+        g_alpha[p * D + d] = R;
+        const float ad = a[d];
         float gw = g_bw ? g_bw[p * D + d] : 0.f;
         for (int c = 0; c < C; ++c) gw += G[c] * ct[d * C + c];
-        float behind;
-        if (fabsf(om) > 1e-6f) {
-            behind = suffix / om;
-        } else {   // d(sum_{j>k} gw_j w_j)/da_k = -T_k * sum_{j>k} gw_j a_j prod_{k<m<j}(1-a_m)
-            float r = 0.f, tt = 1.f;
-            for (int j = d + 1; j < D; ++j) {
-                float gwj = g_bw ? g_bw[p * D + j] : 0.f;
-                for (int c = 0; c < C; ++c) gwj += G[c] * ct[j * C + c];
-                r += gwj * a[j] * tt;
-                tt *= (1.f - a[j]);
-            }
-            behind = Tk * r;
+        R = ad * gw + (1.f - ad) * R;
+    }
+    // front to back: T_k, the content gradient and dL/da_k
+    float Tr = 1.f;
+    for (int d = 0; d < D; ++d) {
+        const float ad = a[d];
+        const float w = ad * Tr;
+        float gw = g_bw ? g_bw[p * D + d] : 0.f;
+        for (int c = 0; c < C; ++c) {
+            gw += G[c] * ct[d * C + c];
+            g_content[(p * D + d) * C + c] = w * G[c];
         }
-        g_alpha[p * D + d] = Tk * gw - behind;
-        suffix += gw * a[d] * Tk;
-        Tk1 = Tk;
+        g_alpha[p * D + d] = Tr * (gw - g_alpha[p * D + d]);
+        Tr *= (1.f - ad);
     }
 }
 
@@ -198,28 +184,28 @@ __global__ __launch_bounds__(256) void nto0_bwd_k(int D, int C, int64_t HW, cons
     if (p >= HW) return;
     float G[8];
     for (int c = 0; c < C; ++c) G[c] = g_rgb[((int64_t)b * C + c) * HW + p];
-    // S = sum_k w_k q_k (front-to-back = d descending), then single sweep with prefix P
-    float Tr = 1.f, S = 0.f;
-    for (int d = D - 1; d >= 0; --d) {
+    // the two sweeps of overcompose_bwd_k with the front at d = D - 1: R_k back to front (d ascending), parked in g_alpha ...
+    float R = 0.f;
+    for (int d = 0; d < D; ++d) {
+        g_alpha[((int64_t)b * D + d) * HW + p] = R;
         const float ad = alpha[b * a_sb + d * a_sd + p];
         float q = 0.f;
         for (int c = 0; c < C; ++c) q += G[c] * content[b * c_sb + d * c_sd + c * c_sc + p];
-        S += ad * Tr * q;
-        Tr *= (1.f - ad);
+        R = ad * q + (1.f - ad) * R;
     }
-    Tr = 1.f;
-    float Pf = 0.f;
+    // ... then T_k front to back (d descending)
+    float Tr = 1.f;
     for (int d = D - 1; d >= 0; --d) {
         const float ad = alpha[b * a_sb + d * a_sd + p];
-        float q = 0.f;
-        for (int c = 0; c < C; ++c) q += G[c] * content[b * c_sb + d * c_sd + c * c_sc + p];
         const float w = ad * Tr;
-        for (int c = 0; c < C; ++c) g_content[(((int64_t)b * D + d) * C + c) * HW + p] = w * G[c];
-        Pf += w * q;
-        const float om = 1.f - ad;
-        const float behind = (fabsf(om) > 1e-12f) ? (S - Pf) / om : 0.f;
-        g_alpha[((int64_t)b * D + d) * HW + p] = Tr * q - behind;
-        Tr *= om;
+        float q = 0.f;
+        for (int c = 0; c < C; ++c) {
+            q += G[c] * content[b * c_sb + d * c_sd + c * c_sc + p];
+            g_content[(((int64_t)b * D + d) * C + c) * HW + p] = w * G[c];
+        }
+        const int64_t i = ((int64_t)b * D + d) * HW + p;
+        g_alpha[i] = Tr * (q - g_alpha[i]);
+        Tr *= (1.f - ad);
     }
 }
 
